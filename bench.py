@@ -27,6 +27,10 @@ Prints ONE JSON line on rank 0 (contract in the task statement), including
   roofline_fwd  -- same for the forward march kernel (the 40 %-of-HBM target of north_star)
   cpu_baseline  -- the CPU oracle (plain-C port of the reference, 1 thread) timed on a bounded
                    sample of the same workload (rank 0, N=1 only)
+
+`--dump-outputs DIR` writes what the last timed step computed (rank 0's exit rays xt, vt and the dL/dn grid, a
+fixed sample of the grid when everything would exceed the budget) as DIR/<name>.npy: the inputs depend on the
+arguments only, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -112,9 +116,16 @@ def parse_args(argv=None):
                          "symmetric, so the work is the same and only the memory order of the cells along the rays differs)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend for N>1 (nccl = RCCL; gloo only "
                                                         "to rehearse the multi-rank flow on a 1-GPU box)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: exit rays xt, vt and the "
+                         "dL/dn grid) as DIR/<name>.npy in float32, under 64 MB in all (see dump_outputs)")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.shard_of and not (0 <= args.shard_index < args.shard_of):
         ap.error("--shard-index must lie in [0, --shard-of)")
     if args.scaling is None:
@@ -271,6 +282,36 @@ def make_workload(R: int, n_rays: int, device, seed: int):
     ds = h / 2                                  # step_res = 2 (core/luneburg_opt.py:38,48-49)
     pos, vel = make_rays(n_rays, seed)
     return make_grid(R, device), pos.to(device), vel.to(device), h, ds
+
+
+DUMP_BYTES = 60 * 2 ** 20      # --dump-outputs: data of all files together (with the .npy headers: under 64 MB)
+
+
+def dump_outputs(out_dir, arrays, budget=DUMP_BYTES, seed=0):
+    """Write each of `arrays` (name -> tensor) to out_dir/<name>.npy in float32, within `budget` bytes in all.
+    Smaller arrays are written first and whole if they fit their share (what is left of the budget / arrays left); an
+    array larger than its share is replaced by a fixed, seeded sample of its rows along dim 0: the rows
+    torch.randperm(rows, generator seeded with `seed`)[:k], sorted -- the same rows for every run with the same shapes,
+    so that two builds can be compared file for file.  -> {name: (rows written, rows in the array)}"""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    left, info = int(budget), {}
+    items = sorted(arrays.items(), key=lambda kv: kv[1].numel())
+    for i, (name, t) in enumerate(items):
+        t = t.detach()
+        rows = t.shape[0]
+        row_bytes = 4 * (t.numel() // max(rows, 1))
+        share = left // (len(items) - i)
+        if rows * row_bytes > share:
+            k = share // row_bytes
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+            t = t[idx.to(t.device)]
+        a = np.ascontiguousarray(t.to(torch.float32).cpu().numpy())
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        left -= a.nbytes
+        info[name] = (int(a.shape[0]), int(rows))
+    return info
 
 
 def load_pmc():
@@ -491,9 +532,10 @@ def run_rank(args) -> int:
 
     ring_pct = int(lib.drrt_ring_threshold_pct())
 
-    def bench_rays(pos, vel, steps, warmup, force_flags=None, keep=False, rif=rif, robust=False):
+    def bench_rays(pos, vel, steps, warmup, force_flags=None, keep=False, rif=rif, robust=False, dump=False):
         """Time `steps` fwd + adjoint passes over the rays (pos, vel) resident on the device; -> this rank's measurements.
-        force_flags = (fflags, aflags, pair) overrides the pair-copy rule (parity runs on a sub-sample keep the flags)."""
+        force_flags = (fflags, aflags, pair) overrides the pair-copy rule (parity runs on a sub-sample keep the flags).
+        keep / dump: the results of the last step as xt, vt, grad / under `outputs` (for --dump-outputs)."""
         n = pos.shape[0]
         fflags, aflags, pair = force_flags if force_flags is not None else pair_flags(n)
         ws = torch.empty(int(lib.drrt_workspace_bytes_grid(n, nvox, fflags | aflags)) + 1024, dtype=torch.uint8, device=dev)
@@ -648,9 +690,13 @@ def run_rank(args) -> int:
                    ms_sort=avg("sort"), ms_zero=avg("zero"), ms_quad=avg("quad"), ms_allreduce=ms_ar, pair=pair,
                    pos=pos, vel=vel, flags=(fflags, aflags, pair), dbg=dbg, adjoint_kernel=choice, chunking=chunking,
                    overlap=(overlap_info if (K > 1 and use_dist and args.overlap_reduce) else None), ms_allreduce_plain=ms_ar_plain)
-        if keep:                                   # results of the LAST step (the adjoint's grid holds this rank's gradient
-            out.update(xt=xt, vt=vt,               # only when there is no all-reduce: parity_check runs at world == 1)
-                       grad=grad.clone())
+        if keep or dump:                           # results of the LAST step (the adjoint's grid holds this rank's gradient
+            last = dict(xt=xt, vt=vt,              # only when there is no all-reduce: parity_check runs at world == 1)
+                        grad=grad.clone())
+            if keep:
+                out.update(last)
+            if dump:
+                out["outputs"] = last
         return out
 
     def direct_atomics_grad(m, rif=rif):
@@ -715,7 +761,8 @@ def run_rank(args) -> int:
         else:
             g, pos, vel, views, _ = workload_set(args.workload, args.rays, rank)
         out = bench_rays(pos, vel, args.steps, args.warmup,
-                         keep=(world == 1 and mode == "strong" and args.workload == "metric"), rif=g)
+                         keep=(world == 1 and mode == "strong" and args.workload == "metric"), rif=g,
+                         dump=bool(args.dump_outputs) and rank == 0 and mode == modes[0])
         out["mode"] = mode
         out["multi_view"] = views is not None
         return out
@@ -743,6 +790,12 @@ def run_rank(args) -> int:
     results = {m: run_mode(m) for m in modes}
     main_mode = modes[0]
     m = results[main_mode]
+    if rank == 0 and args.dump_outputs:
+        # what a caller of the timed path receives from its last step: rank 0's exit rays and the dL/dn grid (after the
+        # all-reduce when there is one); the inputs depend on the arguments only (seeded sources, analytic media)
+        kept = dump_outputs(args.dump_outputs, m.pop("outputs"))
+        print(f"bench.py: --dump-outputs {args.dump_outputs}: "
+              + ", ".join(f"{k} {r} of {n} rows" for k, (r, n) in kept.items()), file=sys.stderr)
 
     if rank == 0:
         n, fwd_steps, adj_steps = m["n"], m["fwd_steps"], m["adj_steps"]
