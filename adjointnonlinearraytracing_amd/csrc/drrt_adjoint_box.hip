@@ -43,9 +43,6 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_direct(BackArgs a) {
 //
 //   window      kWinX x kWinY x kWinZ voxels of double accumulators, row pitch kWinPX (measured, final
 //               kernels: edge 9 beats 7, 8, 10, 12; padding the pitch or not is within 1 %)
-//   ablations   BackArgs::experiment (bits 8..15 of `flags`, development only): 1 = no accumulation
-//               at all, 2 = no global atomics, 3 = no LDS adds, 4 = hand over all 8 corners on every
-//               leave, 5 = never flush, 6 = no DPP pre-reduction, 7 = the box-window kernel, nothing ablated
 //   anchor      around the cell of the wave's median contributing lane, shifted towards its
 //               direction of travel (most of the window lies ahead of the rays)
 //   re-anchor   as soon as a contributing lane misses the window (wave-uniform decision); if lanes
@@ -71,7 +68,7 @@ constexpr int kWinFloats = kWinSZ * kWinZ;                // 810 slots = 6.3 KiB
 // four: the four LDS exchanges are issued before the first result is used, so a flush costs ceil(rows / 7 / 4) LDS
 // round trips (3 for a 9^3 window) instead of one per pass.
 __device__ __forceinline__ void win_flush(win_t* win, int ox, int oy, int oz, float* __restrict__ grad,
-                                          const Vol& V, int lane, bool no_global = false) {
+                                          const Vol& V, int lane) {
   constexpr int kRowsPerPass = kWave / kWinX, kRowsTotal = kWinY * kWinZ;
   constexpr int kPasses = (kRowsTotal + kRowsPerPass - 1) / kRowsPerPass, kBatch = 4;
   static_assert(kWinX <= 16 && kRowsPerPass <= kWinY, "win_flush: one pass must not span more than two z-slices");
@@ -96,7 +93,7 @@ __device__ __forceinline__ void win_flush(win_t* win, int ox, int oy, int oz, fl
     }
 #pragma unroll
     for (int b = 0; b < kBatch; ++b)
-      if (v[b] != (win_t)0 && !no_global) atomic_add_f32(grad + g[b], (float)v[b]);
+      if (v[b] != (win_t)0) atomic_add_f32(grad + g[b], (float)v[b]);
   }
   wave_lds_fence();
 }
@@ -245,7 +242,8 @@ __global__ void __launch_bounds__(kBlock) k_bundle_classify(BackArgs a) {
 //       accumulator over and flushes every window at its end, saves the state, and reduces the bounding box of the positions
 //       and velocities of the rays that are still marching into a.chunk_progress.  Same arithmetic, same contributions;
 //       only the order in which they reach the grid differs from the one-launch march.
-template <bool ABL, bool PAIR, int MODE = 0, bool CHUNK = false>
+// DBG: the instantiation with the event counters of DRRT_FLAG_DEBUG_COUNTERS (a.dbg), backtrace only.
+template <bool DBG, bool PAIR, int MODE = 0, bool CHUNK = false>
 __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(BackArgs a) {
   if (a.select != nullptr && bundles_want_ring(a.select)) return;
   constexpr int kSlots = kWinFloats;
@@ -278,7 +276,6 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
       s.outside = interp<false>(fetch(a.sdf, c0), c0.wx, c0.wy, c0.wz).n >= 0.f;
     }
   }
-  const int experiment = ABL ? a.experiment : 0;
   WinOrg W;                                                    // the wave's window (wave-uniform)
   W.ox = W.oy = W.oz = -(1 << 28);                             // far away = nothing is inside
   // the cell the ray stands on, located IN PLACE: flat index and coordinates of corner 000, in-cell fractions, strictly
@@ -345,26 +342,11 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
 #define WIN_INDEX(cx, cy, cz) win_index(W.ox, W.oy, W.oz, cx, cy, cz)
     for (int it = 0; it < a.max_steps; ++it) {
       if (!__any(s.active)) break;                                              // wave-uniform exit
-#if defined(DRRT_PAD_VALU)
-      { float pa_ = 1.f, pb_ = 2.f, pc_ = 3.f, pd_ = 4.f;   // sensitivity experiment: 4 * DRRT_PAD_VALU extra v_fma per step
-#pragma unroll
-        for (int k_ = 0; k_ < DRRT_PAD_VALU; ++k_)
-          asm volatile("v_fma_f32 %0, %0, %0, %0\n v_fma_f32 %1, %1, %1, %1\n v_fma_f32 %2, %2, %2, %2\n v_fma_f32 %3, %3, %3, %3"
-                       : "+v"(pa_), "+v"(pb_), "+v"(pc_), "+v"(pd_)); }
-#endif
-#if defined(DRRT_PAD_LDS)
-#pragma unroll
-      for (int k_ = 0; k_ < DRRT_PAD_LDS; ++k_) atomicAdd(win + 64 * k_ + lane, (win_t)0);   // conflict-free ds_add_f64 of 0.0
-#endif
-#if defined(DRRT_PAD_SALU)
-#pragma unroll
-      for (int k_ = 0; k_ < DRRT_PAD_SALU; ++k_) asm volatile("s_nop 0");
-#endif
       // ---- (re-)anchor the window around the cells the rays stand on (wave-uniform branch) ----
       const unsigned long long mm = __ballot(s.active & miss);
       if (mm != 0ull && cooldown == 0) {
         if (dirty) {
-          win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane, experiment == 2);
+          win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane);
           dirty = false; ++n_flush;
         }
         const bool ok = s.active & regular;
@@ -403,7 +385,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
         AdjSample m;
         if (!adj_sample_st<MODE>(V, a.sdf, a.ds, s, c, taps_of<PAIR>(q0, q1), m, st, MODE == 1 && interior)) {
           // the ray has ended (:426-428): it contributes nothing here; hand over what its cell has accumulated
-          if (regular && experiment != 1) used_lds = flat_emit8<true>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
+          if (regular) used_lds = flat_emit8<true>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
         } else {
           ++steps;
           if (CHUNK) { bx0 = fminf(bx0, px); by0 = fminf(by0, py); bz0 = fminf(bz0, pz); bx1 = fmaxf(bx1, px); by1 = fmaxf(by1, py); bz1 = fmaxf(bz1, pz); }
@@ -414,7 +396,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
             if (regular) {
               const CornerPairs cp = splat_weights_pk(wx, wy, wz, dn * a.ds, nds * s.mx, nds * s.my, nds * s.mz);   // :431-432
               p00 += cp.c00; p10 += cp.c10; p01 += cp.c01; p11 += cp.c11;
-            } else if (experiment != 2 && experiment != 1) {
+            } else {
               // clamped boundary cell: taps coincide; straight to the grid
               const Cell cb = locate(V, px, py, pz);
               const Corners w = splat_weights(cb.wx, cb.wy, cb.wz, dn * a.ds, nds * s.mx, nds * s.my, nds * s.mz);
@@ -445,10 +427,10 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
               if (d != 0 || regular != old_regular) {
                 const bool ax = (d == 1) | (d == -1), ay = (d == V.sy) | (d == -V.sy), az = (d == V.sz) | (d == -V.sz);
                 if (old_regular) {
-                  if (regular & (ax | ay | az) & (experiment != 1) & (experiment != 4)) {
+                  if (regular & (ax | ay | az)) {
                     // one face crossed: emit the face left behind, carry the shared one
                     const bool fwd = d > 0;
-                    if (ABL && a.dbg) {
+                    if (DBG && a.dbg) {
                       const int nax = (__ballot(ax) != 0ull) + (__ballot(ay) != 0ull) + (__ballot(az) != 0ull);
                       if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
                     }
@@ -476,47 +458,42 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
                       lp = WSY; lq = WSZ; la = 1; gp = V.sy; gq = V.sz; ga = 1;
                     }
                     if (old_lidx >= 0) {
-                      if (experiment != 3) {
-                        const int qi = old_lidx + (fwd ? 0 : la);
-                        // pair / quad pre-reduction (see shift_emit4): lanes of a quad that go to the same four slots
-                        const int key = qi | ((ay ? 1 : (az ? 2 : 0)) << 16);
-                        const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-                        const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-                        const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
-                        const bool psame = k1 == key;
-                        const bool same = psame & (k2 == key) & (k3 == key);
-                        float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
-                        q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
-                        q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
-                        q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
-                        q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
-                        const float s0 = q0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
-                        const float s1 = q1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
-                        const float s2 = q2 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
-                        const float s3 = q3 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
-                        const unsigned ql = threadIdx.x & 3u;
-                        const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
-                        if (ABL && a.dbg) { ++ev_face; ev_add += add; }
-                        if (experiment == 6) {            // ablation: no pre-reduction, every lane adds its own values
-                          win_t* q = win + qi;
-                          atomicAdd(q, (win_t)e0); atomicAdd(q + lp, (win_t)e1); atomicAdd(q + lq, (win_t)e2); atomicAdd(q + lq + lp, (win_t)e3);
-                        } else if (add) {
-                          win_t* q = win + qi;
-                          atomicAdd(q, (win_t)(same ? s0 : (psame ? q0 : e0)));      atomicAdd(q + lp, (win_t)(same ? s1 : (psame ? q1 : e1)));
-                          atomicAdd(q + lq, (win_t)(same ? s2 : (psame ? q2 : e2))); atomicAdd(q + lq + lp, (win_t)(same ? s3 : (psame ? q3 : e3)));
-                        }
+                      const int qi = old_lidx + (fwd ? 0 : la);
+                      // pair / quad pre-reduction (see shift_emit4): lanes of a quad that go to the same four slots
+                      const int key = qi | ((ay ? 1 : (az ? 2 : 0)) << 16);
+                      const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+                      const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+                      const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
+                      const bool psame = k1 == key;
+                      const bool same = psame & (k2 == key) & (k3 == key);
+                      float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
+                      q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
+                      q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
+                      q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
+                      q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
+                      const float s0 = q0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
+                      const float s1 = q1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
+                      const float s2 = q2 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
+                      const float s3 = q3 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
+                      const unsigned ql = threadIdx.x & 3u;
+                      const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
+                      if (DBG && a.dbg) { ++ev_face; ev_add += add; }
+                      if (add) {
+                        win_t* q = win + qi;
+                        atomicAdd(q, (win_t)(same ? s0 : (psame ? q0 : e0)));      atomicAdd(q + lp, (win_t)(same ? s1 : (psame ? q1 : e1)));
+                        atomicAdd(q + lq, (win_t)(same ? s2 : (psame ? q2 : e2))); atomicAdd(q + lq + lp, (win_t)(same ? s3 : (psame ? q3 : e3)));
                       }
-                      used_lds = experiment != 5;         // ablation 5: never flush (until the end)
-                    } else if (experiment != 2) {
-                      if (ABL && a.dbg) ++ev_glob;
+                      used_lds = true;
+                    } else {
+                      if (DBG && a.dbg) ++ev_glob;
                       float* g = a.grad + old_base + (fwd ? 0 : ga);
                       atomic_add_f32(g, e0); atomic_add_f32(g + gp, e1); atomic_add_f32(g + gq, e2); atomic_add_f32(g + gq + gp, e3);
                     }
                   } else {
                     // jump over more than one face, or into a clamped cell: hand over all eight
-                    if (ABL && a.dbg) ++ev_all8;
+                    if (DBG && a.dbg) ++ev_all8;
                     // (no quad pre-reduction here: two-face crossings are rarely shared by a quad -- 4.87 -> 4.81 ms without it)
-                    if (experiment != 1) used_lds = flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, old_lidx, old_base, p00, p10, p01, p11);
+                    used_lds = flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, old_lidx, old_base, p00, p10, p01, p11);
                     p00 = p10 = p01 = p11 = f2{0.f, 0.f};
                   }
                 }
@@ -528,16 +505,16 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
         }
       }
       dirty = dirty | (__ballot(used_lds) != 0ull);
-      if (ABL && a.dbg) ev_wsteps += lane == 0;
+      if (DBG && a.dbg) ev_wsteps += lane == 0;
     }
   // rays still marching when max_steps ran out keep what their cell has accumulated: hand it over
-  if (s.active && regular && experiment != 1) { if (flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11)) dirty = true; }
+  if (s.active && regular) { if (flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11)) dirty = true; }
 #undef WSY
 #undef WSZ
 #undef WIN_INDEX
   dirty = __ballot(dirty) != 0ull;
   if (dirty) {
-    win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane, experiment == 2);
+    win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane);
     ++n_flush;
   }
   if (CHUNK) {
@@ -569,7 +546,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
       }
     }
   }
-  if (ABL && a.dbg) {
+  if (DBG && a.dbg) {
     if (lane == 0) atomicAdd(&a.dbg[0], (unsigned long long)n_flush);
     if (ev_face) atomicAdd(&a.dbg[4], (unsigned long long)ev_face);
     if (ev_add) atomicAdd(&a.dbg[5], (unsigned long long)ev_add);
@@ -590,24 +567,18 @@ void launch_backtrace_direct(int mode, const BackArgs& a, hipStream_t s) {
 void launch_bundle_classify(const BackArgs& a, hipStream_t s) {
   hipLaunchKernelGGL(k_bundle_classify, dim3((grid_for(a.n) + kClassifyStride - 1) / kClassifyStride), dim3(kBlock), 0, s, a);
 }
-void launch_backtrace_box(int mode, bool abl, const BackArgs& a, hipStream_t s) {
+// PAIR follows the call's pair grid; the other parameters are the launcher's choice
+template <bool DBG, int MODE, bool CHUNK>
+static void launch_flat(const BackArgs& a, hipStream_t s) {
   const dim3 g(adj_grid_for(a.n)), b(kAdjBlock);
-  const bool pair = a.vol.pair != nullptr;
-  if (a.chunk_state != nullptr) {      /* resumable march (drrt_backtrace_chunk_f32): backtrace only */
-    if (pair) hipLaunchKernelGGL((k_backtrace_flat<false, true, 0, true>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_flat<false, false, 0, true>), g, b, 0, s, a);
-    return;
-  }
-  if (mode == 1) {          /* the ablation / counter instantiation exists for backtrace only */
-    if (pair) hipLaunchKernelGGL((k_backtrace_flat<false, true, 1>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_flat<false, false, 1>), g, b, 0, s, a);
-  } else if (abl) {
-    if (pair) hipLaunchKernelGGL((k_backtrace_flat<true, true, 0>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_flat<true, false, 0>), g, b, 0, s, a);
-  } else {
-    if (pair) hipLaunchKernelGGL((k_backtrace_flat<false, true, 0>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_flat<false, false, 0>), g, b, 0, s, a);
-  }
+  if (a.vol.pair != nullptr) hipLaunchKernelGGL((k_backtrace_flat<DBG, true, MODE, CHUNK>), g, b, 0, s, a);
+  else                       hipLaunchKernelGGL((k_backtrace_flat<DBG, false, MODE, CHUNK>), g, b, 0, s, a);
+}
+void launch_backtrace_box(int mode, bool dbg, const BackArgs& a, hipStream_t s) {
+  if (a.chunk_state != nullptr) launch_flat<false, 0, true>(a, s);     // resumable march (drrt_backtrace_chunk_f32): backtrace only
+  else if (mode == 1)           launch_flat<false, 1, false>(a, s);    // the counter instantiation exists for backtrace only
+  else if (dbg)                 launch_flat<true, 0, false>(a, s);
+  else                          launch_flat<false, 0, false>(a, s);
 }
 
 }  // namespace drrt

@@ -58,41 +58,6 @@ namespace drrt {
                                     // on: six rotated views / metric / 4-view tomography set (tools/probe_views.py):
                                     //   never sparse 9.9 / 5.9 / 5.0;  50 % -> 9.0 / 5.9 / 5.2;  70 % -> 8.9 / 6.8 / 5.7;  always sparse 8.9 / 8.8 / 5.9
 #endif
-// Timing-only ablations of the PRODUCT instantiation (tools/build_variant.sh; the results of such a build are wrong by
-// construction and it is never shipped): -DDRRT_RING_T_NO_LDS drops the window adds, -DDRRT_RING_T_U32 makes them 32-bit
-// integer adds, -DDRRT_RING_T_NO_GLOBAL drops every global atomic, -DDRRT_RING_T_NO_FLUSH the flush loops.
-#if defined(DRRT_RING_T_NO_LDS)
-#define RING_ADD(q, v) ((void)0)
-#elif defined(DRRT_RING_T_U32)
-#define RING_ADD(q, v) atomicAdd(reinterpret_cast<unsigned*>(q), __float_as_uint(v))
-#else
-#define RING_ADD(q, v) atomicAdd((q), (win_t)(v))
-#endif
-#if defined(DRRT_RING_T_NO_GLOBAL)
-#define RING_GADD(g, v) ((void)0)
-#else
-#define RING_GADD(g, v) atomic_add_f32((g), (v))
-#endif
-// Diagnostic build only (-DDRRT_RING_STAMPS, tools/ring_stamps.py; never in the product library): wave-level s_memtime
-// brackets around the regions of an iteration, summed over the launch -- where a wave's TIME goes (issue + waiting), which
-// the PMC instruction counts cannot say.  Stamp values go to a buffer of their own that nothing else reads.
-#if defined(DRRT_RING_STAMPS)
-// fixed-point window, per wave: [0] budget used up -> complete flush, [1] a hand-over left the range -> complete flush,
-// [2] budget used up -> the window's largest slot looked at, nothing flushed, [3] re-scales; per lane: [4] hand-overs the
-// guard sent to the grid, [5] hand-overs of the large class
-__device__ unsigned long long g_ring_events[8];
-#define QEVENT(k, n) { if (lane == 0 || (k) >= 4) atomicAdd(&g_ring_events[k], (unsigned long long)(n)); }
-__device__ unsigned long long g_ring_stamps[8];
-#define STAMP_DECL unsigned long long st_t = 0ull, st_acc[6] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull}; unsigned long long st_t0 = __builtin_amdgcn_s_memtime(); st_t = st_t0
-#define STAMP(k) { const unsigned long long st_n = __builtin_amdgcn_s_memtime(); st_acc[k] += st_n - st_t; st_t = st_n; }
-#define STAMP_END { const unsigned long long st_n = __builtin_amdgcn_s_memtime(); \
-    if (lane == 0) { atomicAdd(&g_ring_stamps[0], st_n - st_t0); for (int k_ = 0; k_ < 6; ++k_) atomicAdd(&g_ring_stamps[1 + k_], st_acc[k_]); atomicAdd(&g_ring_stamps[7], 1ull); } }
-#else
-#define STAMP_DECL
-#define STAMP(k)
-#define STAMP_END
-#define QEVENT(k, n)
-#endif
 struct Ring {                      // wave-uniform
   int nx, ny, nz;                  // slots per axis (>= 2)
   int sy, sz;                      // LDS strides of y and z in slots: nx, nx * ny
@@ -136,10 +101,7 @@ __device__ __forceinline__ int ring_locate(const Ring& R, int ix, int iy, int iz
 // WT = double (the general instantiation) or int (the sparse-only one: fixed point, value = slot * qinv).
 template <int A, typename WT>
 __device__ __forceinline__ void ring_flush(WT* win, const Ring& R, int g0, int k, float* __restrict__ grad, const Vol& V,
-                                           int lane, bool no_global, float qinv = 1.0f) {
-#if defined(DRRT_RING_T_NO_FLUSH)
-  return;
-#endif
+                                           int lane, float qinv = 1.0f) {
   wave_lds_fence();
   const int e0 = A == 0 ? k : R.nx, e1 = A == 1 ? k : R.ny, e2 = A == 2 ? k : R.nz;
   const int e01 = e0 * e1, total = e01 * e2;
@@ -173,9 +135,9 @@ __device__ __forceinline__ void ring_flush(WT* win, const Ring& R, int g0, int k
     }
 #pragma unroll
     for (int b = 0; b < kBatch; ++b)
-      if (v[b] != (WT)0 && !no_global) {
+      if (v[b] != (WT)0) {
         const float fv = (std::is_same<WT, int>::value) ? (float)v[b] * qinv : (float)v[b];
-        RING_GADD(grad + g[b], fv);
+        atomic_add_f32(grad + g[b], fv);
       }
   }
   wave_lds_fence();
@@ -183,49 +145,40 @@ __device__ __forceinline__ void ring_flush(WT* win, const Ring& R, int g0, int k
 
 // One lane crosses ONE face along axis A (storage coordinate sA, size nA, LDS stride SA; in-face axes P, Q) from the cell
 // whose slot is `cur`: the four corners left behind (e0..e3 in (p, q) order) go to the window -- pair / quad DPP
-// pre-reduced as in k_backtrace_flat while PRE -- and (cur, sA) move to the neighbour cell, modulo the window.
+// pre-reduced as in k_backtrace_flat -- and (cur, sA) move to the neighbour cell, modulo the window.
 // Returns true when the new cell lies outside the live region on that axis.
-template <bool ABL, typename WT>
-__device__ __forceinline__ bool ring_cross(WT* win, int experiment, bool pre, int axis_id, bool fwd, int& cur, int& sA, int sP,
+template <bool DBG, typename WT>
+__device__ __forceinline__ bool ring_cross(WT* win, int axis_id, bool fwd, int& cur, int& sA, int sP,
                                            int sQ, int nA, int nP, int nQ, int SA, int SP, int SQ, int gA_new, int oA,
-                                           float e0, float e1, float e2, float e3, bool& matched,
+                                           float e0, float e1, float e2, float e3,
                                            unsigned& ev_face, unsigned& ev_add, bool dbg) {
   // neighbour slots of the old cell: + stride, or back to storage layer 0 across the seam
   const int dA = sA == nA - 1 ? -(nA - 1) * SA : SA;
   const int dP = sP == nP - 1 ? -(nP - 1) * SP : SP;
   const int dQ = sQ == nQ - 1 ? -(nQ - 1) * SQ : SQ;
   const int qi = cur + (fwd ? 0 : dA);
-  if (experiment != 3) {
-    if (pre) {
-      const int key = qi | (axis_id << 16);
-      const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-      const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-      const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
-      const bool psame = k1 == key;
-      const bool same = psame & (k2 == key) & (k3 == key);
-      matched |= psame;
-      float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
-      q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
-      q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
-      q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
-      q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
-      const float s0 = q0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
-      const float s1 = q1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
-      const float s2 = q2 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
-      const float s3 = q3 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
-      const unsigned ql = threadIdx.x & 3u;
-      const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
-      if (ABL && dbg) { ++ev_face; ev_add += add; }
-      if (add) {
-        WT* q = win + qi;
-        RING_ADD(q, (same ? s0 : (psame ? q0 : e0)));      RING_ADD(q + dP, (same ? s1 : (psame ? q1 : e1)));
-        RING_ADD(q + dQ, (same ? s2 : (psame ? q2 : e2))); RING_ADD(q + dQ + dP, (same ? s3 : (psame ? q3 : e3)));
-      }
-    } else {
-      if (ABL && dbg) { ++ev_face; ++ev_add; }
-      WT* q = win + qi;
-      RING_ADD(q, e0); RING_ADD(q + dP, e1); RING_ADD(q + dQ, e2); RING_ADD(q + dQ + dP, e3);
-    }
+  const int key = qi | (axis_id << 16);
+  const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+  const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+  const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
+  const bool psame = k1 == key;
+  const bool same = psame & (k2 == key) & (k3 == key);
+  float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
+  q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
+  q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
+  q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
+  q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
+  const float s0 = q0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
+  const float s1 = q1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
+  const float s2 = q2 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
+  const float s3 = q3 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
+  const unsigned ql = threadIdx.x & 3u;
+  const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
+  if (DBG && dbg) { ++ev_face; ev_add += add; }
+  if (add) {
+    WT* q = win + qi;
+    atomicAdd(q, (win_t)(same ? s0 : (psame ? q0 : e0)));      atomicAdd(q + dP, (win_t)(same ? s1 : (psame ? q1 : e1)));
+    atomicAdd(q + dQ, (win_t)(same ? s2 : (psame ? q2 : e2))); atomicAdd(q + dQ + dP, (win_t)(same ? s3 : (psame ? q3 : e3)));
   }
   // the new cell: one step along A in storage
   int t = sA + (fwd ? 1 : -1);
@@ -270,7 +223,7 @@ __device__ __forceinline__ bool ring_cross(WT* win, int experiment, bool pre, in
 //             case: every lane-emit on one slot, one sign, top of its class); otherwise -- and whenever a hand-over left
 //             the range -- the whole window is flushed (and zeroed) and the scale re-chosen.  used + counted <= 2024 and
 //             2024 * 2^20 < 2^31: no slot can overflow whatever the rays do.  Events per wave on the six rotated views
-//             (tools/ring_stamps.py, round 4): 8.6 looks that kept the window, 2.0 + 0.2 complete flushes, 3.8 re-scales;
+//             (round 4, NOTES.md): 8.6 looks that kept the window, 2.0 + 0.2 complete flushes, 3.8 re-scales;
 //             1.5e-4 of the lane hand-overs go to the grid through the guard.  (The looks replaced ~10 complete flushes per
 //             wave and bought nothing measurable: 7.31-7.33 vs 7.32-7.35 ms.  Nor did a second, younger counter that takes
 //             over once the window's rear has passed the place its front had reached -- a moving window renews its slots by
@@ -312,7 +265,7 @@ __device__ __forceinline__ int cvt_rpi_i32(float f) {          // floor(f + 0.5)
 //         through the Luneburg ball, 11 per cell: 6.99-7.21 -> 6.94-7.05) and ruinous where many do (same-address LDS adds
 //         serialise: four views at 4 samples per pixel through the ball, 21 lanes per cell: 6.4 -> 9.0 ms; one view at 45
 //         degrees 6.0 -> 7.6) -- taken per CALL when few pair partners start in the same cell (bundles_want_direct).
-template <bool ABL, bool PAIR, int MODE = 0, bool SPARSE = false, bool DIRECT = false>
+template <bool DBG, bool PAIR, int MODE = 0, bool SPARSE = false, bool DIRECT = false>
 __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : DRRT_RING_WAVES) k_backtrace_ring(BackArgs a) {
   constexpr bool kDirect = SPARSE && DIRECT;
   constexpr int kRingCap = SPARSE ? DRRT_RING_SPARSE_CAP : DRRT_RING_CAP;
@@ -343,8 +296,7 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
       s.outside = interp<false>(fetch(a.sdf, c0), c0.wx, c0.wy, c0.wz).n >= 0.f;
     }
   }
-  const int experiment = ABL ? a.experiment : 0;
-  const bool dbg = ABL && a.dbg != nullptr;
+  const bool dbg = DBG && a.dbg != nullptr;
   Ring R;                                                      // the wave's window (wave-uniform); nothing is inside yet
   R.nx = R.ny = R.nz = 3; R.sy = 3; R.sz = 9; R.tot = SPARSE ? 27 : 0; R.ox = R.oy = R.oz = -(1 << 28); R.bx = R.by = R.bz = 0;
   bool fitted = false;
@@ -413,7 +365,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
   // Sparse: all eight corners handed over on every leave -- 8 instead of ~4 LDS adds per leave, but none of the per-axis
   // blocks, which for rays oblique to the grid all run on every step (measured on the six rotated views: 535 -> 382 VALU
   // instructions per wave-step, 10.5 -> 8.9 ms; on the metric's dense bundles the same choice costs 6.4 -> 8.8 ms).
-  const bool pre = true;
   bool sparse = SPARSE || DRRT_RING_SIMPLE != 0;
   // fixed-point window (SPARSE): scale of the accumulators and of the window, wave-uniform; see above
   float qs = 1.0f, qinv = 1.0f;
@@ -432,7 +383,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
     p00 = f2{p00.x * f, p00.y * f}; p10 = f2{p10.x * f, p10.y * f}; p01 = f2{p01.x * f, p01.y * f}; p11 = f2{p11.x * f, p11.y * f};
     qs = __int_as_float((uni(e_now + de) + 127) << 23); qinv = __int_as_float((uni(-(e_now + de)) + 127) << 23);
     pm_run = 0.f; qset = true; qask = false;
-    QEVENT(3, 1)
   };
   // the wave's largest |accumulator| / hand-over: the order of non-negative floats is the order of their bits
   // (a lane whose values are not finite does not take part: it goes to the grid on its own and must not keep its wave unscaled)
@@ -464,45 +414,40 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
     if constexpr (SPARSE) {
       pm = max3abs(max3abs(p00.x, p00.y, p10.x), max3abs(p10.y, p01.x, p01.y), max3abs(p11.x, p11.y, 0.f));
       const bool okq = qset & (pm < kQGuard);
-      if ((li >= 0) & !okq) { QEVENT(4, 1) }
       qask = qask | ((li >= 0) & !okq & (pm < 3.0e38f));
       li = okq ? li : -1;
     }
     if (li >= 0) {
-      if (experiment != 3) {
-        // the wrap strides -(ny - 1) * sy, -(nz - 1) * sz.  Sparse-only instantiation: two subtractions.  General one (it has
-        // no register for R.tot): as SCALARS -- left to itself the compiler selects the factor per lane and multiplies with
-        // the quarter-rate v_mul_lo_u32
-        const int wY = SPARSE ? R.sy - R.sz : uni(-(R.ny - 1) * R.sy);
-        const int wZ = SPARSE ? R.sz - R.tot : uni(-(R.nz - 1) * R.sz);
-        const int dX = csx == R.nx - 1 ? -(R.nx - 1) : 1;
-        const int dY = csy == R.ny - 1 ? wY : R.sy;
-        const int dZ = csz == R.nz - 1 ? wZ : R.sz;
-        WT* q = win + li;
-        if constexpr (SPARSE) {
-          atomicAdd(q, cvt_rpi_i32(p00.x));             atomicAdd(q + dX, cvt_rpi_i32(p00.y));
-          atomicAdd(q + dY, cvt_rpi_i32(p10.x));        atomicAdd(q + dY + dX, cvt_rpi_i32(p10.y));
-          atomicAdd(q + dZ, cvt_rpi_i32(p01.x));        atomicAdd(q + dZ + dX, cvt_rpi_i32(p01.y));
-          atomicAdd(q + dZ + dY, cvt_rpi_i32(p11.x));   atomicAdd(q + dZ + dY + dX, cvt_rpi_i32(p11.y));
-          pm_run = max_raw(pm_run, pm);
-          qbig = pm >= kQSmall;
-        } else {
-          RING_ADD(q, p00.x);             RING_ADD(q + dX, p00.y);
-          RING_ADD(q + dY, p10.x);        RING_ADD(q + dY + dX, p10.y);
-          RING_ADD(q + dZ, p01.x);        RING_ADD(q + dZ + dX, p01.y);
-          RING_ADD(q + dZ + dY, p11.x);   RING_ADD(q + dZ + dY + dX, p11.y);
-        }
+      // the wrap strides -(ny - 1) * sy, -(nz - 1) * sz.  Sparse-only instantiation: two subtractions.  General one (it has
+      // no register for R.tot): as SCALARS -- left to itself the compiler selects the factor per lane and multiplies with
+      // the quarter-rate v_mul_lo_u32
+      const int wY = SPARSE ? R.sy - R.sz : uni(-(R.ny - 1) * R.sy);
+      const int wZ = SPARSE ? R.sz - R.tot : uni(-(R.nz - 1) * R.sz);
+      const int dX = csx == R.nx - 1 ? -(R.nx - 1) : 1;
+      const int dY = csy == R.ny - 1 ? wY : R.sy;
+      const int dZ = csz == R.nz - 1 ? wZ : R.sz;
+      WT* q = win + li;
+      if constexpr (SPARSE) {
+        atomicAdd(q, cvt_rpi_i32(p00.x));             atomicAdd(q + dX, cvt_rpi_i32(p00.y));
+        atomicAdd(q + dY, cvt_rpi_i32(p10.x));        atomicAdd(q + dY + dX, cvt_rpi_i32(p10.y));
+        atomicAdd(q + dZ, cvt_rpi_i32(p01.x));        atomicAdd(q + dZ + dX, cvt_rpi_i32(p01.y));
+        atomicAdd(q + dZ + dY, cvt_rpi_i32(p11.x));   atomicAdd(q + dZ + dY + dX, cvt_rpi_i32(p11.y));
+        pm_run = max_raw(pm_run, pm);
+        qbig = pm >= kQSmall;
+      } else {
+        atomicAdd(q, (win_t)p00.x);             atomicAdd(q + dX, (win_t)p00.y);
+        atomicAdd(q + dY, (win_t)p10.x);        atomicAdd(q + dY + dX, (win_t)p10.y);
+        atomicAdd(q + dZ, (win_t)p01.x);        atomicAdd(q + dZ + dX, (win_t)p01.y);
+        atomicAdd(q + dZ + dY, (win_t)p11.x);   atomicAdd(q + dZ + dY + dX, (win_t)p11.y);
       }
       return true;
     }
-    if (experiment != 2) {
-      float* g = a.grad + cbase;
-      const float u = SPARSE ? qinv : 1.0f;              // the accumulators of the sparse-only instantiation carry 2^e
-      RING_GADD(g, p00.x * u);                RING_GADD(g + 1, p00.y * u);
-      RING_GADD(g + V.sy, p10.x * u);         RING_GADD(g + V.sy + 1, p10.y * u);
-      RING_GADD(g + V.sz, p01.x * u);         RING_GADD(g + V.sz + 1, p01.y * u);
-      RING_GADD(g + V.sz + V.sy, p11.x * u);  RING_GADD(g + V.sz + V.sy + 1, p11.y * u);
-    }
+    float* g = a.grad + cbase;
+    const float u = SPARSE ? qinv : 1.0f;              // the accumulators of the sparse-only instantiation carry 2^e
+    atomic_add_f32(g, p00.x * u);                atomic_add_f32(g + 1, p00.y * u);
+    atomic_add_f32(g + V.sy, p10.x * u);         atomic_add_f32(g + V.sy + 1, p10.y * u);
+    atomic_add_f32(g + V.sz, p01.x * u);         atomic_add_f32(g + V.sz + 1, p01.y * u);
+    atomic_add_f32(g + V.sz + V.sy, p11.x * u);  atomic_add_f32(g + V.sz + V.sy + 1, p11.y * u);
     return false;
   };
   // (Re-)place every lane in the window; -> lanes next to the window that it still does not hold.  Nobody keeps asking:
@@ -516,7 +461,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
     return ok & (lidx < 0) & nearby;
   };
 
-  STAMP_DECL;
   for (int it = 0; it < it_end; ++it) {
     if (!__any(s.active | pending)) break;                                    // wave-uniform exit
     if (a.fsteps != nullptr) {                                                // step hint (wave-uniform)
@@ -531,7 +475,7 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
       }
       if (it >= a.max_steps) {
         if (s.active & (steps >= (unsigned)a.max_steps)) {
-          if (!kDirect && regular && experiment != 1) { if (emit8(lidx, base, sx, sy, sz)) dirty = true; }
+          if (!kDirect && regular) { if (emit8(lidx, base, sx, sy, sz)) dirty = true; }
           s.active = false;
         }
         // `dirty` guards 64-lane cooperative flushes below: it has to be wave-uniform BEFORE the service of this very
@@ -561,11 +505,10 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
           }
           const unsigned used = ((unsigned)wave_max_dpp(m) >> (DRRT_RING_QBITS + DRRT_RING_QSMALL)) + 1u;
           keep = used < kQBudget / 2u;
-          if (keep) { qbudget = used; pm_run = 0.f; QEVENT(2, 1) }
+          if (keep) { qbudget = used; pm_run = 0.f; }
         }
         if (!keep) {
-          if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, experiment == 2, qinv); dirty = false; ++n_flush; }
-          if (ask) { QEVENT(1, 1) } else { QEVENT(0, 1) }
+          if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, qinv); dirty = false; ++n_flush; }
           qask = ask;
           q_adapt();
         }
@@ -573,12 +516,11 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
     }
     // ---- lanes ahead of (or beside) the window: let it follow them (wave-uniform branch) ----
     const unsigned long long mm = __ballot(s.active & miss);
-    STAMP(0)                                                                  // top of the iteration, step hint
     if (mm != 0ull) {
       const bool ok = s.active & regular;
       const int big = 1 << 28;
       bool settled = false;
-      if (ABL && dbg) ++ev_service;
+      if (DBG && dbg) ++ev_service;
       if (fitted) {
         // Slide along every axis on which lanes are ahead of the window and none is at its rear (or the other way round):
         // the layers every lane has left are flushed and their storage is reused ahead.  Only the lanes in or next to the
@@ -595,8 +537,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
             else    { k = min((R.nx - 2) - wave_max_dpp(cnt ? rel : -big), R.ox); }
             k = uni(min(k, R.nx));
             if (k > 0) {
-              if (hi) { ring_flush<0>(win, R, R.ox, k, a.grad, V, lane, experiment == 2, qinv); R.ox += k; R.bx += k; R.bx = R.bx >= R.nx ? R.bx - R.nx : R.bx; }
-              else    { ring_flush<0>(win, R, R.ox + R.nx - k, k, a.grad, V, lane, experiment == 2, qinv); R.ox -= k; R.bx -= k; R.bx = R.bx < 0 ? R.bx + R.nx : R.bx; }
+              if (hi) { ring_flush<0>(win, R, R.ox, k, a.grad, V, lane, qinv); R.ox += k; R.bx += k; R.bx = R.bx >= R.nx ? R.bx - R.nx : R.bx; }
+              else    { ring_flush<0>(win, R, R.ox + R.nx - k, k, a.grad, V, lane, qinv); R.ox -= k; R.bx -= k; R.bx = R.bx < 0 ? R.bx + R.nx : R.bx; }
               ++n_slide;
             }
           }
@@ -610,8 +552,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
             else    { k = min((R.ny - 2) - wave_max_dpp(cnt ? rel : -big), R.oy); }
             k = uni(min(k, R.ny));
             if (k > 0) {
-              if (hi) { ring_flush<1>(win, R, R.oy, k, a.grad, V, lane, experiment == 2, qinv); R.oy += k; R.by += k; R.by = R.by >= R.ny ? R.by - R.ny : R.by; }
-              else    { ring_flush<1>(win, R, R.oy + R.ny - k, k, a.grad, V, lane, experiment == 2, qinv); R.oy -= k; R.by -= k; R.by = R.by < 0 ? R.by + R.ny : R.by; }
+              if (hi) { ring_flush<1>(win, R, R.oy, k, a.grad, V, lane, qinv); R.oy += k; R.by += k; R.by = R.by >= R.ny ? R.by - R.ny : R.by; }
+              else    { ring_flush<1>(win, R, R.oy + R.ny - k, k, a.grad, V, lane, qinv); R.oy -= k; R.by -= k; R.by = R.by < 0 ? R.by + R.ny : R.by; }
               ++n_slide;
             }
           }
@@ -625,8 +567,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
             else    { k = min((R.nz - 2) - wave_max_dpp(cnt ? rel : -big), R.oz); }
             k = uni(min(k, R.nz));
             if (k > 0) {
-              if (hi) { ring_flush<2>(win, R, R.oz, k, a.grad, V, lane, experiment == 2, qinv); R.oz += k; R.bz += k; R.bz = R.bz >= R.nz ? R.bz - R.nz : R.bz; }
-              else    { ring_flush<2>(win, R, R.oz + R.nz - k, k, a.grad, V, lane, experiment == 2, qinv); R.oz -= k; R.bz -= k; R.bz = R.bz < 0 ? R.bz + R.nz : R.bz; }
+              if (hi) { ring_flush<2>(win, R, R.oz, k, a.grad, V, lane, qinv); R.oz += k; R.bz += k; R.bz = R.bz >= R.nz ? R.bz - R.nz : R.bz; }
+              else    { ring_flush<2>(win, R, R.oz + R.nz - k, k, a.grad, V, lane, qinv); R.oz -= k; R.bz -= k; R.bz = R.bz < 0 ? R.bz + R.nz : R.bz; }
               ++n_slide;
             }
           }
@@ -655,18 +597,18 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
           const bool too_big = uni((int)(ex * ey * ez > kRingCap)) != 0;
           if (too_big && fitted) {
             // the lanes next to the window do not fit any window together: it stays where it is, they go to the grid
-            if (ABL && dbg) ++ev_nofit;
+            if (DBG && dbg) ++ev_nofit;
           } else {
           if (too_big) {
             // no window holds them all: a cube of the capacity around the median lane's cell; the others go to the grid
-            if (ABL && dbg) ++ev_nofit;
+            if (DBG && dbg) ++ev_nofit;
             const int rx = __shfl(ix, ref, kWave), ry = __shfl(iy, ref, kWave), rz = __shfl(iz, ref, kWave);
             const int half = 4;
             x0 = max(x0, rx - half); x1 = min(x1, rx + half); y0 = max(y0, ry - half); y1 = min(y1, ry + half);
             z0 = max(z0, rz - half); z1 = min(z1, rz + half);
             ex = x1 - x0 + 2; ey = y1 - y0 + 2; ez = z1 - z0 + 2;
           }
-          if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, experiment == 2, qinv); dirty = false; ++n_flush; }
+          if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, qinv); dirty = false; ++n_flush; }
           if constexpr (SPARSE) { if (qset) q_adapt(); }     // the window is empty: a chance to re-scale for free
           int nx = ex + DRRT_RING_SLACK_MIN + (int)((float)DRRT_RING_SLACK * fabsf(dx_) * inv_dm + 0.5f);
           int ny = ey + DRRT_RING_SLACK_MIN + (int)((float)DRRT_RING_SLACK * fabsf(dy_) * inv_dm + 0.5f);
@@ -697,14 +639,13 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
           R.ox = uni(ox); R.oy = uni(oy); R.oz = uni(oz);
           R.bx = R.by = R.bz = 0;
           fitted = true; ++n_fit;
-          if (ABL && dbg) ev_vol += (unsigned)(nx * ny * nz);
+          if (DBG && dbg) ev_vol += (unsigned)(nx * ny * nz);
           const bool left = place_all(ok);
-          if (ABL && dbg) ev_left += (unsigned)__popcll(__ballot(left));
+          if (DBG && dbg) ev_left += (unsigned)__popcll(__ballot(left));
           }
         }
       }
     }
-    STAMP(1)                                                                  // window service
     if (!SPARSE && DRRT_RING_SIMPLE == 0 && (it & 15) == 15) {   // a sample of one iteration in 16 (scalar arithmetic only)
       const bool on = s.active & regular;
       const int pb = __builtin_amdgcn_update_dpp(-1, base, 0xB1, 0xF, 0xF, false);   // the pair partner's cell (quad_perm [1,0,3,2])
@@ -712,7 +653,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
       sparse = uni(hits * 100) < uni(lanes * DRRT_RING_DENSE_PCT);
     }
     bool used_lds = false;
-    bool matched = false;                                    // (pair-partner match of this step's crossings: debug counters only)
     if (s.active) {
       if (!interior) taps_set<PAIR>(fetch(V.data, locate(V, s.x, s.y, s.z)), q0, q1);   // boundary cell (clamped neighbours): fetched here, not ahead
       Cell c;
@@ -726,7 +666,7 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
       AdjSample m;
       if (!adj_sample<MODE>(V, a.sdf, a.ds, s, c, taps_of<PAIR>(q0, q1), m)) {
         // the ray has ended (:426-428): hand over what its cell has accumulated
-        if (!kDirect && regular && experiment != 1) used_lds = emit8(lidx, base, sx, sy, sz);
+        if (!kDirect && regular) used_lds = emit8(lidx, base, sx, sy, sz);
       } else {
         ++steps;
         const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);                            // :430
@@ -737,7 +677,7 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
           const CornerPairs cp = splat_weights_pk(wx, wy, wz, (dn * a.ds) * u, ndq * s.mx, ndq * s.my, ndq * s.mz);   // :431-432
           if (kDirect) { p00 = cp.c00; p10 = cp.c10; p01 = cp.c01; p11 = cp.c11; used_lds = emit8(lidx, base, sx, sy, sz); }
           else { p00 += cp.c00; p10 += cp.c10; p01 += cp.c01; p11 += cp.c11; }
-        } else if (experiment != 2 && experiment != 1) {
+        } else {
           const Cell cb = locate(V, px, py, pz);
           const Corners w = splat_weights(cb.wx, cb.wy, cb.wz, dn * a.ds, nds * s.mx, nds * s.my, nds * s.mz);
           float* g = a.grad + cb.base;
@@ -746,7 +686,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
           atomic_add_f32(g + cb.oz, w.c001);             atomic_add_f32(g + cb.oz + cb.ox, w.c101);
           atomic_add_f32(g + cb.oz + cb.oy, w.c011);     atomic_add_f32(g + cb.oz + cb.oy + cb.ox, w.c111);
         }
-        STAMP(2)                                             // sample (waits for the taps), weights, accumulate
         const int old_base = base, old_lidx = lidx;
         const bool old_regular = regular;
         int nbase; bool nregular;
@@ -769,7 +708,6 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
         s.ly = fmaf(a.ds, fmaf(dn, m.gy, m.n * hmy), s.ly);
         s.lz = fmaf(a.ds, fmaf(dn, m.gz, m.n * hmz), s.lz);
         s.mx = fmaf(a.ds, s.lx, s.mx); s.my = fmaf(a.ds, s.ly, s.my); s.mz = fmaf(a.ds, s.lz, s.mz);
-        STAMP(3)                                             // step, locate, gather issue, lambda / mu
         // ---- the ray leaves its cell ----
         if (nbase != old_base || !interior) {
           base = nbase; regular = nregular;
@@ -778,10 +716,10 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
             if (old_regular) {
               const bool unit = dpack >= 0;
               const int ddx = (dpack & 3) - 1, ddy = ((dpack >> 2) & 3) - 1, ddz = ((dpack >> 4) & 3) - 1;
-              if (!SPARSE && !sparse && (regular & unit & (old_lidx >= 0) & (experiment != 1) & (experiment != 4))) {
+              if (!SPARSE && !sparse && (regular & unit & (old_lidx >= 0))) {
                 // one, two or three faces crossed: one crossing after the other (x, y, z), each emits the face left behind
                 // and carries the shared one; the later ones hand over zeros where the earlier ones cleared
-                if (ABL && dbg) {
+                if (DBG && dbg) {
                   const int nax = (__ballot(ddx != 0) != 0ull) + (__ballot(ddy != 0) != 0ull) + (__ballot(ddz != 0) != 0ull);
                   if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
                   if (sparse) ++ev_nopre;
@@ -793,8 +731,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
                   const float e0 = fwd ? p00.x : p00.y, e1 = fwd ? p10.x : p10.y, e2 = fwd ? p01.x : p01.y, e3 = fwd ? p11.x : p11.y;
                   p00 = fwd ? f2{p00.y, 0.f} : f2{0.f, p00.x}; p10 = fwd ? f2{p10.y, 0.f} : f2{0.f, p10.x};
                   p01 = fwd ? f2{p01.y, 0.f} : f2{0.f, p01.x}; p11 = fwd ? f2{p11.y, 0.f} : f2{0.f, p11.x};
-                  out |= ring_cross<ABL, WT>(win, experiment, pre, 0, fwd, cur, sx, sy, sz, R.nx, R.ny, R.nz, 1, R.sy, R.sz, ix, R.ox,
-                                         e0, e1, e2, e3, matched, ev_face, ev_add, dbg);
+                  out |= ring_cross<DBG, WT>(win, 0, fwd, cur, sx, sy, sz, R.nx, R.ny, R.nz, 1, R.sy, R.sz, ix, R.ox,
+                                         e0, e1, e2, e3, ev_face, ev_add, dbg);
                 }
                 if (ddy != 0) {
                   const bool fwd = ddy > 0;
@@ -802,8 +740,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
                   const f2 ka = fwd ? p10 : p00, kb = fwd ? p11 : p01;
                   p00 = fwd ? ka : f2{0.f, 0.f}; p01 = fwd ? kb : f2{0.f, 0.f};
                   p10 = fwd ? f2{0.f, 0.f} : ka; p11 = fwd ? f2{0.f, 0.f} : kb;
-                  out |= ring_cross<ABL, WT>(win, experiment, pre, 1, fwd, cur, sy, sx, sz, R.ny, R.nx, R.nz, R.sy, 1, R.sz, iy, R.oy,
-                                         ea.x, ea.y, eb.x, eb.y, matched, ev_face, ev_add, dbg);
+                  out |= ring_cross<DBG, WT>(win, 1, fwd, cur, sy, sx, sz, R.ny, R.nx, R.nz, R.sy, 1, R.sz, iy, R.oy,
+                                         ea.x, ea.y, eb.x, eb.y, ev_face, ev_add, dbg);
                 }
                 if (ddz != 0) {
                   const bool fwd = ddz > 0;
@@ -811,8 +749,8 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
                   const f2 ka = fwd ? p01 : p00, kb = fwd ? p11 : p10;
                   p00 = fwd ? ka : f2{0.f, 0.f}; p10 = fwd ? kb : f2{0.f, 0.f};
                   p01 = fwd ? f2{0.f, 0.f} : ka; p11 = fwd ? f2{0.f, 0.f} : kb;
-                  out |= ring_cross<ABL, WT>(win, experiment, pre, 2, fwd, cur, sz, sx, sy, R.nz, R.nx, R.ny, R.sz, 1, R.sy, iz, R.oz,
-                                         ea.x, ea.y, eb.x, eb.y, matched, ev_face, ev_add, dbg);
+                  out |= ring_cross<DBG, WT>(win, 2, fwd, cur, sz, sx, sy, R.nz, R.nx, R.ny, R.sz, 1, R.sy, iz, R.oz,
+                                         ea.x, ea.y, eb.x, eb.y, ev_face, ev_add, dbg);
                 }
                 used_lds = true;
                 lidx = out ? -1 : cur;                   // stepped ahead of the window by one cell: ask it to follow
@@ -820,9 +758,9 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
                 relocate = false;
               } else {
                 // out of a cell the window does not hold, into or out of a clamped cell, a jump over more than one cell: all eight
-                if (ABL && dbg) { ++ev_all8; ev_all8g += old_lidx < 0; }
+                if (DBG && dbg) { ++ev_all8; ev_all8g += old_lidx < 0; }
                 if (!kDirect) {
-                  if (experiment != 1) used_lds = emit8(old_lidx, old_base, sx, sy, sz);
+                  used_lds = emit8(old_lidx, old_base, sx, sy, sz);
                   p00 = p10 = p01 = p11 = f2{0.f, 0.f};
                 }
               }
@@ -836,25 +774,21 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
         }
       }
     }
-    STAMP(4)                                                 // leave: hand-over, new slot
     {
       const unsigned long long ul = __ballot(used_lds);
       dirty = dirty | (ul != 0ull);
       if constexpr (SPARSE) {
-        QEVENT(5, qbig ? 1 : 0)
         qbudget += (unsigned)__popcll(ul) + 3u * (unsigned)__popcll(__ballot(used_lds & qbig));
         qbig = false;
       }
     }
-    if (ABL && dbg) ev_wsteps += lane == 0;
+    if (DBG && dbg) ev_wsteps += lane == 0;
   }
-  STAMP(5)
-  STAMP_END
   // rays still marching when max_steps ran out keep what their cell has accumulated: hand it over
-  if (!kDirect && s.active && regular && experiment != 1) { if (emit8(lidx, base, sx, sy, sz)) dirty = true; }
+  if (!kDirect && s.active && regular) { if (emit8(lidx, base, sx, sy, sz)) dirty = true; }
   dirty = __ballot(dirty) != 0ull;
-  if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, experiment == 2, qinv); ++n_flush; }
-  if (ABL && dbg) {
+  if (dirty) { ring_flush<2>(win, R, R.oz, R.nz, a.grad, V, lane, qinv); ++n_flush; }
+  if (DBG && dbg) {
     if (lane == 0) { atomicAdd(&a.dbg[0], (unsigned long long)n_flush); atomicAdd(&a.dbg[1], (unsigned long long)n_slide);
                      atomicAdd(&a.dbg[2], (unsigned long long)n_fit); atomicAdd(&a.dbg[3], 1ull); }
     if (ev_face) atomicAdd(&a.dbg[4], (unsigned long long)ev_face);
@@ -874,52 +808,23 @@ __global__ void __launch_bounds__(kAdjBlock, SPARSE ? DRRT_RING_SPARSE_WAVES : D
   block_stats<kAdjBlock>(a.stats, steps, 0u);
 }
 
-// ---- launcher -----------------------------------------------------------------------------------
+// ---- launchers ----------------------------------------------------------------------------------
+// PAIR follows the call's pair grid; the other parameters are the launcher's choice
+template <bool DBG, int MODE, bool SPARSE = false, bool DIRECT = false>
+static void launch_ring(const BackArgs& a, hipStream_t s) {
+  const dim3 g(adj_grid_for(a.n)), b(kAdjBlock);
+  if (a.vol.pair != nullptr) hipLaunchKernelGGL((k_backtrace_ring<DBG, true, MODE, SPARSE, DIRECT>), g, b, 0, s, a);
+  else                       hipLaunchKernelGGL((k_backtrace_ring<DBG, false, MODE, SPARSE, DIRECT>), g, b, 0, s, a);
+}
 // backtrace only (MODE 0).  which: 0 = the accumulating instantiation, 1 = the direct one, 2 = both (classified call: one returns)
 void launch_backtrace_ring_sparse(const BackArgs& a, hipStream_t s, int which) {
-  const dim3 g(adj_grid_for(a.n)), b(kAdjBlock);
-  const bool pair = a.vol.pair != nullptr;
-  if (which != 1) {
-    if (pair) hipLaunchKernelGGL((k_backtrace_ring<false, true, 0, true, false>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_ring<false, false, 0, true, false>), g, b, 0, s, a);
-  }
-  if (which != 0) {
-    if (pair) hipLaunchKernelGGL((k_backtrace_ring<false, true, 0, true, true>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_ring<false, false, 0, true, true>), g, b, 0, s, a);
-  }
+  if (which != 1) launch_ring<false, 0, true, false>(a, s);
+  if (which != 0) launch_ring<false, 0, true, true>(a, s);
 }
-void launch_backtrace_ring(int mode, bool abl, const BackArgs& a, hipStream_t s) {
-  const dim3 g(adj_grid_for(a.n)), b(kAdjBlock);
-  const bool pair = a.vol.pair != nullptr;
-  if (mode == 1) {
-    if (pair) hipLaunchKernelGGL((k_backtrace_ring<false, true, 1>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_ring<false, false, 1>), g, b, 0, s, a);
-  } else if (abl) {
-    if (pair) hipLaunchKernelGGL((k_backtrace_ring<true, true, 0>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_ring<true, false, 0>), g, b, 0, s, a);
-  } else {
-    if (pair) hipLaunchKernelGGL((k_backtrace_ring<false, true, 0>), g, b, 0, s, a);
-    else      hipLaunchKernelGGL((k_backtrace_ring<false, false, 0>), g, b, 0, s, a);
-  }
+void launch_backtrace_ring(int mode, bool dbg, const BackArgs& a, hipStream_t s) {
+  if (mode == 1) launch_ring<false, 1>(a, s);
+  else if (dbg)  launch_ring<true, 0>(a, s);
+  else           launch_ring<false, 0>(a, s);
 }
 
 }  // namespace drrt
-
-#if defined(DRRT_RING_STAMPS)
-extern "C" __attribute__((visibility("default"))) int drrt_debug_ring_events(unsigned long long* out8, int reset) {
-  if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(drrt::g_ring_events), sizeof(drrt::g_ring_events)) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(drrt::g_ring_events), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-extern "C" __attribute__((visibility("default"))) int drrt_debug_ring_stamps(unsigned long long* out8, int reset) {
-  if (out8 && hipMemcpyFromSymbol(out8, HIP_SYMBOL(drrt::g_ring_stamps), sizeof(drrt::g_ring_stamps)) != hipSuccess) return -1;
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    if (hipMemcpyToSymbol(HIP_SYMBOL(drrt::g_ring_stamps), z, sizeof(z)) != hipSuccess) return -1;
-  }
-  return 0;
-}
-#endif

@@ -427,6 +427,38 @@ __global__ void k_chunk_progress_init(int* p) {
 }
 }  // namespace drrt
 
+// Which adjoint kernels a call launches; run_backtrace launches them in the order classify, ring, box.
+struct BackPlan {
+  bool direct = false;        // the one-atomic-per-tap kernel, nothing else
+  bool classify = false;      // k_bundle_classify first: the windowed kernels launched after it return unless its counters pick them
+  bool ring_general = false;  // k_backtrace_ring, general instantiation (a classified call pins the classification to it)
+  int ring_sparse = -1;       // the sparse-only instantiations (launch_backtrace_ring_sparse's `which`), -1: none
+  bool box = false;           // k_backtrace_flat
+};
+static BackPlan plan_backtrace(int mode, unsigned flags, bool chunk, bool dbg, bool classifiable) {
+  BackPlan p;
+  // DRRT_FLAG_DIRECT_ATOMICS: the kernel every windowed one is cross-checked against
+  if (flags & DRRT_FLAG_DIRECT_ATOMICS) { p.direct = true; return p; }
+  // DRRT_FLAG_RING_WINDOW forces the ring kernel (A-B; not for chunks): sparse-only with DRRT_FLAG_RING_SPARSE (direct with
+  // DRRT_FLAG_RING_DIRECT) where that exists -- backtrace without counters --, general otherwise
+  if ((flags & DRRT_FLAG_RING_WINDOW) && !chunk) {
+    if ((flags & DRRT_FLAG_RING_SPARSE) && mode == 0 && !dbg) p.ring_sparse = (flags & DRRT_FLAG_RING_DIRECT) ? 1 : 0;
+    else p.ring_general = true;
+    return p;
+  }
+  // the box-window kernel (compile-time 9^3 window, for compact bundles) only: DRRT_FLAG_STATIC_WINDOW (A-B), chunks, and
+  // calls without a visit order or without the 512-byte counter block at the end of a drrt_workspace_bytes_grid() workspace
+  p.box = true;
+  if ((flags & DRRT_FLAG_STATIC_WINDOW) || chunk || !classifiable) return p;
+  // otherwise the bundles are classified on the device and BOTH windowed kernels are launched (no host round trip); the
+  // ring kernel (fitted ring window, step hint) in its sparse-only instantiations unless the call is backtrace_sdf, the
+  // debug-counter build or DRRT_FLAG_RING_GENERAL (A-B), which only the general one serves
+  p.classify = true;
+  if (mode == 0 && !dbg && !(flags & DRRT_FLAG_RING_GENERAL)) p.ring_sparse = 2;
+  else p.ring_general = true;
+  return p;
+}
+
 template <int MODE>
 static int run_backtrace(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
                          const void* xt, const void* vt, const void* dx, const void* dv,
@@ -441,6 +473,8 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
   rc = check_steps(h, ds); if (rc) return rc;
   if (!grad) return fail(DRRT_ERR_ARG, "null grad pointer");
   if (MODE == 1 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
+  const unsigned ablation = (flags >> 8) & 0xffu;
+  if (ablation > 1u) return fail(DRRT_ERR_ARG, "flags: bits 8..15 must be 0, or 1 (no adjoint launch)");
   const bool first_chunk = ck == nullptr || ck->it_begin == 0;
   if (ck != nullptr) {
     if (ck->it_begin < 0) return fail(DRRT_ERR_ARG, "chunk: it_begin must be >= 0");
@@ -459,6 +493,7 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
   if (n == 0) return DRRT_OK;
   if (!xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  if (ablation == 1u) return DRRT_OK;       // the gradient stays zero: bench.py's parity check must fail on it
   rc = maybe_sort(a.vol, h, n, xt, vt, -1.f, flags, ws, ws_bytes, &a.perm, s, hint, io_half); if (rc) return rc;
   rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
   a.io_half = io_half;
@@ -473,7 +508,6 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
     if (ck->progress) { hipLaunchKernelGGL(drrt::k_chunk_progress_init, dim3(1), dim3(64), 0, s, ck->progress); LAUNCH_CHECK("k_chunk_progress_init"); }
   }
   a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
-  a.experiment = (int)((flags >> 8) & 0xffu);
   a.fsteps = (hint.steps && hint.steps_n == n) ? hint.steps : nullptr;
   a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
   a.dbg = nullptr;
@@ -483,39 +517,26 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
     hipError_t e = hipMemsetAsync(a.dbg, 0, 512, s);
     if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(dbg)");
   }
+  const size_t ctr_off = (drrt_workspace_bytes(n, flags) + ((flags & DRRT_FLAG_PAIR_GRID) ? (size_t)nvox * 2 * sizeof(float) : 0) + 7) & ~(size_t)7;
+  const bool dbg = a.dbg != nullptr;
+  const BackPlan p = plan_backtrace(MODE, flags, ck != nullptr, dbg, a.perm != nullptr && ws && ws_bytes >= ctr_off + 512);
   {
     ProfScope prof(DRRT_PROF_BACKTRACE, s);
-    if (flags & DRRT_FLAG_DIRECT_ATOMICS)
-      launch_backtrace_direct(MODE, a, s);
-    else {
-      const bool abl = a.experiment != 0 || a.dbg != nullptr;
-      // Two kernels: k_backtrace_flat with its compile-time 9^3 box window for compact bundles, k_backtrace_ring (fitted ring
-      // window, step hint) for the rest.  With a visit order the bundles are classified on the device and BOTH are launched;
-      // the one the counters do not pick returns at once (no host round trip).  Needs the 512-byte counter block at the end
-      // of a drrt_workspace_bytes_grid() workspace; without it, or without an order, the box-window kernel runs.
-      // DRRT_FLAG_STATIC_WINDOW / DRRT_FLAG_RING_WINDOW force one of the two (A-B).
-      a.select = nullptr;
-      const size_t ctr_off = (drrt_workspace_bytes(n, flags) + ((flags & DRRT_FLAG_PAIR_GRID) ? (size_t)nvox * 2 * sizeof(float) : 0) + 7) & ~(size_t)7;
-      const bool force_box = (flags & DRRT_FLAG_STATIC_WINDOW) != 0 || a.experiment == 7 || ck != nullptr;   // chunks: box-window kernel only
-      const bool force_ring = (flags & DRRT_FLAG_RING_WINDOW) != 0 && ck == nullptr;
-      if (!force_box && !force_ring && a.perm != nullptr && ws && ws_bytes >= ctr_off + 512) {
-        a.select = (unsigned*)((char*)ws + ctr_off + 256);
-        g_last_counters = a.select;
-        hipError_t e = hipMemsetAsync(a.select, 0, 32, s);
+    if (p.direct) launch_backtrace_direct(MODE, a, s);
+    if (p.classify) {
+      a.select = (unsigned*)((char*)ws + ctr_off + 256);
+      g_last_counters = a.select;
+      hipError_t e = hipMemsetAsync(a.select, 0, 32, s);
+      if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(select)");
+      if (p.ring_general) {        // [5] != 0: the classification picks the general ring instantiation, never a sparse-only one
+        e = hipMemsetAsync((char*)a.select + 20, 1, 1, s);
         if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(select)");
-        // [5] != 0 pins the general instantiation of the ring kernel: backtrace_sdf, the ablation / counter build and
-        // DRRT_FLAG_RING_GENERAL (A-B) have no sparse-only one
-        const bool sparse_ok = MODE == 0 && !abl && !(flags & DRRT_FLAG_RING_GENERAL);
-        if (!sparse_ok) { e = hipMemsetAsync((char*)a.select + 20, 1, 1, s); if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(select)"); }
-        launch_bundle_classify(a, s);
-        if (sparse_ok) launch_backtrace_ring_sparse(a, s, 2);    // (the classification never picks the general one then)
-        else launch_backtrace_ring(MODE, abl, a, s);
       }
-      if (!force_ring) launch_backtrace_box(MODE, abl, a, s);
-      if (force_ring && (flags & DRRT_FLAG_RING_SPARSE) && MODE == 0 && !abl)
-        launch_backtrace_ring_sparse(a, s, (flags & DRRT_FLAG_RING_DIRECT) ? 1 : 0);
-      else if (force_ring) launch_backtrace_ring(MODE, abl, a, s);
+      launch_bundle_classify(a, s);
     }
+    if (p.ring_general) launch_backtrace_ring(MODE, dbg, a, s);
+    if (p.ring_sparse >= 0) launch_backtrace_ring_sparse(a, s, p.ring_sparse);
+    if (p.box) launch_backtrace_box(MODE, dbg, a, s);
   }
   LAUNCH_CHECK("k_backtrace");
   return DRRT_OK;

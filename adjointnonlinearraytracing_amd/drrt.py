@@ -119,12 +119,7 @@ def _flags(adjoint: bool = False) -> int:
         f |= _lib.FLAG_RING_GENERAL
     if _opt().chord_key:
         f |= _lib.FLAG_CHORD_KEY
-    if adjoint and _EXPERIMENT:
-        f |= (_EXPERIMENT & 0xFF) << 8          # development ablations of the adjoint kernel (include/drrt_hip.h)
     return f
-
-
-_EXPERIMENT = 0
 
 
 def _workspace(n: int, flags: int, device: torch.device, nvox: int = 0) -> torch.Tensor:

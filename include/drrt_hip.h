@@ -105,7 +105,9 @@ extern "C" {
                                        atomics (cell outside the window), [7] leaves that handed over
                                        all eight corners, [8] wave-steps, [9] wave-steps whose one-face
                                        leaves cross two or three different axes.
-                                       Bits 8..15 of `flags` select development ablations (0 = product) */
+                                       Bits 8..15 of `flags` (backtrace*): 0, or 1 = zero `grad` and `stats`
+                                       and launch no adjoint (a known-wrong result, for the benchmark's parity
+                                       test); any other value is refused with DRRT_ERR_ARG */
 
 /* Limits (violations are refused with DRRT_ERR_ARG and a message, never truncated silently):
  *   grid      fewer than 2^29 voxels (2 GiB of fp32), each extent and res[0]*res[1] below 2^24

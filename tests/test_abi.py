@@ -140,6 +140,19 @@ def test_order_hint_never_outlives_one_call(lib):
     assert h.drrt_order_hint_pending() == 0
 
 
+
+def test_backtrace_refuses_unknown_ablation_ids(lib):
+    """Bits 8..15 of an adjoint call's flags take 0 or 1 only (include/drrt_hip.h); any other id is refused before any
+    HIP call, so this runs without a GPU."""
+    import ctypes as C
+    h = lib.load()
+    res = (C.c_int * 3)(4, 4, 4)
+    one = C.c_void_p(0x1000)                    # non-null stand-ins, never dereferenced
+    for ablation in (2, 7, 0xff):
+        assert h.drrt_backtrace_f32(one, 64, res, 128, one, one, one, one, 1.0, 0.5, one, None, None, 0,
+                                    ablation << 8, None) == lib.ERR_ARG
+        assert "bits 8..15" in h.drrt_last_error().decode()
+
 def test_q16_params_host_side(lib):
     """drrt_q16_params is host-only: q_min = -E/16, q_step = 1.125 E / 65535 with E the largest box extent, 2^-14."""
     import ctypes as C
