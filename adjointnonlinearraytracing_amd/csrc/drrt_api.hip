@@ -549,6 +549,37 @@ extern "C" int drrt_backtrace_f32(const float* rif, long long nvox, const int re
   return run_backtrace<0>(rif, nullptr, nvox, res, n, xt, vt, dx, dv, h, ds, grad, stats, ws, ws_bytes, flags, stream);
 }
 
+extern "C" int drrt_backtrace_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                       const float* pos, const float* vel, const float* xt, const float* vt,
+                                       const uint32_t* fwd_steps, const float* dx, const float* dv, float h, float ds,
+                                       float* dpos, float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes,
+                                       unsigned flags, void* stream) {
+  const OrderHint hint = take_hint();
+  g_err[0] = 0;
+  hipStream_t s = (hipStream_t)stream;
+  RayGradArgs a{};
+  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
+  rc = check_steps(h, ds); if (rc) return rc;
+  rc = zero_stats(stats, s); if (rc) return rc;
+  if (n == 0) return DRRT_OK;
+  if (!pos || !vel || !xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's drrt_last_steps())");
+  if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
+  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  rc = maybe_sort(a.vol, h, n, xt, vt, -1.f, flags, ws, ws_bytes, &a.perm, s, hint); if (rc) return rc;
+  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
+  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.fsteps = fwd_steps; a.dx = dx; a.dv = dv;
+  a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
+  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
+  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
+  {
+    ProfScope prof(DRRT_PROF_BACKTRACE_RAYS, s);
+    launch_backtrace_rays(a, s);
+  }
+  LAUNCH_CHECK("k_backtrace_rays");
+  return DRRT_OK;
+}
+
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }
 extern "C" int drrt_backtrace_max_steps(const int res[3], float h, float ds) {
   if (!res || !(h > 0.f) || !(ds > 0.f)) return -1;

@@ -466,14 +466,10 @@ DRRT_HD bool adj_sample(const Vol& V, const float* __restrict__ sdf, float ds, A
   return adj_sample_st<MODE>(V, sdf, ds, s, c, t, m, t, false);
 }
 
-// Second half (:430-435), for a ray that is still active: its contribution `w` to dL/dn at the 8 taps of `c`, then
-// the lambda / mu recurrences.  Nothing here feeds the next sample's position.
-DRRT_HD void adj_contrib(const Vol& V, float ds, float grad_scale, AdjState& s, const Cell& c, const AdjSample& m,
-                         Corners& w) {
+// The lambda / mu recurrences of one adjoint iteration (:434-435), dn = mu . grad n: the exact transpose of the forward
+// step's Jacobian (d(n grad n)/dx = grad n grad n^T + n H, H the mixed partials, Q10).
+DRRT_HD void adj_recur(const Vol& V, float ds, AdjState& s, const AdjSample& m, float dn) {
   const float n = m.n, gx = m.gx, gy = m.gy, gz = m.gz;
-  const float dn = dot3(s.mx, s.my, s.mz, gx, gy, gz);                                  // :430
-  const float nds = (n * ds) * grad_scale;
-  w = splat_weights(c.wx, c.wy, c.wz, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);     // :431-432
   // la += ds*(dn*grad n + n*H*mu), H = mixed partials / h^2, zero diagonal (:434, Q10)
   const float hxy = m.hxy * V.inv_h2, hxz = m.hxz * V.inv_h2, hyz = m.hyz * V.inv_h2;
   const float hmx = fmaf(hxz, s.mz, hxy * s.my);
@@ -483,6 +479,17 @@ DRRT_HD void adj_contrib(const Vol& V, float ds, float grad_scale, AdjState& s, 
   s.ly = fmaf(ds, fmaf(dn, gy, n * hmy), s.ly);
   s.lz = fmaf(ds, fmaf(dn, gz, n * hmz), s.lz);
   s.mx = fmaf(ds, s.lx, s.mx); s.my = fmaf(ds, s.ly, s.my); s.mz = fmaf(ds, s.lz, s.mz);   // :435
+}
+
+// Second half (:430-435), for a ray that is still active: its contribution `w` to dL/dn at the 8 taps of `c`, then
+// the lambda / mu recurrences.  Nothing here feeds the next sample's position.
+DRRT_HD void adj_contrib(const Vol& V, float ds, float grad_scale, AdjState& s, const Cell& c, const AdjSample& m,
+                         Corners& w) {
+  const float n = m.n, gx = m.gx, gy = m.gy, gz = m.gz;
+  const float dn = dot3(s.mx, s.my, s.mz, gx, gy, gz);                                  // :430
+  const float nds = (n * ds) * grad_scale;
+  w = splat_weights(c.wx, c.wy, c.wz, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);     // :431-432
+  adj_recur(V, ds, s, m, dn);
 }
 
 template <int MODE>   // 0 = backtrace, 1 = backtrace_sdf
@@ -727,6 +734,68 @@ DRRT_HD unsigned backtrace_ray(const Vol& V, const float* __restrict__ sdf, floa
     sink(c, w);
   }
   return steps;
+}
+
+// Ray-state adjoint of trace for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the exit ray (xt, vt), given
+// the forward's inputs (p0, v0) and its iteration count K (drrt_last_steps).  No contribution to dL/dn is formed.
+// The forward samples n only while the ray is inside (Q4), so a ray that starts outside flies straight for e
+// iterations first (x_e = x0 + e ds v0) and is refracted by the samples at x_e .. x_{K-1}: K - e iterations.
+//   * K >= max_steps (the forward's Q5 bound): the ray failed (vt is the stale v0, Q6) -> zero gradient, failed = true.
+//     A ray that exits on exactly the last allowed iteration looks the same and is treated the same.
+//   * the prefix is replayed from (p0, v0) with the forward's own operations; no in-box sample among x_0 .. x_{K-1}:
+//     the ray never entered, (xt, vt) = (p0, v0) and the gradient is the identity (dx, dv).
+//   * otherwise K - e reverse iterations from (xt, vt) seeded like adj_init (lambda = dx, mu = dv + ds dx), with
+//     neither the backward-escape test nor the adjoint's own step bound; after the last one lambda = dL/dx_e and the
+//     mu it was updated from is dL/dv_e, so dpos = lambda and dvel = mu_prev + (e ds) lambda.  The last reverse
+//     iteration samples at the replayed x_e itself instead of its reconstruction x_{e+1} - ds v_{e+1}: a ray that
+//     starts on a face (x_e on the box boundary, where grad n jumps) would otherwise be sampled a rounding error
+//     outside it.
+// The 1/h of DRRT_FLAG_CORRECTED_H scales only the splat into the grid (Q3): it does not enter here.
+// `taps(c)` returns the 8 taps of cell c (the caller chooses how they are fetched; the floats are the grid's).
+struct RayGrad { float dp[3], dv[3]; unsigned steps; bool failed; };
+
+template <typename TapFn>
+DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsigned K, const float p0[3],
+                                    const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                    const float dv[3], TapFn&& taps) {
+  RayGrad g;
+  g.steps = 0; g.failed = false;
+  if (max_steps <= 0 || K >= (unsigned)max_steps) {
+    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    g.failed = true;
+    return g;
+  }
+  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
+  float px = p0[0], py = p0[1], pz = p0[2];
+  unsigned e = 0;
+  while (e < K && !inbounds(V, px, py, pz)) {
+    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
+    ++e;
+  }
+  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  for (unsigned k = K; k > e; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
+    const Cell c = locate(V, s.x, s.y, s.z);
+    AdjSample m;
+    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
+    const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);           // :430
+    qx = s.mx; qy = s.my; qz = s.mz;
+    adj_recur(V, ds, s, m, dn);
+  }
+  const float eds = (float)e * ds;
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
+  g.steps = K - e;
+  return g;
 }
 
 // trace_cable for ONE ray (src/tracer.cpp:312-382)

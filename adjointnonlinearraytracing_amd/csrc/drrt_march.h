@@ -7,6 +7,7 @@
 //                           classification, the one-atomic-per-tap cross-check kernel
 //   drrt_adjoint_ring.hip   backtrace / backtrace_sdf, fitted ring window (its own translation unit: it is built with a
 //                           different instruction-scheduling strategy, csrc/Makefile)
+//   drrt_adjoint_rays.hip   backtrace_rays: dL/dpos, dL/dvel of trace (ray-state adjoint, no grid writes)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
 //
@@ -389,6 +390,25 @@ __device__ __forceinline__ bool bundles_want_direct(const unsigned* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
+// ray-state adjoint of trace (drrt_adjoint_rays.hip): dL/dpos, dL/dvel, no contribution to dL/dn.  Its own argument
+// block: BackArgs keeps the field offsets the measured adjoint kernels were compiled against.
+// ---------------------------------------------------------------------------------------------
+struct RayGradArgs {
+  Vol vol;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const uint32_t* fsteps;                   // its per-ray iteration counts (drrt_last_steps), caller ray order
+  const float* dx; const float* dv;
+  float* dpos; float* dvel;
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
+// ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
 // of the gradient profile (ds_add_f64) and flushes it once per block -- millions of rays would
@@ -417,6 +437,8 @@ void launch_bundle_classify(const BackArgs& a, hipStream_t s);
 void launch_backtrace_box(int mode, bool dbg, const BackArgs& a, hipStream_t s);
 void launch_backtrace_ring(int mode, bool dbg, const BackArgs& a, hipStream_t s);
 void launch_backtrace_ring_sparse(const BackArgs& a, hipStream_t s, int which);   // the sparse-only instantiations (backtrace)
+// ray-state adjoint (drrt_adjoint_rays.hip)
+void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

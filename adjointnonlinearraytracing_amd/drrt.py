@@ -89,6 +89,10 @@ last_stats: Optional[torch.Tensor] = None
 # ctx, dist.ShardedBackTracerC -- take a private copy with keep_order().  Handed to the paired backtrace
 # (drrt_set_order_hint) the adjoint visits rays in the forward's bundle order (include/drrt_hip.h, "visit order hand-over").
 last_order: Optional[torch.Tensor] = None
+# Per-ray iteration counts (int32, caller ray order) of the last trace / trace_pln call, whether or not it sorted: a
+# workspace VIEW with the same lifetime rules as `last_order` (keep_steps() takes the private copy).  The ray-state
+# adjoint (TracerC.backtrace_rays) needs them.
+last_steps: Optional[torch.Tensor] = None
 _order_gen: Dict[tuple, int] = {}            # per workspace key: how often its order / state region has been rewritten
 
 # one scratch buffer per (device, stream): calls queued on different streams must not share scratch
@@ -291,6 +295,28 @@ def _capture_order(n: int, device: torch.device) -> None:
             last_order.drrt_steps = ws[off_s:off_s + 4 * n].view(torch.int32)
 
 
+def _capture_steps(n: int, device: torch.device) -> None:
+    """Hand out the per-ray iteration counts the forward march just left in the workspace (a view) -> `last_steps`."""
+    global last_steps
+    last_steps = None
+    cnt = C.c_size_t(0)
+    ptr = _lib.load().drrt_last_steps(C.byref(cnt))
+    if not ptr or cnt.value != n:
+        return
+    key = _wkey(device)
+    ws = _workspaces[key]
+    off = int(ptr) - ws.data_ptr()
+    if 0 <= off and off + 4 * n <= ws.numel():
+        last_steps = ws[off:off + 4 * n].view(torch.int32)
+        last_steps.drrt_gen = (key, _order_gen.get(key, 0))
+
+
+def keep_steps(steps: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """A private copy of `last_steps` that stays valid whatever is called next; None for a stale or missing view."""
+    steps = _valid_order(steps)
+    return None if steps is None else steps.clone()
+
+
 def keep_order(order: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
     """A private copy of a visit order (with its iteration counts) that stays valid whatever is called next; None for a
     stale or missing order.  For holders that keep the order across other tracer calls (autograd ctx)."""
@@ -476,6 +502,7 @@ class TracerC:
                 _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), float(h), float(ds),
                 _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
             _capture_order(n, dev)
+            _capture_steps(n, dev)
             _warn_failed(st)
         return xt, vt
 
@@ -496,6 +523,7 @@ class TracerC:
                 float(h), float(ds), _p(xt), _p(vt), _p(fm), _p(st), _p(ws), ws.numel(), fl,
                 _stream(dev)))
             _capture_order(n, dev)
+            _capture_steps(n, dev)
             _warn_failed(st)
         return xt, vt, fm
 
@@ -587,6 +615,38 @@ class TracerC:
             finally:
                 _clear_hint()
         return grad
+
+    def backtrace_rays(self, rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds,
+                       order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ray-state adjoint of ``trace`` (drrt_backtrace_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel), (n,3) fp32.
+        `pos`, `vel` are the forward call's inputs, `xt`, `vt` its outputs and `steps` its per-ray iteration counts
+        (``keep_steps(last_steps)`` right after it); `dx`, `dv` the seeds on (xt, vt).  Rays that failed the forward get a
+        zero gradient (and the "failed to exit all rays" message).  Not in the reference's C++ Tracer: its ADTracerC gets
+        these through enoki autodiff (core/tracer.py:16-66).  fp32 rays only."""
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            order = _valid_order(order)
+            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
+            n = pos_.shape[0]
+            vel_, xt_, vt_ = _rays(vel, dev, n), _rays(xt, dev, n), _rays(vt, dev, n)
+            dx_, dv_ = _rays(dx, dev, n), _rays(dv, dev, n)
+            steps_ = steps.detach().to(device=dev).contiguous()
+            if steps_.dtype != torch.int32 or steps_.numel() != n:
+                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (drrt.last_steps)")
+            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
+            fl = _flags(adjoint=True)
+            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
+            try:
+                if not _hint(order, n):
+                    _bump_order_gen(dev)               # sorts for itself: it rewrites the order region
+                _lib.check(_lib.load().drrt_backtrace_rays_f32(
+                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
+                    _p(dx_), _p(dv_), float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl,
+                    _stream(dev)))
+            finally:
+                _clear_hint()
+            _warn_failed(st)
+        return dpos, dvel
 
     def backtrace_chunked(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None, chunks: int = 4,
                           on_chunk=None) -> torch.Tensor:

@@ -9,7 +9,7 @@ Contract reproduced from the reference:
     ``ctx.save_for_backward`` -- no copies, and autograd's version check turns an in-place update of ``rif`` (or of
     the returned exit rays) between forward and backward into a RuntimeError instead of a silently wrong gradient;
   * backward returns ``drif`` reshaped to ``rif.shape`` and ``None`` for every other input
-    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``);
+    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC (below) is the class with ray gradients;
   * ``BackPlaneTracerC`` / ``BackTargetTracerC`` backward run the GENERIC ``backtrace`` from the
     recorded state (``:376,422``); ``BackPlaneTracerC.backward`` zeroes ``grad_x`` on
     rays whose ``outmask`` gradient is set, as written (``:366-367``).
@@ -131,11 +131,58 @@ class BackCableTracerC(torch.autograd.Function):
         return drif, None, None, None, None, None, None
 
 
-# The enoki-autodiff classes of the reference (core/tracer.py:16-291) are out of scope (two of
-# them are broken upstream).  Scripts select them with `autodiff=True`
-# (core/luneburg_opt.py:80-83); the names resolve to the adjoint classes so that flag keeps
-# working, with the documented difference that no gradient flows to x, v.
-ADTracerC = BackTracerC
+class ADTracerC(torch.autograd.Function):
+    """core/tracer.py:16-66 -- ``apply(rif, x, v, h, ds) -> (xt, vt)`` with gradients for ``rif`` AND the rays.
+
+    The reference differentiates its enoki march (``enoki.gradient(ctx.x)``, ``ctx.v``); here the forward is the call
+    BackTracerC makes, dL/drif is the same ``backtrace`` and dL/dx, dL/dv come from the ray-state adjoint
+    ``TracerC.backtrace_rays`` (drrt_backtrace_rays_f32), which needs the forward's inputs and per-ray iteration counts:
+    those are kept (private copies) only when ``x`` or ``v`` requires grad.  Each adjoint runs only for the inputs that
+    ask for a gradient, so with neither ray input requiring grad this launches exactly what BackTracerC launches.
+    Rays that failed the forward (ran out of steps) get a zero ray gradient.  fp32 rays only when ray gradients are
+    asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, h, ds):
+        ctx.shape = rif.shape
+        ctx.h, ctx.ds = h, ds
+        ray_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
+            raise RuntimeError("ADTracerC: gradients w.r.t. x, v need float32 rays")
+        outx, outv = drrt.TracerC().trace(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), h, ds)
+        ctx.order = drrt.keep_order(drrt.last_order)
+        if ray_grad:
+            steps = drrt.keep_steps(drrt.last_steps)
+            if steps is None:
+                raise RuntimeError("ADTracerC: the forward march left no iteration counts")
+            ctx.ray_devices = (x.device, v.device)
+            ctx.rays = (x.detach().to(outx.device).clone(), v.detach().to(outx.device).clone(), steps)
+        ctx.save_for_backward(rif, outx, outv)
+        return outx, outv
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v):
+        rif, outx, outv = ctx.saved_tensors
+        drif = dx0 = dv0 = None
+        if ctx.needs_input_grad[0]:
+            drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
+                                            ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            x0, v0, steps = ctx.rays
+            dpos, dvel = drrt.TracerC().backtrace_rays(rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps,
+                                                       grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
+            if ctx.needs_input_grad[1]:
+                dx0 = dpos.to(ctx.ray_devices[0])
+            if ctx.needs_input_grad[2]:
+                dv0 = dvel.to(ctx.ray_devices[1])
+        return drif, dx0, dv0, None, None
+
+
+# The other enoki-autodiff classes of the reference (core/tracer.py:69-291; two of them are broken upstream, SURVEY Q15)
+# resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working, with the documented
+# difference that no gradient flows to x, v.  Only ADTracerC carries ray gradients: its ray-state adjoint is exact for
+# trace, whose rays end at the sample where they leave the box.  The plane and target stops record a sample that is not
+# where the iteration count K ends (the march runs on past it), and the SDF and cable marches have kernels of their own.
 ADPlaneTracerC = BackPlaneTracerC
 ADSDFTracerC = BackSDFTracerC
 ADCableTracerC = BackCableTracerC

@@ -294,6 +294,33 @@ DRRT_API int drrt_backtrace_f32(const float* rif, long long nvox, const int res[
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* Ray-state adjoint of drrt_trace_f32 (the reference's ADTracerC, core/tracer.py:16-66, through enoki autodiff): dL/dpos and
+ * dL/dvel of the rays that went INTO a trace call, from the seeds dx = dL/dxt, dv = dL/dvt on its exit rays.  Not in the
+ * reference's C++ Tracer.  Nothing is written to a gradient grid: dL/dn is drrt_backtrace_f32's.
+ *   pos, vel    the forward call's inputs; xt, vt its outputs; fwd_steps its per-ray iteration counts K (drrt_last_steps()
+ *               right after that call; copy them out of the workspace if anything runs in between), all caller ray order
+ *   dpos, dvel  out: (n,3) fp32, caller ray order
+ * Contract (the exact derivative of the forward's recurrences): the forward samples n only inside the box
+ * (Q4), so a ray entering from outside flies straight for e iterations first (x_e = pos + e ds vel).  The call replays that
+ * prefix from (pos, vel) with the forward's own fp32 operations, then runs K - e reverse iterations from (xt, vt), seeded
+ * like drrt_backtrace_f32 (lambda = dx, mu = dv + ds dx) -- no backward-escape test, no adjoint step bound -- and writes
+ * dpos = lambda, dvel = mu before its last update + e ds lambda.  A ray whose prefix never samples inside (it never
+ * entered: xt = pos, vt = vel) gets (dx, dv).  A ray with K >= the forward's max_steps failed (Q5, Q6: vt is the stale
+ * vel) and gets a zero gradient and counts in stats->n_failed; a ray that exited on exactly its last allowed iteration is
+ * indistinguishable from one and is treated the same.  stats->ray_steps = reverse iterations executed.  The result does
+ * not depend on DRRT_FLAG_CORRECTED_H (the 1/h of Q3 scales the grid splat only) nor on the visit order.
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE and DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_backtrace_f32;
+ * the order hint (normally the paired forward's) is consumed like there, the step hint is ignored (fwd_steps is the
+ * argument).  fp32 only.                                                                                                 */
+DRRT_API int drrt_backtrace_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, float h, float ds,
+                       float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -477,6 +504,7 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_SORT       3   /* entry-voxel keys + radix sort        */
 #define DRRT_PROF_ZERO       4   /* zero-fill of the gradient grid       */
 #define DRRT_PROF_QUAD       5   /* build of the pair copy of the grid   */
+#define DRRT_PROF_BACKTRACE_RAYS 6   /* ray-state adjoint (drrt_backtrace_rays_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);
