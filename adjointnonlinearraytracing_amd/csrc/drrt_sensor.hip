@@ -235,11 +235,18 @@ __global__ void __launch_bounds__(256) k_sensor_splat_bwd(SensorArgs a) {
 struct TexTaps { float W, fw, fda, fdb, sda, sdb; };
 // The taps follow the point (their texels are clipped, not the taps), so a point anywhere off the texture still has its
 // 16 taps around it -- unlike the splat, which drops rays that miss the image: re-derive the tap origin without that test.
-__device__ __forceinline__ void tex_origin(SensorRay& r) {
+// Once floor(u) is below -4 or above res + 2 every tap clips to the edge texel, and the interpolant depends on frac(u)
+// only; the point is folded back to that many texels off the edge, keeping frac(u): u - floor(u) is exact and so is
+// adding the (smaller) integer back, so value and derivative are unchanged -- and a point 2^20 or more texels away no
+// longer gets 16 zero weights (0/0).  An infinite u folds to inf - inf = NaN, a NaN u stays: both give NaN.
+__device__ __forceinline__ void tex_origin(const SensorArgs& a, SensorRay& r) {
+  const float lo = -4.f, hi = (float)(a.res + 2);
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const float f = fminf(fmaxf(floorf(r.u[k]), -1048576.f), 1048576.f);     // NaN -> a bound; the weights are NaN/0 then
-    r.i1[k] = (int)f;
+    const float fl = floorf(r.u[k]);
+    if (fl < lo) r.u[k] = (r.u[k] - fl) + lo;
+    else if (fl > hi) r.u[k] = (r.u[k] - fl) + hi;
+    r.i1[k] = (int)fminf(fmaxf(floorf(r.u[k]), lo), hi);                 // NaN -> a bound; the weights are NaN/0 then
   }
   r.ok = true;
 }
@@ -273,7 +280,7 @@ __global__ void __launch_bounds__(256) k_sensor_tex_get(SensorArgs a) {
   if (i >= a.n_rays) return;
   float x[3], v[3];
   SensorRay r = sensor_locate(a, i, x, v);
-  tex_origin(r);
+  tex_origin(a, r);
   const TexTaps t = tex_taps(a, r);
   a.f_out[i] = t.fw / t.W;                                            // NaN coordinates: all weights 0 -> 0/0 = NaN
 }
@@ -284,7 +291,7 @@ __global__ void __launch_bounds__(256) k_sensor_tex_get_bwd(SensorArgs a) {
   if (i >= a.n_rays) return;
   float x[3], v[3];
   SensorRay r = sensor_locate(a, i, x, v);
-  tex_origin(r);
+  tex_origin(a, r);
   float gx[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f};
   {
     const TexTaps t = tex_taps(a, r);

@@ -170,12 +170,25 @@ class _SensorSplat(torch.autograd.Function):
         return gx, gv, None, None, None, None, None, None, None
 
 
+def _refuse_grad(op, **inputs):
+    """The fused splats return gradients of the rays only.  In the reference generate_sensor / generate_inf_sensor are
+    plain torch, so a per-ray `e` or a plane that requires grad gets a gradient there: refuse such an input instead of
+    dropping its gradient silently (as _TexGet does for the texture)."""
+    if not torch.is_grad_enabled():
+        return
+    for name, t in inputs.items():
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError(f"{op}: the fused operator is not differentiable w.r.t. `{name}`; pass {name}.detach() "
+                               f"(the reference experiments compute it under torch.no_grad())")
+
+
 def generate_sensor(rays, e, plane, res, span, tangent=None):
     """core/sensor.py:5-28: image (res, res) of the rays splatted onto the sensor plane
     (p, n given as (1,3) tensors, one plane per call as in the reference); differentiable w.r.t.
-    the rays."""
+    the rays only (an `e`, plane or tangent that requires grad raises)."""
     x, v = rays
     p, n = plane
+    _refuse_grad("generate_sensor", e=e, p=p, n=n, tangent=tangent)
     t1, t2 = get_tan_vecs(n, tangent)
     return _SensorSplat.apply(x, v, e, p, n, t1, t2, res, span)
 
@@ -228,9 +241,11 @@ class _FarSensorSplat(torch.autograd.Function):
 def generate_inf_sensor(rays, e, plane, res, angle_span=120, tangent=None):
     """core/sensor.py:31-53: far-field image (res, res) -- the normalised ray directions splatted in the sensor
     frame over [-ang_cut, ang_cut]^2, ang_cut = sin(angle_span / 2); differentiable w.r.t. the directions (the
-    positions do not enter, as in the reference)."""
+    positions and the plane point do not enter, as in the reference; an `e`, normal or tangent that requires grad
+    raises)."""
     x, v = rays
     p, n = plane
+    _refuse_grad("generate_inf_sensor", e=e, n=n, tangent=tangent)
     ang_cut = float(torch.sin(0.5 * torch.deg2rad(torch.tensor(float(angle_span), dtype=torch.float32))))   # :38
     t1, t2 = get_tan_vecs(n, tangent)
     return _FarSensorSplat.apply(v, e, t1, t2, res, ang_cut)

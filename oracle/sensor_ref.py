@@ -133,3 +133,62 @@ def generate_inf_sensor_backward(v, e, n, res, grad_img, angle_span=120.0, tange
     gb = (F / W) * ((g * dwb).sum(axis=(1, 2)) - G * dwb.sum(axis=(1, 2))) / hs
     gp = ga[:, None] * t1[None, :] + gb[:, None] * t2[None, :]        # dL/d vhat
     return (gp - vh * (vh * gp).sum(-1, keepdims=True)) / nv          # (I - vh vh^T)/|v|
+
+
+def sdf_coords(x, v, p, n, arg, tangent=None, far=False, dtype=np.float64):
+    """The sensor coordinates of get_sdf_vals_near (core/sensor.py:102-119) / get_sdf_vals_far (:122-138)
+    -> dict(xn (N,2), span, t, den, t1, t2).  Near: the rays' intersection with the plane in the frame (t1 = n x t2, t2)
+    + span/2, span = arg.  Far: the direction AS IT IS (not normalised, :134) in the frame + ang_cut,
+    span = 2 ang_cut, ang_cut = sin(arg/2) with arg in degrees (:128-129)."""
+    x = np.asarray(x, dtype=dtype); v = np.asarray(v, dtype=dtype)
+    p = np.asarray(p, dtype=dtype).reshape(3); n = np.asarray(n, dtype=dtype).reshape(3)
+    t1, t2 = (a.astype(dtype) for a in tan_vecs(n, tangent))
+    if far:
+        ac = _ang_cut(arg)
+        xn = np.stack([v @ t1, v @ t2], -1) + ac
+        return dict(xn=xn, span=2 * ac, t=np.zeros(len(v)), den=np.ones(len(v)), t1=t1, t2=t2)
+    den = v @ n
+    t = ((p - x) @ n) / den                             # sensor.py:199-200
+    q = x + t[:, None] * v - p
+    xn = np.stack([q @ t1, q @ t2], -1) + arg / 2       # :115-116
+    return dict(xn=xn, span=float(arg), t=t, den=den, t1=t1, t2=t2)
+
+
+def tent_get(xn, tex, span):
+    """core/grid.py:100-124 Grid.Get with the tent kernel on a square 2-D texture: f = sum w f_i / sum w over the 16 taps,
+    tap indices CLIPPED to the texture (:51), and its analytic derivative d f / d xn (Get's second value).
+    -> (f (N,), fx (N,2), taps) with taps = (hs, ia, ib, da, db, r, w, fi)."""
+    tex = np.asarray(tex, dtype=np.float64)
+    res = tex.shape[0]
+    hs, ia, ib, da, db, r, w, _ = _taps(np.asarray(xn, dtype=np.float64), res, span)
+    fi = tex[np.clip(ia, 0, res - 1), np.clip(ib, 0, res - 1)]
+    W = w.sum(axis=(1, 2))
+    f = (w * fi).sum(axis=(1, 2)) / W
+    wx = -(r < SQRT2).astype(np.float64)                # rbf_tent, grid.py:80
+    r0 = np.where(np.isclose(r, 0.0), 1.0, r)          # :57-58
+    ua, ub = da / r0, db / r0                           # d r / d u
+    fx = np.stack([((wx * fi * ua).sum(axis=(1, 2)) - f * (wx * ua).sum(axis=(1, 2))) / W,
+                   ((wx * fi * ub).sum(axis=(1, 2)) - f * (wx * ub).sum(axis=(1, 2))) / W], -1) / hs
+    return f, fx, (hs, ia, ib, da, db, r, w, fi)
+
+
+def get_sdf_vals(x, v, tex, p, n, arg, tangent=None, far=False):
+    """core/sensor.py get_sdf_vals_near (far=False, arg = span) / get_sdf_vals_far (far=True, arg = ang_span in
+    degrees) -> (N,) texture values."""
+    c = sdf_coords(x, v, p, n, arg, tangent, far)
+    return tent_get(c["xn"], tex, c["span"])[0]
+
+
+def get_sdf_vals_backward(x, v, tex, p, n, arg, tangent=None, far=False, grad_f=None):
+    """Gradient of sum(grad_f * get_sdf_vals(...)) w.r.t. (x, v) -- what torch.autograd produces through the
+    reference's get_sdf_vals_near / _far (the far field does not depend on x: zeros)."""
+    x = np.asarray(x, dtype=np.float64); v = np.asarray(v, dtype=np.float64)
+    n = np.asarray(n, dtype=np.float64).reshape(3)
+    c = sdf_coords(x, v, p, n, arg, tangent, far)
+    _, fx, _ = tent_get(c["xn"], tex, c["span"])
+    g = fx * np.asarray(grad_f, dtype=np.float64)[:, None]                   # dL / d xn
+    gq = g[:, :1] * c["t1"][None, :] + g[:, 1:] * c["t2"][None, :]
+    if far:
+        return np.zeros_like(x), gq
+    gx = gq - n[None, :] * ((v * gq).sum(-1) / c["den"])[:, None]          # (I - v n^T/den)^T gq
+    return gx, c["t"][:, None] * gx                                         # d x' / d v = t (I - v n^T/den)

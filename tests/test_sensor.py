@@ -251,6 +251,67 @@ def test_rays_to_plane_fused_matches_reference_run(gpu, tag):
 GS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "sdf_vals.npz")
 
 
+@pytest.mark.parametrize("tag", ["near", "far"])
+def test_sdf_vals_restatement_matches_reference_run(tag):
+    """The float64 restatement (oracle/sensor_ref.py get_sdf_vals / get_sdf_vals_backward, what tests/test_sensor_fuzz.py
+    compares the kernels with) reproduces the fixture made by RUNNING the reference: values and both ray gradients,
+    rays off the texture included."""
+    from oracle import sensor_ref as S
+    z = np.load(GS)
+    args = (z["x"], z["v"], z["tex"], z["p"], z["n"], float(z[f"{tag}_arg"]), z["t"], tag == "far")
+    want = z[f"{tag}_f"]
+    assert np.abs(S.get_sdf_vals(*args) - want).max() <= 1e-10 * np.abs(want).max()
+    gx, gv = S.get_sdf_vals_backward(*args, grad_f=z[f"{tag}_gf"])
+    for got, key in ((gx, "gx"), (gv, "gv")):
+        w = z[f"{tag}_{key}"]
+        assert np.abs(got - w).max() <= 1e-10 * np.abs(w).max(), key       # far: gx is 0 on both sides
+
+
+@pytest.mark.parametrize("op,arg", [("near", "e"), ("near", "p"), ("near", "n"), ("near", "tangent"),
+                                    ("far", "e"), ("far", "n"), ("far", "tangent")])
+def test_splats_refuse_inputs_they_do_not_differentiate(op, arg):
+    """The fused splats return gradients of the rays only.  In the reference generate_sensor / generate_inf_sensor are
+    plain torch, so a per-ray `e` or a plane that requires grad gets a gradient there: refuse it here instead of
+    dropping it silently (the check runs before anything touches a device)."""
+    from adjointnonlinearraytracing_amd import sensor
+    N = 8
+    ins = dict(e=torch.rand(N), p=torch.tensor([[0.5, 1.2, 0.5]]), n=torch.tensor([[0.0, 1.0, 0.0]]),
+               tangent=torch.tensor([[0.0, 0.0, 1.0]]))
+    ins[arg] = ins[arg].clone().requires_grad_(True)
+    rays = (torch.rand(N, 3), torch.rand(N, 3))
+    fn = sensor.generate_sensor if op == "near" else sensor.generate_inf_sensor
+    with pytest.raises(RuntimeError, match=f"w.r.t. `{arg}`.*{arg}.detach"):
+        fn(rays, ins["e"], (ins["p"], ins["n"]), 16, 1.0, tangent=ins["tangent"])
+
+
+@pytest.mark.gpu
+def test_splats_take_inputs_made_without_grad(gpu):
+    """What the reference experiments do still works: `e` and planes computed under no_grad (focalstack_opt), a call
+    made under no_grad, and a far-field plane point that requires grad (it does not enter the far-field image, so
+    its gradient is zero)."""
+    from adjointnonlinearraytracing_amd import sensor
+    N, res = 512, 32
+    torch.manual_seed(5)
+    x = (torch.rand(N, 3, device=gpu) * 0.8 + 0.1).requires_grad_(True)
+    v = torch.randn(N, 3, device=gpu) * 0.1
+    v[:, 1] = 1.0
+    v.requires_grad_(True)
+    w = torch.rand(N, device=gpu, requires_grad=True)
+    with torch.no_grad():
+        e = w * 2.0
+        p = torch.tensor([[0.5, 1.2, 0.5]], device=gpu) * w.mean() / w.mean()
+        n = torch.tensor([[0.0, 1.0, 0.0]], device=gpu) + 0.0 * w.mean()
+    t = torch.tensor([[0.0, 0.0, 1.0]], device=gpu)
+    (sensor.generate_sensor((x, v), e, (p, n), res, 1.0, t) ** 2).sum().backward()
+    assert torch.isfinite(x.grad).all() and float(x.grad.abs().sum()) > 0
+    pg = p.clone().requires_grad_(True)
+    (sensor.generate_inf_sensor((x, v), e, (pg, n), res, 120, t) ** 2).sum().backward()
+    assert torch.isfinite(v.grad).all() and pg.grad is None
+    with torch.no_grad():
+        img = sensor.generate_sensor((x, v), w, (p, n), res, 1.0, t)
+    assert img.shape == (res, res) and torch.isfinite(img).all()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag", ["near", "far"])
 def test_sdf_vals_match_reference_run(gpu, tag):
