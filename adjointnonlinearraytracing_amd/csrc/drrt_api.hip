@@ -1,6 +1,6 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout, visit-order / step hand-over, per-kernel timing, and the launches of the
-// kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip / drrt_cable.hip.  Host code, plus the three
+// kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the three
 // small utility kernels that belong to no march (pair copy of the grid, q16 encode / decode).
 #include "drrt_march.h"
 
@@ -637,7 +637,10 @@ extern "C" int drrt_trace_cable_f32(const float* rif, size_t rres, float radius,
   a.max_steps = (int)(4.0f * length / ds);                                   // src/tracer.cpp:332
   a.pos = pos; a.vel = vel; a.target = target; a.xt = xt; a.vt = vt; a.dist2 = dist2;
   a.stats = stats; a.n = n;
-  launch_trace_cable(a, s);
+  {
+    ProfScope prof(DRRT_PROF_TRACE, s);
+    launch_trace_cable(a, s);
+  }
   LAUNCH_CHECK("k_trace_cable");
   return DRRT_OK;
 }
@@ -665,7 +668,40 @@ extern "C" int drrt_backtrace_cable_f32(const float* rif, size_t rres, float rad
   a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
   a.max_steps = (int)(4.0f * length / ds);                                   // src/tracer.cpp:544
   a.pos = xt; a.vel = vt; a.dx = dx; a.dv = dv; a.grad = grad; a.stats = stats; a.n = n;
-  launch_backtrace_cable(a, s);
+  {
+    ProfScope prof(DRRT_PROF_BACKTRACE, s);
+    launch_backtrace_cable(a, s);
+  }
   LAUNCH_CHECK("k_backtrace_cable");
+  return DRRT_OK;
+}
+
+extern "C" int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                                             const float* pos, const float* vel, const float* target,
+                                             const float* dx, const float* dv, float ds, float* dpos, float* dvel,
+                                             drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags,
+                                             void* stream) {
+  (void)ws; (void)ws_bytes; (void)flags;
+  (void)take_hint();
+  g_err[0] = 0;
+  hipStream_t s = (hipStream_t)stream;
+  if (!rif) return fail(DRRT_ERR_ARG, "null rif pointer");
+  if (rres < 2 || rres > 0x7fffffffULL) return fail(DRRT_ERR_BAD_RES, "volume: invalid resolution!");
+  if (!(radius > 0.f) || !(length > 0.f) || !(ds > 0.f) || !(ds < 3.0e38f))
+    return fail(DRRT_ERR_ARG, "radius, length and ds must be positive and finite");
+  int rc = zero_stats(stats, s); if (rc) return rc;
+  if (n == 0) return DRRT_OK;
+  if (!pos || !vel || !target || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
+  CableRayGradArgs a{};
+  a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
+  a.max_steps = (int)(4.0f * length / ds);                                   // the forward's bound, src/tracer.cpp:332
+  a.pos = pos; a.vel = vel; a.target = target; a.dx = dx; a.dv = dv; a.dpos = dpos; a.dvel = dvel;
+  a.stats = stats; a.n = n;
+  {
+    ProfScope prof(DRRT_PROF_BACKTRACE_CABLE_RAYS, s);
+    launch_backtrace_cable_rays(a, s);
+  }
+  LAUNCH_CHECK("k_backtrace_cable_rays");
   return DRRT_OK;
 }

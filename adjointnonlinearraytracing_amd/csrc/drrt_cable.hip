@@ -4,16 +4,6 @@
 
 namespace drrt {
 
-__device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_tot, unsigned steps_max, unsigned fail_tot) {
-  if (!stats) return;
-  unsigned wm = wave_max_u32(steps_max), ws = wave_sum_u32(steps_tot), wf = wave_sum_u32(fail_tot);
-  if ((threadIdx.x & (kWave - 1)) == 0) {
-    if (wm) atomicMax(&stats->iters, wm);
-    if (ws) atomicAdd(&stats->ray_steps, (unsigned long long)ws);
-    if (wf) atomicAdd(&stats->n_failed, (unsigned long long)wf);
-  }
-}
-
 __global__ void __launch_bounds__(kBlock) k_trace_cable(CableArgs a) {
   extern __shared__ float s_prof[];
   const bool use_lds = a.rres <= kCableMaxRes;
@@ -92,11 +82,6 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_cable(CableArgs a) {
 }
 
 // ---- launchers ----------------------------------------------------------------------------------
-static unsigned cable_grid(size_t n) {
-  // grid-stride: at most 4 blocks per CU so that the per-block LDS gradient flush stays small
-  const unsigned want = grid_for(n);
-  return want < 1024u ? want : 1024u;
-}
 void launch_trace_cable(const CableArgs& a, hipStream_t s) {
   const size_t lds = (a.rres <= kCableMaxRes) ? a.rres * sizeof(float) : 0;
   hipLaunchKernelGGL(k_trace_cable, dim3(cable_grid(a.n)), dim3(kBlock), lds, s, a);

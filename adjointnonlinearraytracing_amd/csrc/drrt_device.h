@@ -567,33 +567,51 @@ DRRT_HD void cable_fwd_step(const Cyl& C, float ds, FwdState& s) {
   s.inside = cur_inside;
 }
 
+// What one reverse cable iteration samples at (s.x, s.z): n, n' and grad n = n' rhat (y component 0).  Steps v back
+// (:550) and leaves x alone.  Shared by the dL/dn adjoint and the ray-state adjoint.
+struct CylAdjSample { CylCell c; float n, rx, gx, gz; };
+
+DRRT_HD CylAdjSample cable_adj_sample(const Cyl& C, float ds, AdjState& s) {
+  CylAdjSample m;
+  m.c = cyl_locate(C, s.x, s.z);
+  float v0 = C.data[m.c.i0], v1 = C.data[m.c.i1];
+  m.n = fmaf(v1, m.c.w0, v0 * (1.f - m.c.w0));                          // :53
+  m.rx = (v1 - v0) * C.inv_h;                                           // :54 / :88
+  m.gx = m.rx * m.c.rhx; m.gz = m.rx * m.c.rhz;                         // grad n (y comp 0)
+  float mdsn = -ds * m.n;
+  s.vx = fmaf(mdsn, m.gx, s.vx); s.vz = fmaf(mdsn, m.gz, s.vz);         // :550
+  return m;
+}
+
+// The lambda / mu recurrences of one reverse cable iteration (:561-562), dn = mu . grad n taken before them.  The sample
+// is passed by value: by reference the compiler orders two multiplies of k_backtrace_cable the other way round.
+DRRT_HD void cable_adj_recur(float ds, AdjState& s, CylAdjSample m, float dn) {
+  const CylCell& c = m.c;
+  // Hessian (:88-108): (I - rhat rhat^T)_{xz} * (n'/r), zero when r < eps
+  float sH = c.tiny ? 0.f : m.rx / c.r;
+  float h00 = (1.f - c.rhx * c.rhx) * sH, h02 = -(c.rhx * c.rhz) * sH, h22 = (1.f - c.rhz * c.rhz) * sH;
+  float hmx = fmaf(h02, s.mz, h00 * s.mx), hmz = fmaf(h22, s.mz, h02 * s.mx);
+  s.lx = fmaf(ds, fmaf(dn, m.gx, m.n * hmx), s.lx);                     // :561 (y row of H is 0)
+  s.lz = fmaf(ds, fmaf(dn, m.gz, m.n * hmz), s.lz);
+  s.mx = fmaf(ds, s.lx, s.mx); s.my = fmaf(ds, s.ly, s.my); s.mz = fmaf(ds, s.lz, s.mz);   // :562
+}
+
 // one adjoint cable iteration (src/tracer.cpp:547-562); contribution: a0 at i0, a1 at i1
 DRRT_HD bool cable_adj_step(const Cyl& C, float ds, AdjState& s, int& i0, int& i1, float& a0, float& a1) {
   s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);     // :547
-  CylCell c = cyl_locate(C, s.x, s.z);
-  float v0 = C.data[c.i0], v1 = C.data[c.i1];
+  const CylAdjSample m = cable_adj_sample(C, ds, s);
+  const CylCell& c = m.c;
   float w0 = c.w0, w1 = 1.f - c.w0;
-  float n = fmaf(v1, w0, v0 * w1);                                      // :53
-  float rx = (v1 - v0) * C.inv_h;                                       // :54 / :88
-  float gx = rx * c.rhx, gz = rx * c.rhz;                               // grad n (y comp 0)
-  float mdsn = -ds * n;
-  s.vx = fmaf(mdsn, gx, s.vx); s.vz = fmaf(mdsn, gz, s.vz);             // :550
   s.active = !cyl_escaped(C, s.x, s.y, s.z, -s.vx, -s.vy, -s.vz);       // :552
   if (!s.active) return false;
-  float dn = fmaf(s.mz, gz, s.mx * gx);                                 // :557
+  float dn = fmaf(s.mz, m.gz, s.mx * m.gx);                             // :557
   // cylinder_volume::splat (:113-148): value taps val*w, gradient taps -+(grad.rhat)/h
   float val = dn * ds;
-  float gv = (n * ds) * fmaf(s.mz, c.rhz, s.mx * c.rhx);                // dot(dnx*ds, rhat); 0 if tiny
+  float gv = (m.n * ds) * fmaf(s.mz, c.rhz, s.mx * c.rhx);              // dot(dnx*ds, rhat); 0 if tiny
   float gvh = gv * C.inv_h;
   i0 = c.i0; i1 = c.i1;
   a0 = fmaf(val, w1, -gvh); a1 = fmaf(val, w0, gvh);
-  // Hessian (:88-108): (I - rhat rhat^T)_{xz} * (n'/r), zero when r < eps
-  float sH = c.tiny ? 0.f : rx / c.r;
-  float h00 = (1.f - c.rhx * c.rhx) * sH, h02 = -(c.rhx * c.rhz) * sH, h22 = (1.f - c.rhz * c.rhz) * sH;
-  float hmx = fmaf(h02, s.mz, h00 * s.mx), hmz = fmaf(h22, s.mz, h02 * s.mx);
-  s.lx = fmaf(ds, fmaf(dn, gx, n * hmx), s.lx);                         // :561 (y row of H is 0)
-  s.lz = fmaf(ds, fmaf(dn, gz, n * hmz), s.lz);
-  s.mx = fmaf(ds, s.lx, s.mx); s.my = fmaf(ds, s.ly, s.my); s.mz = fmaf(ds, s.lz, s.mz);   // :562
+  cable_adj_recur(ds, s, m, dn);
   return true;
 }
 
@@ -839,6 +857,70 @@ DRRT_HD unsigned cable_backtrace_ray(const Cyl& C, float ds, int max_steps, cons
     sink(i0, i1, a0, a1);
   }
   return steps;
+}
+
+// Ray-state adjoint of trace_cable for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the recorded closest-approach
+// state (xt, vt) = (x_j, v_j), given only the forward's inputs (p0, v0) and its target.  The forward does not report j, so
+//   * the forward is replayed from (p0, v0) with cable_fwd_step itself, looped as cable_trace_ray loops it; j is the
+//     iteration count at the last record update (0: the record is the input) and the replayed record is (xt, vt), so the
+//     caller cannot hand in a mismatched pair;
+//   * j = 0: the gradient is the identity (dx, dv);
+//   * otherwise j reverse iterations from (xt, vt), seeded like cable_backtrace_ray (lambda = dx, mu = dv + ds dx), with
+//     neither its backward-escape test nor its step bound; after the last one lambda = dL/dx_0 and the mu it was updated
+//     from is dL/dv_0.  There is no free-flight prefix (the cable march samples from p0 on, clamped beyond the radius).
+//     The last reverse iteration samples at p0 itself instead of its reconstruction x_1 - ds v_1: a start exactly on a
+//     profile knot or on the axis must see the forward's sample.
+// j is held fixed (as autograd through a masked select does); a seed on dist2 does not enter.  A ray that ran out of
+// steps still has a valid record and a gradient: `failed` stays false.  steps = replay + reverse iterations.
+// `rec` (optional) receives the replayed record.
+struct CableRecord { float xt[3], vt[3]; unsigned j; };
+
+DRRT_HD RayGrad cable_backtrace_ray_state(const Cyl& C, float ds, int max_steps, const float p0[3], const float v0[3],
+                                          const float tg[3], const float dx[3], const float dv[3],
+                                          CableRecord* rec = nullptr) {
+  FwdState f;
+  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
+  f.xtx = f.x; f.xty = f.y; f.xtz = f.z; f.vtx = f.vx; f.vty = f.vy; f.vtz = f.vz;
+  f.aux0 = tg[0]; f.aux1 = tg[1]; f.aux2 = tg[2]; f.aux4 = f.aux5 = 0.f;
+  float ex = f.x - tg[0], ey = f.y - tg[1], ez = f.z - tg[2];
+  f.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
+  f.inside = cyl_inbounds(C, f.x, f.y, f.z);                              // :344
+  f.esc = false;
+  unsigned steps = 0, j = 0;
+  for (int it = 0; it < max_steps; ++it) {
+    const float best = f.aux3;
+    cable_fwd_step(C, ds, f);
+    ++steps;
+    if (f.aux3 < best) j = steps;                                         // the record was updated (strict <, :365)
+    if (f.esc) break;
+  }
+  if (rec) {
+    rec->xt[0] = f.xtx; rec->xt[1] = f.xty; rec->xt[2] = f.xtz;
+    rec->vt[0] = f.vtx; rec->vt[1] = f.vty; rec->vt[2] = f.vtz; rec->j = j;
+  }
+  RayGrad g;
+  g.failed = false;
+  g.steps = steps + j;
+  if (j == 0) {
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+    return g;
+  }
+  AdjState s;
+  s.x = f.xtx; s.y = f.xty; s.z = f.xtz; s.vx = f.vtx; s.vy = f.vty; s.vz = f.vtz;
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                               // :536
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);  // :537
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  for (unsigned k = j; k > 0; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :547
+    if (k == 1u) { s.x = p0[0]; s.y = p0[1]; s.z = p0[2]; }              // the forward's first sample, as it took it
+    const CylAdjSample m = cable_adj_sample(C, ds, s);
+    const float dn = fmaf(s.mz, m.gz, s.mx * m.gx);                       // :557
+    qx = s.mx; qy = s.my; qz = s.mz;
+    cable_adj_recur(ds, s, m, dn);
+  }
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  return g;
 }
 
 #if defined(__HIPCC__)

@@ -9,6 +9,7 @@
 //                           different instruction-scheduling strategy, csrc/Makefile)
 //   drrt_adjoint_rays.hip   backtrace_rays: dL/dpos, dL/dvel of trace (ray-state adjoint, no grid writes)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
+//   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
 //
 // Reference semantics: /root/reference/src/tracer.cpp, src/volume.cpp, src/cylinder_volume.cpp.  Quirk numbers
@@ -425,8 +426,34 @@ struct CableArgs {
   size_t n;
 };
 
+// ray-state adjoint of trace_cable (drrt_cable_rays.hip).  Its own argument block: CableArgs keeps the field offsets the
+// two cable kernels were compiled against.
+struct CableRayGradArgs {
+  const float* rif; int rres; float radius, length, ds; int max_steps;
+  const float* pos; const float* vel; const float* target;    // the forward's inputs
+  const float* dx; const float* dv;                           // seeds on the recorded (xt, vt)
+  float* dpos; float* dvel;
+  drrt_stats* stats;
+  size_t n;
+};
+
+__device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_tot, unsigned steps_max, unsigned fail_tot) {
+  if (!stats) return;
+  unsigned wm = wave_max_u32(steps_max), ws = wave_sum_u32(steps_tot), wf = wave_sum_u32(fail_tot);
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    if (wm) atomicMax(&stats->iters, wm);
+    if (ws) atomicAdd(&stats->ray_steps, (unsigned long long)ws);
+    if (wf) atomicAdd(&stats->n_failed, (unsigned long long)wf);
+  }
+}
+
 // ---- launchers (host): one per kernel family, defined next to the kernels ------------------------------------------
 static inline unsigned grid_for(size_t n) { return (unsigned)((n + kBlock - 1) / kBlock); }
+static inline unsigned cable_grid(size_t n) {
+  // grid-stride: at most 4 blocks per CU so that the per-block LDS gradient flush stays small
+  const unsigned want = grid_for(n);
+  return want < 1024u ? want : 1024u;
+}
 // forward (drrt_forward.hip).  mode: 0 = trace, 1 = trace_plane, 2 = trace_sdf
 void launch_trace(int mode, const TraceArgs& a, hipStream_t s);
 void launch_trace_again(int mode, const TraceArgs& a, hipStream_t s);
@@ -442,5 +469,7 @@ void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);
+// ray-state adjoint of the cable march (drrt_cable_rays.hip)
+void launch_backtrace_cable_rays(const CableRayGradArgs& a, hipStream_t s);
 
 }  // namespace drrt

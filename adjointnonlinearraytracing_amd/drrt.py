@@ -734,6 +734,25 @@ class TracerC:
                 _p(dv_), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
         return grad
 
+    def backtrace_cable_rays(self, rif, radius, length, pos, vel, target, dx, dv, ds) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ray-state adjoint of ``trace_cable`` (drrt_backtrace_cable_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),
+        (n,3) fp32.  `pos`, `vel`, `target` are the forward call's inputs, `dx`, `dv` the seeds on its (xt, vt); the call
+        replays the forward to find the iteration of the closest-approach record, so it takes neither (xt, vt) nor a step
+        count.  A seed on dist2 does not enter.  Not in the reference's C++ Tracer: its ADCableTracerC gets these through
+        enoki autodiff (core/tracer.py:237-291).  fp32 rays only."""
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
+            n = pos_.shape[0]
+            vel_, tg = _rays(vel, dev, n), _rays(target, dev, n)
+            dx_, dv_ = _rays(dx, dev, n), _rays(dv, dev, n)
+            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
+            ws, st = _workspace(n, 0, dev), _new_stats(dev)
+            _lib.check(_lib.load().drrt_backtrace_cable_rays_f32(
+                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(vel_), _p(tg), _p(dx_), _p(dv_),
+                float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
+        return dpos, dvel
+
     # ---- print-only smoke methods of the reference (src/tracer.cpp:16-33) ------------------
     def test(self) -> torch.Tensor:
         """Tracer::tester: returns a zero 3-vector."""

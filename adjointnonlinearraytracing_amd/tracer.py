@@ -9,7 +9,8 @@ Contract reproduced from the reference:
     ``ctx.save_for_backward`` -- no copies, and autograd's version check turns an in-place update of ``rif`` (or of
     the returned exit rays) between forward and backward into a RuntimeError instead of a silently wrong gradient;
   * backward returns ``drif`` reshaped to ``rif.shape`` and ``None`` for every other input
-    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC (below) is the class with ray gradients;
+    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC and ADCableTracerC (below) are the classes
+    with ray gradients;
   * ``BackPlaneTracerC`` / ``BackTargetTracerC`` backward run the GENERIC ``backtrace`` from the
     recorded state (``:376,422``); ``BackPlaneTracerC.backward`` zeroes ``grad_x`` on
     rays whose ``outmask`` gradient is set, as written (``:366-367``).
@@ -178,11 +179,56 @@ class ADTracerC(torch.autograd.Function):
         return drif, dx0, dv0, None, None
 
 
-# The other enoki-autodiff classes of the reference (core/tracer.py:69-291; two of them are broken upstream)
+class ADCableTracerC(torch.autograd.Function):
+    """core/tracer.py:237-291 -- ``apply(rif (Rr,), radius, length, x, v, sp, ds) -> (xt, vt, dist2)`` with gradients for
+    ``rif`` AND the rays that enter the fibre march.
+
+    The reference differentiates its enoki march; here the forward is the call BackCableTracerC makes, dL/drif is the same
+    ``backtrace_cable`` and dL/dx, dL/dv come from the ray-state adjoint ``TracerC.backtrace_cable_rays``
+    (drrt_backtrace_cable_rays_f32).  That call replays the forward from its inputs, so the inputs (x, v, sp) are kept
+    (private copies) only when ``x`` or ``v`` requires grad.  Each adjoint runs only for the inputs that ask for a
+    gradient, so with neither ray input requiring grad this launches exactly what BackCableTracerC launches.  The
+    iteration of the closest-approach record is held fixed, and the gradient arriving on ``dist2`` is ignored, as in the
+    reference (``:268-272``) and in BackCableTracerC; no gradient flows to ``sp``.  A ray that ran out of steps still has
+    a record and a gradient.  fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, radius, length, x, v, sp, ds):
+        ctx.radius, ctx.length, ctx.ds = radius, length, ds
+        ray_grad = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
+            raise RuntimeError("ADCableTracerC: gradients w.r.t. x, v need float32 rays")
+        outx, outv, dist2 = drrt.TracerC().trace_cable(
+            rif.detach().flatten(), radius, length, x.detach(), v.detach(), sp.detach(), ds)
+        if ray_grad:
+            ctx.ray_devices = (x.device, v.device)
+            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v, sp))
+        ctx.save_for_backward(rif, outx, outv)
+        return outx, outv, dist2
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, outdist):
+        rif, outx, outv = ctx.saved_tensors
+        drif = dx0 = dv0 = None
+        if ctx.needs_input_grad[0]:
+            drif = drrt.TracerC().backtrace_cable(rif.detach().flatten(), ctx.radius, ctx.length, outx, outv,
+                                                  grad_x, grad_v, ctx.ds).reshape(rif.shape)
+        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            x0, v0, sp = ctx.rays
+            dpos, dvel = drrt.TracerC().backtrace_cable_rays(rif.detach().flatten(), ctx.radius, ctx.length, x0, v0, sp,
+                                                             grad_x, grad_v, ctx.ds)
+            if ctx.needs_input_grad[3]:
+                dx0 = dpos.to(ctx.ray_devices[0])
+            if ctx.needs_input_grad[4]:
+                dv0 = dvel.to(ctx.ray_devices[1])
+        return drif, None, None, dx0, dv0, None, None
+
+
+# The other enoki-autodiff classes of the reference (core/tracer.py:69-236; two of them are broken upstream, SURVEY Q15)
 # resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working, with the documented
-# difference that no gradient flows to x, v.  Only ADTracerC carries ray gradients: its ray-state adjoint is exact for
-# trace, whose rays end at the sample where they leave the box.  The plane and target stops record a sample that is not
-# where the iteration count K ends (the march runs on past it), and the SDF and cable marches have kernels of their own.
+# difference that no gradient flows to x, v.  ADTracerC and ADCableTracerC carry ray gradients: the ray-state adjoint of
+# trace is exact because its rays end at the sample where they leave the box, and the cable's replays its forward to find
+# the iteration of the recorded sample.  The plane and target stops record a sample that is not where the iteration count
+# K ends (the march runs on past it), and the SDF march has a kernel of its own.
 ADPlaneTracerC = BackPlaneTracerC
 ADSDFTracerC = BackSDFTracerC
-ADCableTracerC = BackCableTracerC

@@ -1,11 +1,12 @@
 #!/usr/bin/env python3
 """The reference's fibre experiment (core/fiber_opt.py:100-280) on this package's mirrors: optimise the RADIAL index profile
 of a cylindrical fibre so that light entering through a cone (or as a plane wave) refocuses on the axis point it left
-from, one "hop" further down, and again a hop later -- `tracer.BackCableTracerC` (HIP cable march + adjoint),
+from, one "hop" further down, and again a hop later -- `tracer.BackCableTracerC` (HIP cable march + adjoint; `--autodiff`:
+`tracer.ADCableTracerC`, which adds the gradient through the rays entering the march),
 a three-line radial lookup for the boundary index (the reference: `cable.Cable.GetLinear`, core/fiber_opt.py:158-160), `source.cone_source3_rand` / `plane_source3_rand`, Adam with the
 experiment's own midpoint up-sampling between levels.
 
-    python examples/fiber_demo.py [--res 5 9 17] [--iters 30] [--nbins 32] [--src cone|planar]
+    python examples/fiber_demo.py [--res 5 9 17] [--iters 30] [--nbins 32] [--src cone|planar] [--autodiff]
 """
 from __future__ import annotations
 
@@ -38,9 +39,21 @@ def upres_scene(n: torch.Tensor) -> torch.Tensor:
     return nn.requires_grad_(True)
 
 
+def trace(nt, rays, target, cable_radius, cable_length, autodiff=False):
+    """core/fiber_opt.py:145-163: scale the directions by the boundary index, then march to the closest approach to
+    `target` -> (xt, vt, dist2).  The boundary index is a function of the profile `nt` too.  With `autodiff` (the reference's
+    ADCableTracerC branch, :148-149) the march also returns dL/dv to the rays that entered it, so that term reaches
+    nt.grad; without it, only the march's own dL/dn does."""
+    x, v = rays
+    sds = cable_radius / nt.shape[0] / 2
+    v = v / radial_index(nt, cable_radius, x)[:, None]
+    fn = tracer.ADCableTracerC if autodiff else tracer.BackCableTracerC
+    return fn.apply(nt, cable_radius, cable_length, x, v, target, sds)
+
+
 def run(res_list=(5, 9, 17), iters=30, nbins=32, spp=1, src_type="cone", cable_length=5.0, cable_radius=1.0,
         camera_span=0.1, cone_ang=60.0, sensor_dist=1.57, hop_dist=3.14, hop_weight=0.1, lr=0.01, plane_eps=0.001,
-        seed=0, verbose=True):
+        seed=0, verbose=True, autodiff=False):
     dev = torch.device("cuda:0")
     torch.manual_seed(seed)
     drrt.options.check_failed = False
@@ -51,12 +64,6 @@ def run(res_list=(5, 9, 17), iters=30, nbins=32, spp=1, src_type="cone", cable_l
                                              sensor_dist=sensor_dist - cable_radius * 2, device=dev)
         return source.cone_source3_rand(torch.tensor(0.0), (nbins, nbins), spp, cable_radius * 2,
                                         sensor_dist=sensor_dist, cone_angle=cone_ang, device=dev)
-
-    def trace(nt, rays, target):                                          # :152-163
-        x, v = rays
-        sds = cable_radius / nt.shape[0] / 2
-        v = v / radial_index(nt, cable_radius, x)[:, None]
-        return tracer.BackCableTracerC.apply(nt, cable_radius, cable_length, x, v, target, sds)
 
     n = torch.ones(res_list[0], device=dev).requires_grad_(True)
     opto = optim.Adam([n], lr=lr)
@@ -69,7 +76,7 @@ def run(res_list=(5, 9, 17), iters=30, nbins=32, spp=1, src_type="cone", cable_l
             sp, sn = planes[:, 0, :], planes[:, 1, :]
             total = 0.0
             for target, weight in ((sp, 1.0), (sp + hop_dist * sn, hop_weight)):     # :196-216
-                xm, vm, dist2 = trace(n, (x, v), target)
+                xm, vm, dist2 = trace(n, (x, v), target, cable_radius, cable_length, autodiff)
                 keep = dist2 > plane_eps ** 2
                 loss = weight * torch.sum((xm[keep] - target[keep]) ** 2 / nrays / cable_radius) / camera_span
                 loss.backward()
@@ -93,7 +100,9 @@ if __name__ == "__main__":
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--nbins", type=int, default=32)
     ap.add_argument("--src", default="cone")
+    ap.add_argument("--autodiff", action="store_true",
+                    help="ADCableTracerC: the boundary index's dependence on the profile enters the gradient")
     a = ap.parse_args()
-    n, hist = run(tuple(a.res), a.iters, a.nbins, src_type=a.src)
+    n, hist = run(tuple(a.res), a.iters, a.nbins, src_type=a.src, autodiff=a.autodiff)
     print(f"loss {hist[0]:.5f} -> {hist[-1]:.5f};  profile (axis -> cladding): "
           + " ".join(f"{float(t):.3f}" for t in n[:: max(1, n.shape[0] // 8)]))

@@ -373,6 +373,25 @@ DRRT_API int drrt_backtrace_cable_f32(const float* rif, size_t rres, float radiu
                              drrt_stats* stats, void* workspace, size_t workspace_bytes,
                              unsigned flags, void* stream);
 
+/* Ray-state adjoint of Tracer::trace_cable: dL/dpos, dL/dvel of the rays that entered drrt_trace_cable_f32 (the reference
+ * gets them from enoki autodiff, core/tracer.py:237-291 ADCableTracerC).  No contribution to dL/dn is formed.
+ *   pos, vel, target   the forward call's inputs, (n,3) fp32
+ *   dx, dv             seeds on its outputs (xt, vt); a seed on dist2 does not enter (as in the reference, :268-272)
+ *   dpos, dvel         out: (n,3) fp32
+ * Contract: (xt, vt) is the state (x_j, v_j) of the iteration j with the smallest squared distance to the target (first
+ * minimum; j = 0 is the input itself).  The forward does not report j, so the call replays the forward march from
+ * (pos, vel) with the forward's own fp32 operations and takes j and (xt, vt) from the replay; then it runs j reverse
+ * iterations from (xt, vt), seeded like drrt_backtrace_cable_f32 (lambda = dx, mu = dv + ds dx) -- no backward-escape
+ * test, no adjoint step bound -- and writes dpos = lambda, dvel = mu before its last update.  j = 0 gives (dx, dv).
+ * j is held fixed.  A ray that ran out of steps keeps its record and its gradient: stats->n_failed = 0.
+ * stats->ray_steps = replay + reverse iterations.  The workspace and flags are not used.  fp32 only.                */
+DRRT_API int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                             const float* pos, const float* vel, const float* target,
+                             const float* dx, const float* dv, float ds,
+                             float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
 /* ---- sensor image splat (SURVEY.md 8.8 "next" row 1; the reference does this in torch) ----------
  * Forward: core/sensor.py:5-28 generate_sensor = trace_rays_to_plane (:195-202) + sensor frame
  * (t1 = n x t2, t2; get_tan_vecs :219-231 is evaluated by the caller) + foreshortening |v.n| +
@@ -505,6 +524,7 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_ZERO       4   /* zero-fill of the gradient grid       */
 #define DRRT_PROF_QUAD       5   /* build of the pair copy of the grid   */
 #define DRRT_PROF_BACKTRACE_RAYS 6   /* ray-state adjoint (drrt_backtrace_rays_f32) */
+#define DRRT_PROF_BACKTRACE_CABLE_RAYS 7   /* ray-state adjoint of the cable march (drrt_backtrace_cable_rays_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

@@ -1,0 +1,445 @@
+"""Ray-state adjoint of the fibre march (drrt_backtrace_cable_rays_f32, tracer.ADCableTracerC): dL/dpos and dL/dvel.
+
+CPU tier: the host build of the product's per-ray routine (tests/cable_raygrad_host, cable_backtrace_ray_state of
+csrc/drrt_device.h) against torch.autograd in float64 through tests/cable_ad.trace_cable, on the rays whose fp32 and fp64
+records agree.  The float64 march takes the fp32 march's record iteration j* as an input, so the two cannot pick different
+iterations; what is left to drop are the rays whose fp32 state has drifted more than TIE_TOL from the fp64 one by then.
+GPU tier: k_backtrace_cable_rays against that host build bit for bit, ADCableTracerC end to end, its launches, and the
+boundary-index term of the fibre experiment.
+
+On the parent commit every test here fails: tests/cable_raygrad_host does not compile (no cable_backtrace_ray_state), the
+library has no drrt_backtrace_cable_rays_f32, and ADCableTracerC is BackCableTracerC (x.grad is None)."""
+import ctypes as C
+import os
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import cable_ad
+import cable_raygrad_host_lib as CRG
+import cases
+import hostcheck_lib as HC
+
+TIE_TOL = 1e-5          # fp32 vs fp64 records (the constants of test_raygrad.py)
+GRAD_TOL = 1e-3         # per-ray relative error of (dpos, dvel) against float64 autograd
+MAX_DROPPED = 0.20      # share of a scene's rays that may be left out as not tie-free
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------
+def _unit(v):
+    return v / np.linalg.norm(v, axis=1, keepdims=True)
+
+
+def profile(kind):
+    if kind == "luneburg65":                               # the profile of test_cable_variants
+        return np.sqrt(2.0 - np.linspace(0, 1, 65) ** 2).astype(np.float32)
+    if kind == "random33":
+        return (1.0 + 0.5 * np.random.default_rng(9).random(33)).astype(np.float32)
+    if kind == "two":
+        return np.array([1.5, 1.3], np.float32)
+    raise KeyError(kind)
+
+
+SCENES = {
+    # name: (profile, radius, length, ds in radial samples h = radius / (rres - 1), or None for radius / rres / 2)
+    # The lengths keep every march within about 300 iterations: over more, the fp32 state drifts past TIE_TOL from the
+    # fp64 one on most rays (65 samples and 780 iterations: 88 % of the rays) and nothing is left to compare.
+    "luneburg65_half": ("luneburg65", 1.0, 2.0, None),
+    "random33_half": ("random33", 1.0, 1.2, 0.25),
+    "two_samples": ("two", 0.7, 2.5, 0.012),
+    # 1.7 samples a step: a march down y = 0..7 also stays within 300 iterations, but then the fp32 rounding of y alone
+    # (half an ulp of 4..8 an iteration) passes TIE_TOL on a fifth of the rays; half that length keeps them
+    "luneburg65_multi": ("luneburg65", 1.0, 3.5, 1.7),
+}
+
+
+def ray_sets(radius, length, ds, seed):
+    """-> {name: (pos, vel)}: inside, on the axis, beyond the radius, before y = 0 and past the far end."""
+    rng = np.random.default_rng(seed)
+    n = 96
+    out = {}
+
+    def disc(rmax, rmin=0.0):
+        ang = rng.uniform(0, 2 * np.pi, n)
+        rad = radius * np.sqrt(rng.uniform((rmin / rmax) ** 2, 1, n)) * rmax
+        return radius + rad * np.cos(ang), radius + rad * np.sin(ang)
+
+    def fwd(spread=0.08, sign=1.0):
+        d = rng.normal(0, spread, (n, 3)); d[:, 1] = sign
+        return _unit(d)
+    x, z = disc(0.8)
+    out["inside"] = (np.stack([x, np.full(n, 0.37 * ds), z], -1), fwd())
+    # on the axis heading straight down it (r < 1e-6 throughout), starting anywhere along the fibre; the last 8 do not
+    # move at all: they use every step the forward allows and keep the record they started with
+    p = np.stack([np.full(n, radius), rng.uniform(0, 0.5, n) * length, np.full(n, radius)], -1)
+    d = np.tile([[0.0, 1.0, 0.0]], (n, 1)); d[-8:] = 0.0
+    out["axis"] = (p, d)
+    # beyond the radius: half heading inwards (they enter), half outwards (they stop on the first iteration)
+    x, z = disc(1.2, 1.02)
+    p = np.stack([x, rng.uniform(0.05, 0.5, n) * length, z], -1)
+    d = fwd(0.05)
+    inward = np.stack([radius - x, np.zeros(n), radius - z], -1) / radius
+    d = _unit(d + np.where(np.arange(n)[:, None] < n // 2, 0.6, -0.6) * inward)
+    out["beyond"] = (p, d)
+    # before y = 0 heading in, and past the far end: half heading on (first-iteration stop), half heading back in
+    x, z = disc(0.7)
+    out["before"] = (np.stack([x, -rng.uniform(0.5, 20, n) * ds, z], -1), fwd())
+    x, z = disc(0.7)
+    out["past"] = (np.stack([x, length + rng.uniform(0.5, 20, n) * ds, z], -1),
+                   fwd(sign=np.where(np.arange(n) < n // 2, 1.0, -1.0)))
+    return {k: (a.astype(np.float32), b.astype(np.float32)) for k, (a, b) in out.items()}
+
+
+def scene(name, seed=0):
+    kind, radius, length, step = SCENES[name]
+    prof = profile(kind)
+    ds = radius / len(prof) / 2 if step is None else step * radius / (len(prof) - 1)      # core/fiber_opt.py:156
+    ds = float(np.float32(ds))
+    sets = ray_sets(radius, length, ds, seed)
+    pos = np.concatenate([s[0] for s in sets.values()])
+    vel = np.concatenate([s[1] for s in sets.values()])
+    labels = np.concatenate([[k] * len(s[0]) for k, s in sets.items()])
+    rng = np.random.default_rng(seed + 11)
+    n = len(pos)
+    # targets behind the start (the record stays the input, j* = 0), near the path ahead (interior j*), and far beyond
+    # the end of the march along the ray's heading (the last state is the closest, j* = K)
+    kind_t = rng.integers(0, 3, n)
+    t_on = rng.uniform(0.15, 0.6, n) * length
+    along = np.where(kind_t == 0, -0.3 * length, np.where(kind_t == 1, t_on, 20.0 * length))
+    tg = pos + along[:, None] * vel + (kind_t == 1)[:, None] * rng.normal(0, 0.02 * radius, (n, 3))
+    tg[vel.any(1) == 0] += [0.0, 0.5, 0.0]                 # the rays that never move: any target, j* = 0
+    dx = rng.normal(size=pos.shape).astype(np.float32)
+    dv = rng.normal(size=pos.shape).astype(np.float32)
+    return dict(prof=prof, radius=radius, length=length, ds=ds, pos=pos, vel=vel, tg=tg.astype(np.float32),
+                labels=labels, dx=dx, dv=dv)
+
+
+def host(s):
+    return CRG.backtrace_cable_rays(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["dx"], s["dv"],
+                                    s["ds"])
+
+
+def autograd64(s, jstar, dtype=torch.float64):
+    """torch.autograd of L = <dx, xt> + <dv, vt> through cable_ad.trace_cable -> (xt, vt, dpos, dvel)."""
+    T = lambda a: torch.tensor(np.asarray(a), dtype=dtype)      # noqa: E731
+    p = T(s["pos"]).requires_grad_(True)
+    v = T(s["vel"]).requires_grad_(True)
+    xt, vt = cable_ad.trace_cable(T(s["prof"]), s["radius"], s["length"], p, v, jstar.astype(np.int64), s["ds"])
+    L = (xt * T(s["dx"])).sum() + (vt * T(s["dv"])).sum()
+    gp, gv = torch.autograd.grad(L, (p, v))
+    return xt.detach().numpy(), vt.detach().numpy(), gp.numpy(), gv.numpy()
+
+
+def rel_err(dp, dv, gp, gv):
+    a = np.concatenate([dp, dv], 1).astype(np.float64)
+    b = np.concatenate([gp, gv], 1).astype(np.float64)
+    return np.linalg.norm(a - b, axis=1) / np.maximum(np.linalg.norm(b, axis=1), 1e-30)
+
+
+# ---- CPU tier -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(SCENES))
+def test_host_routine_matches_float64_autograd(name):
+    """Per-ray relative error of (dpos, dvel) <= GRAD_TOL on the tie-free rays, which are at least 80 % of every scene.
+
+    Mutation check (tried by hand): scaling the Hessian term (sH in cable_adj_recur) by 1 + 1e-3 makes all four scenes
+    fail.  Scaling the returned q (dvel) by 1 + 1e-3 does not: dvel is part of the vector the error is relative to, so that
+    mutation cannot move the error past 1e-3 (measured: max 9.97e-4, median 7e-4 against 1e-7 unmutated); by 1 + 2e-3 all
+    four scenes fail, and the 1 + 1e-3 scaling is caught by test_one_iteration_closed_form (dvel to 1e-6)."""
+    s = scene(name)
+    r = host(s)
+    j, K = r["jstar"], r["steps"] - r["jstar"]
+    x64, v64, gp, gv = autograd64(s, j)
+    tie_free = (np.abs(x64 - r["xt"]).max(1) <= TIE_TOL) & (np.abs(v64 - r["vt"]).max(1) <= TIE_TOL)
+    dropped = 1.0 - tie_free.mean()
+    err = rel_err(r["dpos"], r["dvel"], gp, gv)[tie_free]
+    print(f"{name}: {len(j)} rays, iterations max {K.max()}, j* max {j.max()}; dropped as not tie-free "
+          f"{100 * dropped:.2f} %; rel err max {err.max():.3e} median {np.median(err):.3e}")
+    assert dropped <= MAX_DROPPED
+    # every kind of record and every ray set is represented among the rays compared
+    assert ((j == 0) & tie_free).sum() >= 10 and ((j > 0) & (j < K) & tie_free).sum() >= 10
+    assert ((j == K) & tie_free).sum() >= 10
+    for kind in ("inside", "axis", "beyond", "before", "past"):
+        assert tie_free[s["labels"] == kind].sum() >= 10, kind
+    assert err.max() <= GRAD_TOL
+    # a ray that used every step the forward allows has a record and a gradient like any other
+    max_steps = int(np.float32(4.0) * np.float32(s["length"]) / np.float32(s["ds"]))
+    assert (K == max_steps).sum() >= 8 and np.isfinite(r["dpos"][K == max_steps]).all()
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+def test_record_on_the_input_returns_the_seeds_bitwise(name):
+    s = scene(name)
+    r = host(s)
+    z = r["jstar"] == 0
+    assert z.sum() >= 10
+    assert np.array_equal(r["dpos"][z], s["dx"][z]) and np.array_equal(r["dvel"][z], s["dv"][z])
+    assert np.array_equal(r["xt"][z], s["pos"][z]) and np.array_equal(r["vt"][z], s["vel"][z])
+
+
+def test_one_iteration_closed_form():
+    """j* = K = 1: dpos = dx + ds J(x0)^T (dv + ds dx), dvel = dv + ds dx, J = d(n grad n)/dx at x0."""
+    prof, radius, length = profile("luneburg65"), 1.0, 2.0
+    ds = radius / 65 / 2
+    pos = np.array([[1.31, length + 0.4 * ds, 0.82]], np.float32)      # past the far end, heading on: stops at once
+    vel = np.array([[0.1, 1.0, -0.05]], np.float32)
+    tg = pos + 5.0 * vel
+    dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
+    r = CRG.backtrace_cable_rays(prof, radius, length, pos, vel, tg, dx, dv, ds)
+    assert r["jstar"][0] == 1 and r["steps"][0] == 2
+    P = torch.tensor(prof, dtype=torch.float64)
+    f = lambda y: cable_ad.sample(P, radius, y[None])[1][0]            # noqa: E731
+    J = torch.autograd.functional.jacobian(f, torch.tensor(pos[0], dtype=torch.float64)).numpy()
+    assert np.abs(J).max() > 0.1
+    mu = dv[0].astype(np.float64) + ds * dx[0]
+    np.testing.assert_allclose(r["dvel"][0], mu, rtol=1e-6)
+    np.testing.assert_allclose(r["dpos"][0], dx[0] + ds * J.T @ mu, rtol=1e-5, atol=1e-6)
+
+
+@pytest.mark.parametrize("name", list(SCENES) + ["fuzz1", "fuzz2"])
+def test_replayed_record_is_the_forward_march(name):
+    """The routine's replay == the product's cable_trace_ray (tests/hostcheck), bit for bit, iteration counts included;
+    the record iteration it found is consistent with that record."""
+    s = _fuzz(int(name[4:])) if name.startswith("fuzz") else scene(name)
+    r = host(s)
+    k = HC.trace_cable(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["ds"])
+    assert np.array_equal(r["xt"], k["xt"], equal_nan=True) and np.array_equal(r["vt"], k["vt"], equal_nan=True)
+    K = r["steps"].astype(np.int64) - r["jstar"]
+    assert K.sum() == k["steps_total"] and (r["jstar"] <= K).all()
+    moved = (r["xt"] != s["pos"]).any(1) | (r["vt"] != s["vel"]).any(1)
+    assert (r["jstar"][moved] > 0).all()
+
+
+def test_abi_and_python_surface():
+    """The C symbol is exported and bound, and ADCableTracerC is a class of its own; the other two names stay aliases."""
+    from adjointnonlinearraytracing_amd import _lib, drrt, tracer
+    lib = C.CDLL(_lib.LIB_PATH)
+    assert hasattr(lib, "drrt_backtrace_cable_rays_f32")
+    assert "drrt_backtrace_cable_rays_f32" in _lib.SIGNATURES and _lib.PROF_NAMES[7] == "backtrace_cable_rays"
+    assert callable(drrt.TracerC.backtrace_cable_rays)
+    assert issubclass(tracer.ADCableTracerC, torch.autograd.Function)
+    assert tracer.ADCableTracerC is not tracer.BackCableTracerC
+    assert tracer.ADPlaneTracerC is tracer.BackPlaneTracerC and tracer.ADSDFTracerC is tracer.BackSDFTracerC
+
+
+def test_abi_argument_checks():
+    """Null pointers and a bad profile length, radius, length or step are refused before anything is launched."""
+    from adjointnonlinearraytracing_amd import _lib
+    lib = _lib.load()
+    prof = np.ones(8, np.float32)
+    a = np.zeros((4, 3), np.float32)
+    P = lambda x: C.c_void_p(x.ctypes.data) if x is not None else None    # noqa: E731 (host pointers: never launched)
+
+    def call(rif=prof, rres=8, radius=1.0, length=2.0, n=4, pos=a, tg=a, dx=a, dpos=a, dvel=a, ds=0.01):
+        return lib.drrt_backtrace_cable_rays_f32(P(rif), rres, radius, length, n, P(pos), P(a), P(tg), P(dx), P(a), ds,
+                                                 P(dpos), P(dvel), None, None, 0, 0, None)
+    for kw, rc, msg in ((dict(rif=None), _lib.ERR_ARG, "null rif"), (dict(rres=1), _lib.ERR_BAD_RES, "resolution"),
+                        (dict(rres=1 << 31), _lib.ERR_BAD_RES, "resolution"),
+                        (dict(radius=0.0), _lib.ERR_ARG, "positive"), (dict(length=float("nan")), _lib.ERR_ARG, "positive"),
+                        (dict(ds=0.0), _lib.ERR_ARG, "positive"), (dict(ds=float("inf")), _lib.ERR_ARG, "positive"),
+                        (dict(pos=None), _lib.ERR_ARG, "null ray"), (dict(tg=None), _lib.ERR_ARG, "null ray"),
+                        (dict(dx=None), _lib.ERR_ARG, "null ray"), (dict(dpos=None), _lib.ERR_ARG, "dpos"),
+                        (dict(dvel=None), _lib.ERR_ARG, "dpos")):
+        assert call(**kw) == rc, kw
+        assert msg in _lib.last_error(), (kw, _lib.last_error())
+    assert call(n=0) == 0 and _lib.last_error() == ""       # a valid call clears the message (no state left behind)
+
+
+# ---- GPU tier -------------------------------------------------------------------------------------------------------
+def _t(a, dev):
+    return torch.as_tensor(np.asarray(a), device=dev)
+
+
+def _fuzz(seed, rres=None):
+    c = cases.fuzz_cable_config(seed)
+    s = dict(prof=c["prof"], radius=c["radius"], length=c["length"], ds=c["ds"], pos=c["pos"], vel=c["vel"], tg=c["tg"],
+             dx=c["dx"], dv=c["dv"])
+    if rres is not None:       # a profile above kCableMaxRes (4096): the kernels read it from global memory
+        s["prof"] = (1.5 - 0.4 * np.linspace(0, 1, rres) ** 2 + 0.01 * np.sin(np.arange(rres))).astype(np.float32)
+        s["ds"] = float(np.float32(s["radius"] / (rres - 1) * 40.0))
+    return s
+
+
+GPU_CASES = list(SCENES) + ["fuzz0", "fuzz1", "fuzz2", "fuzz3", "fuzz4", "fuzz1_global5000", "fuzz2_global4097"]
+
+
+def _gpu_case(name):
+    if not name.startswith("fuzz"):
+        return scene(name)
+    seed, _, glob = name[4:].partition("_global")
+    return _fuzz(int(seed), int(glob) if glob else None)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", GPU_CASES)
+def test_kernel_matches_host_routine_bitwise(gpu, name):
+    """k_backtrace_cable_rays == the host build, bit for bit (non-finite values in the same places), and so are the
+    iteration statistics; profiles below and above kCableMaxRes (LDS-staged and read from global memory)."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_case(name)
+    r = host(s)
+    T = drrt.TracerC()
+    dpos, dvel = T.backtrace_cable_rays(_t(s["prof"], gpu), s["radius"], s["length"], _t(s["pos"], gpu), _t(s["vel"], gpu),
+                                        _t(s["tg"], gpu), _t(s["dx"], gpu), _t(s["dv"], gpu), s["ds"])
+    st = drrt.read_stats()
+    dpos, dvel = dpos.cpu().numpy(), dvel.cpu().numpy()
+    assert np.array_equal(np.isfinite(dpos), np.isfinite(r["dpos"])) and np.array_equal(np.isfinite(dvel), np.isfinite(r["dvel"]))
+    assert np.array_equal(dpos, r["dpos"], equal_nan=True) and np.array_equal(dvel, r["dvel"], equal_nan=True)
+    assert st["ray_steps"] == r["ray_steps"] and st["iters"] == r["iters"] and st["n_failed"] == 0
+    # and the forward kernel's record is the one the routine replayed
+    xt, vt, _ = T.trace_cable(_t(s["prof"], gpu), s["radius"], s["length"], _t(s["pos"], gpu), _t(s["vel"], gpu),
+                              _t(s["tg"], gpu), s["ds"])
+    assert np.array_equal(xt.cpu().numpy(), r["xt"], equal_nan=True) and np.array_equal(vt.cpu().numpy(), r["vt"], equal_nan=True)
+
+
+def _grads(cls, s, dev, rif_grad=True, x_grad=False, v_grad=False):
+    rif = _t(s["prof"], dev).requires_grad_(rif_grad)
+    x = _t(s["pos"], dev).requires_grad_(x_grad)
+    v = _t(s["vel"], dev).requires_grad_(v_grad)
+    xt, vt, d2 = cls.apply(rif, s["radius"], s["length"], x, v, _t(s["tg"], dev), s["ds"])
+    ((xt * _t(s["dx"], dev)).sum() + (vt * _t(s["dv"], dev)).sum() + d2.sum()).backward()     # the seed on dist2 is ignored
+    torch.cuda.synchronize()
+    return rif.grad, x.grad, v.grad
+
+
+@pytest.mark.gpu
+def test_adcabletracer_end_to_end(gpu):
+    """ADCableTracerC.apply -> linear loss -> backward: x.grad and v.grad are backtrace_cable_rays' (on the parent x.grad
+    is None), rif.grad is BackCableTracerC's bit for bit whichever ray inputs require grad.  64 rays: one wave, so the
+    adjoint's own summation order is fixed and bitwise equality is meaningful."""
+    from adjointnonlinearraytracing_amd import drrt, tracer
+    s = scene("luneburg65_half")
+    sel = np.random.default_rng(0).choice(len(s["pos"]), 64, replace=False)
+    for k in ("pos", "vel", "tg", "dx", "dv"):
+        s[k] = s[k][sel]
+    dpos, dvel = drrt.TracerC().backtrace_cable_rays(_t(s["prof"], gpu), s["radius"], s["length"], _t(s["pos"], gpu),
+                                                     _t(s["vel"], gpu), _t(s["tg"], gpu), _t(s["dx"], gpu),
+                                                     _t(s["dv"], gpu), s["ds"])
+    assert float(dpos.abs().sum()) > 0
+    g_back, gx, gv = _grads(tracer.BackCableTracerC, s, gpu, True, True, True)
+    assert gx is None and gv is None and float(g_back.abs().sum()) > 0
+    for xg, vg in ((False, False), (True, False), (False, True), (True, True)):
+        g, gx, gv = _grads(tracer.ADCableTracerC, s, gpu, True, xg, vg)
+        assert torch.equal(g, g_back), (xg, vg)
+        assert (gx is not None) == xg and (gv is not None) == vg
+        assert (gx is None or torch.equal(gx, dpos)) and (gv is None or torch.equal(gv, dvel))
+    g, gx, gv = _grads(tracer.ADCableTracerC, s, gpu, False, True, True)
+    assert g is None and torch.equal(gx, dpos) and torch.equal(gv, dvel)
+    with pytest.raises(RuntimeError, match="float32"):
+        tracer.ADCableTracerC.apply(_t(s["prof"], gpu), s["radius"], s["length"],
+                                    _t(s["pos"], gpu).double().requires_grad_(True), _t(s["vel"], gpu), _t(s["tg"], gpu),
+                                    s["ds"])
+
+
+@pytest.mark.gpu
+def test_adcabletracer_launches(gpu):
+    """No ray-gradient kernel without a ray input requiring grad (then the launches are BackCableTracerC's); no dL/dn
+    adjoint with the profile frozen."""
+    from adjointnonlinearraytracing_amd import _lib, tracer
+    s = scene("two_samples")
+    lib = _lib.load()
+
+    def launches(cls, **kw):
+        lib.drrt_profile_begin(256)
+        try:
+            _grads(cls, s, gpu, **kw)
+            return [name for name, _ in _lib.profile_collect()]
+        finally:
+            lib.drrt_profile_end()
+    back = launches(tracer.BackCableTracerC)
+    ad = launches(tracer.ADCableTracerC)
+    assert back == ["trace", "backtrace"] and ad == back
+    frozen = launches(tracer.ADCableTracerC, rif_grad=False, x_grad=True, v_grad=True)
+    assert frozen == ["trace", "backtrace_cable_rays"]
+    both = launches(tracer.ADCableTracerC, v_grad=True)
+    assert sorted(both) == ["backtrace", "backtrace_cable_rays", "trace"]
+
+
+def _demo_case():
+    """A small fibre-experiment case: 17-sample profile, rays on the entry plane (0 < y < ds, so that the product's
+    backward march stops where the forward began), targets 1.2 down the axis: about 80 iterations."""
+    rng = np.random.default_rng(21)
+    radius, length, n = 1.0, 3.0, 512
+    prof = (1.5 - 0.12 * np.linspace(0, 1, 17) ** 2 + 0.01 * rng.random(17)).astype(np.float32)
+    sds = radius / 17 / 2
+    ang = rng.uniform(0, 2 * np.pi, n); rad = 0.7 * radius * np.sqrt(rng.uniform(0, 1, n))
+    pos = np.stack([radius + rad * np.cos(ang), np.full(n, 0.37 * sds), radius + rad * np.sin(ang)], -1).astype(np.float32)
+    vel = rng.normal(0, 0.15, (n, 3)); vel[:, 1] = 1.0
+    vel = _unit(vel).astype(np.float32)
+    tg = np.tile(np.array([[radius, 1.2, radius]], np.float32), (n, 1))
+    return dict(prof=prof, radius=radius, length=length, pos=pos, vel=vel, tg=tg, sds=sds)
+
+
+def _demo_loss(xm, tg, n, radius):
+    return torch.sum((xm - tg) ** 2 / n / radius) / 0.1          # examples/fiber_demo.py run(), camera_span = 0.1
+
+
+@pytest.mark.gpu
+def test_fibre_demo_boundary_index_term(gpu, oracle):
+    """examples/fiber_demo.trace(autodiff=True): the rays entering the march are v / n(boundary), so dL/dv0 . dv0/dn
+    reaches n.grad.  Checked (a) against the autodiff=False gradient plus that term formed by hand from
+    backtrace_cable_rays, and (b) against float64 autograd of the whole radial_index + march restatement.
+
+    Tolerance of (b): the fp32-vs-fp64 spread of the existing dL/dn adjoint on this very case -- the oracle's
+    backtrace_cable in float32 (the kernels' arithmetic) against itself in float64, same records and seeds -- times 2.
+    Measured on an MI355X: spread 9.08e-7, so the bound is 1.82e-6; the autodiff=True gradient is 1.85e-7 from float64
+    autograd and the autodiff=False gradient, which lacks the term, 1.67e-2 (the term is 1.7 % of the gradient here)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import fiber_demo
+    from adjointnonlinearraytracing_amd import drrt
+    c = _demo_case()
+    n, radius, length = len(c["pos"]), c["radius"], c["length"]
+    x, v, tg = _t(c["pos"], gpu), _t(c["vel"], gpu), _t(c["tg"], gpu)
+    grads, seeds = {}, None
+    for ad in (False, True):
+        nt = _t(c["prof"], gpu).requires_grad_(True)
+        xm, vm, _ = fiber_demo.trace(nt, (x, v), tg, radius, length, autodiff=ad)
+        L = _demo_loss(xm, tg, n, radius)
+        seeds = torch.autograd.grad(L, xm, retain_graph=True)[0]
+        L.backward()
+        grads[ad] = nt.grad.clone()
+    # (a) the boundary term by hand
+    nt = _t(c["prof"], gpu).requires_grad_(True)
+    v0 = v / fiber_demo.radial_index(nt, radius, x)[:, None]
+    _, dvel = drrt.TracerC().backtrace_cable_rays(nt.detach(), radius, length, x, v0.detach(), tg, seeds,
+                                                  torch.zeros_like(seeds), c["sds"])
+    term, = torch.autograd.grad((v0 * dvel).sum(), nt)
+    assert torch.allclose(grads[True] - grads[False], term, rtol=1e-4, atol=1e-6 * float(term.abs().max()))
+    # (b) float64 autograd of the whole chain, records at the fp32 march's iterations
+    v0_np = v0.detach().cpu().numpy()
+    r = CRG.backtrace_cable_rays(c["prof"], radius, length, c["pos"], v0_np, c["tg"], seeds.cpu().numpy(),
+                                 np.zeros_like(c["pos"]), c["sds"])
+    P = torch.tensor(c["prof"], dtype=torch.float64, requires_grad=True)
+    X, V, TG = (torch.tensor(a, dtype=torch.float64) for a in (c["pos"], c["vel"], c["tg"]))
+    V0 = V / fiber_demo.radial_index(P, radius, X)[:, None]
+    xt64, _ = cable_ad.trace_cable(P, radius, length, X, V0, r["jstar"].astype(np.int64), c["sds"])
+    g64, = torch.autograd.grad(_demo_loss(xt64, TG, n, radius), P)
+    g64 = g64.numpy()
+    # the yardstick: the oracle's own fp32-vs-fp64 spread of backtrace_cable on this case
+    zeros = np.zeros_like(c["pos"])
+    with oracle.arith("factored"):
+        o32 = oracle.backtrace_cable(c["prof"], radius, length, r["xt"], r["vt"], seeds.cpu().numpy(), zeros, c["sds"],
+                                     dtype=np.float32)
+    o64 = oracle.backtrace_cable(c["prof"], radius, length, r["xt"], r["vt"], seeds.cpu().numpy(), zeros, c["sds"],
+                                 dtype=np.float64)
+    spread = cases.rel_l2(o32["grad"], o64["grad"])
+    e_ad = cases.rel_l2(grads[True].cpu().numpy(), g64)
+    e_no = cases.rel_l2(grads[False].cpu().numpy(), g64)
+    print(f"fibre demo: oracle fp32-vs-fp64 spread of backtrace_cable {spread:.3e} (bound {2 * spread:.3e}); "
+          f"autodiff=True vs float64 autograd {e_ad:.3e}; autodiff=False {e_no:.3e}")
+    assert e_ad <= 2 * spread
+    # and the term is no rounding matter: without it the gradient is far outside that bound
+    assert e_no > 100 * 2 * spread and float(term.norm()) > 100 * 2 * spread * float(grads[True].norm())
+
+
+@pytest.mark.gpu
+def test_fibre_demo_optimises_with_autodiff(gpu):
+    """examples/fiber_demo.run(autodiff=True): the experiment's flow with the boundary-index term in the gradient -- finite
+    throughout, and the loss falls as it does without the term (test_end_to_end.test_fibre_experiment_flow)."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    import fiber_demo
+    n, hist = fiber_demo.run(res_list=(5, 9), iters=20, nbins=24, src_type="cone", verbose=False, autodiff=True)
+    assert n.shape == (9,) and bool(torch.isfinite(n).all()) and np.isfinite(hist).all()
+    print(f"fibre demo, autodiff=True: loss {hist[0]:.5f} -> {hist[-1]:.5f}")
+    assert np.mean(hist[-5:]) < np.mean(hist[:5])
