@@ -73,6 +73,8 @@ SIGNATURES = {
     "drrt_backtrace_sdf_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail),
     "drrt_backtrace_cable_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _f, _vp] + _tail),
     "drrt_backtrace_cable_rays_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp] + _tail),
+    "drrt_backtrace_pln_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
+    "drrt_backtrace_sdf_rays_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_sensor_splat_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _u, _vp]),
     "drrt_sensor_splat_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
     "drrt_sensor_far_splat_f32": (_i, [_sz, _vp, _vp, _f, _vp, _vp, _i, _f, _vp, _u, _vp]),
@@ -107,7 +109,7 @@ SIGNATURES = {
 }
 
 PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "backtrace_rays",
-              7: "backtrace_cable_rays"}
+              7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays"}
 
 _lib: Optional[C.CDLL] = None
 

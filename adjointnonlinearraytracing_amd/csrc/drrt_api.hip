@@ -1,6 +1,6 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout, visit-order / step hand-over, per-kernel timing, and the launches of the
-// kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the three
+// kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip / drrt_cable.hip / drrt_cable_rays.hip / drrt_stop_rays.hip.  Host code, plus the three
 // small utility kernels that belong to no march (pair copy of the grid, q16 encode / decode).
 #include "drrt_march.h"
 
@@ -224,6 +224,21 @@ static int maybe_sort(const Vol& V, float h, size_t n, const void* pos, const vo
 #define LAUNCH_CHECK(where)                                              \
   do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail_hip(e_, where); } while (0)
 
+// The second pass of trace_pln / trace_sdf and of their ray-state adjoints needs the global loop count of the first: a
+// library-owned stats block, one per device (allocated once), for callers that pass none.  It is shared by every stream of
+// that device: callers that run such calls concurrently on several streams of one device must pass their own stats block.
+static int private_stats(drrt_stats** stats) {
+  constexpr int kMaxDev = 64;
+  static drrt_stats* priv[kMaxDev] = {};
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
+  if (dev < 0 || dev >= kMaxDev) return fail(DRRT_ERR_ARG, "device ordinal out of range; pass a stats block");
+  if (!priv[dev]) { e = hipMalloc((void**)&priv[dev], sizeof(drrt_stats)); if (e != hipSuccess) return fail_hip(e, "hipMalloc(stats)"); }
+  *stats = priv[dev];
+  return DRRT_OK;
+}
+
 template <int MODE>
 static int run_trace(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
                      const void* pos, const void* vel, const float* pln_o, const float* pln_d,
@@ -238,19 +253,7 @@ static int run_trace(const float* rif, const float* sdf, long long nvox, const i
   if (n == 0) return zero_stats(stats, s);
   if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (MODE == 1 && (!pln_o || !pln_d || !failmask)) return fail(DRRT_ERR_ARG, "null plane/failmask pointer");
-  if ((MODE == 1 || MODE == 2) && !stats) {
-    // the second pass needs the global loop count: library-owned block, one per device (allocated once).  It is
-    // shared by every stream of that device: callers that run trace_pln / trace_sdf concurrently on several streams
-    // of one device must pass their own stats block.
-    constexpr int kMaxDev = 64;
-    static drrt_stats* priv[kMaxDev] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail_hip(e, "hipGetDevice");
-    if (dev < 0 || dev >= kMaxDev) return fail(DRRT_ERR_ARG, "device ordinal out of range; pass a stats block");
-    if (!priv[dev]) { e = hipMalloc((void**)&priv[dev], sizeof(drrt_stats)); if (e != hipSuccess) return fail_hip(e, "hipMalloc(stats)"); }
-    stats = priv[dev];
-  }
+  if ((MODE == 1 || MODE == 2) && !stats) { rc = private_stats(&stats); if (rc) return rc; }
   if (MODE == 2 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
   if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
   rc = zero_stats(stats, s); if (rc) return rc;
@@ -578,6 +581,64 @@ extern "C" int drrt_backtrace_rays_f32(const float* rif, long long nvox, const i
   }
   LAUNCH_CHECK("k_backtrace_rays");
   return DRRT_OK;
+}
+
+// ray-state adjoints of trace_plane (MODE 1) and trace_sdf (MODE 2): drrt_stop_rays.hip
+template <int MODE>
+static int run_backtrace_stop_rays(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
+                                   const float* pos, const float* vel, const float* pln_o, const float* pln_d,
+                                   const float* dx, const float* dv, float h, float ds, float* dpos, float* dvel,
+                                   drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  const OrderHint hint = take_hint();
+  g_err[0] = 0;
+  hipStream_t s = (hipStream_t)stream;
+  StopRayGradArgs a{};
+  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
+  rc = check_steps(h, ds); if (rc) return rc;
+  if (MODE == 2 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
+  if (n == 0) return zero_stats(stats, s);
+  if (!pos || !vel || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (MODE == 1 && (!pln_o || !pln_d)) return fail(DRRT_ERR_ARG, "null plane pointer");
+  if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
+  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  const size_t off = (flags & DRRT_FLAG_SORT_RAYS) ? align_up(sort_workspace_bytes(n), 256) : 0;   // as trace_sdf's flags
+  if (!ws || ws_bytes < off + n) return fail(DRRT_ERR_ARG, "workspace too small for the second-pass flags (see drrt_workspace_bytes)");
+  if (!stats) { rc = private_stats(&stats); if (rc) return rc; }
+  rc = zero_stats(stats, s); if (rc) return rc;
+  rc = maybe_sort(a.vol, h, n, pos, vel, 1.f, flags, ws, ws_bytes, &a.perm, s, hint); if (rc) return rc;
+  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
+  a.again = (uint8_t*)ws + off;
+  if (a.perm != nullptr) {                  // an order that lives where the flags go (a hint into this very workspace from a
+    const char* o = (const char*)a.perm;    // call that sorted, handed to one that does not) is not used: slower, never wrong
+    const char* f = (const char*)a.again;
+    if (o < f + n && f < o + n * sizeof(uint32_t)) a.perm = nullptr;
+  }
+  a.sdf = sdf; a.pos = pos; a.vel = vel; a.pln_o = pln_o; a.pln_d = pln_d; a.dx = dx; a.dv = dv;
+  a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
+  a.max_steps = (MODE == 2) ? steps_sdf(h, res, ds) : steps_fwd(h, res, ds);      // the forward's bound
+  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
+  {
+    ProfScope prof(MODE == 1 ? DRRT_PROF_BACKTRACE_PLN_RAYS : DRRT_PROF_BACKTRACE_SDF_RAYS, s);
+    launch_backtrace_stop_rays(MODE, a, s);
+  }
+  LAUNCH_CHECK("k_backtrace_stop_rays");
+  return DRRT_OK;
+}
+
+extern "C" int drrt_backtrace_pln_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                           const float* pos, const float* vel, const float* pln_o, const float* pln_d,
+                                           const float* dx, const float* dv, float h, float ds, float* dpos, float* dvel,
+                                           drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  return run_backtrace_stop_rays<1>(rif, nullptr, nvox, res, n, pos, vel, pln_o, pln_d, dx, dv, h, ds, dpos, dvel, stats,
+                                    ws, ws_bytes, flags, stream);
+}
+
+extern "C" int drrt_backtrace_sdf_rays_f32(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
+                                           const float* pos, const float* vel, const float* dx, const float* dv, float h,
+                                           float ds, float* dpos, float* dvel, drrt_stats* stats, void* ws,
+                                           size_t ws_bytes, unsigned flags, void* stream) {
+  return run_backtrace_stop_rays<2>(rif, sdf, nvox, res, n, pos, vel, nullptr, nullptr, dx, dv, h, ds, dpos, dvel, stats,
+                                    ws, ws_bytes, flags, stream);
 }
 
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }

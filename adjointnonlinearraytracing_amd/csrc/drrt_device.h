@@ -923,6 +923,144 @@ DRRT_HD RayGrad cable_backtrace_ray_state(const Cyl& C, float ds, int max_steps,
   return g;
 }
 
+// Ray-state adjoint of trace_plane (MODE 1) / trace_sdf (MODE 2) for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on
+// the record (xt, vt) = (x_j, v_j), given only the forward's inputs (p0, v0) and its plane / SDF.  j = the iteration count at
+// the LAST cross (fwd_step_c :378-386), 0 when there was none (the record is the input).  Iteration k samples n grad n at x_k
+// only when m_k, the forward's `inside` flag at that moment, was set; j and every m_k are held fixed (as autograd through a
+// masked select does).
+//   * The forward is replayed from (p0, v0) with fwd_init / fwd_step_c<MODE> themselves, looped as trace_ray loops them
+//     (FULL = false: until the ray is flagged escaped, at most max_steps) or as ray_full does (FULL = true: exactly `total`
+//     iterations of the reference's global loop, for the rays the first pass flags with `again`, see plane_again and
+//     trace_ray<2>).  A flagged ray of the first pass returns after its replay: only its second pass knows the record.
+//   * trace_plane, never flagged escaped (failmask set; xt is the final x, vt stale): zero gradient, failed = true.
+//     trace_sdf has no such fix-up: a ray that never crosses keeps (xt, vt) = (p0, v0), j = 0.
+//   * j = 0: the gradient is the identity (dx, dv).
+//   * otherwise the iterations j-1 .. 0 are undone run by run, a run being a stretch [lo, hi) of equal m_k, seeded like adj_init
+//     (lambda = dx, mu = dv + ds dx, and q = dv: q is dL/dv_k, mu runs one iteration ahead of it as adj_recur leaves it):
+//       sampled run   hi - lo reverse iterations of adj_sample<0> / adj_recur with neither the backward-escape test nor the
+//                     adjoint's step bound; the last of them samples at the replayed x_lo itself instead of its
+//                     reconstruction x_{lo+1} - ds v_{lo+1} (a start exactly on a face; both existing routines do the same);
+//       free flight   lambda unchanged, mu and q += (hi - lo) ds lambda, and x set to the replayed x_lo.
+//     First pass: the march stops at its first cross, so the masks are F^e T^(j-e) -- the run that ends at j is known from
+//     the replay and what is left of it is the free-flight prefix from p0.  Second pass: the masks need not be monotone
+//     (a ray that starts in bounds past its plane and heads back through it: T, F..F, T..T, F -- m_0 carries no plane term);
+//     each earlier run is found by replaying the forward again up to it, so no mask is stored and any sequence is honoured.
+//   * steps = every forward iteration replayed + every reverse iteration; fwd = the iterations of the first replay (the
+//     ray's count in the forward's own statistics: its maximum over the call is the global loop count of the second pass).
+// The 1/h of DRRT_FLAG_CORRECTED_H does not enter; no gradient flows to the plane, the SDF, h or ds.
+// `taps(c)` returns the 8 taps of cell c of the index grid.  `rec` (optional) receives the replayed record.
+struct StopRecord { float xt[3], vt[3]; unsigned j; bool esc; };
+struct StopGrad { float dp[3], dv[3]; unsigned steps, fwd; bool failed, again; };
+
+template <int MODE>
+DRRT_HD void stop_fwd_begin(const Vol& V, const float p0[3], const float v0[3], const float* pln_o, const float* pln_d,
+                            FwdState& f, Cell& c) {
+  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
+  f.aux0 = f.aux1 = f.aux2 = f.aux3 = f.aux4 = f.aux5 = 0.f;
+  if (MODE == 1) {
+    f.aux0 = pln_o[0]; f.aux1 = pln_o[1]; f.aux2 = pln_o[2];
+    f.aux3 = pln_d[0]; f.aux4 = pln_d[1]; f.aux5 = pln_d[2];
+  }
+  fwd_init(V, f);
+  c = locate(V, f.x, f.y, f.z);
+}
+
+template <int MODE, bool FULL, typename TapFn>
+DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict__ sdf, float ds, int max_steps,
+                                          unsigned total, const float p0[3], const float v0[3], const float* pln_o,
+                                          const float* pln_d, const float dx[3], const float dv[3], TapFn&& taps,
+                                          StopRecord* rec = nullptr) {
+  static_assert(MODE == 1 || MODE == 2, "trace_plane or trace_sdf");
+  FwdState f;
+  Cell c;
+  stop_fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
+  const unsigned lim = FULL ? total : (max_steps > 0 ? (unsigned)max_steps : 0u);
+  unsigned steps = 0, j = 0;
+  unsigned lo = 0, jlo = 0;                          // first iteration of the current sampled run / of the one that ended at j
+  float lx = f.x, ly = f.y, lz = f.z, jx = f.x, jy = f.y, jz = f.z;   // the positions sampled there
+  bool prev = false;
+  for (unsigned it = 0; it < lim; ++it) {
+    const bool was = f.inside;
+    if (was & !prev) { lo = it; lx = f.x; ly = f.y; lz = f.z; }
+    prev = was;
+    Taps t = taps_zero();
+    if (was) t = taps(c);
+    fwd_step_c<MODE>(V, sdf, ds, f, c, t);
+    ++steps;
+    if (was & !f.inside) { j = steps; jlo = lo; jx = lx; jy = ly; jz = lz; }     // cross: the record was written
+    if (!FULL && f.esc) break;
+  }
+  if (rec) {
+    rec->xt[0] = f.xtx; rec->xt[1] = f.xty; rec->xt[2] = f.xtz;
+    rec->vt[0] = f.vtx; rec->vt[1] = f.vty; rec->vt[2] = f.vtz;
+    if (MODE == 1 && !f.esc) { rec->xt[0] = f.x; rec->xt[1] = f.y; rec->xt[2] = f.z; }   // :167
+    rec->j = j; rec->esc = f.esc;
+  }
+  StopGrad g;
+  g.failed = false; g.again = false; g.fwd = steps; g.steps = steps;
+  g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+  if (MODE == 1 && !f.esc) {
+    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    g.failed = true;
+    return g;
+  }
+  if (!FULL) {
+    g.again = MODE == 1 ? (f.esc && plane_again(V, f)) : (f.esc & f.inside);
+    if (g.again) return g;
+  }
+  if (j == 0) return g;
+  AdjState s;
+  s.x = f.xtx; s.y = f.xty; s.z = f.xtz; s.vx = f.vtx; s.vy = f.vty; s.vz = f.vtz;
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
+  s.active = true; s.outside = false;
+  float qx = dv[0], qy = dv[1], qz = dv[2];
+  unsigned hi = j;
+  bool sampled = true;
+  lo = jlo; lx = jx; ly = jy; lz = jz;
+  for (;;) {
+    if (sampled) {
+      for (unsigned k = hi; k > lo; --k) {
+        s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+        if (k == lo + 1u) { s.x = lx; s.y = ly; s.z = lz; }                // the run's first sample, as the forward took it
+        const Cell ca = locate(V, s.x, s.y, s.z);
+        AdjSample m;
+        (void)adj_sample<0>(V, nullptr, ds, s, ca, taps(ca), m);            // v_{k-1}; the escape test is not used
+        const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);         // :430
+        qx = s.mx; qy = s.my; qz = s.mz;
+        adj_recur(V, ds, s, m, dn);
+      }
+      g.steps += hi - lo;
+    } else {
+      const float ads = (float)(hi - lo) * ds;
+      qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
+      s.mx = fmaf(ads, s.lx, s.mx); s.my = fmaf(ads, s.ly, s.my); s.mz = fmaf(ads, s.lz, s.mz);
+      s.x = lx; s.y = ly; s.z = lz;
+    }
+    hi = lo;
+    if (hi == 0) break;
+    if (!FULL) {                                     // F^e T^(j-e): the free-flight prefix from p0
+      sampled = false; lo = 0;
+      continue;
+    }
+    // the run that holds iteration hi - 1: replay the forward up to it
+    stop_fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
+    for (unsigned it = 0;; ++it) {
+      if (it == 0 || f.inside != prev) { lo = it; lx = f.x; ly = f.y; lz = f.z; }
+      prev = f.inside;
+      if (it == hi - 1u) break;
+      Taps t = taps_zero();
+      if (f.inside) t = taps(c);
+      fwd_step_c<MODE>(V, sdf, ds, f, c, t);
+      ++g.steps;
+    }
+    sampled = prev;
+  }
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  return g;
+}
+
 #if defined(__HIPCC__)
 // fp32 atomic add without return: one global_atomic_add_f32 on gfx950 (no CAS loop).
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }

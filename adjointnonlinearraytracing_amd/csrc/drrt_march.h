@@ -8,6 +8,8 @@
 //   drrt_adjoint_ring.hip   backtrace / backtrace_sdf, fitted ring window (its own translation unit: it is built with a
 //                           different instruction-scheduling strategy, csrc/Makefile)
 //   drrt_adjoint_rays.hip   backtrace_rays: dL/dpos, dL/dvel of trace (ray-state adjoint, no grid writes)
+//   drrt_stop_rays.hip      backtrace_pln_rays / backtrace_sdf_rays: dL/dpos, dL/dvel of trace_plane / trace_sdf (ray-state
+//                           adjoint with the forward replayed, no grid writes)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -409,6 +411,23 @@ struct RayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// ray-state adjoint of trace_plane / trace_sdf (drrt_stop_rays.hip): takes the forward's inputs only and replays it
+struct StopRayGradArgs {
+  Vol vol;
+  const float* sdf;                         // trace_sdf
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* pln_o; const float* pln_d;   // trace_plane
+  const float* dx; const float* dv;         // seeds on the recorded (xt, vt)
+  float* dpos; float* dvel;
+  uint8_t* again;                           // workspace, n bytes: rays the first pass hands to the second
+  const uint32_t* perm;                     // nullable: visit order (first pass)
+  drrt_stats* stats;                        // never null: iters carries the global loop count from the first pass to the second
+  size_t n;
+  float ds;
+  int max_steps;                            // the FORWARD's (steps_fwd / steps_sdf)
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -466,6 +485,8 @@ void launch_backtrace_ring(int mode, bool dbg, const BackArgs& a, hipStream_t s)
 void launch_backtrace_ring_sparse(const BackArgs& a, hipStream_t s, int which);   // the sparse-only instantiations (backtrace)
 // ray-state adjoint (drrt_adjoint_rays.hip)
 void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
+// ray-state adjoint of trace_plane (mode 1) / trace_sdf (mode 2): first pass, then the flagged rays (drrt_stop_rays.hip)
+void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

@@ -753,6 +753,55 @@ class TracerC:
                 float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
         return dpos, dvel
 
+    def _backtrace_stop_rays(self, rif, sdf, res, pos, vel, pln, dx, dv, h, ds, order):
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            order = _valid_order(order)
+            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
+            n = pos_.shape[0]
+            vel_, dx_, dv_ = _rays(vel, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
+            if sdf is not None:
+                sdf_ = _f32(sdf, dev).reshape(-1)
+                if sdf_.numel() != rif_.numel():
+                    raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
+            else:
+                po, pd = _rays(pln[0], dev, n), _rays(pln[1], dev, n)
+            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
+            fl = _flags()
+            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
+            tail = (float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev))
+            try:
+                _hint(order, n)
+                _bump_order_gen(dev)                   # the second-pass flags go where the forward left its iteration counts
+                if sdf is not None:
+                    _lib.check(_lib.load().drrt_backtrace_sdf_rays_f32(
+                        _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(dx_), _p(dv_), *tail))
+                else:
+                    _lib.check(_lib.load().drrt_backtrace_pln_rays_f32(
+                        _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd), _p(dx_), _p(dv_), *tail))
+            finally:
+                _clear_hint()
+            if sdf is None:
+                _warn_failed(st)
+        return dpos, dvel
+
+    def backtrace_pln_rays(self, rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds,
+                           order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ray-state adjoint of ``trace_pln`` (drrt_backtrace_pln_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),
+        (n,3) fp32.  `pos`, `vel`, `pln_o`, `pln_d` are the forward call's inputs, `dx`, `dv` the seeds on its (xt, vt); the
+        call replays the forward (both of its passes) to find the iteration of each ray's record and which iterations
+        were refracted, so it takes neither (xt, vt) nor a step count.  Rays that failed the forward get a zero gradient
+        (and the "failed to exit all rays" message).  Not in the reference's C++ Tracer: it gets these through enoki
+        autodiff (core/tracer.py:122-178).  fp32 rays only."""
+        return self._backtrace_stop_rays(rif, None, res, pos, vel, (pln_o, pln_d), dx, dv, h, ds, order)
+
+    def backtrace_sdf_rays(self, rif, sdf, res, pos, vel, dx, dv, h, ds,
+                           order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ray-state adjoint of ``trace_sdf`` (drrt_backtrace_sdf_rays_f32) -> (dL/dpos, dL/dvel), (n,3) fp32; as
+        ``backtrace_pln_rays``.  A ray that never crosses the surface keeps its input as the record and gets (dx, dv).
+        The reference: enoki autodiff, core/tracer.py:181-234.  fp32 rays only."""
+        return self._backtrace_stop_rays(rif, sdf, res, pos, vel, None, dx, dv, h, ds, order)
+
     # ---- print-only smoke methods of the reference (src/tracer.cpp:16-33) ------------------
     def test(self) -> torch.Tensor:
         """Tracer::tester: returns a zero 3-vector."""

@@ -9,8 +9,8 @@ Contract reproduced from the reference:
     ``ctx.save_for_backward`` -- no copies, and autograd's version check turns an in-place update of ``rif`` (or of
     the returned exit rays) between forward and backward into a RuntimeError instead of a silently wrong gradient;
   * backward returns ``drif`` reshaped to ``rif.shape`` and ``None`` for every other input
-    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC and ADCableTracerC (below) are the classes
-    with ray gradients;
+    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC, ADCableTracerC, ADRayPlaneTracerC and
+    ADRaySDFTracerC (below) are the classes with ray gradients;
   * ``BackPlaneTracerC`` / ``BackTargetTracerC`` backward run the GENERIC ``backtrace`` from the
     recorded state (``:376,422``); ``BackPlaneTracerC.backward`` zeroes ``grad_x`` on
     rays whose ``outmask`` gradient is set, as written (``:366-367``).
@@ -224,11 +224,108 @@ class ADCableTracerC(torch.autograd.Function):
         return drif, None, None, dx0, dv0, None, None
 
 
-# The other enoki-autodiff classes of the reference (core/tracer.py:69-236; two of them are broken upstream)
-# resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working, with the documented
-# difference that no gradient flows to x, v.  ADTracerC and ADCableTracerC carry ray gradients: the ray-state adjoint of
-# trace is exact because its rays end at the sample where they leave the box, and the cable's replays its forward to find
-# the iteration of the recorded sample.  The plane and target stops record a sample that is not where the iteration count
-# K ends (the march runs on past it), and the SDF march has a kernel of its own.
+class ADRayPlaneTracerC(torch.autograd.Function):
+    """``apply(rif, x, v, sp, sn, h, ds) -> (xt, vt, failmask bool)`` with gradients for ``rif`` AND the rays: what the
+    reference's ADPlaneTracerC (core/tracer.py:122-178, broken upstream) is meant to be.  The name is new because
+    ``ADPlaneTracerC`` stays the alias of BackPlaneTracerC it has always been here.
+
+    The forward is the call BackPlaneTracerC makes, dL/drif is the same generic ``backtrace`` from the recorded state and
+    dL/dx, dL/dv come from the ray-state adjoint ``TracerC.backtrace_pln_rays`` (drrt_backtrace_pln_rays_f32), which replays
+    the forward from its inputs: (x, v, sp, sn) are kept (private copies) only when ``x`` or ``v`` requires grad.  Each
+    adjoint runs only for the inputs that ask for a gradient, so with neither ray input requiring grad this launches
+    exactly what BackPlaneTracerC launches.  The incoming seeds are treated as BackPlaneTracerC.backward treats them and
+    the same seeds go to both adjoints.  Rays that failed the forward get a zero ray gradient; no gradient flows to the
+    plane or to ``failmask``.  fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, sp, sn, h, ds):
+        ctx.shape = rif.shape
+        ctx.h, ctx.ds = h, ds
+        ray_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
+            raise RuntimeError("ADRayPlaneTracerC: gradients w.r.t. x, v need float32 rays")
+        outx, outv, outmask = drrt.TracerC().trace_pln(
+            rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), sp.detach(), sn.detach(), h, ds)
+        ctx.order = drrt.keep_order(drrt.last_order)
+        if ray_grad:
+            ctx.ray_devices = (x.device, v.device)
+            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v, sp, sn))
+        outmask = outmask.to(torch.bool)
+        ctx.mark_non_differentiable(outmask)
+        ctx.save_for_backward(rif, outx, outv)
+        return outx, outv, outmask
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, outmask):
+        rif, outx, outv = ctx.saved_tensors
+        if outmask is not None and outmask.dtype == torch.bool:     # as BackPlaneTracerC.backward
+            grad_x = grad_x.clone()
+            grad_x[outmask] = 0
+        drif = dx0 = dv0 = None
+        if ctx.needs_input_grad[0]:
+            drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
+                                            ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            x0, v0, sp, sn = ctx.rays
+            dpos, dvel = drrt.TracerC().backtrace_pln_rays(rif.detach().flatten(), ctx.shape, x0, v0, sp, sn,
+                                                           grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
+            if ctx.needs_input_grad[1]:
+                dx0 = dpos.to(ctx.ray_devices[0])
+            if ctx.needs_input_grad[2]:
+                dv0 = dvel.to(ctx.ray_devices[1])
+        return drif, dx0, dv0, None, None, None, None
+
+
+class ADRaySDFTracerC(torch.autograd.Function):
+    """``apply(rif, sdf, x, v, h, ds) -> (xt, vt)`` with gradients for ``rif`` AND the rays (the reference's ADSDFTracerC,
+    core/tracer.py:181-234; ``ADSDFTracerC`` stays the alias of BackSDFTracerC here).
+
+    The forward is the call BackSDFTracerC makes, dL/drif is the same ``backtrace_sdf`` and dL/dx, dL/dv come from
+    ``TracerC.backtrace_sdf_rays`` (drrt_backtrace_sdf_rays_f32), which replays the forward from (x, v): private copies
+    of those are kept only when ``x`` or ``v`` requires grad (the SDF is saved anyway).  Each adjoint runs only for the
+    inputs that ask for a gradient.  A ray that never crosses the surface has its input as its record and the identity as
+    its ray gradient; no gradient flows to the SDF.  fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, sdf, x, v, h, ds):
+        ctx.shape = rif.shape
+        ctx.h, ctx.ds = h, ds
+        ray_grad = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
+        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
+            raise RuntimeError("ADRaySDFTracerC: gradients w.r.t. x, v need float32 rays")
+        outx, outv = drrt.TracerC().trace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, x.detach(),
+                                              v.detach(), h, ds)
+        ctx.order = drrt.keep_order(drrt.last_order)
+        if ray_grad:
+            ctx.ray_devices = (x.device, v.device)
+            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v))
+        ctx.save_for_backward(rif, sdf, outx, outv)
+        return outx, outv
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v):
+        rif, sdf, outx, outv = ctx.saved_tensors
+        drif = dx0 = dv0 = None
+        if ctx.needs_input_grad[0]:
+            drif = drrt.TracerC().backtrace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, outx, outv,
+                                                grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
+        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
+            x0, v0 = ctx.rays
+            dpos, dvel = drrt.TracerC().backtrace_sdf_rays(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape,
+                                                           x0, v0, grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
+            if ctx.needs_input_grad[2]:
+                dx0 = dpos.to(ctx.ray_devices[0])
+            if ctx.needs_input_grad[3]:
+                dv0 = dvel.to(ctx.ray_devices[1])
+        return drif, None, dx0, dv0, None, None
+
+
+# The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken
+# upstream, SURVEY Q15) resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working,
+# with the documented difference that no gradient flows to x, v through THESE names.  The classes with ray gradients are
+# ADTracerC, ADCableTracerC, ADRayPlaneTracerC and ADRaySDFTracerC: the ray-state adjoint of trace is exact because its rays
+# end at the sample where they leave the box; the other three replay their forward to find the iteration of the recorded
+# sample (and, for the plane and SDF stops, which iterations were refracted).  trace_target has no AD class in the
+# reference and none here.
 ADPlaneTracerC = BackPlaneTracerC
 ADSDFTracerC = BackSDFTracerC

@@ -392,6 +392,43 @@ DRRT_API int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, float 
                              drrt_stats* stats, void* workspace, size_t workspace_bytes,
                              unsigned flags, void* stream);
 
+/* Ray-state adjoints of Tracer::trace_plane and Tracer::trace_sdf: dL/dpos, dL/dvel of the rays that entered
+ * drrt_trace_pln_f32 / drrt_trace_sdf_f32 (the reference gets them from enoki autodiff through those marches,
+ * core/tracer.py:122-234).  No contribution to dL/dn is formed.
+ *   pos, vel       the forward call's inputs, (n,3) fp32;  pln_o, pln_d / sdf: its plane / signed-distance grid
+ *   dx, dv         seeds on its outputs (xt, vt)
+ *   dpos, dvel     out: (n,3) fp32
+ * Contract: (xt, vt) is the state (x_j, v_j) after the LAST iteration j at which the ray went from inside to outside
+ * (j = 0: the input itself), and iteration k is refracted only when the forward's `inside` flag m_k was set.  The forward
+ * reports neither, so the call replays it from (pos, vel) with the forward's own fp32 operations -- both of its passes: every
+ * ray until it is flagged escaped, then the rays whose record can still change over the call's global iteration count (the
+ * maximum over its rays), see drrt_trace_pln_f32 -- and then undoes the iterations j-1 .. 0 from (xt, vt), seeded like
+ * drrt_backtrace_f32 (lambda = dx, mu = dv + ds dx), with j and every m_k held fixed: a refracted iteration is one reverse
+ * iteration of drrt_backtrace_f32 without its backward-escape test and step bound, a masked one is free flight (lambda
+ * unchanged, mu += ds lambda).  The first sample of every refracted stretch is taken at the replayed position itself.
+ * j = 0 gives (dx, dv) bit for bit.  trace_plane: a ray that never escaped (failmask set: xt is its final position, vt is
+ * stale) gets a zero gradient and counts in stats->n_failed.  trace_sdf: a ray that never crosses keeps (xt, vt) = (pos, vel)
+ * and gets (dx, dv); stats->n_failed = 0.  stats->ray_steps = replayed forward iterations + reverse iterations;
+ * stats->iters = the replayed forward's global iteration count (drrt_trace_*'s own stats->iters).  The result does not
+ * depend on DRRT_FLAG_CORRECTED_H nor on the visit order; no gradient flows to the plane, the SDF, h or ds.
+ * Workspace: as for drrt_trace_sdf_f32 (n flag bytes behind the sort buffers; drrt_workspace_bytes() covers them).  Without
+ * a stats block the library's per-device one carries the iteration count, as in drrt_trace_pln_f32.
+ * Flags: DRRT_FLAG_SORT_RAYS (sorts the rays by their entry voxel), DRRT_FLAG_PAIR_GRID / _PAIR_REUSE and
+ * DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32; the order hint (normally the paired forward's) is consumed like there,
+ * the step hint is ignored.  fp32 only.                                                                                  */
+DRRT_API int drrt_backtrace_pln_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                             const float* pos, const float* vel, const float* pln_o, const float* pln_d,
+                             const float* dx, const float* dv, float h, float ds,
+                             float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+DRRT_API int drrt_backtrace_sdf_rays_f32(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
+                             const float* pos, const float* vel,
+                             const float* dx, const float* dv, float h, float ds,
+                             float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
 /* ---- sensor image splat (SURVEY.md 8.8 "next" row 1; the reference does this in torch) ----------
  * Forward: core/sensor.py:5-28 generate_sensor = trace_rays_to_plane (:195-202) + sensor frame
  * (t1 = n x t2, t2; get_tan_vecs :219-231 is evaluated by the caller) + foreshortening |v.n| +
@@ -525,6 +562,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_QUAD       5   /* build of the pair copy of the grid   */
 #define DRRT_PROF_BACKTRACE_RAYS 6   /* ray-state adjoint (drrt_backtrace_rays_f32) */
 #define DRRT_PROF_BACKTRACE_CABLE_RAYS 7   /* ray-state adjoint of the cable march (drrt_backtrace_cable_rays_f32) */
+#define DRRT_PROF_BACKTRACE_PLN_RAYS 8   /* ray-state adjoint of trace_plane (drrt_backtrace_pln_rays_f32), both passes */
+#define DRRT_PROF_BACKTRACE_SDF_RAYS 9   /* ray-state adjoint of trace_sdf (drrt_backtrace_sdf_rays_f32), both passes */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);
