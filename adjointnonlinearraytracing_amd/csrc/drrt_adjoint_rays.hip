@@ -1,6 +1,6 @@
 // drrt_adjoint_rays.hip -- gfx950 kernel of the ray-state adjoint of Tracer::trace: dL/dpos and dL/dvel of the rays
 // that entered a trace call (drrt_backtrace_rays_f32; the reference's ADTracerC returns them through enoki autodiff,
-// core/tracer.py:16-66).  Per-ray arithmetic: backtrace_ray_state of drrt_device.h, which tests/raygrad_host runs on the
+// core/tracer.py:16-66).  Per-ray arithmetic: backtrace_ray_state of drrt_device.h, which tests/hostcheck runs on the
 // host; shared pieces: drrt_march.h.
 //
 // One ray per lane, the whole reverse march in registers: (x, v, lambda, mu) and the taps of the current cell.  Nothing

@@ -1,7 +1,7 @@
 // drrt_cable_rays.hip -- gfx950 kernel of the ray-state adjoint of Tracer::trace_cable: dL/dpos and dL/dvel of the rays
 // that entered a fibre march (drrt_backtrace_cable_rays_f32; the reference's ADCableTracerC returns them through enoki
 // autodiff, core/tracer.py:237-291).  Per-ray arithmetic: cable_backtrace_ray_state of drrt_device.h, which
-// tests/cable_raygrad_host runs on the host; shared pieces: drrt_march.h.
+// tests/hostcheck runs on the host; shared pieces: drrt_march.h.
 //
 // One ray per lane, grid-stride like the two cable kernels, the profile staged into LDS under their rule.  A lane replays
 // the forward march of its ray to find the iteration j of the closest-approach record (the forward does not report it),

@@ -1,7 +1,7 @@
 // drrt_stop_rays.hip -- gfx950 kernels of the ray-state adjoints of Tracer::trace_plane and Tracer::trace_sdf: dL/dpos and
 // dL/dvel of the rays that entered such a call (drrt_backtrace_pln_rays_f32, drrt_backtrace_sdf_rays_f32; the reference gets
 // them through enoki autodiff, core/tracer.py:122-234).  Per-ray arithmetic: stop_backtrace_ray_state of drrt_device.h, which
-// tests/stop_raygrad_host runs on the host; shared pieces: drrt_march.h.
+// tests/hostcheck runs on the host; shared pieces: drrt_march.h.
 //
 // One ray per lane: the replay of the forward, then the reverse march, all in registers -- (x, v, lambda, mu) and the taps of
 // the current cell.  Nothing is written to the grid: no LDS window, no atomics.  A lane keeps the taps of a strictly interior

@@ -415,6 +415,24 @@ def _clear_hint() -> None:
     _lib.load().drrt_set_step_hint(None, 0)
 
 
+@contextlib.contextmanager
+def _paired_adjoint(rif_, res, n: int, h, ds, device, order, replay: bool = False, flags: int = 0):
+    """The call sequence of an adjoint that may be paired with its forward march through `order` (the forward's visit
+    order): validate the order, workspace + final flags, a fresh stats block, order / step hint armed -> yields
+    (order, flags, workspace, stats) for the library call -> hint cleared.  The order region of the workspace counts as
+    rewritten when the call sorts for itself (no hint taken), and always for the adjoints that `replay` their forward:
+    their second-pass flags go where the forward left its iteration counts, and they march with the forward's flags."""
+    order = _valid_order(order)
+    fl = _flags(adjoint=not replay) | flags
+    (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, device, paired=order is not None, adjoint=True), _new_stats(device)
+    try:
+        if not _hint(order, n) or replay:
+            _bump_order_gen(device)
+        yield order, fl, ws, st
+    finally:
+        _clear_hint()
+
+
 # "failed to exit all rays" (src/tracer.cpp:90) without a host sync per call: the stats block is copied to pinned
 # host memory asynchronously behind the kernels, and looked at when the copy has landed -- at the next tracer call,
 # at flush_warnings(), or at interpreter exit.  The message can therefore appear one call late; it is never lost.
@@ -590,7 +608,6 @@ class TracerC:
         float16 xt, vt, dx, dv select the fp16 ray-state variant (fp32 recurrences and accumulation)."""
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            order = _valid_order(order)
             half = _is_half(xt, vt, dx, dv)
             q16 = _is_q16(xt, vt)                      # q16 exit rays + IEEE-half seeds (drrt_backtrace_q16io)
             qpos = (not q16) and xt.dtype == torch.int16           # q16 positions; directions and seeds fp32
@@ -601,19 +618,14 @@ class TracerC:
             vt_ = _rays(vt, dev, n, half=half, q16=q16)
             dx_, dv_ = _rays(dx, dev, n, half=half or q16), _rays(dv, dev, n, half=half or q16)
             grad = torch.empty_like(rif_)
-            fl = _flags(adjoint=True) | (_lib.FLAG_Q16_POS_ONLY if qpos else 0)
             q16 = q16 or qpos
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
             fn = _lib.load().drrt_backtrace_q16io if q16 else (_lib.load().drrt_backtrace_f16io if half else _lib.load().drrt_backtrace_f32)
-            try:
-                if not _hint(order, n):
-                    _bump_order_gen(dev)               # the adjoint sorts for itself: it rewrites the order region
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order,
+                                 flags=_lib.FLAG_Q16_POS_ONLY if qpos else 0) as (_, fl, ws, st):
                 _lib.check(fn(
                     _p(rif_), rif_.numel(), _res3(res), n, _p(xt_), _p(vt_), _p(dx_), _p(dv_),
                     float(h), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
                 _capture_counters(ws)
-            finally:
-                _clear_hint()
         return grad
 
     def backtrace_rays(self, rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds,
@@ -625,7 +637,6 @@ class TracerC:
         these through enoki autodiff (core/tracer.py:16-66).  fp32 rays only."""
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            order = _valid_order(order)
             rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
             n = pos_.shape[0]
             vel_, xt_, vt_ = _rays(vel, dev, n), _rays(xt, dev, n), _rays(vt, dev, n)
@@ -634,17 +645,11 @@ class TracerC:
             if steps_.dtype != torch.int32 or steps_.numel() != n:
                 raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (drrt.last_steps)")
             dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
-            fl = _flags(adjoint=True)
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
-            try:
-                if not _hint(order, n):
-                    _bump_order_gen(dev)               # sorts for itself: it rewrites the order region
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (_, fl, ws, st):
                 _lib.check(_lib.load().drrt_backtrace_rays_f32(
                     _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
                     _p(dx_), _p(dv_), float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl,
                     _stream(dev)))
-            finally:
-                _clear_hint()
             _warn_failed(st)
         return dpos, dvel
 
@@ -660,13 +665,10 @@ class TracerC:
         used by ``dist`` to reduce final slabs of dL/dn across ranks while the next chunk marches.  fp32 rays only."""
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            order = _valid_order(order)
             rif_, xt_ = _f32(rif, dev).reshape(-1), _rays(xt, dev)
             n = xt_.shape[0]
             vt_, dx_, dv_ = _rays(vt, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
             grad = torch.empty_like(rif_)
-            fl = _flags(adjoint=True)
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
             lib = _lib.load()
             total = int(lib.drrt_backtrace_max_steps(_res3(res), float(h), float(ds)))
             if total < 0:
@@ -674,13 +676,10 @@ class TracerC:
             chunks = max(1, min(int(chunks), max(total, 1)))
             state = torch.empty(int(lib.drrt_backtrace_chunk_state_bytes(n)), dtype=torch.uint8, device=dev)
             bounds = [total * k // chunks for k in range(chunks + 1)]
-            try:
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (order, fl, ws, st):     # armed for the first chunk
                 for k in range(chunks):
                     progress = torch.empty(20, dtype=torch.int32, device=dev)
-                    if k == 0:
-                        if not _hint(order, n):
-                            _bump_order_gen(dev)           # the first chunk sorts for itself
-                    else:                                  # later chunks: the order the first chunk used
+                    if k > 0:                              # later chunks: the order the first chunk used
                         if order is not None:
                             _hint(order, n)
                         elif fl & _lib.FLAG_SORT_RAYS:
@@ -691,15 +690,12 @@ class TracerC:
                         bounds[k], bounds[k + 1] - bounds[k], _p(progress)))
                     if on_chunk is not None:
                         on_chunk(k, grad, progress)
-            finally:
-                _clear_hint()
         return grad
 
     def backtrace_sdf(self, rif, sdf, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tracer::backtrace_sdf, src/tracer.cpp:443-509."""
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            order = _valid_order(order)
             rif_, sdf_ = _f32(rif, dev).reshape(-1), _f32(sdf, dev).reshape(-1)
             if sdf_.numel() != rif_.numel():
                 raise RuntimeError("Resolution doesn't match data")
@@ -707,17 +703,11 @@ class TracerC:
             n = xt_.shape[0]
             vt_, dx_, dv_ = _rays(vt, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
             grad = torch.empty_like(rif_)
-            fl = _flags(adjoint=True)
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
-            try:
-                if not _hint(order, n):
-                    _bump_order_gen(dev)
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (_, fl, ws, st):
                 _lib.check(_lib.load().drrt_backtrace_sdf_f32(
                     _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(xt_), _p(vt_), _p(dx_), _p(dv_),
                     float(h), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
                 _capture_counters(ws)
-            finally:
-                _clear_hint()
         return grad
 
     def backtrace_cable(self, rif, radius, length, xt, vt, dx, dv, ds) -> torch.Tensor:
@@ -756,7 +746,6 @@ class TracerC:
     def _backtrace_stop_rays(self, rif, sdf, res, pos, vel, pln, dx, dv, h, ds, order):
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            order = _valid_order(order)
             rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
             n = pos_.shape[0]
             vel_, dx_, dv_ = _rays(vel, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
@@ -767,20 +756,14 @@ class TracerC:
             else:
                 po, pd = _rays(pln[0], dev, n), _rays(pln[1], dev, n)
             dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
-            fl = _flags()
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev, paired=order is not None, adjoint=True), _new_stats(dev)
-            tail = (float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev))
-            try:
-                _hint(order, n)
-                _bump_order_gen(dev)                   # the second-pass flags go where the forward left its iteration counts
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order, replay=True) as (_, fl, ws, st):
+                tail = (float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev))
                 if sdf is not None:
                     _lib.check(_lib.load().drrt_backtrace_sdf_rays_f32(
                         _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(dx_), _p(dv_), *tail))
                 else:
                     _lib.check(_lib.load().drrt_backtrace_pln_rays_f32(
                         _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd), _p(dx_), _p(dv_), *tail))
-            finally:
-                _clear_hint()
             if sdf is None:
                 _warn_failed(st)
         return dpos, dvel

@@ -24,6 +24,36 @@ import torch
 from . import drrt
 
 
+def _mask_plane_seed(grad_x, outmask):
+    """The plane classes' incoming position seed, zeroed on the rays whose ``outmask`` gradient is set (as written,
+    core/tracer.py:366-367)."""
+    if outmask is not None and outmask.dtype == torch.bool:
+        grad_x = grad_x.clone()
+        grad_x[outmask] = 0
+    return grad_x
+
+
+# Plumbing of the AD*TracerC classes, whose ray inputs x, v sit at positions (ix, iv) of apply().
+def _ray_grad_wanted(ctx, ix, iv, name, x, v):
+    """Whether x or v requires grad; the ray-state adjoints take fp32 rays only."""
+    wanted = ctx.needs_input_grad[ix] or ctx.needs_input_grad[iv]
+    if wanted and (x.dtype != torch.float32 or v.dtype != torch.float32):
+        raise RuntimeError(f"{name}: gradients w.r.t. x, v need float32 rays")
+    return wanted
+
+
+def _keep_rays(ctx, x, v, device, *extra):
+    """Private fp32 copies on the march's `device` of the forward's ray inputs (x, v, *extra) -> ``ctx.rays``."""
+    ctx.ray_devices = (x.device, v.device)
+    ctx.rays = tuple(t.detach().to(device=device, dtype=torch.float32).clone() for t in (x, v) + extra)
+
+
+def _return_ray_grads(ctx, ix, iv, dpos, dvel):
+    """(dL/dx, dL/dv) on the callers' devices, None where not asked for."""
+    return (dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[ix] else None,
+            dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[iv] else None)
+
+
 class BackTracerC(torch.autograd.Function):
     """core/tracer.py:294-335 -- ``apply(rif, x, v, h, ds) -> (xt, vt)``."""
 
@@ -63,9 +93,7 @@ class BackPlaneTracerC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_x, grad_v, outmask):
         rif, outx, outv = ctx.saved_tensors
-        if outmask is not None and outmask.dtype == torch.bool:     # as written, :366-367
-            grad_x = grad_x.clone()
-            grad_x[outmask] = 0
+        grad_x = _mask_plane_seed(grad_x, outmask)
         drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
                                         ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
         return drif, None, None, None, None, None, None
@@ -147,17 +175,15 @@ class ADTracerC(torch.autograd.Function):
     def forward(ctx, rif, x, v, h, ds):
         ctx.shape = rif.shape
         ctx.h, ctx.ds = h, ds
-        ray_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
-            raise RuntimeError("ADTracerC: gradients w.r.t. x, v need float32 rays")
+        ray_grad = _ray_grad_wanted(ctx, 1, 2, "ADTracerC", x, v)
         outx, outv = drrt.TracerC().trace(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), h, ds)
         ctx.order = drrt.keep_order(drrt.last_order)
         if ray_grad:
             steps = drrt.keep_steps(drrt.last_steps)
             if steps is None:
                 raise RuntimeError("ADTracerC: the forward march left no iteration counts")
-            ctx.ray_devices = (x.device, v.device)
-            ctx.rays = (x.detach().to(outx.device).clone(), v.detach().to(outx.device).clone(), steps)
+            _keep_rays(ctx, x, v, outx.device)
+            ctx.rays += (steps,)
         ctx.save_for_backward(rif, outx, outv)
         return outx, outv
 
@@ -170,12 +196,9 @@ class ADTracerC(torch.autograd.Function):
                                             ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
             x0, v0, steps = ctx.rays
-            dpos, dvel = drrt.TracerC().backtrace_rays(rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps,
-                                                       grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
-            if ctx.needs_input_grad[1]:
-                dx0 = dpos.to(ctx.ray_devices[0])
-            if ctx.needs_input_grad[2]:
-                dv0 = dvel.to(ctx.ray_devices[1])
+            dx0, dv0 = _return_ray_grads(ctx, 1, 2, *drrt.TracerC().backtrace_rays(
+                rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps, grad_x, grad_v, ctx.h, ctx.ds,
+                order=ctx.order))
         return drif, dx0, dv0, None, None
 
 
@@ -195,14 +218,11 @@ class ADCableTracerC(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rif, radius, length, x, v, sp, ds):
         ctx.radius, ctx.length, ctx.ds = radius, length, ds
-        ray_grad = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
-            raise RuntimeError("ADCableTracerC: gradients w.r.t. x, v need float32 rays")
+        ray_grad = _ray_grad_wanted(ctx, 3, 4, "ADCableTracerC", x, v)
         outx, outv, dist2 = drrt.TracerC().trace_cable(
             rif.detach().flatten(), radius, length, x.detach(), v.detach(), sp.detach(), ds)
         if ray_grad:
-            ctx.ray_devices = (x.device, v.device)
-            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v, sp))
+            _keep_rays(ctx, x, v, outx.device, sp)
         ctx.save_for_backward(rif, outx, outv)
         return outx, outv, dist2
 
@@ -214,13 +234,8 @@ class ADCableTracerC(torch.autograd.Function):
             drif = drrt.TracerC().backtrace_cable(rif.detach().flatten(), ctx.radius, ctx.length, outx, outv,
                                                   grad_x, grad_v, ctx.ds).reshape(rif.shape)
         if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            x0, v0, sp = ctx.rays
-            dpos, dvel = drrt.TracerC().backtrace_cable_rays(rif.detach().flatten(), ctx.radius, ctx.length, x0, v0, sp,
-                                                             grad_x, grad_v, ctx.ds)
-            if ctx.needs_input_grad[3]:
-                dx0 = dpos.to(ctx.ray_devices[0])
-            if ctx.needs_input_grad[4]:
-                dv0 = dvel.to(ctx.ray_devices[1])
+            dx0, dv0 = _return_ray_grads(ctx, 3, 4, *drrt.TracerC().backtrace_cable_rays(
+                rif.detach().flatten(), ctx.radius, ctx.length, *ctx.rays, grad_x, grad_v, ctx.ds))
         return drif, None, None, dx0, dv0, None, None
 
 
@@ -241,15 +256,12 @@ class ADRayPlaneTracerC(torch.autograd.Function):
     def forward(ctx, rif, x, v, sp, sn, h, ds):
         ctx.shape = rif.shape
         ctx.h, ctx.ds = h, ds
-        ray_grad = ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
-            raise RuntimeError("ADRayPlaneTracerC: gradients w.r.t. x, v need float32 rays")
+        ray_grad = _ray_grad_wanted(ctx, 1, 2, "ADRayPlaneTracerC", x, v)
         outx, outv, outmask = drrt.TracerC().trace_pln(
             rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), sp.detach(), sn.detach(), h, ds)
         ctx.order = drrt.keep_order(drrt.last_order)
         if ray_grad:
-            ctx.ray_devices = (x.device, v.device)
-            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v, sp, sn))
+            _keep_rays(ctx, x, v, outx.device, sp, sn)
         outmask = outmask.to(torch.bool)
         ctx.mark_non_differentiable(outmask)
         ctx.save_for_backward(rif, outx, outv)
@@ -258,21 +270,14 @@ class ADRayPlaneTracerC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_x, grad_v, outmask):
         rif, outx, outv = ctx.saved_tensors
-        if outmask is not None and outmask.dtype == torch.bool:     # as BackPlaneTracerC.backward
-            grad_x = grad_x.clone()
-            grad_x[outmask] = 0
+        grad_x = _mask_plane_seed(grad_x, outmask)                  # as BackPlaneTracerC.backward
         drif = dx0 = dv0 = None
         if ctx.needs_input_grad[0]:
             drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
                                             ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
         if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            x0, v0, sp, sn = ctx.rays
-            dpos, dvel = drrt.TracerC().backtrace_pln_rays(rif.detach().flatten(), ctx.shape, x0, v0, sp, sn,
-                                                           grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
-            if ctx.needs_input_grad[1]:
-                dx0 = dpos.to(ctx.ray_devices[0])
-            if ctx.needs_input_grad[2]:
-                dv0 = dvel.to(ctx.ray_devices[1])
+            dx0, dv0 = _return_ray_grads(ctx, 1, 2, *drrt.TracerC().backtrace_pln_rays(
+                rif.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order))
         return drif, dx0, dv0, None, None, None, None
 
 
@@ -290,15 +295,12 @@ class ADRaySDFTracerC(torch.autograd.Function):
     def forward(ctx, rif, sdf, x, v, h, ds):
         ctx.shape = rif.shape
         ctx.h, ctx.ds = h, ds
-        ray_grad = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        if ray_grad and (x.dtype != torch.float32 or v.dtype != torch.float32):
-            raise RuntimeError("ADRaySDFTracerC: gradients w.r.t. x, v need float32 rays")
+        ray_grad = _ray_grad_wanted(ctx, 2, 3, "ADRaySDFTracerC", x, v)
         outx, outv = drrt.TracerC().trace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, x.detach(),
                                               v.detach(), h, ds)
         ctx.order = drrt.keep_order(drrt.last_order)
         if ray_grad:
-            ctx.ray_devices = (x.device, v.device)
-            ctx.rays = tuple(t.detach().to(device=outx.device, dtype=torch.float32).clone() for t in (x, v))
+            _keep_rays(ctx, x, v, outx.device)
         ctx.save_for_backward(rif, sdf, outx, outv)
         return outx, outv
 
@@ -310,13 +312,9 @@ class ADRaySDFTracerC(torch.autograd.Function):
             drif = drrt.TracerC().backtrace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, outx, outv,
                                                 grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
         if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            x0, v0 = ctx.rays
-            dpos, dvel = drrt.TracerC().backtrace_sdf_rays(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape,
-                                                           x0, v0, grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
-            if ctx.needs_input_grad[2]:
-                dx0 = dpos.to(ctx.ray_devices[0])
-            if ctx.needs_input_grad[3]:
-                dv0 = dvel.to(ctx.ray_devices[1])
+            dx0, dv0 = _return_ray_grads(ctx, 2, 3, *drrt.TracerC().backtrace_sdf_rays(
+                rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds,
+                order=ctx.order))
         return drif, None, dx0, dv0, None, None
 
 

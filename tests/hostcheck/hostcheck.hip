@@ -5,9 +5,14 @@
 // with `hipcc --cuda-host-only -ffp-contract=off`, so that the CPU-only test tier can compare the
 // product's arithmetic and control flow with the oracle's `factored` mode bit for bit, without a
 // GPU.  The real kernels are exercised by the `-m gpu` tests.
+//
+// The ray-state adjoints (backtrace_ray_state, cable_backtrace_ray_state, stop_backtrace_ray_state) follow the marches:
+// the CPU tier compares them with float64 autograd, the GPU tier compares their kernels with them bit for bit.
 #include <stdint.h>
 #include <stddef.h>
 #include <string.h>
+
+#include <vector>
 
 #include "../../adjointnonlinearraytracing_amd/csrc/drrt_device.h"
 
@@ -127,5 +132,101 @@ EXPORT int hostcheck_backtrace_cable(const float* rif, int rres, float radius, f
   for (size_t i = 0; i < n; ++i)
     st += cable_backtrace_ray(C, ds, max_steps, xt + 3 * i, vt + 3 * i, dx + 3 * i, dv + 3 * i, sink);
   if (steps_total) *steps_total = st;
+  return 0;
+}
+
+// ---- ray-state adjoints: dL/dpos, dL/dvel --------------------------------------------------------------------------
+
+// dpos, dvel: (n,3); steps: the forward's per-ray iteration counts; *ray_steps, *n_failed as in drrt_stats
+EXPORT int raygrad_host_backtrace_rays(const float* rif, const int* res, size_t n, const float* pos, const float* vel,
+                                       const float* xt, const float* vt, const uint32_t* steps, const float* dx,
+                                       const float* dv, float h, float ds, float* dpos, float* dvel,
+                                       long long* ray_steps, long long* n_failed) {
+  Vol V = make_vol(rif, res, h);
+  const int max_steps = (int)(4.0f * h * (float)max3(res) / ds);     // the forward's bound (drrt_api.hip steps_fwd)
+  long long st = 0, nf = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const RayGrad g = backtrace_ray_state(V, ds, max_steps, steps[i], pos + 3 * i, vel + 3 * i, xt + 3 * i, vt + 3 * i,
+                                          dx + 3 * i, dv + 3 * i, [&](const Cell& c) { return fetch(V.data, c); });
+    for (int k = 0; k < 3; ++k) { dpos[3 * i + k] = g.dp[k]; dvel[3 * i + k] = g.dv[k]; }
+    st += g.steps; nf += g.failed ? 1 : 0;
+  }
+  *ray_steps = st; *n_failed = nf;
+  return 0;
+}
+
+// dpos, dvel, xt, vt: (n,3); jstar: the iteration of the replayed closest-approach record; steps: replay + reverse
+// iterations per ray (their sum is drrt_stats.ray_steps, their maximum drrt_stats.iters)
+EXPORT int cable_raygrad_host_backtrace_rays(const float* rif, int rres, float radius, float length, size_t n,
+                                             const float* pos, const float* vel, const float* target, const float* dx,
+                                             const float* dv, float ds, float* dpos, float* dvel, float* xt, float* vt,
+                                             uint32_t* jstar, uint32_t* steps) {
+  const Cyl C = make_cyl(rif, rres, radius, length);
+  const int max_steps = (int)(4.0f * length / ds);                   // the forward's bound (drrt_trace_cable_f32)
+  for (size_t i = 0; i < n; ++i) {
+    CableRecord rec;
+    const RayGrad g = cable_backtrace_ray_state(C, ds, max_steps, pos + 3 * i, vel + 3 * i, target + 3 * i, dx + 3 * i,
+                                                dv + 3 * i, &rec);
+    for (int k = 0; k < 3; ++k) {
+      dpos[3 * i + k] = g.dp[k]; dvel[3 * i + k] = g.dv[k]; xt[3 * i + k] = rec.xt[k]; vt[3 * i + k] = rec.vt[k];
+    }
+    jstar[i] = rec.j; steps[i] = g.steps;
+    if (g.failed) return 1;
+  }
+  return 0;
+}
+
+// The two passes of the plane / SDF ray-state adjoint, looped as drrt_api.hip launches them: every ray with per-ray
+// termination, then the flagged rays over the maximum of the first pass's iteration counts.
+template <int MODE>
+static void stop_backtrace_rays(const float* rif, const float* sdf, const int* res, size_t n, const float* pos,
+                                const float* vel, const float* pln_o, const float* pln_d, const float* dx, const float* dv,
+                                float h, float ds, float* dpos, float* dvel, float* xt, float* vt, uint32_t* jstar,
+                                uint32_t* steps, uint32_t* fwd, uint8_t* flags, uint32_t* iters) {
+  Vol V = make_vol(rif, res, h);
+  const int max_steps = MODE == 2 ? (int)(2.0f * h * (float)max3(res) / ds) : (int)(4.0f * h * (float)max3(res) / ds);
+  auto taps = [&](const Cell& c) -> Taps { return fetch(V.data, c); };
+  const float zero[3] = {0.f, 0.f, 0.f};
+  unsigned total = 0;
+  auto store = [&](size_t i, const StopGrad& g, const StopRecord& rec) {
+    for (int k = 0; k < 3; ++k) {
+      dpos[3 * i + k] = g.dp[k]; dvel[3 * i + k] = g.dv[k]; xt[3 * i + k] = rec.xt[k]; vt[3 * i + k] = rec.vt[k];
+    }
+    jstar[i] = rec.j;
+  };
+  std::vector<size_t> again;
+  for (size_t i = 0; i < n; ++i) {
+    const float* po = MODE == 1 ? pln_o + 3 * i : zero; const float* pd = MODE == 1 ? pln_d + 3 * i : zero;
+    StopRecord rec;
+    const StopGrad g = stop_backtrace_ray_state<MODE, false>(V, sdf, ds, max_steps, 0u, pos + 3 * i, vel + 3 * i, po, pd,
+                                                             dx + 3 * i, dv + 3 * i, taps, &rec);
+    steps[i] = g.steps; fwd[i] = g.fwd;
+    flags[i] = (g.failed ? 1 : 0) | (g.again ? 2 : 0);
+    if (g.fwd > total) total = g.fwd;
+    if (g.again) again.push_back(i); else store(i, g, rec);
+  }
+  for (size_t i : again) {
+    const float* po = MODE == 1 ? pln_o + 3 * i : zero; const float* pd = MODE == 1 ? pln_d + 3 * i : zero;
+    StopRecord rec;
+    const StopGrad g = stop_backtrace_ray_state<MODE, true>(V, sdf, ds, max_steps, total, pos + 3 * i, vel + 3 * i, po, pd,
+                                                            dx + 3 * i, dv + 3 * i, taps, &rec);
+    steps[i] += g.steps;
+    store(i, g, rec);
+  }
+  *iters = total;
+}
+
+// mode 1 = trace_plane, 2 = trace_sdf.  dpos, dvel, xt, vt: (n,3); jstar: the iteration of the replayed record; steps:
+// replayed forward + reverse iterations per ray (their sum is drrt_stats.ray_steps); fwd: the iterations of the first
+// pass's replay (the forward's own per-ray count); flags: bit 0 failed, bit 1 the ray went
+// through the second pass; iters: the global loop count (drrt_stats.iters)
+EXPORT int stop_raygrad_host_backtrace_rays(int mode, const float* rif, const float* sdf, const int* res, size_t n,
+                                            const float* pos, const float* vel, const float* pln_o, const float* pln_d,
+                                            const float* dx, const float* dv, float h, float ds, float* dpos, float* dvel,
+                                            float* xt, float* vt, uint32_t* jstar, uint32_t* steps, uint32_t* fwd,
+                                            uint8_t* flags, uint32_t* iters) {
+  if (mode == 1) stop_backtrace_rays<1>(rif, sdf, res, n, pos, vel, pln_o, pln_d, dx, dv, h, ds, dpos, dvel, xt, vt, jstar, steps, fwd, flags, iters);
+  else if (mode == 2) stop_backtrace_rays<2>(rif, sdf, res, n, pos, vel, pln_o, pln_d, dx, dv, h, ds, dpos, dvel, xt, vt, jstar, steps, fwd, flags, iters);
+  else return 1;
   return 0;
 }

@@ -1,6 +1,7 @@
 """Loader for tests/hostcheck/hostcheck.hip (TEST INFRASTRUCTURE ONLY): the product's own
 __host__ __device__ per-ray code compiled for the host, so CPU-only tests can compare it with the
-oracle's `factored` arithmetic bit for bit.  Never imported by the package."""
+oracle's `factored` arithmetic bit for bit, and its ray-state adjoints with float64 autograd.  Never imported by the
+package."""
 import ctypes as C
 import os
 import subprocess
@@ -8,7 +9,7 @@ import subprocess
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-_SRC = os.path.join(_HERE, "hostcheck", "hostcheck.hip")
+SOURCES = [os.path.join(_HERE, "hostcheck", "hostcheck.hip")]     # what a build of the library compiles
 _HDR = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc", "drrt_device.h")
 _SO = os.path.join(_HERE, "hostcheck", "_build", "libhostcheck.so")
 _lib = None
@@ -18,9 +19,9 @@ def lib():
     global _lib
     if _lib is None:
         os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if (not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(_SRC), os.path.getmtime(_HDR))):
+        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in SOURCES + [_HDR]):
             subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC",
-                            "-ffp-contract=off", "-mfma", "-shared", "-fvisibility=hidden", "-o", _SO, _SRC],
+                            "-ffp-contract=off", "-mfma", "-shared", "-fvisibility=hidden", "-o", _SO] + SOURCES,
                            check=True, capture_output=True)
         _lib = C.CDLL(_SO)
     return _lib
@@ -30,9 +31,8 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
-def _f(a, cols=None):
-    a = np.ascontiguousarray(np.asarray(a, dtype=np.float32))
-    return a
+def _f(a):
+    return np.ascontiguousarray(np.asarray(a, dtype=np.float32))
 
 
 def _res(res):
@@ -92,3 +92,66 @@ def backtrace_cable(rif, radius, length, xt, vt, dx, dv, ds):
                                     C.c_size_t(len(xt)), _p(xt), _p(vt), _p(dx), _p(dv), C.c_float(ds),
                                     _p(grad), C.byref(st))
     return dict(grad=grad, steps_total=st.value)
+
+
+# ---- ray-state adjoints: dL/dpos, dL/dvel ---------------------------------------------------------------------------
+def backtrace_rays(rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds):
+    """-> dict(dpos, dvel, ray_steps, n_failed), the host build of what drrt_backtrace_rays_f32 computes."""
+    rif = _f(rif).reshape(-1)
+    pos, vel, xt, vt, dx, dv = (_f(a) for a in (pos, vel, xt, vt, dx, dv))
+    steps = np.ascontiguousarray(np.asarray(steps).astype(np.uint32))
+    n = len(pos)
+    dpos, dvel = np.empty_like(pos), np.empty_like(vel)
+    st, nf = C.c_longlong(0), C.c_longlong(0)
+    lib().raygrad_host_backtrace_rays(_p(rif), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), _p(xt), _p(vt), _p(steps),
+                                      _p(dx), _p(dv), C.c_float(h), C.c_float(ds), _p(dpos), _p(dvel),
+                                      C.byref(st), C.byref(nf))
+    return dict(dpos=dpos, dvel=dvel, ray_steps=st.value, n_failed=nf.value)
+
+
+def backtrace_cable_rays(rif, radius, length, pos, vel, target, dx, dv, ds):
+    """-> dict(dpos, dvel, xt, vt, jstar, steps, ray_steps, iters): the host build of what drrt_backtrace_cable_rays_f32
+    computes, plus the record it replayed (xt, vt, and its iteration jstar) and the per-ray iteration counts."""
+    rif = _f(rif).reshape(-1)
+    pos, vel, target, dx, dv = (_f(a) for a in (pos, vel, target, dx, dv))
+    n = len(pos)
+    dpos, dvel, xt, vt = (np.empty_like(pos) for _ in range(4))
+    jstar, steps = np.empty(n, np.uint32), np.empty(n, np.uint32)
+    rc = lib().cable_raygrad_host_backtrace_rays(_p(rif), C.c_int(rif.size), C.c_float(radius), C.c_float(length),
+                                                 C.c_size_t(n), _p(pos), _p(vel), _p(target), _p(dx), _p(dv),
+                                                 C.c_float(ds), _p(dpos), _p(dvel), _p(xt), _p(vt), _p(jstar), _p(steps))
+    assert rc == 0, "the cable ray-state adjoint never marks a ray failed"
+    return dict(dpos=dpos, dvel=dvel, xt=xt, vt=vt, jstar=jstar, steps=steps,
+                ray_steps=int(steps.astype(np.int64).sum()), iters=int(steps.max()) if n else 0)
+
+
+def _backtrace_stop_rays(mode, rif, sdf, res, pos, vel, po, pd, dx, dv, h, ds):
+    rif = _f(rif).reshape(-1)
+    sdf = None if sdf is None else _f(sdf).reshape(-1)
+    pos, vel, dx, dv = (_f(a) for a in (pos, vel, dx, dv))
+    po, pd = (None if a is None else _f(a) for a in (po, pd))
+    n = len(pos)
+    dpos, dvel, xt, vt = (np.empty_like(pos) for _ in range(4))
+    jstar, steps, fwd = (np.empty(n, np.uint32) for _ in range(3))
+    flags = np.empty(n, np.uint8)
+    iters = C.c_uint32(0)
+    rc = lib().stop_raygrad_host_backtrace_rays(C.c_int(mode), _p(rif), _p(sdf), _p(_res(res)), C.c_size_t(n), _p(pos),
+                                                _p(vel), _p(po), _p(pd), _p(dx), _p(dv), C.c_float(h), C.c_float(ds),
+                                                _p(dpos), _p(dvel), _p(xt), _p(vt), _p(jstar), _p(steps), _p(fwd),
+                                                _p(flags), C.byref(iters))
+    assert rc == 0
+    failed, again = (flags & 1).astype(bool), (flags & 2).astype(bool)
+    return dict(dpos=dpos, dvel=dvel, xt=xt, vt=vt, jstar=jstar, steps=steps, fwd=fwd, failed=failed, again=again,
+                ray_steps=int(steps.astype(np.int64).sum()), iters=int(iters.value), n_failed=int(failed.sum()))
+
+
+def backtrace_pln_rays(rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds):
+    """-> dict(dpos, dvel, xt, vt, jstar, steps, fwd, failed, again, ray_steps, iters, n_failed): the host build of what
+    drrt_backtrace_pln_rays_f32 computes, plus the record it replayed (xt, vt, its iteration jstar) and which rays went
+    through the second pass (again)."""
+    return _backtrace_stop_rays(1, rif, None, res, pos, vel, pln_o, pln_d, dx, dv, h, ds)
+
+
+def backtrace_sdf_rays(rif, sdf, res, pos, vel, dx, dv, h, ds):
+    """The same for drrt_backtrace_sdf_rays_f32."""
+    return _backtrace_stop_rays(2, rif, sdf, res, pos, vel, None, None, dx, dv, h, ds)

@@ -1,6 +1,6 @@
 """Ray-state adjoint of the fibre march (drrt_backtrace_cable_rays_f32, tracer.ADCableTracerC): dL/dpos and dL/dvel.
 
-CPU tier: the host build of the product's per-ray routine (tests/cable_raygrad_host, cable_backtrace_ray_state of
+CPU tier: the host build of the product's per-ray routine (tests/hostcheck, cable_backtrace_ray_state of
 csrc/drrt_device.h) against torch.autograd in float64 through tests/cable_ad.trace_cable, on the rays whose fp32 and fp64
 records agree.  The float64 march takes the fp32 march's record iteration j* as an input, so the two cannot pick different
 iterations; what is left to drop are the rays whose fp32 state has drifted more than TIE_TOL from the fp64 one by then.
@@ -18,20 +18,14 @@ import pytest
 import torch
 
 import cable_ad
-import cable_raygrad_host_lib as CRG
 import cases
 import hostcheck_lib as HC
+from raygrad_common import GRAD_TOL, TIE_TOL, _t, _unit, grads, rel_err
 
-TIE_TOL = 1e-5          # fp32 vs fp64 records (the constants of test_raygrad.py)
-GRAD_TOL = 1e-3         # per-ray relative error of (dpos, dvel) against float64 autograd
 MAX_DROPPED = 0.20      # share of a scene's rays that may be left out as not tie-free
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------
-def _unit(v):
-    return v / np.linalg.norm(v, axis=1, keepdims=True)
-
-
 def profile(kind):
     if kind == "luneburg65":                               # the profile of test_cable_variants
         return np.sqrt(2.0 - np.linspace(0, 1, 65) ** 2).astype(np.float32)
@@ -117,7 +111,7 @@ def scene(name, seed=0):
 
 
 def host(s):
-    return CRG.backtrace_cable_rays(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["dx"], s["dv"],
+    return HC.backtrace_cable_rays(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["dx"], s["dv"],
                                     s["ds"])
 
 
@@ -130,12 +124,6 @@ def autograd64(s, jstar, dtype=torch.float64):
     L = (xt * T(s["dx"])).sum() + (vt * T(s["dv"])).sum()
     gp, gv = torch.autograd.grad(L, (p, v))
     return xt.detach().numpy(), vt.detach().numpy(), gp.numpy(), gv.numpy()
-
-
-def rel_err(dp, dv, gp, gv):
-    a = np.concatenate([dp, dv], 1).astype(np.float64)
-    b = np.concatenate([gp, gv], 1).astype(np.float64)
-    return np.linalg.norm(a - b, axis=1) / np.maximum(np.linalg.norm(b, axis=1), 1e-30)
 
 
 # ---- CPU tier -------------------------------------------------------------------------------------------------------
@@ -186,7 +174,7 @@ def test_one_iteration_closed_form():
     vel = np.array([[0.1, 1.0, -0.05]], np.float32)
     tg = pos + 5.0 * vel
     dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
-    r = CRG.backtrace_cable_rays(prof, radius, length, pos, vel, tg, dx, dv, ds)
+    r = HC.backtrace_cable_rays(prof, radius, length, pos, vel, tg, dx, dv, ds)
     assert r["jstar"][0] == 1 and r["steps"][0] == 2
     P = torch.tensor(prof, dtype=torch.float64)
     f = lambda y: cable_ad.sample(P, radius, y[None])[1][0]            # noqa: E731
@@ -247,10 +235,6 @@ def test_abi_argument_checks():
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-def _t(a, dev):
-    return torch.as_tensor(np.asarray(a), device=dev)
-
-
 def _fuzz(seed, rres=None):
     c = cases.fuzz_cable_config(seed)
     s = dict(prof=c["prof"], radius=c["radius"], length=c["length"], ds=c["ds"], pos=c["pos"], vel=c["vel"], tg=c["tg"],
@@ -293,14 +277,11 @@ def test_kernel_matches_host_routine_bitwise(gpu, name):
     assert np.array_equal(xt.cpu().numpy(), r["xt"], equal_nan=True) and np.array_equal(vt.cpu().numpy(), r["vt"], equal_nan=True)
 
 
-def _grads(cls, s, dev, rif_grad=True, x_grad=False, v_grad=False):
-    rif = _t(s["prof"], dev).requires_grad_(rif_grad)
-    x = _t(s["pos"], dev).requires_grad_(x_grad)
-    v = _t(s["vel"], dev).requires_grad_(v_grad)
-    xt, vt, d2 = cls.apply(rif, s["radius"], s["length"], x, v, _t(s["tg"], dev), s["ds"])
-    ((xt * _t(s["dx"], dev)).sum() + (vt * _t(s["dv"], dev)).sum() + d2.sum()).backward()     # the seed on dist2 is ignored
-    torch.cuda.synchronize()
-    return rif.grad, x.grad, v.grad
+def _grads(cls, s, dev, *a, **kw):
+    def apply(rif, x, v):
+        xt, vt, d2 = cls.apply(rif, s["radius"], s["length"], x, v, _t(s["tg"], dev), s["ds"])
+        return xt, vt, d2.sum()                                     # the seed on dist2 is ignored
+    return grads(apply, s, dev, *a, rif="prof", **kw)
 
 
 @pytest.mark.gpu
@@ -408,7 +389,7 @@ def test_fibre_demo_boundary_index_term(gpu, oracle):
     assert torch.allclose(grads[True] - grads[False], term, rtol=1e-4, atol=1e-6 * float(term.abs().max()))
     # (b) float64 autograd of the whole chain, records at the fp32 march's iterations
     v0_np = v0.detach().cpu().numpy()
-    r = CRG.backtrace_cable_rays(c["prof"], radius, length, c["pos"], v0_np, c["tg"], seeds.cpu().numpy(),
+    r = HC.backtrace_cable_rays(c["prof"], radius, length, c["pos"], v0_np, c["tg"], seeds.cpu().numpy(),
                                  np.zeros_like(c["pos"]), c["sds"])
     P = torch.tensor(c["prof"], dtype=torch.float64, requires_grad=True)
     X, V, TG = (torch.tensor(a, dtype=torch.float64) for a in (c["pos"], c["vel"], c["tg"]))

@@ -189,8 +189,8 @@ def test_sanitized_nonfinite_inputs(tmp_path):
         pytest.skip("no clang sanitizer runtime in this image")
     so = str(tmp_path / "libhostcheck_asan.so")
     subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O1", "-g", "-std=c++17", "-fPIC", "-ffp-contract=off",
-                    "-mfma", "-shared", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", so,
-                    os.path.join(here, "hostcheck", "hostcheck.hip")], check=True, capture_output=True)
+                    "-mfma", "-shared", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", so]
+                   + H.SOURCES, check=True, capture_output=True)
     env = dict(os.environ, LD_PRELOAD=rt[0], ASAN_OPTIONS="detect_leaks=0")
     r = subprocess.run([sys.executable, os.path.join(here, "hostcheck", "sanitize_run.py"), so], env=env,
                        capture_output=True, text=True, timeout=600)

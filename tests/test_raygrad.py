@@ -1,6 +1,6 @@
 """Ray-state adjoint of trace (drrt_backtrace_rays_f32, tracer.ADTracerC): dL/dpos and dL/dvel.
 
-CPU tier: the host build of the product's per-ray routine (tests/raygrad_host, backtrace_ray_state of csrc/drrt_device.h)
+CPU tier: the host build of the product's per-ray routine (tests/hostcheck, backtrace_ray_state of csrc/drrt_device.h)
 against torch.autograd in float64 through oracle/torch_ad.trace, on the rays whose fp32 and fp64 forward exit samples agree
 (tie-free: a ray that leaves on another iteration in fp64 has another derivative).  GPU tier: k_backtrace_rays against that
 host build bit for bit, ADTracerC end to end, the settings the result must not depend on, the launches, a pose gradient
@@ -13,76 +13,11 @@ import torch
 
 import cases
 import hostcheck_lib as HC
-import raygrad_host_lib as RG
 from oracle import torch_ad
-
-TIE_TOL = 1e-5          # fp32 vs fp64 exit samples
-GRAD_TOL = 1e-3         # per-ray relative error of (dpos, dvel) against float64 autograd
+from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grads, grid, ray_sets, rel_err
 
 
-# ---- ray sets -------------------------------------------------------------------------------------------------------
-def _unit(v):
-    return v / np.linalg.norm(v, axis=1, keepdims=True)
-
-
-def ray_sets(ext, ds, seed=0):
-    """ext = (ex, ey, ez), the box extents ((res - 1) h).  -> {name: (pos, vel)} fp32."""
-    ext = np.asarray(ext, np.float64)
-    rng = np.random.default_rng(seed)
-    out = {}
-    # plane source outside the y = 0 face (the package's plane sources), and a point source below it
-    p, v = cases.plane_rays(96, 1.0, ds, seed=seed, tilt=0.1)
-    out["plane"] = (p * ext.astype(np.float32), v)
-    n = 96
-    d = rng.normal(0, 0.15, (n, 3)); d[:, 1] = 1.0
-    out["point"] = (np.tile(np.array([[0.5, -0.35, 0.45]]) * ext, (n, 1)), _unit(d))
-    # strictly inside, any direction
-    out["inside"] = (rng.uniform(0.15, 0.85, (n, 3)) * ext, _unit(rng.normal(size=(n, 3))))
-    # starting exactly on a face (x = 0, and the far z face heading back in)
-    p = rng.uniform(0.1, 0.9, (n, 3)) * ext
-    d = rng.normal(0, 0.2, (n, 3))
-    p[: n // 2, 0] = 0.0; d[: n // 2, 0] = 1.0
-    p[n // 2:, 2] = ext[2]; d[n // 2:, 2] = -1.0
-    out["face"] = (p, _unit(d))
-    # never entering: parallel to a face outside the box, and pointing away from it
-    p = rng.uniform(0.1, 0.9, (n, 3)) * ext
-    d = np.zeros((n, 3))
-    p[: n // 2, 1] = -0.2 * ext[1]; d[: n // 2, 0] = 1.0; p[: n // 2, 0] = -0.1 * ext[0]
-    p[n // 2:, 2] = -0.1 * ext[2]; d[n // 2:] = _unit(rng.normal(0, 0.1, (n - n // 2, 3)) + [0, 0, -1.0])
-    out["never"] = (p, d)
-    # grazing an edge: along x just inside / just outside the (y = 0, z = 0) edge
-    p = np.zeros((n, 3)); d = np.zeros((n, 3))
-    p[:, 0] = -0.1 * ext[0]
-    p[:, 1] = rng.uniform(-0.02, 0.02, n) * ext[1]; p[:, 2] = rng.uniform(-0.02, 0.02, n) * ext[2]
-    d[:, 0] = 1.0; d[:, 1] = rng.uniform(-0.02, 0.05, n); d[:, 2] = rng.uniform(-0.02, 0.05, n)
-    out["graze"] = (p, _unit(d))
-    # zero velocity: outside the box (fails the forward), and inside (n grad n sets it moving: an ordinary ray)
-    p = rng.uniform(0.1, 0.9, (n, 3)) * ext
-    p[: n // 2, 1] = -0.1 * ext[1]
-    out["zero"] = (p, np.zeros((n, 3)))
-    return {k: (a.astype(np.float32), b.astype(np.float32)) for k, (a, b) in out.items()}
-
-
-SCENES = {
-    # name: (torch-order grid (D, H, W), h, ds)
-    "lens16_h1_half": ("lens16", 1.0, 0.5),
-    "lens16_h05_half": ("lens16", 0.5, 0.25),
-    "lens16_h1_multi": ("lens16", 1.0, 1.7),
-    "box7x11x5_h1_half": ("box", 1.0, 0.5),
-    "box7x11x5_h05_multi": ("box", 0.5, 0.8),
-}
-
-
-def grid(kind):
-    if kind == "lens16":
-        return cases.luneburg(16)
-    rng = np.random.default_rng(5)
-    D, H, W = 5, 11, 7
-    z, y, x = np.meshgrid(np.linspace(0, 1, D), np.linspace(0, 1, H), np.linspace(0, 1, W), indexing="ij")
-    f = 1.0 + 0.3 * np.sin(2.1 * x + 0.4) * np.cos(1.7 * y - 0.3) * np.sin(2.6 * z + 1.1) + 0.05 * rng.random((D, H, W))
-    return f.astype(np.float32)
-
-
+# ---- scenes ---------------------------------------------------------------------------------------------------------
 def scene(name, seed=0):
     kind, h, ds = SCENES[name]
     rif = grid(kind)
@@ -126,18 +61,12 @@ def reference(oracle, s):
     return k, tie_free, gp, gv, ms
 
 
-def rel_err(dp, dv, gp, gv):
-    a = np.concatenate([dp, dv], 1).astype(np.float64)
-    b = np.concatenate([gp, gv], 1)
-    return np.linalg.norm(a - b, axis=1) / np.maximum(np.linalg.norm(b, axis=1), 1e-30)
-
-
 # ---- CPU tier -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("name", list(SCENES))
 def test_host_routine_matches_float64_autograd(oracle, name):
     s = scene(name)
     k, tie_free, gp, gv, ms = reference(oracle, s)
-    r = RG.backtrace_rays(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"],
+    r = HC.backtrace_rays(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"],
                           s["h"], s["ds"])
     lab = s["labels"]
     # every ray set is represented among the tie-free rays (zero velocity fails by construction)
@@ -166,7 +95,7 @@ def test_exit_on_first_iteration_closed_form():
     k = HC.trace(rif, res, pos, vel, h, ds)
     assert k["steps"][0] == 1
     dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
-    r = RG.backtrace_rays(rif, res, pos, vel, k["xt"], k["vt"], k["steps"], dx, dv, h, ds)
+    r = HC.backtrace_rays(rif, res, pos, vel, k["xt"], k["vt"], k["steps"], dx, dv, h, ds)
     x = torch.tensor(pos[0], dtype=torch.float64, requires_grad=True)
     n, g = torch_ad.eval_grad(torch.tensor(rif, dtype=torch.float64), x[None], h, torch.tensor([True]))
     f = lambda y: (lambda nn, gg: (nn[:, None] * gg)[0])(*torch_ad.eval_grad(torch.tensor(rif, dtype=torch.float64),
@@ -209,10 +138,6 @@ def test_abi_argument_checks():
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-def _t(a, dev):
-    return torch.as_tensor(np.asarray(a), device=dev)
-
-
 def _gpu_forward(T, s, dev):
     xt, vt = T.trace(_t(s["rif"], dev), s["res"], _t(s["pos"], dev), _t(s["vel"], dev), s["h"], s["ds"])
     from adjointnonlinearraytracing_amd import drrt
@@ -235,7 +160,7 @@ def test_kernel_matches_host_routine_bitwise(gpu, name, pair):
     xt_h, vt_h, steps_h = xt.cpu().numpy(), vt.cpu().numpy(), steps.cpu().numpy()
     k = HC.trace(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(xt_h, k["xt"]) and np.array_equal(vt_h, k["vt"]) and np.array_equal(steps_h, k["steps"])
-    r = RG.backtrace_rays(s["rif"], s["res"], s["pos"], s["vel"], xt_h, vt_h, steps_h, s["dx"], s["dv"], s["h"], s["ds"])
+    r = HC.backtrace_rays(s["rif"], s["res"], s["pos"], s["vel"], xt_h, vt_h, steps_h, s["dx"], s["dv"], s["h"], s["ds"])
     assert np.array_equal(dpos.cpu().numpy(), r["dpos"]) and np.array_equal(dvel.cpu().numpy(), r["dvel"])
     assert st["ray_steps"] == r["ray_steps"] and st["n_failed"] == r["n_failed"] > 0
 
@@ -284,14 +209,8 @@ def test_ray_gradients_ignore_corrected_h_and_sort(gpu):
         assert torch.equal(dp, outs[0][0]) and torch.equal(dv, outs[0][1])
 
 
-def _grads(cls, s, dev, rif_grad=True, x_grad=False, v_grad=False):
-    rif = _t(s["rif"], dev).requires_grad_(rif_grad)
-    x = _t(s["pos"], dev).requires_grad_(x_grad)
-    v = _t(s["vel"], dev).requires_grad_(v_grad)
-    xt, vt = cls.apply(rif, x, v, s["h"], s["ds"])
-    ((xt * _t(s["dx"], dev)).sum() + (vt * _t(s["dv"], dev)).sum()).backward()
-    torch.cuda.synchronize()
-    return rif.grad, x.grad, v.grad
+def _grads(cls, s, dev, *a, **kw):
+    return grads(lambda rif, x, v: cls.apply(rif, x, v, s["h"], s["ds"]), s, dev, *a, **kw)
 
 
 @pytest.mark.gpu

@@ -1,7 +1,7 @@
 """Ray-state adjoints of the plane and SDF marches (drrt_backtrace_pln_rays_f32 / drrt_backtrace_sdf_rays_f32,
 tracer.ADRayPlaneTracerC / ADRaySDFTracerC): dL/dpos and dL/dvel.
 
-CPU tier: the host build of the product's per-ray routine (tests/stop_raygrad_host, stop_backtrace_ray_state of
+CPU tier: the host build of the product's per-ray routine (tests/hostcheck, stop_backtrace_ray_state of
 csrc/drrt_device.h, both passes) against torch.autograd in float64 through tests/stop_ad (the reference's whole global
 loop with its masks), on the tie-free rays: those whose fp32 and fp64 records agree to TIE_TOL and were written on the same
 iteration.  Rays that failed the plane march (zero gradient by contract) are checked on their own and are not part of the
@@ -30,11 +30,8 @@ import torch
 import cases
 import hostcheck_lib as HC
 import stop_ad
-import stop_raygrad_host_lib as SG
-import test_raygrad as TR
+from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, _unit, grads, grid, ray_sets, rel_err
 
-TIE_TOL = TR.TIE_TOL
-GRAD_TOL = TR.GRAD_TOL
 MAX_DROPPED = 0.10      # share of a case's non-failed rays that may be left out as not tie-free
 
 PLANES = {
@@ -42,11 +39,6 @@ PLANES = {
     "axis": ((0.5, 0.6, 0.5), (0.0, 1.0, 0.0)),
     "tilted": ((0.5, 0.45, 0.5), (0.3, 0.9, 0.1)),
 }
-
-
-def _unit(v):
-    v = np.asarray(v, np.float64)
-    return v / np.linalg.norm(v, axis=-1, keepdims=True)
 
 
 def _concat(s, sets):
@@ -60,16 +52,17 @@ def _concat(s, sets):
 
 
 def _base(name):
-    kind, h, ds = TR.SCENES[name]
-    rif = TR.grid(kind)
+    kind, h, ds = SCENES[name]
+    rif = grid(kind)
     D, H, W = rif.shape
     ext = np.array([(W - 1) * h, (H - 1) * h, (D - 1) * h])
-    return dict(rif=rif, res=(W, H, D), h=h, ds=ds, ext=ext), dict(TR.ray_sets(ext, ds, 0))
+    return dict(rif=rif, res=(W, H, D), h=h, ds=ds, ext=ext), dict(ray_sets(ext, ds, 0))
 
 
 def plane_scene(name, plane):
-    """test_raygrad's scene and ray sets, one sensor plane for all rays, and the "back" set: rays that start in bounds
-    PAST the plane and head back through it (the global-loop case: their record is overwritten when they leave again)."""
+    """The box march's scene and ray sets (raygrad_common), one sensor plane for all rays, and the "back" set: rays that
+    start in bounds PAST the plane and head back through it (the global-loop case: their record is overwritten when they
+    leave again)."""
     s, sets = _base(name)
     ext = s["ext"]
     o = np.array(PLANES[plane][0]) * ext
@@ -96,8 +89,8 @@ def sphere_sdf(s):
 
 
 def sdf_scene(name):
-    """test_raygrad's scene and ray sets, a sphere of radius 0.42 of the smallest extent as the object, and the "object"
-    set: rays that start inside it."""
+    """The box march's scene and ray sets (raygrad_common), a sphere of radius 0.42 of the smallest extent as the object,
+    and the "object" set: rays that start inside it."""
     s, sets = _base(name)
     s["sdf"] = sphere_sdf(s)
     rng = np.random.default_rng(29)
@@ -107,15 +100,15 @@ def sdf_scene(name):
     return _concat(s, sets)
 
 
-PLANE_CASES = [(n, p) for n in TR.SCENES for p in PLANES]
+PLANE_CASES = [(n, p) for n in SCENES for p in PLANES]
 
 
 def host_plane(s):
-    return SG.backtrace_pln_rays(s["rif"], s["res"], s["pos"], s["vel"], s["po"], s["pd"], s["dx"], s["dv"], s["h"], s["ds"])
+    return HC.backtrace_pln_rays(s["rif"], s["res"], s["pos"], s["vel"], s["po"], s["pd"], s["dx"], s["dv"], s["h"], s["ds"])
 
 
 def host_sdf(s):
-    return SG.backtrace_sdf_rays(s["rif"], s["sdf"], s["res"], s["pos"], s["vel"], s["dx"], s["dv"], s["h"], s["ds"])
+    return HC.backtrace_sdf_rays(s["rif"], s["sdf"], s["res"], s["pos"], s["vel"], s["dx"], s["dv"], s["h"], s["ds"])
 
 
 def autograd64(s, mode):
@@ -139,7 +132,7 @@ def _compare(tag, s, r, mode):
     live = ~r["failed"]
     tie_free = live & ~fm64 & (j64 == j) & (np.abs(x64 - r["xt"]).max(1) <= TIE_TOL) & (np.abs(v64 - r["vt"]).max(1) <= TIE_TOL)
     dropped = 1.0 - tie_free[live].mean()
-    err = TR.rel_err(r["dpos"], r["dvel"], gp, gv)
+    err = rel_err(r["dpos"], r["dvel"], gp, gv)
     print(f"{tag}: {len(j)} rays, {int(r['failed'].sum())} failed, second pass {int(r['again'].sum())}, global loop "
           f"{r['iters']}; dropped as not tie-free {100 * dropped:.2f} %; rel err max {err[tie_free].max():.3e} median "
           f"{np.median(err[tie_free]):.3e}")
@@ -175,7 +168,7 @@ def cases_inbounds(s):
     return ((p >= 0) & (p < s["ext"].astype(np.float32))).all(1)
 
 
-@pytest.mark.parametrize("name", list(TR.SCENES))
+@pytest.mark.parametrize("name", list(SCENES))
 def test_sdf_host_routine_matches_float64_autograd(name):
     s = sdf_scene(name)
     r = host_sdf(s)
@@ -210,7 +203,7 @@ def test_plane_replay_is_the_forward_march(case):
     assert np.array_equal(r["dvel"][z & ~r["failed"]], s["dv"][z & ~r["failed"]])
 
 
-@pytest.mark.parametrize("case", list(TR.SCENES) + [f"fuzz{k}" for k in range(6)])
+@pytest.mark.parametrize("case", list(SCENES) + [f"fuzz{k}" for k in range(6)])
 def test_sdf_replay_is_the_forward_march(case):
     s = _fuzz(int(case[4:])) if case.startswith("fuzz") else sdf_scene(case)
     r = host_sdf(s)
@@ -233,12 +226,12 @@ def test_one_iteration_closed_form(mode):
     dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
     if mode == "plane":                                         # 0.2 h before the plane y = 9.6 h, heading through it
         pos = np.array([[3.3, 9.4, 11.2]], np.float32) * np.float32(h); vel = np.array([[0.1, 1.0, -0.05]], np.float32)
-        r = SG.backtrace_pln_rays(rif, res, pos, vel, np.array([[7.5, 9.6, 7.5]], np.float32) * np.float32(h),
+        r = HC.backtrace_pln_rays(rif, res, pos, vel, np.array([[7.5, 9.6, 7.5]], np.float32) * np.float32(h),
                                   np.array([[0.0, 1.0, 0.0]], np.float32), dx, dv, h, ds)
     else:                                                       # 0.2 h inside the sphere of radius 6.3 h, heading out
         s = dict(res=res, h=h, ext=np.array([15.0, 15.0, 15.0]) * h)
         pos = np.array([[13.6, 7.2, 7.9]], np.float32) * np.float32(h); vel = np.array([[1.0, 0.1, -0.05]], np.float32)
-        r = SG.backtrace_sdf_rays(rif, sphere_sdf(s), res, pos, vel, dx, dv, h, ds)
+        r = HC.backtrace_sdf_rays(rif, sphere_sdf(s), res, pos, vel, dx, dv, h, ds)
     assert r["jstar"][0] == 1 and r["fwd"][0] == 1 and r["steps"][0] == 2 and not r["again"][0]
     R = torch.tensor(rif, dtype=torch.float64)
     J = torch.autograd.functional.jacobian(lambda y: stop_ad.n_grad_n(R, y, h), torch.tensor(pos[0], dtype=torch.float64)).numpy()
@@ -298,10 +291,6 @@ def test_abi_argument_checks():
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-def _t(a, dev):
-    return torch.as_tensor(np.asarray(a), device=dev)
-
-
 def _gpu_case(mode, case):
     if case.startswith("fuzz"):
         return _fuzz(int(case[4:]))
@@ -325,7 +314,7 @@ def _gpu_forward(T, mode, s, dev):
     return xt, vt, None
 
 
-GPU_CASES = [("plane", f"{n}/{p}") for n, p in PLANE_CASES] + [("sdf", n) for n in TR.SCENES] + \
+GPU_CASES = [("plane", f"{n}/{p}") for n, p in PLANE_CASES] + [("sdf", n) for n in SCENES] + \
     [(m, f"fuzz{k}") for m in ("plane", "sdf") for k in range(5)]
 
 
@@ -405,17 +394,11 @@ def _cube_case(mode, n=64):
     return s
 
 
-def _grads(cls, mode, s, dev, rif_grad=True, x_grad=False, v_grad=False, dtype=torch.float32):
-    rif = _t(s["rif"], dev).requires_grad_(rif_grad)
-    x = _t(s["pos"], dev).to(dtype).requires_grad_(x_grad)
-    v = _t(s["vel"], dev).requires_grad_(v_grad)
+def _grads(cls, mode, s, dev, *a, **kw):
     if mode == "plane":
-        xt, vt, fm = cls.apply(rif, x, v, _t(s["po"], dev), _t(s["pd"], dev), s["h"], s["ds"])
-    else:
-        xt, vt = cls.apply(rif, _t(s["sdf"], dev), x, v, s["h"], s["ds"])
-    ((xt * _t(s["dx"], dev)).sum() + (vt * _t(s["dv"], dev)).sum()).backward()
-    torch.cuda.synchronize()
-    return rif.grad, x.grad, v.grad
+        return grads(lambda rif, x, v: cls.apply(rif, x, v, _t(s["po"], dev), _t(s["pd"], dev), s["h"], s["ds"])[:2],
+                     s, dev, *a, **kw)
+    return grads(lambda rif, x, v: cls.apply(rif, _t(s["sdf"], dev), x, v, s["h"], s["ds"]), s, dev, *a, **kw)
 
 
 @pytest.mark.gpu
@@ -494,6 +477,6 @@ def test_metric_size(gpu):
     idx = torch.randperm(n, generator=gen)[:4096]
     sub = {k: t[idx.to(gpu)].cpu().numpy() for k, t in dict(pos=pos, vel=vel, po=po, pd=pd, dx=dx, dv=dv, dpos=dpos,
                                                               dvel=dvel).items()}
-    r = SG.backtrace_pln_rays(rif.cpu().numpy(), res, sub["pos"], sub["vel"], sub["po"], sub["pd"], sub["dx"], sub["dv"], h, ds)
+    r = HC.backtrace_pln_rays(rif.cpu().numpy(), res, sub["pos"], sub["vel"], sub["po"], sub["pd"], sub["dx"], sub["dv"], h, ds)
     assert not r["again"].any() and (r["jstar"] == r["fwd"]).mean() > 0.99     # the record is the last iteration
     assert np.array_equal(sub["dpos"], r["dpos"]) and np.array_equal(sub["dvel"], r["dvel"])

@@ -1,17 +1,47 @@
 #!/usr/bin/env python3
-"""Times the ray-state adjoint (drrt_backtrace_rays_f32, k_backtrace_rays) at the metric's configuration -- Luneburg ball
-on a 256^3 grid, 1 048 576 rays of bench.py's plane source, ds = h / 2 (~512 iterations per ray) -- next to the calls it
-goes with, each with device events around the library's own launches (drrt_profile_*) and as a whole call:
+"""Times the ray-state adjoints (dL/dpos, dL/dvel) next to the calls they go with, one workload per sub-command.  Each
+prints one JSON object.
 
-    forward            TracerC.trace                     (sort + pair copy + k_trace_flat)
-    backtrace          TracerC.backtrace                 (dL/dn: classification + window kernel)
-    backtrace_rays     TracerC.backtrace_rays            (dL/dpos, dL/dvel: k_backtrace_rays)
-    backward_both      tracer.ADTracerC backward with rif, x and v requiring grad (both adjoints)
-    backward_rif       tracer.BackTracerC backward       (the same without ray gradients)
+cube    drrt_backtrace_rays_f32 (k_backtrace_rays) at the metric's configuration -- Luneburg ball on a 256^3 grid,
+        1 048 576 rays of bench.py's plane source, ds = h / 2 (~512 iterations per ray) -- each phase with device events
+        around the library's own launches (drrt_profile_*) and as a whole call:
+            forward            TracerC.trace                     (sort + pair copy + k_trace_flat)
+            backtrace          TracerC.backtrace                 (dL/dn: classification + window kernel)
+            backtrace_rays     TracerC.backtrace_rays            (dL/dpos, dL/dvel: k_backtrace_rays)
+            backward_both      tracer.ADTracerC backward with rif, x and v requiring grad (both adjoints)
+            backward_rif       tracer.BackTracerC backward       (the same without ray gradients)
+        usage: bench_raygrad.py cube [--grid 256] [--rays 1048576] [--iters 10] [--warmup 3]
+        Output: per phase the median whole-call time (ms, device events on the stream) and the median time of each
+        library launch inside it; the ray-state kernel's ray-steps/s (stats.ray_steps / its kernel time).
 
-usage: bench_raygrad.py [--grid 256] [--rays 1048576] [--iters 10] [--warmup 3]
-Prints one JSON object: per phase the median whole-call time (ms, device events on the stream) and the median time of
-each library launch inside it; the ray-state kernel's ray-steps/s (stats.ray_steps / its kernel time)."""
+cable   drrt_backtrace_cable_rays_f32 (k_backtrace_cable_rays) on the workload of tools/bench_cable.py -- 257-sample
+        Luneburg-like profile, 4 194 304 rays x ~512 steps, closest approach to a target at 0.75 length -- for rays in
+        random order and in source-pixel order:
+            trace_cable            TracerC.trace_cable            (k_trace_cable)
+            backtrace_cable        TracerC.backtrace_cable        (k_backtrace_cable: dL/dn)
+            backtrace_cable_rays   TracerC.backtrace_cable_rays   (k_backtrace_cable_rays: dL/dpos, dL/dvel; replay + reverse)
+        usage: bench_raygrad.py cable [--side 2048] [--rounds 7] [--warmup 2] [--once]
+
+stop    drrt_backtrace_pln_rays_f32 / drrt_backtrace_sdf_rays_f32 (k_backtrace_stop_rays + k_backtrace_stop_rays_again)
+        next to the calls whose work they do:
+          plane  256^3 Luneburg, 1 048 576 rays of bench.py's plane source, sensor plane behind the volume: every ray's
+                 record is its last iteration, so the new call does one forward replay plus one backtrace_rays.
+                     trace_pln            TracerC.trace_pln            (k_trace_flat<.., 1> + k_trace_again)
+                     backtrace_rays       TracerC.backtrace_rays       (k_backtrace_rays, from trace_pln's exit rays and counts)
+                     backtrace_pln_rays   TracerC.backtrace_pln_rays   (the new call, in trace_pln's visit order)
+          sdf    the trace_sdf case of tools/run_configs.py: the rays of that source moved to the mid-plane that start
+                 within 0.4 of the centre (about 527k), ending on a sphere of radius 0.45 inside the lens.
+                     trace_sdf            TracerC.trace_sdf            (k_trace<2> + k_trace_again)
+                     backtrace_rays       TracerC.backtrace_rays       (from a plain trace of the same rays: trace_sdf leaves
+                                                                        no iteration counts; those rays run on to the box, so
+                                                                        this yardstick does somewhat MORE reverse iterations)
+                     backtrace_sdf_rays   TracerC.backtrace_sdf_rays   (the new call, in trace_sdf's visit order)
+        usage: bench_raygrad.py stop [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once]
+
+cable and stop time the three calls of a case alternately (one of each per round) with device events around the whole
+call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
+over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
+ones.  --once: a single call of each (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
 import argparse
 import json
 import os
@@ -25,15 +55,39 @@ import bench  # noqa: E402
 from adjointnonlinearraytracing_amd import _lib, drrt, tracer  # noqa: E402
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--grid", type=int, default=256)
-    ap.add_argument("--rays", type=int, default=1024 * 1024)
-    ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--warmup", type=int, default=3)
-    a = ap.parse_args()
-    dev = torch.device("cuda:0")
-    drrt.options.check_failed = False
+def time_alternately(calls, new, a):
+    """`calls` = {name: fn}, two existing calls and the `new` one -> the JSON of one case; None with --once, which makes
+    a single call of each instead."""
+    if a.once:
+        for fn in calls.values():
+            fn()
+        torch.cuda.synchronize()
+        return None
+    steps, ms = {}, {k: [] for k in calls}
+    for k, fn in calls.items():
+        for _ in range(max(a.warmup, 1)):
+            fn()
+        steps[k] = drrt.read_stats()["ray_steps"]
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    res = {k: dict(median_ms=statistics.median(v), min_ms=min(v), max_ms=max(v), ray_steps=steps[k])
+           for k, v in ms.items()}
+    old = [k for k in calls if k != new]
+    both = [x + y for x, y in zip(ms[old[0]], ms[old[1]])]
+    res["sum_existing_median_ms"] = statistics.median(both)
+    res["new_over_sum_existing"] = statistics.median(ms[new]) / statistics.median(both)
+    return res
+
+
+# ---- cube -----------------------------------------------------------------------------------------------------------
+def cube(a, dev):
     rif, pos, vel, h, ds = bench.make_workload(a.grid, a.rays, dev, seed=0)
     res = tuple(rif.shape)
     gen = torch.Generator(device="cpu").manual_seed(1)
@@ -100,7 +154,134 @@ def main():
     if k_ms:
         out["backtrace_rays"]["ray_steps_per_s_kernel"] = state["ray_steps"] / (k_ms * 1e-3)
     out["backward_both_over_backward_rif"] = out["backward_both"]["call_ms"] / out["backward_rif"]["call_ms"]
-    print(json.dumps(out))
+    return out
+
+
+# ---- cable ----------------------------------------------------------------------------------------------------------
+def cable_rays(order, side, radius, ds, dev):
+    n = side * side
+    if order == "random":
+        g = torch.Generator(device=dev).manual_seed(0)
+        ang = torch.rand(n, device=dev, generator=g) * 6.2831853
+        rad = 0.9 * radius * torch.sqrt(torch.rand(n, device=dev, generator=g))
+        pos = torch.stack([radius + rad * torch.cos(ang), torch.full((n,), 0.37 * ds, device=dev),
+                           radius + rad * torch.sin(ang)], -1)
+        vel = torch.randn(n, 3, device=dev, generator=g) * 0.05
+        vel[:, 1] = 1
+        vel /= vel.norm(dim=1, keepdim=True)
+        return pos.contiguous(), vel.contiguous()
+    i = torch.arange(side, device=dev, dtype=torch.float32)
+    X, Z = torch.meshgrid(i, i, indexing="ij")
+    px = (X.flatten() + 0.5) / side * 2 * radius
+    pz = (Z.flatten() + 0.5) / side * 2 * radius
+    pos = torch.stack([px, torch.full((n,), 0.37 * ds, device=dev), pz], -1)
+    vel = torch.zeros(n, 3, device=dev)
+    vel[:, 1] = 1
+    return pos.contiguous(), vel
+
+
+def cable(a, dev):
+    rres, radius = 257, 1.0
+    ds = radius / (rres - 1) / 2
+    length = 512 * ds
+    prof = torch.sqrt(2.0 - torch.linspace(0, 1, rres) ** 2).to(dev)
+    n = a.side * a.side
+    tg = torch.tensor([[radius, 0.75 * length, radius]], device=dev).expand(n, 3).contiguous()
+    T = drrt.TracerC()
+    out = dict(rays=n, rres=rres, ds=ds, length=length, rounds=a.rounds)
+    for order in ("random", "pixel"):
+        pos, vel = cable_rays(order, a.side, radius, ds, dev)
+        xt, vt, _ = T.trace_cable(prof, radius, length, pos, vel, tg, ds)
+        one = torch.ones_like(xt)
+        res = time_alternately({
+            "trace_cable": lambda: T.trace_cable(prof, radius, length, pos, vel, tg, ds),
+            "backtrace_cable": lambda: T.backtrace_cable(prof, radius, length, xt, vt, one, one, ds),
+            "backtrace_cable_rays": lambda: T.backtrace_cable_rays(prof, radius, length, pos, vel, tg, one, one, ds),
+        }, "backtrace_cable_rays", a)
+        if res is not None:
+            out[order] = res
+    return out
+
+
+# ---- stop -----------------------------------------------------------------------------------------------------------
+def plane_case(T, R, n, dev):
+    rif, pos, vel, h, ds = bench.make_workload(R, n, dev, seed=0)
+    res = tuple(rif.shape)
+    ext = (R - 1) * h
+    po = torch.tensor([[0.5 * ext, 1.5 * ext, 0.5 * ext]], device=dev).expand(pos.shape[0], 3).contiguous()
+    pd = torch.tensor([[0.0, 1.0, 0.0]], device=dev).expand(pos.shape[0], 3).contiguous()
+    xt, vt, _ = T.trace_pln(rif, res, pos, vel, po, pd, h, ds)
+    steps, order = drrt.keep_steps(drrt.last_steps), drrt.keep_order(drrt.last_order)
+    one = torch.ones_like(xt)
+    return pos.shape[0], "backtrace_pln_rays", {
+        "trace_pln": lambda: T.trace_pln(rif, res, pos, vel, po, pd, h, ds),
+        "backtrace_rays": lambda: T.backtrace_rays(rif, res, pos, vel, xt, vt, steps, one, one, h, ds, order=order),
+        "backtrace_pln_rays": lambda: T.backtrace_pln_rays(rif, res, pos, vel, po, pd, one, one, h, ds, order=order),
+    }
+
+
+def sdf_case(T, R, n, dev):
+    rif, pos, vel, h, ds = bench.make_workload(R, n, dev, seed=1)
+    res = tuple(rif.shape)
+    g = torch.linspace(0, 1.0, R, device=dev)
+    Z, Y, X = torch.meshgrid(g, g, g, indexing="ij")
+    sdf = (torch.sqrt((X - .5) ** 2 + (Y - .5) ** 2 + (Z - .5) ** 2) - 0.45).contiguous()
+    p2 = pos.clone()
+    p2[:, 1] = 0.5
+    keep = (p2 - 0.5).norm(dim=1) < 0.4
+    p2, v2 = p2[keep].contiguous(), vel[keep].contiguous()
+    xt, vt = T.trace(rif, res, p2, v2, h, ds)
+    steps = drrt.keep_steps(drrt.last_steps)
+    T.trace_sdf(rif, sdf, res, p2, v2, h, ds)
+    order = drrt.keep_order(drrt.last_order)
+    one = torch.ones_like(xt)
+    return p2.shape[0], "backtrace_sdf_rays", {
+        "trace_sdf": lambda: T.trace_sdf(rif, sdf, res, p2, v2, h, ds),
+        "backtrace_rays": lambda: T.backtrace_rays(rif, res, p2, v2, xt, vt, steps, one, one, h, ds, order=order),
+        "backtrace_sdf_rays": lambda: T.backtrace_sdf_rays(rif, sdf, res, p2, v2, one, one, h, ds, order=order),
+    }
+
+
+def stop(a, dev):
+    T = drrt.TracerC()
+    out = dict(grid=a.grid, rounds=a.rounds)
+    for case, build in (("plane", plane_case), ("sdf", sdf_case)):
+        n, new, calls = build(T, a.grid, a.rays, dev)
+        res = time_alternately(calls, new, a)
+        if res is not None:
+            out[case] = dict(res, rays=n)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
+    sub = ap.add_subparsers(dest="workload", required=True)
+    p_cube = sub.add_parser("cube")
+    p_cube.add_argument("--grid", type=int, default=256)
+    p_cube.add_argument("--rays", type=int, default=1024 * 1024)
+    p_cube.add_argument("--iters", type=int, default=10)
+    p_cube.add_argument("--warmup", type=int, default=3)
+    p_cube.set_defaults(run=cube)
+    p_cable = sub.add_parser("cable")
+    p_cable.add_argument("--side", type=int, default=2048, help="rays = side^2")
+    p_cable.set_defaults(run=cable)
+    p_stop = sub.add_parser("stop")
+    p_stop.add_argument("--grid", type=int, default=256)
+    p_stop.add_argument("--rays", type=int, default=1 << 20)
+    p_stop.set_defaults(run=stop)
+    for p in (p_cable, p_stop):
+        p.add_argument("--rounds", type=int, default=7)
+        p.add_argument("--warmup", type=int, default=2)
+        p.add_argument("--once", action="store_true")
+    a = ap.parse_args()
+    if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
+        ap.error("--side and --rounds must be positive, --warmup non-negative")
+    if a.workload == "stop" and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+        ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
+    if not torch.cuda.is_available():
+        sys.exit("bench_raygrad: needs a GPU")
+    drrt.options.check_failed = False
+    print(json.dumps(a.run(a, torch.device("cuda:0"))))
 
 
 if __name__ == "__main__":
