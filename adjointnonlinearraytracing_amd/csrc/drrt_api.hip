@@ -1,7 +1,8 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
-// src/volume.cpp:28,37,124), workspace layout, visit-order / step hand-over, per-kernel timing, and the launches of the
-// kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip / drrt_cable.hip / drrt_cable_rays.hip / drrt_stop_rays.hip.  Host code, plus the three
-// small utility kernels that belong to no march (pair copy of the grid, q16 encode / decode).
+// src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
+// and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
+// utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_march.h"
 
 using namespace drrt;
@@ -29,39 +30,36 @@ namespace drrt { int sensor_fail(int code, const char* msg) { return fail(code, 
 
 extern "C" const char* drrt_last_error(void) { return g_err; }
 
-// ---- visit-order hand-over between paired calls (per host thread) ----------------------------
-static thread_local const uint32_t* g_last_order = nullptr;   // order used by the last sorted call
-static thread_local size_t g_last_order_n = 0;
-static thread_local const uint32_t* g_hint_order = nullptr;   // order to use in the NEXT march call
-static thread_local size_t g_hint_n = 0;
-
-// Every march entry point takes (reads AND clears) the hint as its FIRST statement, so no return path --
-// validation failure included -- can leave a stale device pointer armed for a later call.
-static thread_local const uint32_t* g_last_steps = nullptr;   // per-ray iteration counts written by the last forward march
-static thread_local size_t g_last_steps_n = 0;
-static thread_local const uint32_t* g_hint_steps = nullptr;   // step hint for the NEXT adjoint call
-static thread_local size_t g_hint_steps_n = 0;
+// ---- visit-order / step / counter hand-over between paired calls (per host thread) -----------
 struct OrderHint { const uint32_t* order; size_t n; const uint32_t* steps; size_t steps_n; };
-static inline OrderHint take_hint() {
-  OrderHint h{g_hint_order, g_hint_n, g_hint_steps, g_hint_steps_n};
-  g_hint_order = nullptr; g_hint_n = 0;
-  g_hint_steps = nullptr; g_hint_steps_n = 0;
-  return h;
-}
+struct ThreadState {
+  const uint32_t* last_order = nullptr;     // order used by the last sorted call (maybe_sort)
+  const uint32_t* last_steps = nullptr;     // per-ray iteration counts written by the last forward march
+  size_t last_order_n = 0, last_steps_n = 0;
+  const unsigned* last_counters = nullptr;  // bundle classification of the last adjoint call (device, in its workspace)
+  OrderHint hint{};                         // order and steps for the NEXT march call
+  // Every march entry point takes (reads AND clears) the hint as its FIRST statement -- by making its GridCall or calling
+  // cable_begin --, so no return path, validation failure included, can leave a stale device pointer armed for a later call.
+  OrderHint take_hint() { const OrderHint h = hint; hint = OrderHint{}; return h; }
+  // one reset point per kind of call: a forward march forgets the iteration counts of the one before it (trace / trace_pln
+  // once they are about to launch, the marches that write none at their entry), a dL/dn adjoint the last classification
+  void reset_last_steps() { last_steps = nullptr; last_steps_n = 0; }
+  void reset_last_counters() { last_counters = nullptr; }
+};
+static thread_local ThreadState g_ts;
 
 extern "C" const uint32_t* drrt_last_order(size_t* n_out) {
-  if (n_out) *n_out = g_last_order_n;
-  return g_last_order;
+  if (n_out) *n_out = g_ts.last_order_n;
+  return g_ts.last_order;
 }
-extern "C" void drrt_set_order_hint(const uint32_t* order, size_t n) { g_hint_order = order; g_hint_n = order ? n : 0; }
-extern "C" size_t drrt_order_hint_pending(void) { return g_hint_order ? g_hint_n : (g_hint_steps ? g_hint_steps_n : 0); }
+extern "C" void drrt_set_order_hint(const uint32_t* order, size_t n) { g_ts.hint.order = order; g_ts.hint.n = order ? n : 0; }
+extern "C" size_t drrt_order_hint_pending(void) { const OrderHint& h = g_ts.hint; return h.order ? h.n : (h.steps ? h.steps_n : 0); }
 extern "C" const uint32_t* drrt_last_steps(size_t* n_out) {
-  if (n_out) *n_out = g_last_steps_n;
-  return g_last_steps;
+  if (n_out) *n_out = g_ts.last_steps_n;
+  return g_ts.last_steps;
 }
-extern "C" void drrt_set_step_hint(const uint32_t* steps, size_t n) { g_hint_steps = steps; g_hint_steps_n = steps ? n : 0; }
-static thread_local const unsigned* g_last_counters = nullptr;   // bundle classification of the last adjoint call (device, in its workspace)
-extern "C" const unsigned* drrt_last_bundle_counters(void) { return g_last_counters; }
+extern "C" void drrt_set_step_hint(const uint32_t* steps, size_t n) { g_ts.hint.steps = steps; g_ts.hint.steps_n = steps ? n : 0; }
+extern "C" const unsigned* drrt_last_bundle_counters(void) { return g_ts.last_counters; }
 extern "C" int drrt_ring_threshold_pct(void) { return DRRT_RING_MIN_NOFIT_PCT; }
 extern "C" int drrt_ring_long_threshold_permille(void) { return DRRT_RING_MIN_LONG_PERMILLE; }
 extern "C" int drrt_ring_direct_threshold_pct(void) { return DRRT_RING_DIRECT_MAX_PAIR_PCT; }
@@ -122,19 +120,55 @@ extern "C" const char* drrt_version(void) { return "drrt_hip 0.3 gfx950 src:" DR
 
 static inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-extern "C" size_t drrt_workspace_bytes(size_t n, unsigned flags) {
-  size_t b = 0;
-  if (flags & DRRT_FLAG_SORT_RAYS) b += align_up(sort_workspace_bytes(n), 256);
-  b += align_up(n * 7 * sizeof(float), 256);       // trace_target state (cheap; always counted)
-  return b;
+// ---- the workspace: one caller-owned device buffer, laid out here and nowhere else -------------------------------------
+//   every call but trace_target   [ sort buffers | per-ray slot ][ pair copy of the grid ][ counters, 512 B ]
+//   trace_target                  [ per-ray slot | sort buffers ][ pair copy of the grid ][ counters, 512 B ]
+//                                 |<-- drrt_workspace_bytes() -->|
+//                                 |<------------------- drrt_workspace_bytes_grid() ---------------------->|
+// sort buffers  keys, indices and the sort's own scratch (split by drrt_sort.hip); the visit order the sort leaves,
+//               drrt_last_order(), lies in here.  Padded to 256 B; none without DRRT_FLAG_SORT_RAYS.
+// per-ray slot  n * 7 floats padded to 256 B, always counted.  ONE slot with three tenants, one per call: the iteration
+//               counts of trace / trace_pln (n uint32, drrt_last_steps(); written where the buffer has room), the
+//               second-pass flags of trace_sdf and of the plane / SDF ray adjoints (n bytes), and the phase-A state of
+//               trace_target (n * 7 floats).  Safe, because flags and state live and die inside their call, and the one
+//               tenant that outlives its call, the iteration counts, is only ever a hint: a forward march forgets the
+//               pointer (reset_last_steps) before it writes the slot, and an adjoint handed counts that another call has
+//               overwritten since loses speed, never a result (include/drrt_hip.h, "step hint").
+// trace_target  keeps its state FIRST and the sort buffers behind it, as it always has: drrt_last_order() after it points
+//               behind the slot, and bindings look for it there.
+// pair copy     8 B per voxel (k_build_pair) with DRRT_FLAG_PAIR_GRID, at a multiple of 256 B.
+// counters      the last 512 B of a drrt_workspace_bytes_grid() buffer; the select counters of the bundle classification
+//               (32 B, drrt_last_bundle_counters()) sit 256 B into the block.
+// debug counters (DRRT_FLAG_DEBUG_COUNTERS)  512 B that END, 8-aligned, where the caller's buffer ends, whatever its size:
+//               in a buffer of exactly drrt_workspace_bytes_grid() bytes they are the counter block.
+// A new region is a pair of fields here and a line in ws_layout.
+constexpr size_t kCtrBytes = 512;
+struct WsLayout {
+  size_t sort_off, sort_bytes, sort_need;   // sort_need: what the sort uses of its padded region
+  size_t slot_off, slot_bytes;
+  size_t ray_bytes;                         // sort + slot: drrt_workspace_bytes()
+  size_t pair_off, pair_bytes;
+  size_t ctr_off, select_off;               // the counter block, and the select counters in it
+  size_t grid_bytes;                        // everything: drrt_workspace_bytes_grid()
+  size_t dbg_off;                           // from ws_bytes (0 when that is below kCtrBytes)
+};
+static WsLayout ws_layout(size_t n, long long nvox, unsigned flags, size_t ws_bytes, bool target_order = false) {
+  WsLayout L{};
+  if (flags & DRRT_FLAG_SORT_RAYS) { L.sort_need = sort_workspace_bytes(n); L.sort_bytes = align_up(L.sort_need, 256); }
+  L.slot_bytes = align_up(n * 7 * sizeof(float), 256);
+  L.sort_off = target_order ? L.slot_bytes : 0;
+  L.slot_off = target_order ? 0 : L.sort_bytes;
+  L.pair_off = L.ray_bytes = L.sort_bytes + L.slot_bytes;
+  L.pair_bytes = ((flags & DRRT_FLAG_PAIR_GRID) && nvox > 0) ? (size_t)nvox * 2 * sizeof(float) : 0;
+  L.ctr_off = L.pair_off + L.pair_bytes;
+  L.select_off = L.ctr_off + 256;
+  L.grid_bytes = L.ctr_off + kCtrBytes;
+  L.dbg_off = ws_bytes >= kCtrBytes ? ((ws_bytes - kCtrBytes) & ~(size_t)7) : 0;
+  return L;
 }
 
-// Workspace layout: [ sort buffers | trace_target state ][ pair copy of the grid, 8 B per voxel ][ 512 B counters ]
-extern "C" size_t drrt_workspace_bytes_grid(size_t n, long long nvox, unsigned flags) {
-  size_t b = drrt_workspace_bytes(n, flags);
-  if ((flags & DRRT_FLAG_PAIR_GRID) && nvox > 0) b += (size_t)nvox * 2 * sizeof(float);
-  return b + 512;
-}
+extern "C" size_t drrt_workspace_bytes(size_t n, unsigned flags) { return ws_layout(n, 0, flags, 0).ray_bytes; }
+extern "C" size_t drrt_workspace_bytes_grid(size_t n, long long nvox, unsigned flags) { return ws_layout(n, nvox, flags, 0).grid_bytes; }
 
 namespace drrt {
 // pair[2 i] = n[i], pair[2 i + 1] = n[i + W] (the y-neighbour, clamped at the far y face -- those entries are never
@@ -148,24 +182,6 @@ __global__ void __launch_bounds__(256) k_build_pair(const float* __restrict__ g,
   q[i] = make_float2(g[i], g[i + y1]);
 }
 }  // namespace drrt
-
-// DRRT_FLAG_PAIR_GRID: place (and, unless DRRT_FLAG_PAIR_REUSE, build) the pair copy in the workspace.
-static int maybe_pair(Vol& V, long long nvox, size_t n, unsigned flags, void* ws, size_t ws_bytes, hipStream_t s) {
-  if (!(flags & DRRT_FLAG_PAIR_GRID)) return DRRT_OK;
-  const size_t off = drrt_workspace_bytes(n, flags), need = off + (size_t)nvox * 2 * sizeof(float) + 512;
-  if (!ws || ws_bytes < need) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_PAIR_GRID (see drrt_workspace_bytes_grid)");
-  if (((uintptr_t)ws + off) % 16 != 0) return fail(DRRT_ERR_ARG, "workspace must be 16-byte aligned for DRRT_FLAG_PAIR_GRID");
-  float2* q = (float2*)((char*)ws + off);
-  if (!(flags & DRRT_FLAG_PAIR_REUSE)) {
-    ProfScope prof(DRRT_PROF_QUAD, s);
-    hipLaunchKernelGGL(drrt::k_build_pair, dim3((unsigned)(((size_t)nvox + 255) / 256)), dim3(256), 0, s, V.data, q, V.W, V.H,
-                       (unsigned)nvox);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail_hip(e, "k_build_pair");
-  }
-  V.pair = (const float*)q;
-  return DRRT_OK;
-}
 
 // volume ctor checks: src/volume.cpp:31-38 (size) and :123-124 (width/height >= 2)
 static int check_steps(float h, float ds) {
@@ -204,25 +220,19 @@ static int zero_stats(drrt_stats* stats, hipStream_t s) {
   return e == hipSuccess ? DRRT_OK : fail_hip(e, "hipMemsetAsync(stats)");
 }
 
-static int maybe_sort(const Vol& V, float h, size_t n, const void* pos, const void* vel, float dir_sign,
-                      unsigned flags, void* ws, size_t ws_bytes, const uint32_t** perm, hipStream_t s,
-                      OrderHint hint, int io_half = 0) {
-  *perm = nullptr;
-  // a hint from the caller (normally the paired forward call's order) replaces the sort; it was consumed
-  // by this call at its entry (take_hint) whether or not it is usable.  Entries are range-checked on the
-  // device (ray_index), so a wrong hint can leave rays unvisited but cannot make a kernel fault.
-  if (hint.order && hint.n == n) { *perm = hint.order; return DRRT_OK; }
-  if (!(flags & DRRT_FLAG_SORT_RAYS) || n < 2) return DRRT_OK;
-  if (!ws || ws_bytes < sort_workspace_bytes(n)) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_SORT_RAYS");
-  ProfScope prof(DRRT_PROF_SORT, s);
-  hipError_t e = sort_rays_by_entry_voxel(V, h, n, pos, vel, io_half, dir_sign, ws, ws_bytes, perm, s,
-                                          (flags & DRRT_FLAG_CHORD_KEY) != 0);
-  if (e == hipSuccess) { g_last_order = *perm; g_last_order_n = n; }
-  return e == hipSuccess ? DRRT_OK : fail_hip(e, "sort_rays_by_entry_voxel");
-}
-
 #define LAUNCH_CHECK(where)                                              \
   do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return fail_hip(e_, where); } while (0)
+
+// the tail of an entry that launches one kernel family: the launch inside its profile record, then the launch check
+template <class Launch>
+static int timed_launch(int prof_id, hipStream_t s, const char* where, Launch launch) {
+  {
+    ProfScope prof(prof_id, s);
+    launch();
+  }
+  LAUNCH_CHECK(where);
+  return DRRT_OK;
+}
 
 // The second pass of trace_pln / trace_sdf and of their ray-state adjoints needs the global loop count of the first: a
 // library-owned stats block, one per device (allocated once), for callers that pass none.  It is shared by every stream of
@@ -239,45 +249,95 @@ static int private_stats(drrt_stats** stats) {
   return DRRT_OK;
 }
 
+// ---- the prologue the grid marches share ------------------------------------------------------------------------------
+// An entry point makes its GridCall first (that takes the hint and clears the error message), then runs the shared steps
+// in this order, with the checks that are its own in between: open() -- grid and steps --, check_ray_count() after its
+// null-pointer checks, place() -- visit order (hint or sort), pair copy, dispatch order: all that touches the workspace.
+struct GridCall {
+  OrderHint hint = g_ts.take_hint();
+  Vol& vol;                       // the argument block's
+  hipStream_t s;
+  float h = 0.f;
+  const uint32_t* perm = nullptr;
+  int xcd_order = 0;              // 1: the launch's blocks take the visit order XCD by XCD
+  GridCall(Vol& v, void* stream) : vol(v), s((hipStream_t)stream) { g_err[0] = 0; }
+
+  int open(const float* rif, long long nvox, const int res[3], float h_, float ds) {
+    h = h_;
+    const int rc = make_vol(rif, nvox, res, h, &vol);
+    return rc ? rc : check_steps(h, ds);
+  }
+  // `key_pos`, `key_vel`, `dir_sign`: the rays the sort keys are made from, and which way they head
+  int place(long long nvox, size_t n, const void* key_pos, const void* key_vel, float dir_sign, unsigned flags,
+            const WsLayout& L, void* ws, size_t ws_bytes, int io_half = 0) {
+    // A hint from the caller (normally the paired forward call's order) replaces the sort; it was consumed when this call
+    // began whether or not it is usable.  Entries are range-checked on the device (ray_index), so a wrong hint can leave
+    // rays unvisited but cannot make a kernel fault.
+    if (hint.order && hint.n == n) {
+      perm = hint.order;
+    } else if ((flags & DRRT_FLAG_SORT_RAYS) && n >= 2) {
+      // (a caller whose sort buffers do not start the workspace -- trace_target -- has checked that it reaches them)
+      if (!ws || ws_bytes - L.sort_off < L.sort_need) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_SORT_RAYS");
+      ProfScope prof(DRRT_PROF_SORT, s);
+      hipError_t e = sort_rays_by_entry_voxel(vol, h, n, key_pos, key_vel, io_half, dir_sign, (char*)ws + L.sort_off,
+                                              ws_bytes - L.sort_off, &perm, s, (flags & DRRT_FLAG_CHORD_KEY) != 0);
+      if (e != hipSuccess) return fail_hip(e, "sort_rays_by_entry_voxel");
+      g_ts.last_order = perm; g_ts.last_order_n = n;
+    }
+    xcd_order = (perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
+    // DRRT_FLAG_PAIR_GRID: the pair copy of the grid, built here unless DRRT_FLAG_PAIR_REUSE
+    if (!(flags & DRRT_FLAG_PAIR_GRID)) return DRRT_OK;
+    if (!ws || ws_bytes < L.grid_bytes) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_PAIR_GRID (see drrt_workspace_bytes_grid)");
+    if (((uintptr_t)ws + L.pair_off) % 16 != 0) return fail(DRRT_ERR_ARG, "workspace must be 16-byte aligned for DRRT_FLAG_PAIR_GRID");
+    float2* q = (float2*)((char*)ws + L.pair_off);
+    if (!(flags & DRRT_FLAG_PAIR_REUSE)) {
+      ProfScope prof(DRRT_PROF_QUAD, s);
+      hipLaunchKernelGGL(drrt::k_build_pair, dim3((unsigned)(((size_t)nvox + 255) / 256)), dim3(256), 0, s, vol.data, q, vol.W,
+                         vol.H, (unsigned)nvox);
+      LAUNCH_CHECK("k_build_pair");
+    }
+    vol.pair = (const float*)q;
+    return DRRT_OK;
+  }
+  void drop_order() { perm = nullptr; xcd_order = 0; }
+};
+static int check_ray_count(size_t n) {
+  return n > 0xffffffffULL ? fail(DRRT_ERR_ARG, "too many rays for uint32 permutation") : DRRT_OK;
+}
+
 template <int MODE>
 static int run_trace(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
                      const void* pos, const void* vel, const float* pln_o, const float* pln_d,
                      float h, float ds, void* xt, void* vt, uint8_t* failmask, drrt_stats* stats,
                      void* ws, size_t ws_bytes, unsigned flags, void* stream, int io_half = 0) {
-  const OrderHint hint = take_hint();
-  g_err[0] = 0;
-  hipStream_t s = (hipStream_t)stream;
   TraceArgs a{};
-  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
-  rc = check_steps(h, ds); if (rc) return rc;
+  GridCall c(a.vol, stream);
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
   if (n == 0) return zero_stats(stats, s);
   if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (MODE == 1 && (!pln_o || !pln_d || !failmask)) return fail(DRRT_ERR_ARG, "null plane/failmask pointer");
   if ((MODE == 1 || MODE == 2) && !stats) { rc = private_stats(&stats); if (rc) return rc; }
   if (MODE == 2 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
-  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  rc = check_ray_count(n); if (rc) return rc;
   rc = zero_stats(stats, s); if (rc) return rc;
-  rc = maybe_sort(a.vol, h, n, pos, vel, 1.f, flags, ws, ws_bytes, &a.perm, s, hint, io_half); if (rc) return rc;
-  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
-  if (MODE == 2) {                      // n flag bytes, in the slack the workspace keeps after the sort buffers
-    const size_t off = (flags & DRRT_FLAG_SORT_RAYS) ? align_up(sort_workspace_bytes(n), 256) : 0;
-    if (!ws || ws_bytes < off + n) return fail(DRRT_ERR_ARG, "workspace too small for trace_sdf (see drrt_workspace_bytes)");
-    a.again = (uint8_t*)ws + off;
+  const WsLayout L = ws_layout(n, nvox, flags, ws_bytes);
+  rc = c.place(nvox, n, pos, vel, 1.f, flags, L, ws, ws_bytes, io_half); if (rc) return rc;
+  if (MODE == 2) {                      // the second-pass flags: n bytes of the per-ray slot
+    if (!ws || ws_bytes < L.slot_off + n) return fail(DRRT_ERR_ARG, "workspace too small for trace_sdf (see drrt_workspace_bytes)");
+    a.again = (uint8_t*)ws + L.slot_off;
   }
-  g_last_steps = nullptr; g_last_steps_n = 0;
-  if (MODE != 2) {
-    // per-ray iteration counts for the paired adjoint (drrt_last_steps): n uint32 in the trace_target slot of the workspace
-    const size_t off = (flags & DRRT_FLAG_SORT_RAYS) ? align_up(sort_workspace_bytes(n), 256) : 0;
-    if (ws && ws_bytes >= off + n * sizeof(uint32_t)) {
-      a.steps_out = (uint32_t*)((char*)ws + off);
-      g_last_steps = a.steps_out; g_last_steps_n = n;
-    }
+  g_ts.reset_last_steps();
+  if (MODE != 2 && ws && ws_bytes >= L.slot_off + n * sizeof(uint32_t)) {
+    // per-ray iteration counts for the paired adjoint (drrt_last_steps): n uint32 of the per-ray slot, where there is room
+    a.steps_out = (uint32_t*)((char*)ws + L.slot_off);
+    g_ts.last_steps = a.steps_out; g_ts.last_steps_n = n;
   }
   a.io_half = io_half;
   a.sdf = sdf; a.pos = pos; a.vel = vel; a.pln_o = pln_o; a.pln_d = pln_d;
   a.xt = xt; a.vt = vt; a.failmask = failmask; a.stats = stats; a.n = n; a.ds = ds;
   a.max_steps = (MODE == 2) ? steps_sdf(h, res, ds) : steps_fwd(h, res, ds);
-  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
   {
     ProfScope prof(DRRT_PROF_TRACE, s);
     launch_trace(MODE, a, s);
@@ -391,30 +451,26 @@ extern "C" int drrt_trace_target_f32(const float* rif, long long nvox, const int
                                      float h, float ds, float* xt, float* vt, float* dist2,
                                      drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags,
                                      void* stream) {
-  g_last_steps = nullptr; g_last_steps_n = 0;     // this forward march writes no iteration counts
-  (void)take_hint();     // never honoured here: the phase-A state buffer at the start of the workspace would overlay
-                         // an order that lives in the same workspace (drrt_last_order() of an earlier call)
-  g_err[0] = 0;
-  hipStream_t s = (hipStream_t)stream;
   TargetArgs a{};
-  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
-  rc = check_steps(h, ds); if (rc) return rc;
+  GridCall c(a.vol, stream);
+  c.hint = OrderHint{};              // never honoured here: the phase-A state at the start of the workspace would overlay an
+                                     // order that lives in the same workspace (drrt_last_order() of an earlier call)
+  g_ts.reset_last_steps();           // this forward march writes no iteration counts
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
   if (n == 0) return zero_stats(stats, s);
   if (!pos || !vel || !target || !xt || !vt || !dist2) return fail(DRRT_ERR_ARG, "null ray pointer");
-  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  rc = check_ray_count(n); if (rc) return rc;
   // the global iteration count lives in stats->iters: a stats block is mandatory here
   if (!stats) return fail(DRRT_ERR_ARG, "trace_target needs a stats block (global loop count)");
-  const size_t state_bytes = align_up(n * 7 * sizeof(float), 256);
-  const size_t sort_bytes = (flags & DRRT_FLAG_SORT_RAYS) ? align_up(sort_workspace_bytes(n), 256) : 0;
-  if (!ws || ws_bytes < state_bytes + sort_bytes) return fail(DRRT_ERR_ARG, "workspace too small for trace_target");
+  const WsLayout L = ws_layout(n, nvox, flags, ws_bytes, /*target_order=*/true);
+  if (!ws || ws_bytes < L.ray_bytes) return fail(DRRT_ERR_ARG, "workspace too small for trace_target");
   rc = zero_stats(stats, s); if (rc) return rc;
-  a.state = (float*)ws;
-  rc = maybe_sort(a.vol, h, n, pos, vel, 1.f, flags, (char*)ws + state_bytes, ws_bytes - state_bytes, &a.perm, s,
-                  OrderHint{nullptr, 0, nullptr, 0});
-  if (rc) return rc;
+  rc = c.place(nvox, n, pos, vel, 1.f, flags, L, ws, ws_bytes); if (rc) return rc;
+  a.state = (float*)((char*)ws + L.slot_off);
+  a.perm = c.perm;
   a.pos = pos; a.vel = vel; a.target = target; a.xt = xt; a.vt = vt; a.dist2 = dist2;
   a.stats = stats; a.n = n; a.ds = ds; a.max_steps = steps_fwd(h, res, ds);
-  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;     // lies behind [state | sort buffers]
   launch_target(a, s);
   LAUNCH_CHECK("k_target");
   return DRRT_OK;
@@ -467,13 +523,11 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
                          const void* xt, const void* vt, const void* dx, const void* dv,
                          float h, float ds, float* grad, drrt_stats* stats, void* ws, size_t ws_bytes,
                          unsigned flags, void* stream, int io_half = 0, const ChunkReq* ck = nullptr) {
-  const OrderHint hint = take_hint();
-  g_last_counters = nullptr;              // set again below when this call classifies its bundles
-  g_err[0] = 0;
-  hipStream_t s = (hipStream_t)stream;
   BackArgs a{};
-  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
-  rc = check_steps(h, ds); if (rc) return rc;
+  GridCall c(a.vol, stream);
+  g_ts.reset_last_counters();             // set again below when this call classifies its bundles
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
   if (!grad) return fail(DRRT_ERR_ARG, "null grad pointer");
   if (MODE == 1 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
   const unsigned ablation = (flags >> 8) & 0xffu;
@@ -484,7 +538,7 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
     if (flags & DRRT_FLAG_DIRECT_ATOMICS) return fail(DRRT_ERR_ARG, "chunk: not available with DRRT_FLAG_DIRECT_ATOMICS");
     if (!ck->state || ck->state_bytes < drrt_backtrace_chunk_state_bytes(n))
       return fail(DRRT_ERR_ARG, "chunk: state buffer too small (see drrt_backtrace_chunk_state_bytes)");
-    if (!first_chunk && (flags & DRRT_FLAG_SORT_RAYS) && !(hint.order && hint.n == n))
+    if (!first_chunk && (flags & DRRT_FLAG_SORT_RAYS) && !(c.hint.order && c.hint.n == n))
       return fail(DRRT_ERR_ARG, "chunk: a resumed chunk needs the visit order of its first chunk (drrt_set_order_hint)");
   }
   if (!(flags & DRRT_FLAG_NO_ZERO) && first_chunk) {                         // src/tracer.cpp:401-403
@@ -495,10 +549,11 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
   if (first_chunk) { rc = zero_stats(stats, s); if (rc) return rc; }
   if (n == 0) return DRRT_OK;
   if (!xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
-  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
+  rc = check_ray_count(n); if (rc) return rc;
   if (ablation == 1u) return DRRT_OK;       // the gradient stays zero: bench.py's parity check must fail on it
-  rc = maybe_sort(a.vol, h, n, xt, vt, -1.f, flags, ws, ws_bytes, &a.perm, s, hint, io_half); if (rc) return rc;
-  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
+  const WsLayout L = ws_layout(n, nvox, flags, ws_bytes);
+  rc = c.place(nvox, n, xt, vt, -1.f, flags, L, ws, ws_bytes, io_half); if (rc) return rc;
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
   a.io_half = io_half;
   a.sdf = sdf; a.xt = xt; a.vt = vt; a.dx = dx; a.dv = dv; a.grad = grad; a.stats = stats;
   a.n = n; a.ds = ds; a.max_steps = steps_adj(h, res, ds);
@@ -511,24 +566,22 @@ static int run_backtrace(const float* rif, const float* sdf, long long nvox, con
     if (ck->progress) { hipLaunchKernelGGL(drrt::k_chunk_progress_init, dim3(1), dim3(64), 0, s, ck->progress); LAUNCH_CHECK("k_chunk_progress_init"); }
   }
   a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
-  a.fsteps = (hint.steps && hint.steps_n == n) ? hint.steps : nullptr;
-  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
+  a.fsteps = (c.hint.steps && c.hint.steps_n == n) ? c.hint.steps : nullptr;
   a.dbg = nullptr;
-  if (flags & DRRT_FLAG_DEBUG_COUNTERS) {        // last 64 bytes of the workspace
-    if (!ws || ws_bytes < 512) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_DEBUG_COUNTERS");
-    a.dbg = (unsigned long long*)((char*)ws + ((ws_bytes - 512) & ~(size_t)7));
-    hipError_t e = hipMemsetAsync(a.dbg, 0, 512, s);
+  if (flags & DRRT_FLAG_DEBUG_COUNTERS) {        // the 512 bytes at the end of the caller's buffer
+    if (!ws || ws_bytes < kCtrBytes) return fail(DRRT_ERR_ARG, "workspace too small for DRRT_FLAG_DEBUG_COUNTERS");
+    a.dbg = (unsigned long long*)((char*)ws + L.dbg_off);
+    hipError_t e = hipMemsetAsync(a.dbg, 0, kCtrBytes, s);
     if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(dbg)");
   }
-  const size_t ctr_off = (drrt_workspace_bytes(n, flags) + ((flags & DRRT_FLAG_PAIR_GRID) ? (size_t)nvox * 2 * sizeof(float) : 0) + 7) & ~(size_t)7;
   const bool dbg = a.dbg != nullptr;
-  const BackPlan p = plan_backtrace(MODE, flags, ck != nullptr, dbg, a.perm != nullptr && ws && ws_bytes >= ctr_off + 512);
+  const BackPlan p = plan_backtrace(MODE, flags, ck != nullptr, dbg, a.perm != nullptr && ws && ws_bytes >= L.grid_bytes);
   {
     ProfScope prof(DRRT_PROF_BACKTRACE, s);
     if (p.direct) launch_backtrace_direct(MODE, a, s);
     if (p.classify) {
-      a.select = (unsigned*)((char*)ws + ctr_off + 256);
-      g_last_counters = a.select;
+      a.select = (unsigned*)((char*)ws + L.select_off);
+      g_ts.last_counters = a.select;
       hipError_t e = hipMemsetAsync(a.select, 0, 32, s);
       if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(select)");
       if (p.ring_general) {        // [5] != 0: the classification picks the general ring instantiation, never a sparse-only one
@@ -557,30 +610,22 @@ extern "C" int drrt_backtrace_rays_f32(const float* rif, long long nvox, const i
                                        const uint32_t* fwd_steps, const float* dx, const float* dv, float h, float ds,
                                        float* dpos, float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes,
                                        unsigned flags, void* stream) {
-  const OrderHint hint = take_hint();
-  g_err[0] = 0;
-  hipStream_t s = (hipStream_t)stream;
   RayGradArgs a{};
-  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
-  rc = check_steps(h, ds); if (rc) return rc;
+  GridCall c(a.vol, stream);
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
   rc = zero_stats(stats, s); if (rc) return rc;
   if (n == 0) return DRRT_OK;
   if (!pos || !vel || !xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's drrt_last_steps())");
   if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
-  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
-  rc = maybe_sort(a.vol, h, n, xt, vt, -1.f, flags, ws, ws_bytes, &a.perm, s, hint); if (rc) return rc;
-  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
+  rc = check_ray_count(n); if (rc) return rc;
+  rc = c.place(nvox, n, xt, vt, -1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
   a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.fsteps = fwd_steps; a.dx = dx; a.dv = dv;
   a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
   a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
-  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
-  {
-    ProfScope prof(DRRT_PROF_BACKTRACE_RAYS, s);
-    launch_backtrace_rays(a, s);
-  }
-  LAUNCH_CHECK("k_backtrace_rays");
-  return DRRT_OK;
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(DRRT_PROF_BACKTRACE_RAYS, s, "k_backtrace_rays", [&] { launch_backtrace_rays(a, s); });
 }
 
 // ray-state adjoints of trace_plane (MODE 1) and trace_sdf (MODE 2): drrt_stop_rays.hip
@@ -589,40 +634,36 @@ static int run_backtrace_stop_rays(const float* rif, const float* sdf, long long
                                    const float* pos, const float* vel, const float* pln_o, const float* pln_d,
                                    const float* dx, const float* dv, float h, float ds, float* dpos, float* dvel,
                                    drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
-  const OrderHint hint = take_hint();
-  g_err[0] = 0;
-  hipStream_t s = (hipStream_t)stream;
   StopRayGradArgs a{};
-  int rc = make_vol(rif, nvox, res, h, &a.vol); if (rc) return rc;
-  rc = check_steps(h, ds); if (rc) return rc;
+  GridCall c(a.vol, stream);
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
   if (MODE == 2 && !sdf) return fail(DRRT_ERR_ARG, "null sdf pointer");
   if (n == 0) return zero_stats(stats, s);
   if (!pos || !vel || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (MODE == 1 && (!pln_o || !pln_d)) return fail(DRRT_ERR_ARG, "null plane pointer");
   if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
-  if (n > 0xffffffffULL) return fail(DRRT_ERR_ARG, "too many rays for uint32 permutation");
-  const size_t off = (flags & DRRT_FLAG_SORT_RAYS) ? align_up(sort_workspace_bytes(n), 256) : 0;   // as trace_sdf's flags
-  if (!ws || ws_bytes < off + n) return fail(DRRT_ERR_ARG, "workspace too small for the second-pass flags (see drrt_workspace_bytes)");
+  rc = check_ray_count(n); if (rc) return rc;
+  const WsLayout L = ws_layout(n, nvox, flags, ws_bytes);
+  if (!ws || ws_bytes < L.slot_off + n) return fail(DRRT_ERR_ARG, "workspace too small for the second-pass flags (see drrt_workspace_bytes)");
   if (!stats) { rc = private_stats(&stats); if (rc) return rc; }
   rc = zero_stats(stats, s); if (rc) return rc;
-  rc = maybe_sort(a.vol, h, n, pos, vel, 1.f, flags, ws, ws_bytes, &a.perm, s, hint); if (rc) return rc;
-  rc = maybe_pair(a.vol, nvox, n, flags, ws, ws_bytes, s); if (rc) return rc;
-  a.again = (uint8_t*)ws + off;
-  if (a.perm != nullptr) {                  // an order that lives where the flags go (a hint into this very workspace from a
-    const char* o = (const char*)a.perm;    // call that sorted, handed to one that does not) is not used: slower, never wrong
+  rc = c.place(nvox, n, pos, vel, 1.f, flags, L, ws, ws_bytes); if (rc) return rc;
+  a.again = (uint8_t*)ws + L.slot_off;      // the second-pass flags: n bytes of the per-ray slot, as trace_sdf's
+  if (c.perm != nullptr) {
+    // An order that lives where the flags go is not used: slower, never wrong.  Only a hinted order can (one this call
+    // sorted lies in its own sort buffers, beside the slot), and a hint is an address, not a region of L -- it may come
+    // from a call that laid this workspace out for other flags -- so the test stays on addresses.
+    const char* o = (const char*)c.perm;
     const char* f = (const char*)a.again;
-    if (o < f + n && f < o + n * sizeof(uint32_t)) a.perm = nullptr;
+    if (o < f + n && f < o + n * sizeof(uint32_t)) c.drop_order();
   }
   a.sdf = sdf; a.pos = pos; a.vel = vel; a.pln_o = pln_o; a.pln_d = pln_d; a.dx = dx; a.dv = dv;
   a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
   a.max_steps = (MODE == 2) ? steps_sdf(h, res, ds) : steps_fwd(h, res, ds);      // the forward's bound
-  a.xcd_order = (a.perm != nullptr && !(flags & DRRT_FLAG_DISPATCH_IN_ORDER)) ? 1 : 0;
-  {
-    ProfScope prof(MODE == 1 ? DRRT_PROF_BACKTRACE_PLN_RAYS : DRRT_PROF_BACKTRACE_SDF_RAYS, s);
-    launch_backtrace_stop_rays(MODE, a, s);
-  }
-  LAUNCH_CHECK("k_backtrace_stop_rays");
-  return DRRT_OK;
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(MODE == 1 ? DRRT_PROF_BACKTRACE_PLN_RAYS : DRRT_PROF_BACKTRACE_SDF_RAYS, s, "k_backtrace_stop_rays",
+                      [&] { launch_backtrace_stop_rays(MODE, a, s); });
 }
 
 extern "C" int drrt_backtrace_pln_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
@@ -677,33 +718,41 @@ extern "C" int drrt_backtrace_sdf_f32(const float* rif, const float* sdf, long l
   return run_backtrace<1>(rif, sdf, nvox, res, n, xt, vt, dx, dv, h, ds, grad, stats, ws, ws_bytes, flags, stream);
 }
 
+// ---- the prologue the three cable entries share, in their common order: the hint (taken, never honoured: the cable kernels
+// visit rays in caller order), the profile and step checks, the adjoint's zero fill of `zero_grad` (nullable), the stats,
+// and the head of the argument block.  `null_msg` (nullable) is the entry's complaint about its own grid pointers.
+template <class Args>
+static int cable_begin(Args& a, const char* null_msg, const float* rif, size_t rres, float radius, float length, float ds,
+                       float* zero_grad, drrt_stats* stats, size_t n, hipStream_t s) {
+  (void)g_ts.take_hint();
+  g_err[0] = 0;
+  if (null_msg) return fail(DRRT_ERR_ARG, null_msg);
+  if (rres < 2 || rres > 0x7fffffffULL) return fail(DRRT_ERR_BAD_RES, "volume: invalid resolution!");
+  if (!(radius > 0.f) || !(length > 0.f) || !(ds > 0.f) || !(ds < 3.0e38f))
+    return fail(DRRT_ERR_ARG, "radius, length and ds must be positive and finite");
+  if (zero_grad) {                                                           // src/tracer.cpp:528-530
+    hipError_t e = hipMemsetAsync(zero_grad, 0, rres * sizeof(float), s);
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
+  }
+  a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
+  a.max_steps = (int)(4.0f * length / ds);                                   // src/tracer.cpp:332, :544
+  a.stats = stats; a.n = n;
+  return zero_stats(stats, s);
+}
+
 extern "C" int drrt_trace_cable_f32(const float* rif, size_t rres, float radius, float length, size_t n,
                                     const float* pos, const float* vel, const float* target, float ds,
                                     float* xt, float* vt, float* dist2, drrt_stats* stats, void* ws,
                                     size_t ws_bytes, unsigned flags, void* stream) {
   (void)ws; (void)ws_bytes; (void)flags;
-  g_last_steps = nullptr; g_last_steps_n = 0;
-  (void)take_hint();     // the cable kernels visit rays in caller order
-  g_err[0] = 0;
   hipStream_t s = (hipStream_t)stream;
-  if (!rif) return fail(DRRT_ERR_ARG, "null rif pointer");
-  if (rres < 2 || rres > 0x7fffffffULL) return fail(DRRT_ERR_BAD_RES, "volume: invalid resolution!");
-  if (!(radius > 0.f) || !(length > 0.f) || !(ds > 0.f) || !(ds < 3.0e38f))
-    return fail(DRRT_ERR_ARG, "radius, length and ds must be positive and finite");
-  int rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  if (!pos || !vel || !target || !xt || !vt || !dist2) return fail(DRRT_ERR_ARG, "null ray pointer");
   CableArgs a{};
-  a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
-  a.max_steps = (int)(4.0f * length / ds);                                   // src/tracer.cpp:332
+  const int rc = cable_begin(a, rif ? nullptr : "null rif pointer", rif, rres, radius, length, ds, nullptr, stats, n, s);
+  g_ts.reset_last_steps();              // this forward march writes no iteration counts, refused or not
+  if (rc || n == 0) return rc;
+  if (!pos || !vel || !target || !xt || !vt || !dist2) return fail(DRRT_ERR_ARG, "null ray pointer");
   a.pos = pos; a.vel = vel; a.target = target; a.xt = xt; a.vt = vt; a.dist2 = dist2;
-  a.stats = stats; a.n = n;
-  {
-    ProfScope prof(DRRT_PROF_TRACE, s);
-    launch_trace_cable(a, s);
-  }
-  LAUNCH_CHECK("k_trace_cable");
-  return DRRT_OK;
+  return timed_launch(DRRT_PROF_TRACE, s, "k_trace_cable", [&] { launch_trace_cable(a, s); });
 }
 
 extern "C" int drrt_backtrace_cable_f32(const float* rif, size_t rres, float radius, float length, size_t n,
@@ -711,30 +760,14 @@ extern "C" int drrt_backtrace_cable_f32(const float* rif, size_t rres, float rad
                                         float ds, float* grad, drrt_stats* stats, void* ws, size_t ws_bytes,
                                         unsigned flags, void* stream) {
   (void)ws; (void)ws_bytes;
-  (void)take_hint();
-  g_err[0] = 0;
   hipStream_t s = (hipStream_t)stream;
-  if (!rif || !grad) return fail(DRRT_ERR_ARG, "null rif/grad pointer");
-  if (rres < 2 || rres > 0x7fffffffULL) return fail(DRRT_ERR_BAD_RES, "volume: invalid resolution!");
-  if (!(radius > 0.f) || !(length > 0.f) || !(ds > 0.f) || !(ds < 3.0e38f))
-    return fail(DRRT_ERR_ARG, "radius, length and ds must be positive and finite");
-  if (!(flags & DRRT_FLAG_NO_ZERO)) {                                        // src/tracer.cpp:528-530
-    hipError_t e = hipMemsetAsync(grad, 0, rres * sizeof(float), s);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
-  }
-  int rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  if (!xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
   CableArgs a{};
-  a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
-  a.max_steps = (int)(4.0f * length / ds);                                   // src/tracer.cpp:544
-  a.pos = xt; a.vel = vt; a.dx = dx; a.dv = dv; a.grad = grad; a.stats = stats; a.n = n;
-  {
-    ProfScope prof(DRRT_PROF_BACKTRACE, s);
-    launch_backtrace_cable(a, s);
-  }
-  LAUNCH_CHECK("k_backtrace_cable");
-  return DRRT_OK;
+  const int rc = cable_begin(a, rif && grad ? nullptr : "null rif/grad pointer", rif, rres, radius, length, ds,
+                             (flags & DRRT_FLAG_NO_ZERO) ? nullptr : grad, stats, n, s);
+  if (rc || n == 0) return rc;
+  if (!xt || !vt || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
+  a.pos = xt; a.vel = vt; a.dx = dx; a.dv = dv; a.grad = grad;
+  return timed_launch(DRRT_PROF_BACKTRACE, s, "k_backtrace_cable", [&] { launch_backtrace_cable(a, s); });
 }
 
 extern "C" int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, float radius, float length, size_t n,
@@ -743,26 +776,12 @@ extern "C" int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, floa
                                              drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags,
                                              void* stream) {
   (void)ws; (void)ws_bytes; (void)flags;
-  (void)take_hint();
-  g_err[0] = 0;
   hipStream_t s = (hipStream_t)stream;
-  if (!rif) return fail(DRRT_ERR_ARG, "null rif pointer");
-  if (rres < 2 || rres > 0x7fffffffULL) return fail(DRRT_ERR_BAD_RES, "volume: invalid resolution!");
-  if (!(radius > 0.f) || !(length > 0.f) || !(ds > 0.f) || !(ds < 3.0e38f))
-    return fail(DRRT_ERR_ARG, "radius, length and ds must be positive and finite");
-  int rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
+  CableRayGradArgs a{};
+  const int rc = cable_begin(a, rif ? nullptr : "null rif pointer", rif, rres, radius, length, ds, nullptr, stats, n, s);
+  if (rc || n == 0) return rc;
   if (!pos || !vel || !target || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
   if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
-  CableRayGradArgs a{};
-  a.rif = rif; a.rres = (int)rres; a.radius = radius; a.length = length; a.ds = ds;
-  a.max_steps = (int)(4.0f * length / ds);                                   // the forward's bound, src/tracer.cpp:332
   a.pos = pos; a.vel = vel; a.target = target; a.dx = dx; a.dv = dv; a.dpos = dpos; a.dvel = dvel;
-  a.stats = stats; a.n = n;
-  {
-    ProfScope prof(DRRT_PROF_BACKTRACE_CABLE_RAYS, s);
-    launch_backtrace_cable_rays(a, s);
-  }
-  LAUNCH_CHECK("k_backtrace_cable_rays");
-  return DRRT_OK;
+  return timed_launch(DRRT_PROF_BACKTRACE_CABLE_RAYS, s, "k_backtrace_cable_rays", [&] { launch_backtrace_cable_rays(a, s); });
 }

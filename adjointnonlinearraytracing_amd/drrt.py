@@ -269,46 +269,44 @@ def _bump_order_gen(device: torch.device) -> None:
     _order_gen[k] = _order_gen.get(k, 0) + 1
 
 
+def _ws_view(ptr, nbytes: int, ws: torch.Tensor) -> Optional[torch.Tensor]:
+    """The `nbytes` at device address `ptr` as a uint8 view of the workspace `ws`; None when they do not lie inside it."""
+    off = int(ptr) - ws.data_ptr() if ptr else -1
+    return ws[off:off + nbytes] if 0 <= off and off + nbytes <= ws.numel() else None
+
+
+def _last_view(fn, n: int, device: torch.device) -> Optional[torch.Tensor]:
+    """What drrt_last_order / drrt_last_steps (`fn`) points at, if it is n words of this (device, stream)'s workspace: an
+    int32 view stamped with the workspace's generation (`drrt_gen`, _valid_order)."""
+    cnt = C.c_size_t(0)
+    ptr = fn(C.byref(cnt))
+    key = _wkey(device)
+    v = _ws_view(ptr, 4 * n, _workspaces[key]) if cnt.value == n else None
+    if v is None:
+        return None
+    v = v.view(torch.int32)
+    v.drrt_gen = (key, _order_gen.get(key, 0))
+    return v
+
+
 def _capture_order(n: int, device: torch.device) -> None:
     """Hand out the permutation (and the per-ray iteration counts) the library just left in the workspace: views, no
     copies -- see `last_order`."""
     global last_order
-    last_order = None
-    if not _opt().sort_rays or n < 2:
-        return
-    cnt = C.c_size_t(0)
-    ptr = _lib.load().drrt_last_order(C.byref(cnt))
-    if not ptr or cnt.value != n:
-        return
-    key = _wkey(device)
-    ws = _workspaces[key]
-    off = int(ptr) - ws.data_ptr()
-    if 0 <= off and off + 4 * n <= ws.numel():
-        last_order = ws[off:off + 4 * n].view(torch.int32)
-        last_order.drrt_gen = (key, _order_gen.get(key, 0))
+    last_order = _last_view(_lib.load().drrt_last_order, n, device) if _opt().sort_rays and n >= 2 else None
+    if last_order is not None:
         # the forward march's per-ray iteration counts ride along ON the order tensor (attribute `drrt_steps`), so every
         # holder of the order hands both to the paired adjoint: its rays then start on the forward march's clock (step
         # hint, include/drrt_hip.h)
-        ptr_s = _lib.load().drrt_last_steps(C.byref(cnt))
-        off_s = int(ptr_s) - ws.data_ptr() if ptr_s else -1
-        if ptr_s and cnt.value == n and 0 <= off_s and off_s + 4 * n <= ws.numel():
-            last_order.drrt_steps = ws[off_s:off_s + 4 * n].view(torch.int32)
+        steps = _last_view(_lib.load().drrt_last_steps, n, device)
+        if steps is not None:
+            last_order.drrt_steps = steps
 
 
 def _capture_steps(n: int, device: torch.device) -> None:
     """Hand out the per-ray iteration counts the forward march just left in the workspace (a view) -> `last_steps`."""
     global last_steps
-    last_steps = None
-    cnt = C.c_size_t(0)
-    ptr = _lib.load().drrt_last_steps(C.byref(cnt))
-    if not ptr or cnt.value != n:
-        return
-    key = _wkey(device)
-    ws = _workspaces[key]
-    off = int(ptr) - ws.data_ptr()
-    if 0 <= off and off + 4 * n <= ws.numel():
-        last_steps = ws[off:off + 4 * n].view(torch.int32)
-        last_steps.drrt_gen = (key, _order_gen.get(key, 0))
+    last_steps = _last_view(_lib.load().drrt_last_steps, n, device)
 
 
 def keep_steps(steps: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -347,13 +345,8 @@ def _capture_counters(ws: torch.Tensor) -> None:
     """The bundle classification of the adjoint call just made (drrt_last_bundle_counters, include/drrt_hip.h): four int32
     copied out of its workspace (device-to-device, async) -> `last_bundle_counters`, or None when the call did not classify."""
     global last_bundle_counters
-    last_bundle_counters = None
-    ptr = _lib.load().drrt_last_bundle_counters()
-    if not ptr:
-        return
-    off = int(ptr) - ws.data_ptr()
-    if 0 <= off and off + 32 <= ws.numel():
-        last_bundle_counters = ws[off:off + 32].view(torch.int32).clone()
+    v = _ws_view(_lib.load().drrt_last_bundle_counters(), 32, ws)
+    last_bundle_counters = None if v is None else v.view(torch.int32).clone()
 
 
 def read_bundle_counters() -> Optional[Dict[str, int]]:
@@ -433,6 +426,22 @@ def _paired_adjoint(rif_, res, n: int, h, ds, device, order, replay: bool = Fals
         _clear_hint()
 
 
+@contextlib.contextmanager
+def _forward_march(rif_, res, n: int, h, ds, device, flags: int = 0, steps: bool = True, warn: bool = True):
+    """The call sequence of a forward grid march, the twin of `_paired_adjoint`: workspace + final flags, a fresh stats
+    block, the order / state region of the workspace counted as rewritten -> yields (flags, workspace, stats) for the
+    library call -> `last_order` captured, `last_steps` too for the marches that leave iteration counts (`steps`), failed
+    rays reported (`warn`).  Nothing is captured when the call raises."""
+    (fl, ws), st = _march_workspace(rif_, res, n, h, ds, _flags() | flags, device), _new_stats(device)
+    _bump_order_gen(device)
+    yield fl, ws, st
+    _capture_order(n, device)
+    if steps:
+        _capture_steps(n, device)
+    if warn:
+        _warn_failed(st)
+
+
 # "failed to exit all rays" (src/tracer.cpp:90) without a host sync per call: the stats block is copied to pinned
 # host memory asynchronously behind the kernels, and looked at when the copy has landed -- at the next tracer call,
 # at flush_warnings(), or at interpreter exit.  The message can therefore appear one call late; it is never lost.
@@ -495,6 +504,24 @@ def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
     return C.c_void_p(0 if t is None else t.data_ptr())
 
 
+def _cable_call(name: str, rif, radius, length, ds, rays, make_outputs, warn: bool = False) -> tuple:
+    """One call of a cable entry point (they share their shape: profile, radius, length, n, the (n,3) ray tensors `rays`, ds,
+    the outputs, the usual tail) -> the outputs, made by ``make_outputs(profile, first ray tensor)``."""
+    dev = _dev(rif)
+    with torch.cuda.device(dev):
+        rif_, first = _f32(rif, dev).reshape(-1), _rays(rays[0], dev)
+        n = first.shape[0]
+        rays_ = [first] + [_rays(t, dev, n) for t in rays[1:]]
+        out = make_outputs(rif_, first)
+        ws, st = _workspace(n, 0, dev), _new_stats(dev)
+        _lib.check(getattr(_lib.load(), name)(
+            _p(rif_), rif_.numel(), float(radius), float(length), n, *map(_p, rays_), float(ds), *map(_p, out),
+            _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
+        if warn:
+            _warn_failed(st)
+    return out
+
+
 class TracerC:
     """GPU tracer without autodiff -- mirror of ``drrt.TracerC`` (``src/drrt.cpp:47-58``)."""
 
@@ -511,17 +538,12 @@ class TracerC:
             n = pos_.shape[0]
             vel_ = _rays(vel, dev, n, half=half, q16=q16)
             xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            fl = _flags() | (_lib.FLAG_Q16_POS_ONLY if qpos else 0)
             q16 = q16 or qpos
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev), _new_stats(dev)
-            _bump_order_gen(dev)
             fn = _lib.load().drrt_trace_q16io if q16 else (_lib.load().drrt_trace_f16io if half else _lib.load().drrt_trace_f32)
-            _lib.check(fn(
-                _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), float(h), float(ds),
-                _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-            _capture_order(n, dev)
-            _capture_steps(n, dev)
-            _warn_failed(st)
+            with _forward_march(rif_, res, n, h, ds, dev, flags=_lib.FLAG_Q16_POS_ONLY if qpos else 0) as (fl, ws, st):
+                _lib.check(fn(
+                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), float(h), float(ds),
+                    _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
         return xt, vt
 
     def trace_pln(self, rif, res, pos, vel, pln_o, pln_d, h, ds):
@@ -533,16 +555,10 @@ class TracerC:
             vel_, po, pd = _rays(vel, dev, n), _rays(pln_o, dev, n), _rays(pln_d, dev, n)
             xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
             fm = torch.empty(n, dtype=torch.uint8, device=dev)
-            fl = _flags()
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev), _new_stats(dev)
-            _bump_order_gen(dev)
-            _lib.check(_lib.load().drrt_trace_pln_f32(
-                _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd),
-                float(h), float(ds), _p(xt), _p(vt), _p(fm), _p(st), _p(ws), ws.numel(), fl,
-                _stream(dev)))
-            _capture_order(n, dev)
-            _capture_steps(n, dev)
-            _warn_failed(st)
+            with _forward_march(rif_, res, n, h, ds, dev) as (fl, ws, st):
+                _lib.check(_lib.load().drrt_trace_pln_f32(
+                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd),
+                    float(h), float(ds), _p(xt), _p(vt), _p(fm), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
         return xt, vt, fm
 
     def trace_target(self, rif, res, pos, vel, target, h, ds):
@@ -554,15 +570,10 @@ class TracerC:
             vel_, tg = _rays(vel, dev, n), _rays(target, dev, n)
             xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
             d2 = torch.empty(n, dtype=torch.float32, device=dev)
-            fl = _flags()
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev), _new_stats(dev)
-            _bump_order_gen(dev)
-            _lib.check(_lib.load().drrt_trace_target_f32(
-                _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(tg),
-                float(h), float(ds), _p(xt), _p(vt), _p(d2), _p(st), _p(ws), ws.numel(), fl,
-                _stream(dev)))
-            _capture_order(n, dev)
-            _warn_failed(st)
+            with _forward_march(rif_, res, n, h, ds, dev, steps=False) as (fl, ws, st):
+                _lib.check(_lib.load().drrt_trace_target_f32(
+                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(tg),
+                    float(h), float(ds), _p(xt), _p(vt), _p(d2), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
         return xt, vt, d2
 
     def trace_sdf(self, rif, sdf, res, pos, vel, h, ds):
@@ -576,30 +587,16 @@ class TracerC:
             n = pos_.shape[0]
             vel_ = _rays(vel, dev, n)
             xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            fl = _flags()
-            (fl, ws), st = _march_workspace(rif_, res, n, h, ds, fl, dev), _new_stats(dev)
-            _bump_order_gen(dev)
-            _lib.check(_lib.load().drrt_trace_sdf_f32(
-                _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_),
-                float(h), float(ds), _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-            _capture_order(n, dev)
+            with _forward_march(rif_, res, n, h, ds, dev, steps=False, warn=False) as (fl, ws, st):
+                _lib.check(_lib.load().drrt_trace_sdf_f32(
+                    _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_),
+                    float(h), float(ds), _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
         return xt, vt
 
     def trace_cable(self, rif, radius, length, pos, vel, target, ds):
         """Tracer::trace_cable, src/tracer.cpp:312-382 -> (xt, vt, dist2)."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, tg = _rays(vel, dev, n), _rays(target, dev, n)
-            xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            d2 = torch.empty(n, dtype=torch.float32, device=dev)
-            ws, st = _workspace(n, 0, dev), _new_stats(dev)
-            _lib.check(_lib.load().drrt_trace_cable_f32(
-                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(vel_), _p(tg),
-                float(ds), _p(xt), _p(vt), _p(d2), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
-            _warn_failed(st)
-        return xt, vt, d2
+        return _cable_call("drrt_trace_cable_f32", rif, radius, length, ds, (pos, vel, target),
+                           lambda rif_, r: (torch.empty_like(r), torch.empty_like(r), r.new_empty(r.shape[0])), warn=True)
 
     # ---- adjoint ------------------------------------------------------------------------
     def backtrace(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -712,17 +709,8 @@ class TracerC:
 
     def backtrace_cable(self, rif, radius, length, xt, vt, dx, dv, ds) -> torch.Tensor:
         """Tracer::backtrace_cable, src/tracer.cpp:511-567 -> dL/d(profile) fp32[rres]."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, xt_ = _f32(rif, dev).reshape(-1), _rays(xt, dev)
-            n = xt_.shape[0]
-            vt_, dx_, dv_ = _rays(vt, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
-            grad = torch.empty_like(rif_)
-            ws, st = _workspace(n, 0, dev), _new_stats(dev)
-            _lib.check(_lib.load().drrt_backtrace_cable_f32(
-                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(xt_), _p(vt_), _p(dx_),
-                _p(dv_), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
-        return grad
+        return _cable_call("drrt_backtrace_cable_f32", rif, radius, length, ds, (xt, vt, dx, dv),
+                           lambda rif_, r: (torch.empty_like(rif_),))[0]
 
     def backtrace_cable_rays(self, rif, radius, length, pos, vel, target, dx, dv, ds) -> Tuple[torch.Tensor, torch.Tensor]:
         """Ray-state adjoint of ``trace_cable`` (drrt_backtrace_cable_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),
@@ -730,18 +718,8 @@ class TracerC:
         replays the forward to find the iteration of the closest-approach record, so it takes neither (xt, vt) nor a step
         count.  A seed on dist2 does not enter.  Not in the reference's C++ Tracer: its ADCableTracerC gets these through
         enoki autodiff (core/tracer.py:237-291).  fp32 rays only."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, tg = _rays(vel, dev, n), _rays(target, dev, n)
-            dx_, dv_ = _rays(dx, dev, n), _rays(dv, dev, n)
-            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
-            ws, st = _workspace(n, 0, dev), _new_stats(dev)
-            _lib.check(_lib.load().drrt_backtrace_cable_rays_f32(
-                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(vel_), _p(tg), _p(dx_), _p(dv_),
-                float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
-        return dpos, dvel
+        return _cable_call("drrt_backtrace_cable_rays_f32", rif, radius, length, ds, (pos, vel, target, dx, dv),
+                           lambda rif_, r: (torch.empty_like(r), torch.empty_like(r)))
 
     def _backtrace_stop_rays(self, rif, sdf, res, pos, vel, pln, dx, dv, h, ds, order):
         dev = _dev(rif)

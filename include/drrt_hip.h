@@ -132,7 +132,8 @@ typedef struct drrt_stats {
 /* Bytes of device scratch a call over `n` rays may need (0 when flags need none). */
 DRRT_API size_t drrt_workspace_bytes(size_t n, unsigned flags);
 /* Same, for a call on a grid of `nvox` voxels: adds the pair copy when DRRT_FLAG_PAIR_GRID is set and the
- * 512-byte counter block.  Layout: [sort buffers | trace_target state][pair copy][counters].          */
+ * 512-byte counter block.  Layout: [sort buffers | trace_target state][pair copy][counters].  The one place that
+ * draws and computes it, region by region, is the comment above ws_layout() in csrc/drrt_api.hip.    */
 DRRT_API size_t drrt_workspace_bytes_grid(size_t n, long long nvox, unsigned flags);
 
 /* Message of the last error on this thread ("" if none). */

@@ -153,6 +153,192 @@ def test_backtrace_refuses_unknown_ablation_ids(lib):
                                     ablation << 8, None) == lib.ERR_ARG
         assert "bits 8..15" in h.drrt_last_error().decode()
 
+
+def test_workspace_sizes_are_pinned(lib):
+    """drrt_workspace_bytes / drrt_workspace_bytes_grid over n x flags at nvox = 17^3, and the chunk state size: the
+    numbers the library returned before the workspace layout was gathered into one place.  Host-only.  The sort buffers
+    include rocPRIM's temporary storage, which the library asks rocPRIM for and bounds by a formula when no device is
+    visible; so that the numbers are the same on every machine they are read in a child process that sees no device."""
+    import json
+    import sys
+    S, P = lib.FLAG_SORT_RAYS, lib.FLAG_PAIR_GRID
+    table = {       # n: ((bytes, bytes_grid) for flags 0, S, P, S|P)
+        0: ((0, 512), (256, 768), (0, 39816), (256, 40072)),
+        1: ((256, 768), (1536, 2048), (256, 40072), (1536, 41352)),
+        64: ((1792, 2304), (3584, 4096), (1792, 41608), (3584, 43400)),
+        1000: ((28160, 28672), (52992, 53504), (28160, 67976), (52992, 92808)),
+        4097: ((114944, 115456), (1394176, 1394688), (114944, 154760), (1394176, 1433992)),
+    }
+    child = ("import ctypes as C, json, sys\n"
+             "l = C.CDLL(sys.argv[1])\n"
+             "for f in (l.drrt_workspace_bytes, l.drrt_workspace_bytes_grid, l.drrt_backtrace_chunk_state_bytes):\n"
+             "    f.restype = C.c_size_t\n"
+             "l.drrt_workspace_bytes.argtypes = [C.c_size_t, C.c_uint]\n"
+             "l.drrt_workspace_bytes_grid.argtypes = [C.c_size_t, C.c_longlong, C.c_uint]\n"
+             "l.drrt_backtrace_chunk_state_bytes.argtypes = [C.c_size_t]\n"
+             "q = json.loads(sys.argv[2])\n"
+             "print(json.dumps([[[l.drrt_workspace_bytes(n, f), l.drrt_workspace_bytes_grid(n, 4913, f)] for f in q['flags']]"
+             " for n in q['n']] + [l.drrt_backtrace_chunk_state_bytes(1000)]))\n")
+    env = dict(os.environ, HIP_VISIBLE_DEVICES="", ROCR_VISIBLE_DEVICES="")
+    out = subprocess.run([sys.executable, "-c", child, lib.LIB_PATH, json.dumps(dict(n=list(table), flags=[0, S, P, S | P]))],
+                         check=True, capture_output=True, text=True, env=env).stdout
+    *rows, chunk = json.loads(out)
+    assert [tuple(map(tuple, r)) for r in rows] == list(table.values())
+    assert chunk == 53248
+
+
+# ---- which check fires first ------------------------------------------------------------------------------------------
+# Argument names of every march entry point in call order (include/drrt_hip.h); all end in stats, ws, ws_bytes, flags, stream.
+_GRID = "rif nvox res n"
+_ENTRY_ARGS = {
+    "drrt_trace_f32": _GRID + " pos vel h ds xt vt",
+    "drrt_trace_f16io": _GRID + " pos vel h ds xt vt",
+    "drrt_trace_q16io": _GRID + " pos vel h ds xt vt",
+    "drrt_trace_pln_f32": _GRID + " pos vel pln_o pln_d h ds xt vt failmask",
+    "drrt_trace_sdf_f32": "rif sdf nvox res n pos vel h ds xt vt",
+    "drrt_trace_target_f32": _GRID + " pos vel target h ds xt vt dist2",
+    "drrt_backtrace_f32": _GRID + " xt vt dx dv h ds grad",
+    "drrt_backtrace_f16io": _GRID + " xt vt dx dv h ds grad",
+    "drrt_backtrace_q16io": _GRID + " xt vt dx dv h ds grad",
+    "drrt_backtrace_sdf_f32": "rif sdf nvox res n xt vt dx dv h ds grad",
+    "drrt_backtrace_chunk_f32": _GRID + " xt vt dx dv h ds grad",
+    "drrt_backtrace_rays_f32": _GRID + " pos vel xt vt fwd_steps dx dv h ds dpos dvel",
+    "drrt_backtrace_pln_rays_f32": _GRID + " pos vel pln_o pln_d dx dv h ds dpos dvel",
+    "drrt_backtrace_sdf_rays_f32": "rif sdf nvox res n pos vel dx dv h ds dpos dvel",
+    "drrt_trace_cable_f32": "rif rres radius length n pos vel target ds xt vt dist2",
+    "drrt_backtrace_cable_f32": "rif rres radius length n xt vt dx dv ds grad",
+    "drrt_backtrace_cable_rays_f32": "rif rres radius length n pos vel target dx dv ds dpos dvel",
+}
+_TAIL = "stats ws ws_bytes flags stream"
+_CHUNK_TAIL = " state state_bytes it_begin it_count progress"
+_RAYS = ("pos", "vel", "xt", "vt", "dx", "dv", "target", "dist2")      # what "null ray pointer" covers
+_STATE_128 = 6656                                                      # drrt_backtrace_chunk_state_bytes(128)
+_BIG_N = 1 << 33                                                       # "too many rays for uint32 permutation"
+_NO_ZERO, _DIRECT, _DEBUG, _SORT, _PAIR = 4, 8, 16, 1, 64
+_BACK = ("drrt_backtrace_f32", "drrt_backtrace_f16io", "drrt_backtrace_q16io", "drrt_backtrace_sdf_f32",
+         "drrt_backtrace_chunk_f32")
+_STOP = ("drrt_backtrace_pln_rays_f32", "drrt_backtrace_sdf_rays_f32")
+_CABLE = ("drrt_trace_cable_f32", "drrt_backtrace_cable_f32", "drrt_backtrace_cable_rays_f32")
+
+
+def _invalid_calls():
+    """[(entry, row name, overrides)]: calls that are refused before the first HIP call.  A row that names an early fault
+    also carries the later ones (bad step, null rays, too many rays), so that it pins WHICH check answers."""
+    null_rays = dict({k: None for k in _RAYS}, n=_BIG_N)
+    bad_ds = dict(null_rays, ds=0.0)
+    rows = []
+    for e in _ENTRY_ARGS:
+        if e in _CABLE:
+            rows += [(e, "null_rif", dict(rif=None, rres=1)), (e, "rres1", dict(rres=1, radius=0.0)),
+                     (e, "radius0", dict(null_rays, radius=0.0))]
+            continue
+        # an adjoint fills grad with zeros before it looks at the rays unless told not to: DRRT_FLAG_NO_ZERO keeps these
+        # rows in front of the first HIP call
+        late = dict(flags=_NO_ZERO) if e in _BACK else {}
+        rows += [(e, "nvox", dict(bad_ds, res=(4, 4, 5))), (e, "res_x1", dict(bad_ds, res=(1, 8, 8))),
+                 (e, "nvox_2p29", dict(bad_ds, res=(1024, 1024, 512), nvox=1 << 29)), (e, "ds", bad_ds),
+                 (e, "null_rays", dict(null_rays, **late))]
+        # trace_pln / trace_sdf fetch the library's own stats block (HIP) before they count the rays
+        if e not in ("drrt_trace_pln_f32", "drrt_trace_sdf_f32"):
+            rows.append((e, "too_many_rays", dict(n=_BIG_N, **late)))
+        if e in _BACK:
+            rows += [(e, "null_grad", dict(grad=None, sdf=None, flags=2 << 8)), (e, "ablation2", dict(flags=2 << 8, it_begin=-1))]
+        if e in _STOP or e == "drrt_backtrace_rays_f32":
+            rows += [(e, "null_dpos", dict(dpos=None, n=_BIG_N))]
+        if e in _STOP:
+            rows += [(e, "ws_small", {}), (e, "ws_small_sorted", dict(flags=_SORT))]
+    rows += [
+        ("drrt_trace_pln_f32", "null_plane", dict(pln_o=None)),
+        ("drrt_trace_target_f32", "no_stats", {}),
+        ("drrt_trace_target_f32", "ws_small", dict(stats=0x1000)),      # refused before the stats block is touched
+        ("drrt_trace_f32", "sort_ws_small", dict(flags=_SORT)),
+        ("drrt_trace_f32", "pair_ws_small", dict(flags=_PAIR)),
+        ("drrt_trace_f32", "pair_ws_unaligned", dict(flags=_PAIR, ws=0x1008, ws_bytes=1 << 30)),
+        ("drrt_backtrace_sdf_f32", "null_sdf", dict(sdf=None, flags=2 << 8)),
+        ("drrt_backtrace_f32", "sort_ws_small", dict(flags=_NO_ZERO | _SORT)),
+        ("drrt_backtrace_f32", "pair_ws_small", dict(flags=_NO_ZERO | _PAIR | _DEBUG)),
+        ("drrt_backtrace_f32", "debug_ws_small", dict(flags=_NO_ZERO | _DEBUG)),
+        ("drrt_backtrace_chunk_f32", "it_begin", dict(it_begin=-1, flags=_DIRECT, state=None)),
+        ("drrt_backtrace_chunk_f32", "direct", dict(flags=_DIRECT, state=None)),
+        ("drrt_backtrace_chunk_f32", "state_null", dict(state=None, it_begin=5, flags=_SORT)),
+        ("drrt_backtrace_chunk_f32", "state_small", dict(state_bytes=_STATE_128 - 1)),
+        ("drrt_backtrace_chunk_f32", "resumed_unordered", dict(it_begin=5, flags=_SORT)),
+        ("drrt_backtrace_rays_f32", "null_fwd_steps", dict(fwd_steps=None, dpos=None, n=_BIG_N)),
+        ("drrt_backtrace_rays_f32", "pair_ws_small", dict(flags=_PAIR)),
+        ("drrt_backtrace_pln_rays_f32", "null_plane", dict(pln_d=None, dpos=None)),
+        ("drrt_backtrace_sdf_rays_f32", "null_sdf", dict(null_rays, sdf=None)),
+    ]
+    return rows
+
+
+def _invoke(h, entry, overrides):
+    import ctypes as C
+    names = (_ENTRY_ARGS[entry] + " " + _TAIL + (_CHUNK_TAIL if entry.endswith("chunk_f32") else "")).split()
+    vals = dict(nvox=64, res=(4, 4, 4), n=128, h=1.0, ds=0.5, rres=64, radius=1.0, length=1.0, stats=None, ws=None,
+                ws_bytes=0, flags=0, stream=None, state_bytes=1 << 44, it_begin=0, it_count=-1, progress=None)
+    unknown = set(overrides) - set(names) - {"sdf", "it_begin", "state", *_RAYS}
+    assert not unknown, (entry, unknown)
+    args = []
+    for k in names:
+        v = overrides[k] if k in overrides else vals.get(k, 0x1000)       # 0x1000: a non-null pointer, never dereferenced
+        args.append((C.c_int * 3)(*v) if k == "res" else v)
+    return getattr(h, entry)(*args)
+
+
+# (return code, drrt_last_error()) of every row, as the library answered before the call prologues were shared
+_BY_ROW = {                     # row name: the answer of every entry point that has the row ...
+    'nvox': (-1, "Resolution doesn't match data"),
+    'res_x1': (-2, 'volume: invalid resolution!'),
+    'nvox_2p29': (-3, 'grid too large (>= 2^29 voxels) for 32-bit byte offsets'),
+    'ds': (-3, 'h and ds must be positive and finite'),
+    'null_rays': (-3, 'null ray pointer'),
+    'too_many_rays': (-3, 'too many rays for uint32 permutation'),
+    'null_grad': (-3, 'null grad pointer'),
+    'ablation2': (-3, 'flags: bits 8..15 must be 0, or 1 (no adjoint launch)'),
+    'null_dpos': (-3, 'null dpos/dvel pointer'),
+    'ws_small': (-3, 'workspace too small for the second-pass flags (see drrt_workspace_bytes)'),
+    'ws_small_sorted': (-3, 'workspace too small for the second-pass flags (see drrt_workspace_bytes)'),
+    'null_rif': (-3, 'null rif pointer'),
+    'rres1': (-2, 'volume: invalid resolution!'),
+    'radius0': (-3, 'radius, length and ds must be positive and finite'),
+    'null_plane': (-3, 'null plane/failmask pointer'),
+    'no_stats': (-3, 'trace_target needs a stats block (global loop count)'),
+    'sort_ws_small': (-3, 'workspace too small for DRRT_FLAG_SORT_RAYS'),
+    'pair_ws_small': (-3, 'workspace too small for DRRT_FLAG_PAIR_GRID (see drrt_workspace_bytes_grid)'),
+    'pair_ws_unaligned': (-3, 'workspace must be 16-byte aligned for DRRT_FLAG_PAIR_GRID'),
+    'null_sdf': (-3, 'null sdf pointer'),
+    'debug_ws_small': (-3, 'workspace too small for DRRT_FLAG_DEBUG_COUNTERS'),
+    'it_begin': (-3, 'chunk: it_begin must be >= 0'),
+    'direct': (-3, 'chunk: not available with DRRT_FLAG_DIRECT_ATOMICS'),
+    'state_null': (-3, 'chunk: state buffer too small (see drrt_backtrace_chunk_state_bytes)'),
+    'state_small': (-3, 'chunk: state buffer too small (see drrt_backtrace_chunk_state_bytes)'),
+    'resumed_unordered': (-3, 'chunk: a resumed chunk needs the visit order of its first chunk (drrt_set_order_hint)'),
+    'null_fwd_steps': (-3, "null fwd_steps pointer (the forward's drrt_last_steps())"),
+}
+_BY_ENTRY = {                   # ... but for these
+    'drrt_backtrace_cable_f32/null_rif': (-3, 'null rif/grad pointer'),
+    'drrt_trace_target_f32/ws_small': (-3, 'workspace too small for trace_target'),
+    'drrt_backtrace_pln_rays_f32/null_plane': (-3, 'null plane pointer'),
+}
+
+
+def test_invalid_calls_are_refused_by_the_same_check(lib):
+    """Every invalid call of _invalid_calls() returns the code and the message it returned before the entry points shared
+    their prologues -- with several faults in one call, that is the order of the checks -- and consumes an armed hint.
+    Null stats throughout; nothing here reaches a HIP call, so this runs without a GPU."""
+    import ctypes as C
+    h = lib.load()
+    rows = _invalid_calls()
+    assert len({(e, r) for e, r, _ in rows}) == len(rows) == 127
+    assert {r for _, r, _ in rows} == set(_BY_ROW) and {f"{e}/{r}" for e, r, _ in rows} >= set(_BY_ENTRY)
+    for entry, row, overrides in rows:
+        h.drrt_set_order_hint(C.c_void_p(0xDEAD0000), 77)          # 77 is no row's ray count: never honoured
+        assert h.drrt_order_hint_pending() == 77
+        rc = _invoke(h, entry, overrides)
+        assert (rc, h.drrt_last_error().decode()) == _BY_ENTRY.get(f"{entry}/{row}", _BY_ROW[row]), (entry, row)
+        assert h.drrt_order_hint_pending() == 0, (entry, row)
+
+
 def test_q16_params_host_side(lib):
     """drrt_q16_params is host-only: q_min = -E/16, q_step = 1.125 E / 65535 with E the largest box extent, 2^-14."""
     import ctypes as C

@@ -631,6 +631,8 @@ def test_order_hint_lifetime_and_range_check(gpu, drrt_mod):
     assert order is not None
     cnt = C.c_size_t(0)
     inws = lib.drrt_last_order(C.byref(cnt))
+    # trace_target alone keeps its state first and the sort buffers, the order in them, behind it (ws_layout, drrt_api.hip)
+    assert inws - drrt_mod._workspaces[drrt_mod._wkey(gpu)].data_ptr() >= lib.drrt_workspace_bytes(n, 0)
     lib.drrt_set_order_hint(C.c_void_p(inws), n)
     b = T.trace_target(rif, rif.shape, pos_t, vel_t, tg, h, ds)
     assert all(torch.equal(u, w) for u, w in zip(a, b))

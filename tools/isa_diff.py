@@ -5,7 +5,8 @@ the working tree.
 Every unit of the library is compiled with the Makefile's own commands (``make -n``: its CXXFLAGS, and RINGFLAGS for
 the ring-window unit) with ``-c`` replaced by ``--cuda-device-only -S``, once from ``git archive BASE_REV`` and once
 from the working tree.  The bodies of k_backtrace_flat, k_backtrace_ring, k_backtrace_direct, k_backtrace_rays,
-k_backtrace_cable*, k_backtrace_stop_rays*, k_bundle_classify and k_trace* are compared instantiation by instantiation, with the label numbers
+k_backtrace_cable*, k_backtrace_stop_rays*, k_bundle_classify, k_trace* and the utility kernels of drrt_api.hip (k_build_pair,
+k_q16_*, k_chunk_progress_init) are compared instantiation by instantiation, with the label numbers
 (which depend on a function's position in its unit) normalised and comments dropped.  Prints one line per
 instantiation and exits 1 if any present on both sides differs.
 """
@@ -16,7 +17,7 @@ import sys
 import tempfile
 
 KERNELS = ("k_backtrace_flat", "k_backtrace_ring", "k_backtrace_direct", "k_backtrace_rays", "k_backtrace_cable",
-           "k_backtrace_stop_rays", "k_bundle_classify", "k_trace")
+           "k_backtrace_stop_rays", "k_bundle_classify", "k_trace", "k_build_pair", "k_q16_", "k_chunk_progress_init")
 CSRC = "adjointnonlinearraytracing_amd/csrc"
 FILT = "c++filt"
 
