@@ -12,6 +12,7 @@ functions that call it with stand-ins, so the sharding / reduction logic is test
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import List, Optional, Sequence, Tuple, Union
 
@@ -187,7 +188,7 @@ class ShardedBackTracerC(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 class SlabReducer:
     def __init__(self, grad: torch.Tensor, shape: Sequence[int], h: float, group=None):
-        """grad: flat fp32 dL/dn of this rank (the grid the chunks accumulate into); shape = rif.shape = (D, H, W)."""
+        """grad: flat fp32 dL/dn of this rank (the grid the chunks accumulate into); shape = (D, H, W) of its [z, y, x] view."""
         self.g3 = grad.view(*shape)                      # [z, y, x]
         self.shape, self.h, self.group = tuple(int(v) for v in shape), float(h), group
         self.on = dist.is_initialized() and dist.get_world_size(group) > 1
@@ -213,6 +214,21 @@ class SlabReducer:
         dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
         return t.cpu().tolist()
 
+    def _pack(self, sl) -> torch.Tensor:
+        """A snapshot of the planes `sl` in storage of its own.  Never ``.contiguous()``: a z-slab (dim 0 of the [z, y, x]
+        view) is contiguous as it stands, so that would hand the grid itself to the collective, and the whole-grid reduce
+        after a violation would sum those planes a second time."""
+        return self.g3[sl].clone(memory_format=torch.contiguous_format)
+
+    @staticmethod
+    def _finite(progress: dict) -> bool:
+        """Whether every box value of a progress block is a finite number (a ray state that has overflowed is not)."""
+        for key in ("pos_min", "pos_max", "vel_min", "vel_max", "sample_min", "sample_max"):
+            box = progress.get(key)
+            if box is not None and not all(math.isfinite(v) for v in box):
+                return False
+        return True
+
     def _start(self, axis: int, lo: int, hi: int, ready_event) -> None:
         """Pack planes [lo, hi) of `axis` and start their all-reduce (side stream on the GPU)."""
         if hi <= lo:
@@ -222,10 +238,10 @@ class SlabReducer:
             if ready_event is not None:
                 self.side.wait_event(ready_event)
             with torch.cuda.stream(self.side):
-                buf = self.g3[sl].contiguous()
+                buf = self._pack(sl)
                 work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True) if self.on else None
         else:
-            buf = self.g3[sl].contiguous()
+            buf = self._pack(sl)
             work = dist.all_reduce(buf, op=dist.ReduceOp.SUM, group=self.group, async_op=True) if self.on else None
         self.parts.append((sl, buf, work))
 
@@ -235,8 +251,13 @@ class SlabReducer:
         n = {0: self.shape[2], 1: self.shape[1], 2: self.shape[0]}
         h = self.h
         # (i) did this chunk's samples stay clear of what has been handed in?  (ii) candidates for what is final now
-        touched = 0.0
-        if self.choice is not None and progress["sample_min"] is not None:
+        # a box that is not a number bounds nothing -- seen before any int(), which raises on NaN / inf on this rank while the
+        # others wait in the collective.  Nothing is final then, and the chunk counts as having touched what was handed
+        # in, also when nothing has been yet: where a ray whose state overflowed contributes is not known, now or later,
+        # so the rest of the march ends in the whole-grid reduce on every rank
+        finite = self._finite(progress)
+        touched = 0.0 if finite else 1.0
+        if finite and self.choice is not None and progress["sample_min"] is not None:
             a, down = self.choice
             if down:
                 touched = 1.0 if int(progress["sample_max"][a] / h) + 1 >= self.edge else 0.0
@@ -245,7 +266,9 @@ class SlabReducer:
         vec = [touched]
         for a in range(3):
             for down in (True, False):
-                if progress["active"] == 0:
+                if not finite:
+                    ok, bound = 0.0, (float(n[a]) if down else -1.0)
+                elif progress["active"] == 0:
                     ok, bound = 1.0, (0.0 if down else float(n[a] - 1))          # nothing marches: everything is final
                 elif down and progress["vel_min"][a] > 0.0:                        # x -= ds * v: moving towards smaller a
                     ok, bound = 1.0, float(min(n[a], max(0, int(progress["pos_max"][a] / h) + 2)))
@@ -313,6 +336,10 @@ class SlabReducer:
                 w.wait()                                     # GPU: the current stream waits for the collective
             elif self.side is not None:
                 torch.cuda.current_stream(self.g3.device).wait_stream(self.side)
+            if self.side is not None:
+                # buf was allocated on the side stream and is read here on the current one: without this the caching
+                # allocator may hand the block out again on the side stream while the copy is still pending
+                buf.record_stream(torch.cuda.current_stream(self.g3.device))
             self.g3[sl].copy_(buf)
         self.parts = []
         return self.g3.reshape(-1)
@@ -345,7 +372,9 @@ def backtrace_allreduce_overlapped(rif_flat, shape, xt, vt, gx, gv, h, ds, order
         done.append((grad, progress, ev))
 
     grad = _hip_backtrace_chunked(rif_flat, shape, xt, vt, gx, gv, h, ds, order, chunks, on_chunk)
-    red = SlabReducer(grad, shape, h, group)
+    # `shape` is what the march is given as its res = (W, H, D) (rif.shape on the cubic grids of the reference's scripts,
+    # SURVEY Q2): the reducer must slice the grid as the kernels lay it out, [z, y, x] = the reverse
+    red = SlabReducer(grad, tuple(reversed(tuple(shape))), h, group)
     for _, progress, ev in done:                             # every chunk is queued; now follow them as they finish
         if ev is not None:
             ev.synchronize()

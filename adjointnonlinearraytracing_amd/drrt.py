@@ -374,6 +374,10 @@ def read_bundle_counters() -> Optional[Dict[str, int]]:
                 kernel=("ring_direct" if direct else "ring_sparse" if sparse else "ring") if ring else "box")
 
 
+# A progress block nothing has been reduced into (k_chunk_progress_init): mins at the largest key, maxs at the smallest
+_EMPTY_PROGRESS = ([0x7FFFFFFF] * 3 + [-0x80000000] * 3) * 2 + [0] + [0x7FFFFFFF] * 3 + [-0x80000000] * 3 + [0]
+
+
 def decode_chunk_progress(progress: torch.Tensor) -> Dict[str, object]:
     """Synchronising read of a chunk's progress block (drrt_backtrace_chunk_f32) -> dict(active, pos_min, pos_max, vel_min,
     vel_max, sample_min, sample_max): the bounding boxes of where the still-marching rays stand and head, and of the
@@ -671,15 +675,27 @@ class TracerC:
             if total < 0:
                 raise RuntimeError("h and ds must be positive and finite")
             chunks = max(1, min(int(chunks), max(total, 1)))
-            state = torch.empty(int(lib.drrt_backtrace_chunk_state_bytes(n)), dtype=torch.uint8, device=dev)
+            state = torch.empty(max(int(lib.drrt_backtrace_chunk_state_bytes(n)), 16), dtype=torch.uint8, device=dev)   # never a null pointer (n = 0)
             bounds = [total * k // chunks for k in range(chunks + 1)]
             with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (order, fl, ws, st):     # armed for the first chunk
+                if n == 1 and order is None and fl & _lib.FLAG_SORT_RAYS:
+                    # one ray is not sorted, so the first chunk leaves no order behind (drrt_last_order() is null, or names
+                    # an earlier call's): every chunk gets the trivial one, which a resumed chunk of a sorted march asks for
+                    order = torch.zeros(1, dtype=torch.int32, device=dev)
+                    _hint(order, n)
                 for k in range(chunks):
-                    progress = torch.empty(20, dtype=torch.int32, device=dev)
+                    if n == 0:
+                        # no rays: the first call zeroes `grad` and the stats, nothing is launched and nothing writes a
+                        # progress block -- every chunk reports the empty one (nothing marches, no samples)
+                        progress = torch.tensor(_EMPTY_PROGRESS, dtype=torch.int32, device=dev)
+                        if k > 0:
+                            if on_chunk is not None:
+                                on_chunk(k, grad, progress)
+                            continue
+                    else:
+                        progress = torch.empty(20, dtype=torch.int32, device=dev)
                     if k > 0:                              # later chunks: the order the first chunk used
-                        if order is not None:
-                            _hint(order, n)
-                        elif fl & _lib.FLAG_SORT_RAYS:
+                        if not _hint(order, n) and fl & _lib.FLAG_SORT_RAYS:
                             lib.drrt_set_order_hint(lib.drrt_last_order(None), n)
                     _lib.check(lib.drrt_backtrace_chunk_f32(
                         _p(rif_), rif_.numel(), _res3(res), n, _p(xt_), _p(vt_), _p(dx_), _p(dv_), float(h), float(ds),

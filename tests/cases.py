@@ -27,6 +27,11 @@ def smooth_field(R, seed=0, amp=0.2):
     return (1.0 + amp * f).astype(np.float32)
 
 
+def uniform(shape, n=1.0):
+    """Uniform medium (src/test.cpp:117-146): rays go straight and keep their velocity; shape = R or (D, H, W)."""
+    return np.full((shape,) * 3 if np.isscalar(shape) else tuple(shape), n, np.float32)
+
+
 def sphere_sdf(R, span=1.0, radius=0.4):
     g = np.linspace(0.0, span, R)
     Z, Y, X = np.meshgrid(g, g, g, indexing="ij")

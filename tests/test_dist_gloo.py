@@ -246,7 +246,40 @@ def _slab_scenarios(rank, shape, h):
         prev = zt * 0.25 * k - lag if k else 0.0
         return _prog(40 if k < 3 else 0, [0.1, 0.1, max(0.0, z_lo)], [0.5, 0.5, min(zt, z_lo + 1.2 * h)], [-.1, -.1, -1.0], [.1, .1, -0.6],
                      [0.1, 0.1, max(0.0, prev)], [0.5, 0.5, min(zt, z_lo + 1.2 * h)])
+    n_of = {0: W, 1: H, 2: D}
+    def march(axis, is_down, k, back=False):
+        """After chunk k of rays that travel along grid axis `axis` (0 = x, 1 = y, 2 = z) towards smaller (`is_down`) or
+        larger coordinates, a quarter of the extent per chunk; the chunk's samples lie between the previous front and the
+        new one -- with `back` they reach back to the face the rays started from, into planes handed in earlier."""
+        far = (n_of[axis] - 1) * h
+        if is_down:
+            front = far * (1.0 - 0.25 * (k + 1)) + lag
+            start = far * (1.0 - 0.25 * k) + lag if k else far
+            p_lo, p_hi, v_lo, v_hi = max(0.0, front - 1.5 * h), front, 0.7, 1.0
+            s_lo, s_hi = front, (far if back else min(far, start))
+        else:
+            front = far * 0.25 * (k + 1) - lag
+            start = far * 0.25 * k - lag if k else 0.0
+            p_lo, p_hi, v_lo, v_hi = front, min(far, front + 1.5 * h), -1.0, -0.7
+            s_lo, s_hi = (0.0 if back else max(0.0, start)), front
+        ext = [0.9 * (n_of[a] - 1) * h for a in range(3)]
+        box = lambda lo, hi, t_lo, t_hi: ([lo if a == axis else t_lo[a] for a in range(3)], [hi if a == axis else t_hi[a] for a in range(3)])
+        (pl, ph), (vl, vh), (sl, sh) = box(p_lo, p_hi, [0.1] * 3, ext), box(v_lo, v_hi, [-.1] * 3, [.1] * 3), box(s_lo, s_hi, [0.1] * 3, ext)
+        return _prog(40 if k < 3 else 0, pl, ph, vl, vh, sl, sh)
+    def bad(pr, key, a, value):                                 # the block `pr` with one box value that is not a number
+        pr = {k: (list(v) if isinstance(v, list) else v) for k, v in pr.items()}
+        pr[key][a] = value
+        return pr
+    # a later chunk of rank 0 alone contributes into planes handed in earlier, for every axis and direction of travel (the
+    # y-down case is "violated" below): the slab results must be dropped, and no plane may be summed twice
+    reach_back = {f"violated_{'xyz'[axis]}_{'down' if is_down else 'up'}":
+                  [march(axis, is_down, 0), march(axis, is_down, 1), march(axis, is_down, 2, back=(rank == 0)), march(axis, is_down, 3)]
+                  for axis, is_down in ((2, False), (2, True), (0, False), (0, True), (1, False))}
     return {
+        **reach_back,
+        # a ray state of rank 0 has overflowed: its boxes are no numbers.  Neither rank may raise or wait for the other
+        "nan_pos": [down(0), bad(down(1), "pos_max", 1, float("nan")) if rank == 0 else down(1), down(2), down(3)],
+        "inf_sample": [down(0), down(1), bad(down(2), "sample_max", 1, float("inf")) if rank == 0 else down(2), down(3)],
         "down_y": [down(k) for k in range(4)],
         "up_z": [up_z(k) for k in range(4)],
         # a ray of rank 1 turns around in chunk 2: nothing more is handed in early, the rest goes at the end
@@ -258,6 +291,25 @@ def _slab_scenarios(rank, shape, h):
     }
 
 
+def _chunk_band(rng, pr, shape, h):
+    """(index into the [z, y, x] view, random values): the voxels a chunk that reports `pr` may contribute to -- per axis the
+    planes floor(sample_min / h) .. floor(sample_max / h) + 1 (the upper tap), clamped to the grid as the splat clamps them;
+    a bound that is not a number stands for the whole axis.  None when the chunk took no sample."""
+    if pr["sample_min"] is None:
+        return None
+    idx = [None] * 3
+    for a in range(3):
+        n = shape[2 - a]
+        lo, hi = pr["sample_min"][a], pr["sample_max"][a]
+        lo = int(np.floor(lo / h)) if np.isfinite(lo) else 0
+        hi = int(np.floor(hi / h)) + 1 if np.isfinite(hi) else n - 1
+        lo, hi = min(max(lo, 0), n - 1), min(max(hi, 0), n - 1)
+        idx[2 - a] = slice(lo, hi + 1)
+    idx = tuple(idx)
+    size = tuple(len(range(*sl.indices(shape[d]))) for d, sl in enumerate(idx))
+    return idx, torch.from_numpy(rng.uniform(0.5, 1.5, size).astype(np.float32))
+
+
 def _slab_worker(rank, world, port, out_dir):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world),
                       LOCAL_RANK=str(rank))
@@ -266,14 +318,27 @@ def _slab_worker(rank, world, port, out_dir):
     shape, h = (7, 13, 9), 0.1                                   # (D, H, W): non-cubic on purpose
     report = {}
     for name, seq in _slab_scenarios(rank, shape, h).items():
-        g = torch.from_numpy(np.random.default_rng(100 + rank).normal(size=shape).astype(np.float32)).reshape(-1).clone()
-        want = g.clone(); dist.all_reduce(want)                 # the whole-grid reduce: the reference result
+        rng = np.random.default_rng(100 + rank)
+        g = torch.from_numpy(rng.normal(size=shape).astype(np.float32)).reshape(-1).clone()
+        # what each chunk adds to the grid before it reports: random values in the planes its sample box names.  The
+        # completed grid is built in a copy of its own (never from g, which the reducer works on), and the whole-grid
+        # reduce of that copy is the reference result
+        bands = [_chunk_band(rng, pr, shape, h) for pr in seq]
+        want = g.clone().view(*shape)
+        for band in bands:
+            if band is not None:
+                want[band[0]] += band[1]
+        want = want.reshape(-1); dist.all_reduce(want)
         red = D.SlabReducer(g, shape, h)
-        for pr in seq:
+        for pr, band in zip(seq, bands):
+            if band is not None:
+                g.view(*shape)[band[0]] += band[1]               # the grid grows: a slab handed in earlier is a snapshot
             red.after_chunk(pr)
         early = sum(int(np.prod(b.shape)) for _, b, _ in red.parts)          # voxels handed in BEFORE the end
         out = red.finish()
-        assert torch.equal(out, want), name                      # slab-wise == whole-grid, bit for bit (same two summands)
+        bad = torch.nonzero(out != want).flatten().tolist()     # slab-wise == whole-grid, bit for bit (same two summands)
+        assert torch.equal(out, want), (name, f"{len(bad)} voxels differ, first: got {float(out[bad[0]])}, want {float(want[bad[0]])}"
+                                        if bad else "not equal")
         report[name] = dict(early=early, violated=red.violated, stopped=red.stopped, choice=red.choice)
     np.save(os.path.join(out_dir, f"slab_{rank}.npy"), np.asarray([repr(report)]))
     dist.destroy_process_group()
@@ -295,6 +360,14 @@ def test_world2_slabwise_allreduce_equals_whole_grid_allreduce(tmp_path):
     assert r["turned"]["stopped"] and 0 < r["turned"]["early"] < r["down_y"]["early"]
     assert r["violated"]["violated"]
     assert r["no_axis"]["choice"] is None and r["no_axis"]["early"] == 0
+    # a chunk that reaches back, on every axis and in both directions: noticed, and only AFTER slabs had been handed in --
+    # otherwise the scenario would not show that their results are dropped (and that none is counted twice)
+    for name, choice in (("violated_z_up", (2, False)), ("violated_z_down", (2, True)), ("violated_x_up", (0, False)),
+                         ("violated_x_down", (0, True)), ("violated_y_up", (1, False))):
+        assert r[name]["choice"] == choice and r[name]["violated"] and r[name]["early"] > 0, (name, r[name])
+    assert r["violated"]["early"] > 0
+    # boxes that are no numbers on one rank: both ranks finished, with the whole-grid reduce
+    assert r["nan_pos"]["violated"] and r["inf_sample"]["violated"]
 
 
 def _chunked_standin(rif_flat, shape, xt, vt, gx, gv, h, ds, order, chunks, on_chunk):
@@ -307,6 +380,46 @@ def _chunked_standin(rif_flat, shape, xt, vt, gx, gv, h, ds, order, chunks, on_c
         on_chunk(k, g, _prog(10 if k < chunks - 1 else 0, [0, max(0.0, y_hi - h), 0], [1, y_hi, 1], [-.1, .8, -.1], [.1, 1, .1],
                              [0, y_hi, 0], [1, (H - 1) * h * (1.0 - k / chunks), 1]))
     return g
+
+
+def _overlap_noncubic(D, rank):
+    """backtrace_allreduce_overlapped on a grid with three different extents: the march's res is (W, H, D) = (13, 17, 9),
+    so the reducer has to slice the flat grid as [z, y, x] = (9, 17, 13).  Stand-in rays march down z; every slab handed in
+    must be whole z planes of 17 x 13 voxels (sliced with the extents in the march's order they would be 17 x 9)."""
+    res, h = (13, 17, 9), 0.1
+    g = torch.from_numpy(np.random.default_rng(300 + rank).normal(size=9 * 17 * 13).astype(np.float32))
+    want = g.clone(); dist.all_reduce(want)
+    made = []
+
+    class Recording(D.SlabReducer):
+        def __init__(self, *a, **kw):
+            super().__init__(*a, **kw)
+            made.append(self)
+
+        def finish(self, *a, **kw):
+            self.slabs = [tuple(buf.shape) for _, buf, _ in self.parts]
+            return super().finish(*a, **kw)
+
+    def standin(rif_flat, shape, xt, vt, gx, gv, h, ds, order, chunks, on_chunk):
+        assert tuple(shape) == res
+        top = (res[2] - 1) * h
+        for k in range(chunks):
+            z_hi = top * (1.0 - (k + 1) / chunks)
+            on_chunk(k, g, _prog(10 if k < chunks - 1 else 0, [0, 0, max(0.0, z_hi - h)], [1, 1, z_hi], [-.1, -.1, .8], [.1, .1, 1],
+                                 [0, 0, z_hi], [1, 1, top * (1.0 - k / chunks)]))
+        return g
+
+    real = D.SlabReducer, D._hip_backtrace_chunked
+    D.SlabReducer, D._hip_backtrace_chunked = Recording, standin
+    try:
+        out = D.backtrace_allreduce_overlapped(None, res, None, None, None, None, h, h / 2, chunks=4)
+    finally:
+        D.SlabReducer, D._hip_backtrace_chunked = real
+    red = made[0]
+    assert red.shape == (9, 17, 13) and red.choice == (2, True) and not red.violated
+    assert len(red.slabs) >= 2 and all(s[1:] == (17, 13) for s in red.slabs), red.slabs
+    assert sum(s[0] for s in red.slabs) <= 9
+    assert torch.equal(out, want)
 
 
 def _overlap_worker(rank, world, port, out_dir):
@@ -330,6 +443,7 @@ def _overlap_worker(rank, world, port, out_dir):
         grads[chunks] = rif.grad.numpy().copy()
     assert np.array_equal(grads[0], grads[4])
     np.save(os.path.join(out_dir, f"ov_{rank}.npy"), grads[4])
+    _overlap_noncubic(D, rank)
     dist.destroy_process_group()
 
 
