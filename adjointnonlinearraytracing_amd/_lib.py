@@ -47,6 +47,22 @@ _vp, _f, _sz, _u, _ll, _i = C.c_void_p, C.c_float, C.c_size_t, C.c_uint, C.c_lon
 _d = C.c_double
 _tail = [_vp, _vp, _sz, _u, _vp]          # stats, workspace, workspace_bytes, flags, stream
 
+
+def _sensor_signatures():
+    """The 12 sensor entries, drrt_sensor_{family}[_dframe][_bwd]_f32: the family's rays, then its frame -- host float[3]
+    vectors (p, n, t1, t2; the far field t1, t2), or ONE device pointer for a `_dframe` twin --, then the tail of the
+    direction (res, span, ..., stream).  A twin differs from its plain entry in the frame only."""
+    e = [_vp, _f]                                              # e (nullable), e_scalar
+    splat = ([_i, _f, _vp, _u, _vp], [_i, _f, _vp, _vp, _vp, _vp])     # image, flags | grad_image, grad_x, grad_v
+    families = {       # family: (rays, host vectors of the frame, forward tail, backward tail)
+        "splat": ([_sz, _vp, _vp] + e, 4) + splat,
+        "far_splat": ([_sz, _vp] + e, 2) + splat,
+        "tex_get": ([_sz, _vp, _vp], 4, [_vp, _i, _f, _i, _vp, _vp], [_vp, _i, _f, _i, _vp, _vp, _vp, _vp]),   # tex .. mode, outputs
+    }
+    return {f"drrt_sensor_{family}{dframe}{bwd}_f32": (_i, rays + [_vp] * (1 if dframe else host) + tails[bool(bwd)])
+            for family, (rays, host, *tails) in families.items() for dframe in ("", "_dframe") for bwd in ("", "_bwd")}
+
+
 SIGNATURES = {
     # name: (restype, argtypes)   -- must stay in sync with include/drrt_hip.h
     "drrt_workspace_bytes": (_sz, [_sz, _u]),
@@ -75,18 +91,7 @@ SIGNATURES = {
     "drrt_backtrace_cable_rays_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp] + _tail),
     "drrt_backtrace_pln_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_backtrace_sdf_rays_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
-    "drrt_sensor_splat_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _u, _vp]),
-    "drrt_sensor_splat_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
-    "drrt_sensor_far_splat_f32": (_i, [_sz, _vp, _vp, _f, _vp, _vp, _i, _f, _vp, _u, _vp]),
-    "drrt_sensor_far_splat_bwd_f32": (_i, [_sz, _vp, _vp, _f, _vp, _vp, _i, _f, _vp, _vp, _vp, _vp]),
-    "drrt_sensor_tex_get_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
-    "drrt_sensor_tex_get_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
-    "drrt_sensor_splat_dframe_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _i, _f, _vp, _u, _vp]),
-    "drrt_sensor_splat_dframe_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _f, _vp, _i, _f, _vp, _vp, _vp, _vp]),
-    "drrt_sensor_far_splat_dframe_f32": (_i, [_sz, _vp, _vp, _f, _vp, _i, _f, _vp, _u, _vp]),
-    "drrt_sensor_far_splat_dframe_bwd_f32": (_i, [_sz, _vp, _vp, _f, _vp, _i, _f, _vp, _vp, _vp, _vp]),
-    "drrt_sensor_tex_get_dframe_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp]),
-    "drrt_sensor_tex_get_dframe_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _f, _i, _vp, _vp, _vp, _vp]),
+    **_sensor_signatures(),
     "drrt_rays_to_plane_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "drrt_rays_to_plane_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "drrt_upres_volume_f32": (_i, [_vp, _vp, _vp, _vp, _vp]),
@@ -143,6 +148,17 @@ def profile_collect(max_out: int = 4096):
 
 def last_error() -> str:
     return load().drrt_last_error().decode()
+
+
+def _p(t) -> C.c_void_p:
+    """Device pointer of an optional tensor (None -> NULL)."""
+    return C.c_void_p(0 if t is None else t.data_ptr())
+
+
+def _stream(device) -> C.c_void_p:
+    """The current stream of `device`."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def check(rc: int) -> None:

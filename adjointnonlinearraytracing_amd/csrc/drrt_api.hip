@@ -3,6 +3,7 @@
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
 // drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
 // utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
+#include "drrt_host.h"
 #include "drrt_march.h"
 
 using namespace drrt;
@@ -17,16 +18,14 @@ hipError_t sort_rays_by_entry_voxel(const Vol& V, float h, size_t n, const void*
 
 static thread_local char g_err[512] = "";
 
-static int fail(int code, const char* msg) {
+int drrt::fail(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
 }
-static int fail_hip(hipError_t e, const char* where) {
+int drrt::fail_hip(hipError_t e, const char* where) {
   snprintf(g_err, sizeof(g_err), "%s: %s", where, hipGetErrorString(e));
   return DRRT_ERR_HIP;
 }
-
-namespace drrt { int sensor_fail(int code, const char* msg) { return fail(code, msg); } }   // used by drrt_sensor.hip
 
 extern "C" const char* drrt_last_error(void) { return g_err; }
 

@@ -13,6 +13,10 @@
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
+// The operators before and after the march do not include this header; they share drrt_host.h (error slot, 1-D launch):
+//   drrt_source.hip         ray generation                                       (core/source.py)
+//   drrt_sensor.hip         sensor splats and texture lookups, with backwards    (core/sensor.py)
+//   drrt_ops.hip            rays -> plane, multires up-sampling, fused Adam step (core/sensor.py, core/optimizer.py)
 //
 // Reference semantics: /root/reference/src/tracer.cpp, src/volume.cpp, src/cylinder_volume.cpp.  Quirk numbers
 // (Q1..Q16) refer to SURVEY.md section 8.1.

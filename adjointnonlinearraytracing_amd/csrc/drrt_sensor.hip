@@ -20,7 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/drrt_hip.h"
+#include "drrt_host.h"
 
 namespace drrt {
 
@@ -311,415 +311,180 @@ __global__ void __launch_bounds__(256) k_sensor_tex_get_bwd(SensorArgs a) {
   a.grad_v[3 * i] = gv[0]; a.grad_v[3 * i + 1] = gv[1]; a.grad_v[3 * i + 2] = gv[2];
 }
 
-int sensor_fail(int code, const char* msg);   // drrt_kernels.hip
+// ---- host half: every entry point is one filler (the rays, the frame and the image geometry of its coordinate family ->
+// SensorArgs) followed by one runner (its kind of output -> the launch) --------------------------------------------------
 
-static const float kZero3[3] = {0.f, 0.f, 0.f};
+// Where the sensor frame of a call is: 12 floats on the device (p, n, t1, t2) that the kernel reads itself -- the *_dframe
+// entries --, or host vectors, of which the far field gives the last two only.
+struct Frame {
+  const float* dev;
+  const float* host[4];     // p, n, t1, t2; the first 4 - n_host are absent
+  int n_host;               // 0: the frame is `dev`
+};
+static Frame host_frame(const float* p, const float* n, const float* t1, const float* t2) { return {nullptr, {p, n, t1, t2}, 4}; }
+static Frame host_frame(const float* t1, const float* t2) { return {nullptr, {nullptr, nullptr, t1, t2}, 2}; }
+static Frame device_frame(const float* frame12) { return {frame12, {nullptr, nullptr, nullptr, nullptr}, 0}; }
 
-static int fill_args(SensorArgs& a, size_t n, const float* x, const float* v, const float* e, float e_scalar,
-                     const float p[3], const float nrm[3], const float t1[3], const float t2[3], int res, float span) {
-  if (!x || !v || !p || !nrm || !t1 || !t2) return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  a.frame_dev = nullptr;
-  if (res < 1 || res > 32768 || !(span > 0.f)) return sensor_fail(DRRT_ERR_ARG, "bad sensor resolution / span");
+// Near plane: generate_sensor (rays -> plane -> sensor frame, cell size span / res).
+static int fill_near(SensorArgs& a, size_t n, const float* x, const float* v, const float* e, float e_scalar, const Frame& f,
+                     int res, float span) {
+  if (f.n_host == 0 && !f.dev) return fail(DRRT_ERR_ARG, "null frame pointer");
+  bool null = !x || !v;
+  for (int j = 4 - f.n_host; j < 4; ++j) null |= !f.host[j];
+  if (null) return fail(DRRT_ERR_ARG, "null pointer");
+  if (res < 1 || res > 32768 || !(span > 0.f)) return fail(DRRT_ERR_ARG, "bad sensor resolution / span");
   a.x = x; a.v = v; a.e = e; a.e_scalar = e_scalar; a.n_rays = n;
-  for (int k = 0; k < 3; ++k) { a.p[k] = p[k]; a.n[k] = nrm[k]; a.t1[k] = t1[k]; a.t2[k] = t2[k]; }
+  float* const vec[4] = {a.p, a.n, a.t1, a.t2};       // (absent vectors stay zero)
+  for (int j = 4 - f.n_host; j < 4; ++j)
+    for (int k = 0; k < 3; ++k) vec[j][k] = f.host[j][k];
+  a.frame_dev = f.dev;
   a.res = res; a.span = span; a.inv_hs = 1.0f / (span / (float)res); a.half_span = span / 2;
   a.far = 0;
   return DRRT_OK;
+}
+
+// Far field (core/sensor.py:31-53 generate_inf_sensor, called at core/image_opt.py:116): the splat kernels with
+// SensorArgs::far set.  `ang_cut` = sin(0.5 * deg2rad(angle_span)) is computed by the caller (the reference evaluates it in
+// the rays' dtype, sensor.py:38); the image spans [0, 2*ang_cut)^2.  Reads t1, t2 only; the directions stand in for x.
+static int fill_far(SensorArgs& a, size_t n, const float* v, const float* e, float e_scalar, const Frame& f, int res,
+                    float ang_cut) {
+  if (int rc = fill_near(a, n, v, v, e, e_scalar, f, res, 2.0f * ang_cut)) return rc;
+  a.half_span = ang_cut; a.inv_hs = 1.0f / (2.0f * ang_cut / (float)res);   // Grid(zeros, 2*ang_cut/res), :44
+  a.far = 1;
+  return DRRT_OK;
+}
+
+// Texture lookups (core/sensor.py:102-138), see k_sensor_tex_get.  mode 0: get_sdf_vals_near (rays -> plane -> sensor
+// frame, cell size span / res); mode 1: get_sdf_vals_far (coordinates v . T + ang_cut from the direction as it is, cell
+// size 2 ang_cut / res; pass span = 2 * ang_cut).
+static int fill_tex(SensorArgs& a, size_t n, const float* x, const float* v, const Frame& f, const float* tex, int res,
+                    float span, int mode) {
+  if (int rc = fill_near(a, n, x, v, nullptr, 1.f, f, res, span)) return rc;
+  if (!tex) return fail(DRRT_ERR_ARG, "null texture pointer");
+  if (mode != 0 && mode != 1) return fail(DRRT_ERR_ARG, "mode must be 0 (near) or 1 (far)");
+  a.far = mode == 1 ? 2 : 0;
+  a.grad_image = tex;
+  return DRRT_OK;
+}
+
+// The runners differ in when they look at their outputs, and callers rely on it: the splats check theirs before the
+// n == 0 return (and the forward has zeroed the image by then), the lookups return DRRT_OK for n == 0 first.
+static int run_image(SensorArgs& a, float* image, unsigned flags, void* stream) {
+  if (!image) return fail(DRRT_ERR_ARG, "null image pointer");
+  if (!(flags & DRRT_FLAG_NO_ZERO)) {
+    const hipError_t e = hipMemsetAsync(image, 0, (size_t)a.res * a.res * sizeof(float), (hipStream_t)stream);
+    if (e != hipSuccess) return fail(DRRT_ERR_HIP, hipGetErrorString(e));
+  }
+  if (a.n_rays == 0) return DRRT_OK;
+  a.image = image;
+  return launch_1d(k_sensor_splat, a.n_rays, stream, a);
+}
+
+// `seed`: dL/dimage of a splat, dL/df of a lookup (whose texture fill_tex has put where the splat's dL/dimage goes)
+static int run_ray_grads(bool lookup, SensorArgs& a, const float* seed, float* grad_x, float* grad_v, void* stream) {
+  if (lookup && a.n_rays == 0) return DRRT_OK;
+  if (!seed || !grad_x || !grad_v) return fail(DRRT_ERR_ARG, "null gradient pointer");
+  if (a.n_rays == 0) return DRRT_OK;
+  (lookup ? a.grad_f : a.grad_image) = seed; a.grad_x = grad_x; a.grad_v = grad_v;
+  return launch_1d(lookup ? k_sensor_tex_get_bwd : k_sensor_splat_bwd, a.n_rays, stream, a);
+}
+
+static int run_values(SensorArgs& a, float* f_out, void* stream) {
+  if (a.n_rays == 0) return DRRT_OK;
+  if (!f_out) return fail(DRRT_ERR_ARG, "null output pointer");
+  a.f_out = f_out;
+  return launch_1d(k_sensor_tex_get, a.n_rays, stream, a);
 }
 
 }  // namespace drrt
 
 using namespace drrt;
 
-static int splat_fwd(size_t n, const float* x, const float* v, const float* e, float e_scalar,
-                     const float plane_p[3], const float plane_n[3], const float t1[3], const float t2[3],
-                     const float* frame_dev, int res, float span, float* image, unsigned flags, void* stream) {
-  SensorArgs a{};
-  int rc = fill_args(a, n, x, v, e, e_scalar, plane_p, plane_n, t1, t2, res, span); if (rc) return rc;
-  a.frame_dev = frame_dev;
-  if (!image) return sensor_fail(DRRT_ERR_ARG, "null image pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (!(flags & DRRT_FLAG_NO_ZERO)) {
-    hipError_t e_ = hipMemsetAsync(image, 0, (size_t)res * res * sizeof(float), s);
-    if (e_ != hipSuccess) return sensor_fail(DRRT_ERR_HIP, hipGetErrorString(e_));
-  }
-  if (n == 0) return DRRT_OK;
-  a.image = image;
-  hipLaunchKernelGGL(k_sensor_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
-}
-
 extern "C" int drrt_sensor_splat_f32(size_t n, const float* x, const float* v, const float* e, float e_scalar,
                                      const float plane_p[3], const float plane_n[3], const float t1[3],
                                      const float t2[3], int res, float span, float* image, unsigned flags,
                                      void* stream) {
-  return splat_fwd(n, x, v, e, e_scalar, plane_p, plane_n, t1, t2, nullptr, res, span, image, flags, stream);
+  SensorArgs a{};
+  const int rc = fill_near(a, n, x, v, e, e_scalar, host_frame(plane_p, plane_n, t1, t2), res, span);
+  return rc ? rc : run_image(a, image, flags, stream);
 }
 extern "C" int drrt_sensor_splat_dframe_f32(size_t n, const float* x, const float* v, const float* e, float e_scalar,
                                             const float* frame12, int res, float span, float* image, unsigned flags,
                                             void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return splat_fwd(n, x, v, e, e_scalar, kZero3, kZero3, kZero3, kZero3, frame12, res, span, image, flags, stream);
-}
-
-static int splat_bwd(size_t n, const float* x, const float* v, const float* e, float e_scalar,
-                     const float plane_p[3], const float plane_n[3], const float t1[3], const float t2[3],
-                     const float* frame_dev, int res, float span, const float* grad_image, float* grad_x, float* grad_v,
-                     void* stream) {
   SensorArgs a{};
-  int rc = fill_args(a, n, x, v, e, e_scalar, plane_p, plane_n, t1, t2, res, span); if (rc) return rc;
-  a.frame_dev = frame_dev;
-  if (!grad_image || !grad_x || !grad_v) return sensor_fail(DRRT_ERR_ARG, "null gradient pointer");
-  if (n == 0) return DRRT_OK;
-  a.grad_image = grad_image; a.grad_x = grad_x; a.grad_v = grad_v;
-  hipLaunchKernelGGL(k_sensor_splat_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  const int rc = fill_near(a, n, x, v, e, e_scalar, device_frame(frame12), res, span);
+  return rc ? rc : run_image(a, image, flags, stream);
 }
-
 extern "C" int drrt_sensor_splat_bwd_f32(size_t n, const float* x, const float* v, const float* e, float e_scalar,
                                          const float plane_p[3], const float plane_n[3], const float t1[3],
                                          const float t2[3], int res, float span, const float* grad_image,
                                          float* grad_x, float* grad_v, void* stream) {
-  return splat_bwd(n, x, v, e, e_scalar, plane_p, plane_n, t1, t2, nullptr, res, span, grad_image, grad_x, grad_v, stream);
+  SensorArgs a{};
+  const int rc = fill_near(a, n, x, v, e, e_scalar, host_frame(plane_p, plane_n, t1, t2), res, span);
+  return rc ? rc : run_ray_grads(false, a, grad_image, grad_x, grad_v, stream);
 }
 extern "C" int drrt_sensor_splat_dframe_bwd_f32(size_t n, const float* x, const float* v, const float* e, float e_scalar,
                                                 const float* frame12, int res, float span, const float* grad_image,
                                                 float* grad_x, float* grad_v, void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return splat_bwd(n, x, v, e, e_scalar, kZero3, kZero3, kZero3, kZero3, frame12, res, span, grad_image, grad_x, grad_v, stream);
-}
-
-// ---- far-field sensor (core/sensor.py:31-53 generate_inf_sensor, called at core/image_opt.py:116) ----------------
-// Same splat kernels with SensorArgs::far set: `ang_cut` = sin(0.5 * deg2rad(angle_span)) is computed by the caller
-// (the reference evaluates it in the rays' dtype, sensor.py:38); the image spans [0, 2*ang_cut)^2.
-static int fill_far(SensorArgs& a, size_t n, const float* v, const float* e, float e_scalar, const float t1[3],
-                    const float t2[3], const float* frame_dev, int res, float ang_cut) {
-  const float zero[3] = {0.f, 0.f, 0.f};
-  int rc = fill_args(a, n, v, v, e, e_scalar, zero, zero, t1, t2, res, 2.0f * ang_cut); if (rc) return rc;
-  a.frame_dev = frame_dev;              // (the far field reads t1, t2 only; p and n are not used)
-  a.half_span = ang_cut; a.inv_hs = 1.0f / (2.0f * ang_cut / (float)res);   // Grid(zeros, 2*ang_cut/res), :44
-  a.far = 1;
-  return DRRT_OK;
-}
-
-static int far_fwd(size_t n, const float* v, const float* e, float e_scalar, const float t1[3], const float t2[3],
-                   const float* frame_dev, int res, float ang_cut, float* image, unsigned flags, void* stream) {
   SensorArgs a{};
-  int rc = fill_far(a, n, v, e, e_scalar, t1, t2, frame_dev, res, ang_cut); if (rc) return rc;
-  if (!image) return sensor_fail(DRRT_ERR_ARG, "null image pointer");
-  hipStream_t s = (hipStream_t)stream;
-  if (!(flags & DRRT_FLAG_NO_ZERO)) {
-    hipError_t e_ = hipMemsetAsync(image, 0, (size_t)res * res * sizeof(float), s);
-    if (e_ != hipSuccess) return sensor_fail(DRRT_ERR_HIP, hipGetErrorString(e_));
-  }
-  if (n == 0) return DRRT_OK;
-  a.image = image;
-  hipLaunchKernelGGL(k_sensor_splat, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  const int rc = fill_near(a, n, x, v, e, e_scalar, device_frame(frame12), res, span);
+  return rc ? rc : run_ray_grads(false, a, grad_image, grad_x, grad_v, stream);
 }
 
 extern "C" int drrt_sensor_far_splat_f32(size_t n, const float* v, const float* e, float e_scalar, const float t1[3],
                                          const float t2[3], int res, float ang_cut, float* image, unsigned flags,
                                          void* stream) {
-  return far_fwd(n, v, e, e_scalar, t1, t2, nullptr, res, ang_cut, image, flags, stream);
+  SensorArgs a{};
+  const int rc = fill_far(a, n, v, e, e_scalar, host_frame(t1, t2), res, ang_cut);
+  return rc ? rc : run_image(a, image, flags, stream);
 }
 extern "C" int drrt_sensor_far_splat_dframe_f32(size_t n, const float* v, const float* e, float e_scalar,
                                                 const float* frame12, int res, float ang_cut, float* image,
                                                 unsigned flags, void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return far_fwd(n, v, e, e_scalar, kZero3, kZero3, frame12, res, ang_cut, image, flags, stream);
-}
-
-static int far_bwd(size_t n, const float* v, const float* e, float e_scalar, const float t1[3], const float t2[3],
-                   const float* frame_dev, int res, float ang_cut, const float* grad_image, float* grad_x, float* grad_v,
-                   void* stream) {
   SensorArgs a{};
-  int rc = fill_far(a, n, v, e, e_scalar, t1, t2, frame_dev, res, ang_cut); if (rc) return rc;
-  if (!grad_image || !grad_x || !grad_v) return sensor_fail(DRRT_ERR_ARG, "null gradient pointer");
-  if (n == 0) return DRRT_OK;
-  a.grad_image = grad_image; a.grad_x = grad_x; a.grad_v = grad_v;
-  hipLaunchKernelGGL(k_sensor_splat_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  const int rc = fill_far(a, n, v, e, e_scalar, device_frame(frame12), res, ang_cut);
+  return rc ? rc : run_image(a, image, flags, stream);
 }
-
 extern "C" int drrt_sensor_far_splat_bwd_f32(size_t n, const float* v, const float* e, float e_scalar, const float t1[3],
                                              const float t2[3], int res, float ang_cut, const float* grad_image,
                                              float* grad_x, float* grad_v, void* stream) {
-  return far_bwd(n, v, e, e_scalar, t1, t2, nullptr, res, ang_cut, grad_image, grad_x, grad_v, stream);
+  SensorArgs a{};
+  const int rc = fill_far(a, n, v, e, e_scalar, host_frame(t1, t2), res, ang_cut);
+  return rc ? rc : run_ray_grads(false, a, grad_image, grad_x, grad_v, stream);
 }
 extern "C" int drrt_sensor_far_splat_dframe_bwd_f32(size_t n, const float* v, const float* e, float e_scalar,
                                                     const float* frame12, int res, float ang_cut,
                                                     const float* grad_image, float* grad_x, float* grad_v, void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return far_bwd(n, v, e, e_scalar, kZero3, kZero3, frame12, res, ang_cut, grad_image, grad_x, grad_v, stream);
-}
-
-// ---- texture lookups at the sensor (core/sensor.py:102-138), see k_sensor_tex_get ------------------------------------
-// mode 0: get_sdf_vals_near (rays -> plane -> sensor frame, cell size span / res);
-// mode 1: get_sdf_vals_far  (coordinates v . T + ang_cut from the direction as it is, cell size 2 ang_cut / res; pass
-//         span = 2 * ang_cut).
-static int fill_tex(SensorArgs& a, size_t n, const float* x, const float* v, const float p[3], const float nrm[3],
-                    const float t1[3], const float t2[3], const float* frame_dev, int res, float span, int mode,
-                    const float* tex) {
-  int rc = fill_args(a, n, x, v, nullptr, 1.f, p, nrm, t1, t2, res, span); if (rc) return rc;
-  a.frame_dev = frame_dev;
-  if (!tex) return sensor_fail(DRRT_ERR_ARG, "null texture pointer");
-  if (mode != 0 && mode != 1) return sensor_fail(DRRT_ERR_ARG, "mode must be 0 (near) or 1 (far)");
-  a.far = mode == 1 ? 2 : 0;
-  a.grad_image = tex;
-  return DRRT_OK;
-}
-
-static int tex_fwd(size_t n, const float* x, const float* v, const float plane_p[3], const float plane_n[3],
-                   const float t1[3], const float t2[3], const float* frame_dev, const float* tex, int res, float span,
-                   int mode, float* f_out, void* stream) {
   SensorArgs a{};
-  int rc = fill_tex(a, n, x, v, plane_p, plane_n, t1, t2, frame_dev, res, span, mode, tex); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  if (!f_out) return sensor_fail(DRRT_ERR_ARG, "null output pointer");
-  a.f_out = f_out;
-  hipLaunchKernelGGL(k_sensor_tex_get, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  const int rc = fill_far(a, n, v, e, e_scalar, device_frame(frame12), res, ang_cut);
+  return rc ? rc : run_ray_grads(false, a, grad_image, grad_x, grad_v, stream);
 }
 
 extern "C" int drrt_sensor_tex_get_f32(size_t n, const float* x, const float* v, const float plane_p[3],
                                        const float plane_n[3], const float t1[3], const float t2[3], const float* tex,
                                        int res, float span, int mode, float* f_out, void* stream) {
-  return tex_fwd(n, x, v, plane_p, plane_n, t1, t2, nullptr, tex, res, span, mode, f_out, stream);
+  SensorArgs a{};
+  const int rc = fill_tex(a, n, x, v, host_frame(plane_p, plane_n, t1, t2), tex, res, span, mode);
+  return rc ? rc : run_values(a, f_out, stream);
 }
 extern "C" int drrt_sensor_tex_get_dframe_f32(size_t n, const float* x, const float* v, const float* frame12,
                                               const float* tex, int res, float span, int mode, float* f_out, void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return tex_fwd(n, x, v, kZero3, kZero3, kZero3, kZero3, frame12, tex, res, span, mode, f_out, stream);
-}
-
-static int tex_bwd(size_t n, const float* x, const float* v, const float plane_p[3], const float plane_n[3],
-                   const float t1[3], const float t2[3], const float* frame_dev, const float* tex, int res, float span,
-                   int mode, const float* grad_f, float* grad_x, float* grad_v, void* stream) {
   SensorArgs a{};
-  int rc = fill_tex(a, n, x, v, plane_p, plane_n, t1, t2, frame_dev, res, span, mode, tex); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  if (!grad_f || !grad_x || !grad_v) return sensor_fail(DRRT_ERR_ARG, "null gradient pointer");
-  a.grad_f = grad_f; a.grad_x = grad_x; a.grad_v = grad_v;
-  hipLaunchKernelGGL(k_sensor_tex_get_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  const int rc = fill_tex(a, n, x, v, device_frame(frame12), tex, res, span, mode);
+  return rc ? rc : run_values(a, f_out, stream);
 }
-
 extern "C" int drrt_sensor_tex_get_bwd_f32(size_t n, const float* x, const float* v, const float plane_p[3],
                                            const float plane_n[3], const float t1[3], const float t2[3],
                                            const float* tex, int res, float span, int mode, const float* grad_f,
                                            float* grad_x, float* grad_v, void* stream) {
-  return tex_bwd(n, x, v, plane_p, plane_n, t1, t2, nullptr, tex, res, span, mode, grad_f, grad_x, grad_v, stream);
+  SensorArgs a{};
+  const int rc = fill_tex(a, n, x, v, host_frame(plane_p, plane_n, t1, t2), tex, res, span, mode);
+  return rc ? rc : run_ray_grads(true, a, grad_f, grad_x, grad_v, stream);
 }
 extern "C" int drrt_sensor_tex_get_dframe_bwd_f32(size_t n, const float* x, const float* v, const float* frame12,
                                                   const float* tex, int res, float span, int mode, const float* grad_f,
                                                   float* grad_x, float* grad_v, void* stream) {
-  if (!frame12) return sensor_fail(DRRT_ERR_ARG, "null frame pointer");
-  return tex_bwd(n, x, v, kZero3, kZero3, kZero3, kZero3, frame12, tex, res, span, mode, grad_f, grad_x, grad_v, stream);
+  SensorArgs a{};
+  const int rc = fill_tex(a, n, x, v, device_frame(frame12), tex, res, span, mode);
+  return rc ? rc : run_ray_grads(true, a, grad_f, grad_x, grad_v, stream);
 }
-
-// =============================================================================================
-// multires up-sampling of a volume (SURVEY.md 8.8 "next" row 3)
-//
-// Reference: core/optimizer.py:7-10 upres_scene -> core/grid.py:318-330 upres_volume: trilinear
-// resampling of the (R,R,R) volume at linspace(0,1,S)^3 through Grid.GetLinear (:227-273), carried
-// out in float64 and cast back.  The reference materialises an (S^3, 3) float64 point list plus ~20
-// (S^3, 8)-sized temporaries (several GB at S = 256); this is one pass, one thread per output voxel.
-// =============================================================================================
-namespace drrt {
-
-__global__ void __launch_bounds__(256) k_upres(const float* __restrict__ src, int r0, int r1, int r2,
-                                               float* __restrict__ dst, int s0, int s1, int s2) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  const size_t total = (size_t)s0 * s1 * s2;
-  if (i >= total) return;
-  const int k = (int)(i % s2), j = (int)((i / s2) % s1), m = (int)(i / ((size_t)s2 * s1));
-  const int idx[3] = {m, j, k}, sn[3] = {s0, s1, s2};
-  const int rr = r0;                                   // the reference clips every axis with res[0] (grid.py:242)
-  const double h = 1.0 / (double)(rr > 1 ? rr - 1 : 1);   // grid.py:319-320
-  int i0[3], i1[3]; double w[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    // torch.linspace(0, 1, s): step*i for the first half, 1 - step*(s-1-i) for the second
-    const double step = sn[a] > 1 ? 1.0 / (double)(sn[a] - 1) : 0.0;
-    const double x = (idx[a] < sn[a] / 2) ? step * idx[a] : 1.0 - step * (double)(sn[a] - 1 - idx[a]);
-    const double nx = x / h;                           // grid.py:232
-    const double fl = floor(nx);
-    double ww = nx - fl; ww = ww < 0.0 ? 0.0 : (ww > 1.0 ? 1.0 : ww);   // :235
-    w[a] = ww;
-    const int b = (int)fl;
-    i0[a] = min(max(b, 0), rr - 1); i1[a] = min(max(b + 1, 0), rr - 1);  // :243
-  }
-  double acc = 0.0;
-#pragma unroll
-  for (int c = 0; c < 8; ++c) {
-    const int a0 = (c & 4) ? i1[0] : i0[0], a1 = (c & 2) ? i1[1] : i0[1], a2 = (c & 1) ? i1[2] : i0[2];
-    const double ww = ((c & 4) ? w[0] : 1.0 - w[0]) * ((c & 2) ? w[1] : 1.0 - w[1]) * ((c & 1) ? w[2] : 1.0 - w[2]);
-    acc += ww * (double)src[((size_t)a0 * r1 + a1) * r2 + a2];
-  }
-  dst[i] = (float)acc;
-}
-
-}  // namespace drrt
-
-extern "C" int drrt_upres_volume_f32(const float* src, const int src_shape[3], float* dst, const int dst_shape[3],
-                                     void* stream) {
-  if (!src || !dst || !src_shape || !dst_shape) return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  for (int a = 0; a < 3; ++a)
-    if (src_shape[a] < 1 || dst_shape[a] < 1) return sensor_fail(DRRT_ERR_ARG, "bad shape");
-  if (src_shape[0] != src_shape[1] || src_shape[0] != src_shape[2])
-    return sensor_fail(DRRT_ERR_ARG, "upres_volume expects a cubic source volume (the reference clips all axes with res[0])");
-  const size_t total = (size_t)dst_shape[0] * dst_shape[1] * dst_shape[2];
-  hipLaunchKernelGGL(k_upres, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, src,
-                     src_shape[0], src_shape[1], src_shape[2], dst, dst_shape[0], dst_shape[1], dst_shape[2]);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
-}
-
-// =============================================================================================
-// one optimiser iteration's tail (SURVEY.md 8.8 "next" row 3): boundary-gradient mask + Adam + clamp
-//
-// Reference: core/optimizer.py:57-69 -- `n.grad[mask] = 0` (mask = the outermost voxel layer, :54-55),
-// `opto.step()` with torch.optim.Adam, `n.clamp_(min=1)`.  In torch that is a boolean-mask index_put (a nonzero()
-// with a host sync), ~10 element-wise launches and three extra passes over the volume and its two moments; here it
-// is ONE pass: 16 B read + 12 B written per voxel.  The update is torch's Adam (torch/optim/adam.py
-// _single_tensor_adam, amsgrad = maximize = False), bias corrections computed by the caller in double:
-//   g     = grad (0 on the boundary layer; written back there like the reference's in-place mask) + weight_decay * p
-//   m    += (g - m) * (1 - beta1)                      (exp_avg.lerp_)
-//   v     = beta2 * v + (1 - beta2) * g * g
-//   p    -= step_size * m / (sqrt(v) / sqrt(bias_correction2) + eps),   step_size = lr / bias_correction1
-//   p     = p < clamp_min ? clamp_min : p              (NaN stays NaN, like clamp_)
-// =============================================================================================
-namespace drrt {
-
-struct AdamArgs {
-  float* p; float* g; float* m; float* v;
-  size_t n; int s0, s1, s2;             // torch shape (z, y, x): x fastest
-  float step_size, bc2_sqrt, beta2, omb1, omb2, eps, weight_decay, clamp_min;   // omb = 1 - beta, rounded from double like torch's scalars
-  int mask_boundary, clamp;
-};
-
-__global__ void __launch_bounds__(256) k_adam_masked(AdamArgs a) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= a.n) return;
-  float g = a.g[i];
-  if (a.mask_boundary) {
-    const int x = (int)(i % (size_t)a.s2), y = (int)((i / (size_t)a.s2) % (size_t)a.s1), z = (int)(i / ((size_t)a.s2 * a.s1));
-    if ((x == 0) | (x == a.s2 - 1) | (y == 0) | (y == a.s1 - 1) | (z == 0) | (z == a.s0 - 1)) { g = 0.f; a.g[i] = 0.f; }
-  }
-  float p = a.p[i], m = a.m[i], v = a.v[i];
-  if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
-  m = fmaf(g - m, a.omb1, m);
-  v = fmaf(a.omb2, g * g, a.beta2 * v);
-  const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
-  p = fmaf(-a.step_size, m / denom, p);
-  if (a.clamp) p = (p < a.clamp_min) ? a.clamp_min : p;
-  a.p[i] = p; a.m[i] = m; a.v[i] = v;
-}
-
-}  // namespace drrt
-
-extern "C" int drrt_adam_step_f32(float* param, float* grad, float* exp_avg, float* exp_avg_sq, const int shape[3],
-                                  double step, double lr, double beta1, double beta2, double eps, double weight_decay,
-                                  double clamp_min, unsigned flags, void* stream) {
-  if (!param || !grad || !exp_avg || !exp_avg_sq || !shape) return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  for (int k = 0; k < 3; ++k) if (shape[k] < 1) return sensor_fail(DRRT_ERR_ARG, "bad shape");
-  if (!(step >= 1.0)) return sensor_fail(DRRT_ERR_ARG, "step must be >= 1 (the value AFTER the increment, like torch's)");
-  drrt::AdamArgs a{};
-  a.p = param; a.g = grad; a.m = exp_avg; a.v = exp_avg_sq;
-  a.s0 = shape[0]; a.s1 = shape[1]; a.s2 = shape[2];
-  a.n = (size_t)shape[0] * shape[1] * shape[2];
-  const double bc1 = 1.0 - pow(beta1, step), bc2 = 1.0 - pow(beta2, step);       // torch/optim/adam.py
-  a.step_size = (float)(lr / bc1); a.bc2_sqrt = (float)sqrt(bc2);
-  a.beta2 = (float)beta2; a.omb1 = (float)(1.0 - beta1); a.omb2 = (float)(1.0 - beta2);
-  a.eps = (float)eps; a.weight_decay = (float)weight_decay;
-  a.clamp_min = (float)clamp_min;
-  a.mask_boundary = (flags & DRRT_ADAM_MASK_BOUNDARY) ? 1 : 0;
-  a.clamp = (flags & DRRT_ADAM_CLAMP_MIN) ? 1 : 0;
-  hipLaunchKernelGGL(drrt::k_adam_masked, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
-}
-
-// =============================================================================================
-// ray -> plane intersection as its own operator (the statement right after the march)
-//
-// Reference: core/sensor.py:195-202 trace_rays_to_plane: t = n.(p - x) / n.v ; x_out = x + t v ; v unchanged --
-// written with torch.matmul on (N,1,3) x (N,3,1) operands, i.e. a batched matmul of N one-by-three products, which on
-// the GPU costs ~25 ms forward and ~55 ms backward for 1M rays (tools/bench_iteration.py): 15x the march itself.
-// Here: one thread per ray, forward and analytic backward (gradients w.r.t. the rays; the planes are constants in
-// every experiment of the reference -- the Python wrapper falls back to the torch expressions if they require grad):
-//   a = n.(p - x), b = n.v, t = a / b
-//   d x_out / d x = I - v n^T / b            d x_out / d v = t I - (t / b) v n^T
-//   => gx = g - (g.v / b) n                  gv = t g - (t / b)(g.v) n          (g = dL/dx_out)
-// plane_stride = 3: one plane per ray; 0: one plane for all rays.
-// =============================================================================================
-namespace drrt {
-
-__device__ __forceinline__ float dot3(float ax, float ay, float az, float bx, float by, float bz) {
-  return fmaf(az, bz, fmaf(ay, by, ax * bx));
-}
-
-__global__ void __launch_bounds__(256) k_rays_to_plane(size_t n, const float* __restrict__ x, const float* __restrict__ v,
-                                                       const float* __restrict__ p, const float* __restrict__ nr,
-                                                       int plane_stride, float* __restrict__ xo) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const size_t k = i * (size_t)plane_stride;
-  const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2], v0 = v[3 * i], v1 = v[3 * i + 1], v2 = v[3 * i + 2];
-  const float n0 = nr[k], n1 = nr[k + 1], n2 = nr[k + 2];
-  const float a = dot3(n0, n1, n2, p[k] - x0, p[k + 1] - x1, p[k + 2] - x2);        // :199
-  const float t = a / dot3(n0, n1, n2, v0, v1, v2);                                   // :200
-  xo[3 * i] = fmaf(t, v0, x0); xo[3 * i + 1] = fmaf(t, v1, x1); xo[3 * i + 2] = fmaf(t, v2, x2);   // :202
-}
-
-__global__ void __launch_bounds__(256) k_rays_to_plane_bwd(size_t n, const float* __restrict__ x, const float* __restrict__ v,
-                                                           const float* __restrict__ p, const float* __restrict__ nr,
-                                                           int plane_stride, const float* __restrict__ g,
-                                                           float* __restrict__ gx, float* __restrict__ gv) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const size_t k = i * (size_t)plane_stride;
-  const float x0 = x[3 * i], x1 = x[3 * i + 1], x2 = x[3 * i + 2], v0 = v[3 * i], v1 = v[3 * i + 1], v2 = v[3 * i + 2];
-  const float n0 = nr[k], n1 = nr[k + 1], n2 = nr[k + 2];
-  const float g0 = g[3 * i], g1 = g[3 * i + 1], g2 = g[3 * i + 2];
-  const float a = dot3(n0, n1, n2, p[k] - x0, p[k + 1] - x1, p[k + 2] - x2);
-  const float inv_b = 1.f / dot3(n0, n1, n2, v0, v1, v2);
-  const float t = a * inv_b;
-  const float c = dot3(g0, g1, g2, v0, v1, v2) * inv_b;       // g.v / b
-  gx[3 * i] = fmaf(-c, n0, g0); gx[3 * i + 1] = fmaf(-c, n1, g1); gx[3 * i + 2] = fmaf(-c, n2, g2);
-  const float tc = t * c;
-  gv[3 * i] = fmaf(t, g0, -tc * n0); gv[3 * i + 1] = fmaf(t, g1, -tc * n1); gv[3 * i + 2] = fmaf(t, g2, -tc * n2);
-}
-
-}  // namespace drrt
-
-extern "C" int drrt_rays_to_plane_f32(size_t n, const float* x, const float* v, const float* plane_p, const float* plane_n,
-                                      int plane_stride, float* x_out, void* stream) {
-  if (plane_stride != 0 && plane_stride != 3) return sensor_fail(DRRT_ERR_ARG, "plane_stride must be 0 or 3");
-  if (n == 0) return DRRT_OK;
-  if (!x || !v || !plane_p || !plane_n || !x_out) return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  hipLaunchKernelGGL(drrt::k_rays_to_plane, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, x, v,
-                     plane_p, plane_n, plane_stride, x_out);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
-}
-
-extern "C" int drrt_rays_to_plane_bwd_f32(size_t n, const float* x, const float* v, const float* plane_p,
-                                          const float* plane_n, int plane_stride, const float* grad_x_out,
-                                          float* grad_x, float* grad_v, void* stream) {
-  if (plane_stride != 0 && plane_stride != 3) return sensor_fail(DRRT_ERR_ARG, "plane_stride must be 0 or 3");
-  if (n == 0) return DRRT_OK;
-  if (!x || !v || !plane_p || !plane_n || !grad_x_out || !grad_x || !grad_v) return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  hipLaunchKernelGGL(drrt::k_rays_to_plane_bwd, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, x,
-                     v, plane_p, plane_n, plane_stride, grad_x_out, grad_x, grad_v);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
-}
-

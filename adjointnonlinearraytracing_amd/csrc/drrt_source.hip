@@ -26,11 +26,9 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "../../include/drrt_hip.h"
+#include "drrt_host.h"
 
 namespace drrt {
-
-int sensor_fail(int code, const char* msg);   // drrt_kernels.hip
 
 constexpr int GEN_BLOCK = 256;
 constexpr int GEN_ITEMS = 4;                         // consecutive 256-candidate slabs per block
@@ -249,38 +247,15 @@ extern "C" size_t drrt_gen_workspace_bytes(int n_views, int spp, int p0, int p1)
 static int gen_rays_impl(int kind, double cone_cos, const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
                          double width, double sensor_dist, int circle, int independent,
                          const float* ic_rot_host, double span, float* x, float* v, float* planes,
-                         int* view_counts, void* workspace, size_t workspace_bytes, void* stream);
-
-extern "C" int drrt_gen_rays_f32(int kind, const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
-                                 double width, double sensor_dist, int circle, int independent,
-                                 const float* ic_rot_host, double span, float* x, float* v, float* planes,
-                                 int* view_counts, void* workspace, size_t workspace_bytes, void* stream) {
-  if (kind != 0 && kind != 1) return drrt::sensor_fail(DRRT_ERR_ARG, "source kind must be 0 (plane) or 1 (point)");
-  return gen_rays_impl(kind, 1.0, u, view_rot, n_views, spp, p0, p1, width, sensor_dist, circle, independent, ic_rot_host,
-                       span, x, v, planes, view_counts, workspace, workspace_bytes, stream);
-}
-
-extern "C" int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
-                                      double width, double sensor_dist, double cone_cos, const float* ic_rot_host,
-                                      double span, float* x, float* v, float* planes, int* view_counts, void* workspace,
-                                      size_t workspace_bytes, void* stream) {
-  if (!(cone_cos >= -1.0 && cone_cos <= 1.0)) return drrt::sensor_fail(DRRT_ERR_ARG, "cone_cos must lie in [-1, 1]");
-  return gen_rays_impl(2, cone_cos, u, view_rot, n_views, spp, p0, p1, width, sensor_dist, 0, 0, ic_rot_host, span, x, v,
-                       planes, view_counts, workspace, workspace_bytes, stream);
-}
-
-static int gen_rays_impl(int kind, double cone_cos, const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
-                         double width, double sensor_dist, int circle, int independent,
-                         const float* ic_rot_host, double span, float* x, float* v, float* planes,
                          int* view_counts, void* workspace, size_t workspace_bytes, void* stream) {
   using namespace drrt;
   if (!u || !view_rot || !x || !v || !planes || !view_counts || !workspace)
-    return sensor_fail(DRRT_ERR_ARG, "null pointer");
-  if (n_views < 1 || n_views > 65535 || spp < 1 || p0 < 1 || p1 < 1) return sensor_fail(DRRT_ERR_ARG, "bad view / pixel counts");
+    return fail(DRRT_ERR_ARG, "null pointer");
+  if (n_views < 1 || n_views > 65535 || spp < 1 || p0 < 1 || p1 < 1) return fail(DRRT_ERR_ARG, "bad view / pixel counts");
   const unsigned long long cand = (unsigned long long)spp * p0 * p1;
-  if (cand * (unsigned long long)n_views >= (1ull << 31)) return sensor_fail(DRRT_ERR_ARG, "too many candidate rays (>= 2^31)");
-  if (!(width > 0.0)) return sensor_fail(DRRT_ERR_ARG, "width must be positive");
-  if (workspace_bytes < drrt_gen_workspace_bytes(n_views, spp, p0, p1)) return sensor_fail(DRRT_ERR_ARG, "workspace too small");
+  if (cand * (unsigned long long)n_views >= (1ull << 31)) return fail(DRRT_ERR_ARG, "too many candidate rays (>= 2^31)");
+  if (!(width > 0.0)) return fail(DRRT_ERR_ARG, "width must be positive");
+  if (workspace_bytes < drrt_gen_workspace_bytes(n_views, spp, p0, p1)) return fail(DRRT_ERR_ARG, "workspace too small");
   GenArgs a;
   a.u = u; a.view_rot = view_rot;
   a.has_ic = ic_rot_host != nullptr;
@@ -304,6 +279,23 @@ static int gen_rays_impl(int kind, double cone_cos, const float* u, const float*
   hipLaunchKernelGGL(k_gen_scan, dim3(1), dim3(1024), 0, s, a.block_counts, a.blocks_per_view * (unsigned)n_views,
                      a.blocks_per_view, view_counts, n_views);
   hipLaunchKernelGGL(k_gen_write, grid, dim3(GEN_BLOCK), 0, s, a);
-  hipError_t le = hipGetLastError();
-  return le == hipSuccess ? DRRT_OK : sensor_fail(DRRT_ERR_HIP, hipGetErrorString(le));
+  return launch_status();
+}
+
+extern "C" int drrt_gen_rays_f32(int kind, const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
+                                 double width, double sensor_dist, int circle, int independent,
+                                 const float* ic_rot_host, double span, float* x, float* v, float* planes,
+                                 int* view_counts, void* workspace, size_t workspace_bytes, void* stream) {
+  if (kind != 0 && kind != 1) return drrt::fail(DRRT_ERR_ARG, "source kind must be 0 (plane) or 1 (point)");
+  return gen_rays_impl(kind, 1.0, u, view_rot, n_views, spp, p0, p1, width, sensor_dist, circle, independent, ic_rot_host,
+                       span, x, v, planes, view_counts, workspace, workspace_bytes, stream);
+}
+
+extern "C" int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n_views, int spp, int p0, int p1,
+                                      double width, double sensor_dist, double cone_cos, const float* ic_rot_host,
+                                      double span, float* x, float* v, float* planes, int* view_counts, void* workspace,
+                                      size_t workspace_bytes, void* stream) {
+  if (!(cone_cos >= -1.0 && cone_cos <= 1.0)) return drrt::fail(DRRT_ERR_ARG, "cone_cos must lie in [-1, 1]");
+  return gen_rays_impl(2, cone_cos, u, view_rot, n_views, spp, p0, p1, width, sensor_dist, 0, 0, ic_rot_host, span, x, v,
+                       planes, view_counts, workspace, workspace_bytes, stream);
 }

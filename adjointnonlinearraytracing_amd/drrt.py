@@ -26,6 +26,7 @@ from typing import Dict, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._lib import _p, _stream
 
 
 @dataclass
@@ -245,10 +246,6 @@ def _res3(res: Sequence[int]):
     if len(r) != 3:
         raise RuntimeError("res must have 3 entries")
     return (C.c_int * 3)(*r)
-
-
-def _stream(device: torch.device) -> C.c_void_p:
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _new_stats(device: torch.device) -> torch.Tensor:
@@ -502,10 +499,6 @@ def _warn_failed(stats: torch.Tensor) -> None:
     _pending_warn.append((ev, host))
     if len(_pending_warn) > 64:                          # bounded backlog
         _drain_warnings(block=True)
-
-
-def _p(t: Optional[torch.Tensor]) -> C.c_void_p:
-    return C.c_void_p(0 if t is None else t.data_ptr())
 
 
 def _cable_call(name: str, rif, radius, length, ds, rays, make_outputs, warn: bool = False) -> tuple:

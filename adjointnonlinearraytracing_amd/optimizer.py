@@ -18,6 +18,7 @@ import torch
 import torch.optim as optim
 
 from . import _lib
+from ._lib import _p, _stream
 
 
 def upres_scene(n: torch.Tensor, res: int) -> torch.Tensor:
@@ -30,9 +31,8 @@ def upres_scene(n: torch.Tensor, res: int) -> torch.Tensor:
     if n.dim() != 3:
         raise RuntimeError("upres_scene: only 3-D volumes are supported")
     with torch.cuda.device(n.device):
-        _lib.check(_lib.load().drrt_upres_volume_f32(
-            C.c_void_p(src.data_ptr()), (C.c_int * 3)(*src.shape), C.c_void_p(dst.data_ptr()),
-            (C.c_int * 3)(*dst.shape), C.c_void_p(torch.cuda.current_stream(n.device).cuda_stream)))
+        _lib.check(_lib.load().drrt_upres_volume_f32(_p(src), (C.c_int * 3)(*src.shape), _p(dst), (C.c_int * 3)(*dst.shape),
+                                                     _stream(n.device)))
     return dst.to(n.dtype)
 
 
@@ -81,11 +81,9 @@ class MaskedAdam(optim.Optimizer):
                     v = state["exp_avg_sq"] = v.to(torch.float32).contiguous()
                 with torch.cuda.device(p.device):
                     _lib.check(lib.drrt_adam_step_f32(
-                        C.c_void_p(p.data_ptr()), C.c_void_p(g.data_ptr()), C.c_void_p(m.data_ptr()),
-                        C.c_void_p(v.data_ptr()), (C.c_int * 3)(*p.shape), float(state["step"]), float(group["lr"]),
+                        _p(p), _p(g), _p(m), _p(v), (C.c_int * 3)(*p.shape), float(state["step"]), float(group["lr"]),
                         float(beta1), float(beta2), float(group["eps"]), float(group["weight_decay"]),
-                        float(group["clamp_min"] if group["clamp_min"] is not None else 0.0), flags,
-                        C.c_void_p(torch.cuda.current_stream(p.device).cuda_stream)))
+                        float(group["clamp_min"] if group["clamp_min"] is not None else 0.0), flags, _stream(p.device)))
                 # The kernel wrote p and p.grad through raw pointers: tell autograd, as any in-place torch op would.  The
                 # version counters are what tracer.Back*TracerC's save_for_backward check and the pair-copy reuse token
                 # of drrt._march_workspace key on -- without the bump a retained-graph backward after step() would

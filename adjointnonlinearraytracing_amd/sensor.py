@@ -18,6 +18,13 @@ import ctypes as C
 import torch
 
 from . import _lib
+from ._lib import _p, _stream
+from .drrt import _f32
+
+
+def _ray_grads(x_: torch.Tensor):
+    """The (grad_x, grad_v) outputs of a backward kernel."""
+    return torch.empty_like(x_), torch.empty_like(x_)
 
 
 class _RaysToPlane(torch.autograd.Function):
@@ -26,16 +33,11 @@ class _RaysToPlane(torch.autograd.Function):
     def forward(ctx, x, v, p, n):
         dev = x.device
         with torch.cuda.device(dev):
-            x_ = x.detach().to(torch.float32).contiguous()
-            v_ = v.detach().to(torch.float32).contiguous()
-            p_ = p.detach().to(device=dev, dtype=torch.float32).contiguous()
-            n_ = n.detach().to(device=dev, dtype=torch.float32).contiguous()
+            x_, v_, p_, n_ = (_f32(t, dev) for t in (x, v, p, n))
             stride = 3 if p_.shape[0] > 1 else 0
             xo = torch.empty_like(x_)
-            _lib.check(_lib.load().drrt_rays_to_plane_f32(
-                x_.shape[0], C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()), C.c_void_p(p_.data_ptr()),
-                C.c_void_p(n_.data_ptr()), stride, C.c_void_p(xo.data_ptr()),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            _lib.check(_lib.load().drrt_rays_to_plane_f32(x_.shape[0], _p(x_), _p(v_), _p(p_), _p(n_), stride, _p(xo),
+                                                          _stream(dev)))
         ctx.save_for_backward(x_, v_, p_, n_)
         ctx.stride = stride
         return xo
@@ -45,12 +47,10 @@ class _RaysToPlane(torch.autograd.Function):
         x_, v_, p_, n_ = ctx.saved_tensors
         dev = x_.device
         with torch.cuda.device(dev):
-            g_ = g.detach().to(torch.float32).contiguous()
-            gx, gv = torch.empty_like(x_), torch.empty_like(v_)
-            _lib.check(_lib.load().drrt_rays_to_plane_bwd_f32(
-                x_.shape[0], C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()), C.c_void_p(p_.data_ptr()),
-                C.c_void_p(n_.data_ptr()), ctx.stride, C.c_void_p(g_.data_ptr()), C.c_void_p(gx.data_ptr()),
-                C.c_void_p(gv.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+            g_ = _f32(g, dev)
+            gx, gv = _ray_grads(x_)
+            _lib.check(_lib.load().drrt_rays_to_plane_bwd_f32(x_.shape[0], _p(x_), _p(v_), _p(p_), _p(n_), ctx.stride,
+                                                              _p(g_), _p(gx), _p(gv), _stream(dev)))
         return gx, gv, None, None
 
 
@@ -124,6 +124,25 @@ def _frame(dev, p, n, t1, t2):
     return None, tuple(_vec3(t) for t in given)
 
 
+def _energy(e, nr: int, dev):
+    """The `e` of a splat -> (per-ray tensor or None, scalar): one entry per ray, or one value for all of them."""
+    if isinstance(e, torch.Tensor) and e.numel() > 1:
+        e_ = _f32(e, dev).reshape(-1).contiguous()
+        if e_.numel() != nr:
+            raise RuntimeError("e must be a scalar or have one entry per ray")
+        return e_, 0.0
+    return None, float(e)
+
+
+def _call(entry: str, head, fdev, frame, *tail) -> None:
+    """One sensor entry, ``entry(*head, <frame>, *tail, stream)``: `entry` names it with ``{}`` where ``_dframe`` goes, and
+    that twin is the one called when _frame() packed the frame on the device (``fdev``).  Tensors go in as their device
+    pointers (None as NULL); `head` is (n, rays ...), and the stream is the current one of the rays' device."""
+    fn = getattr(_lib.load(), entry.format("" if fdev is None else "_dframe"))
+    args = (*head, *(frame if fdev is None else (fdev,)), *tail)
+    _lib.check(fn(*(_p(a) if isinstance(a, torch.Tensor) else a for a in args), _stream(head[1].device)))
+
+
 class _SensorSplat(torch.autograd.Function):
 
     @staticmethod
@@ -132,41 +151,21 @@ class _SensorSplat(torch.autograd.Function):
             raise RuntimeError("generate_sensor expects tensors on the cuda (ROCm) device (no CPU path)")
         dev = x.device
         with torch.cuda.device(dev):
-            x_ = x.detach().to(torch.float32).contiguous()
-            v_ = v.detach().to(torch.float32).contiguous()
-            nr = x_.shape[0]
-            if isinstance(e, torch.Tensor) and e.numel() > 1:
-                e_ = e.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-                if e_.numel() != nr:
-                    raise RuntimeError("e must be a scalar or have one entry per ray")
-                e_s = 0.0
-            else:
-                e_, e_s = None, float(e)
+            x_, v_ = _f32(x, dev), _f32(v, dev)
+            e_, e_s = _energy(e, x_.shape[0], dev)
             img = torch.empty(int(res), int(res), dtype=torch.float32, device=dev)
             fdev, frame = _frame(dev, p, n, t1, t2)
-            head = (nr, C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()), C.c_void_p(0 if e_ is None else e_.data_ptr()), e_s)
-            tail = (int(res), float(span), C.c_void_p(img.data_ptr()), 0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_splat_dframe_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_splat_f32(*head, *frame, *tail))
+            _call("drrt_sensor_splat{}_f32", (x_.shape[0], x_, v_, e_, e_s), fdev, frame, int(res), float(span), img, 0)
         ctx.saved = (x_, v_, e_, e_s, fdev, frame, int(res), float(span))
         return img
 
     @staticmethod
     def backward(ctx, grad_img):
         x_, v_, e_, e_s, fdev, frame, res, span = ctx.saved
-        dev = x_.device
-        with torch.cuda.device(dev):
-            g = grad_img.detach().to(torch.float32).contiguous()
-            gx, gv = torch.empty_like(x_), torch.empty_like(v_)
-            head = (x_.shape[0], C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()), C.c_void_p(0 if e_ is None else e_.data_ptr()), e_s)
-            tail = (res, span, C.c_void_p(g.data_ptr()), C.c_void_p(gx.data_ptr()), C.c_void_p(gv.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_splat_dframe_bwd_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_splat_bwd_f32(*head, *frame, *tail))
+        with torch.cuda.device(x_.device):
+            g = _f32(grad_img, x_.device)
+            gx, gv = _ray_grads(x_)
+            _call("drrt_sensor_splat{}_bwd_f32", (x_.shape[0], x_, v_, e_, e_s), fdev, frame, res, span, g, gx, gv)
         return gx, gv, None, None, None, None, None, None, None
 
 
@@ -201,40 +200,21 @@ class _FarSensorSplat(torch.autograd.Function):
             raise RuntimeError("generate_inf_sensor expects tensors on the cuda (ROCm) device (no CPU path)")
         dev = v.device
         with torch.cuda.device(dev):
-            v_ = v.detach().to(torch.float32).contiguous()
-            nr = v_.shape[0]
-            if isinstance(e, torch.Tensor) and e.numel() > 1:
-                e_ = e.detach().to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
-                if e_.numel() != nr:
-                    raise RuntimeError("e must be a scalar or have one entry per ray")
-                e_s = 0.0
-            else:
-                e_, e_s = None, float(e)
+            v_ = _f32(v, dev)
+            e_, e_s = _energy(e, v_.shape[0], dev)
             img = torch.empty(int(res), int(res), dtype=torch.float32, device=dev)
             fdev, frame = _frame(dev, None, None, t1, t2)
-            head = (nr, C.c_void_p(v_.data_ptr()), C.c_void_p(0 if e_ is None else e_.data_ptr()), e_s)
-            tail = (int(res), float(ang_cut), C.c_void_p(img.data_ptr()), 0, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_far_splat_dframe_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_far_splat_f32(*head, *frame, *tail))
+            _call("drrt_sensor_far_splat{}_f32", (v_.shape[0], v_, e_, e_s), fdev, frame, int(res), float(ang_cut), img, 0)
         ctx.saved = (v_, e_, e_s, fdev, frame, int(res), float(ang_cut))
         return img
 
     @staticmethod
     def backward(ctx, grad_img):
         v_, e_, e_s, fdev, frame, res, ang_cut = ctx.saved
-        dev = v_.device
-        with torch.cuda.device(dev):
-            g = grad_img.detach().to(torch.float32).contiguous()
-            gx, gv = torch.empty_like(v_), torch.empty_like(v_)
-            head = (v_.shape[0], C.c_void_p(v_.data_ptr()), C.c_void_p(0 if e_ is None else e_.data_ptr()), e_s)
-            tail = (res, ang_cut, C.c_void_p(g.data_ptr()), C.c_void_p(gx.data_ptr()), C.c_void_p(gv.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_far_splat_dframe_bwd_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_far_splat_bwd_f32(*head, *frame, *tail))
+        with torch.cuda.device(v_.device):
+            g = _f32(grad_img, v_.device)
+            gx, gv = _ray_grads(v_)
+            _call("drrt_sensor_far_splat{}_bwd_f32", (v_.shape[0], v_, e_, e_s), fdev, frame, res, ang_cut, g, gx, gv)
         return gv, None, None, None, None, None
 
 
@@ -265,37 +245,24 @@ class _TexGet(torch.autograd.Function):
         _single_plane(p, n)            # (t1, t2 of get_tan_vecs are set in row 0 only, as in the reference)
         dev = x.device
         with torch.cuda.device(dev):
-            x_ = x.detach().to(torch.float32).contiguous()
-            v_ = v.detach().to(torch.float32).contiguous()
-            tex_ = tex.detach().to(device=dev, dtype=torch.float32).contiguous()
+            x_, v_, tex_ = (_f32(t, dev) for t in (x, v, tex))
             if tex_.dim() != 2 or tex_.shape[0] != tex_.shape[1]:
                 raise RuntimeError("the texture must be square (the reference clips both axes with res[0])")
             fdev, frame = _frame(dev, p, n, t1, t2)
             f = torch.empty(x_.shape[0], dtype=torch.float32, device=dev)
-            head = (x_.shape[0], C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()))
-            tail = (C.c_void_p(tex_.data_ptr()), int(tex_.shape[0]), float(span), int(mode), C.c_void_p(f.data_ptr()),
-                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_tex_get_dframe_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_tex_get_f32(*head, *frame, *tail))
+            _call("drrt_sensor_tex_get{}_f32", (x_.shape[0], x_, v_), fdev, frame, tex_, int(tex_.shape[0]), float(span),
+                  int(mode), f)
         ctx.saved = (x_, v_, tex_, fdev, frame, float(span), int(mode))
         return f
 
     @staticmethod
     def backward(ctx, grad_f):
         x_, v_, tex_, fdev, frame, span, mode = ctx.saved
-        dev = x_.device
-        with torch.cuda.device(dev):
-            g = grad_f.detach().to(torch.float32).contiguous()
-            gx, gv = torch.empty_like(x_), torch.empty_like(v_)
-            head = (x_.shape[0], C.c_void_p(x_.data_ptr()), C.c_void_p(v_.data_ptr()))
-            tail = (C.c_void_p(tex_.data_ptr()), int(tex_.shape[0]), span, mode, C.c_void_p(g.data_ptr()),
-                    C.c_void_p(gx.data_ptr()), C.c_void_p(gv.data_ptr()), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-            if fdev is not None:
-                _lib.check(_lib.load().drrt_sensor_tex_get_dframe_bwd_f32(*head, C.c_void_p(fdev.data_ptr()), *tail))
-            else:
-                _lib.check(_lib.load().drrt_sensor_tex_get_bwd_f32(*head, *frame, *tail))
+        with torch.cuda.device(x_.device):
+            g = _f32(grad_f, x_.device)
+            gx, gv = _ray_grads(x_)
+            _call("drrt_sensor_tex_get{}_bwd_f32", (x_.shape[0], x_, v_), fdev, frame, tex_, int(tex_.shape[0]), span, mode,
+                  g, gx, gv)
         return gx, gv, None, None, None, None, None, None, None
 
 

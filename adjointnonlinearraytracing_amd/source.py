@@ -34,6 +34,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import _p, _stream
 
 
 def _view_matrix(angle, vert=False) -> np.ndarray:
@@ -89,18 +90,14 @@ def _generate(view_mats, pixels, spp, width, circle, sensor_dist, independent, o
         else:
             m = rotmat.detach().cpu().numpy() if isinstance(rotmat, torch.Tensor) else np.asarray(rotmat)
             ic = (C.c_float * 9)(*np.asarray(m, dtype=np.float64).astype(np.float32).reshape(9).tolist())
-        tail = (ic, float(span if span is not None else width),
-                C.c_void_p(x.data_ptr()), C.c_void_p(v.data_ptr()), C.c_void_p(planes.data_ptr()),
-                C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), ws.numel(),
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        tail = (ic, float(span if span is not None else width), _p(x), _p(v), _p(planes), _p(counts), _p(ws), ws.numel(),
+                _stream(dev))
         if kind == 2:
-            _lib.check(lib.drrt_gen_cone_rays_f32(
-                C.c_void_p(u.data_ptr()), C.c_void_p(rots.data_ptr()), nv, spp, p0, p1, float(width), float(sensor_dist),
-                _cone_cos(cone_angle), *tail))
+            _lib.check(lib.drrt_gen_cone_rays_f32(_p(u), _p(rots), nv, spp, p0, p1, float(width), float(sensor_dist),
+                                                  _cone_cos(cone_angle), *tail))
         else:
-            _lib.check(lib.drrt_gen_rays_f32(
-                int(kind), C.c_void_p(u.data_ptr()), C.c_void_p(rots.data_ptr()), nv, spp, p0, p1, float(width),
-                float(sensor_dist), int(bool(circle)), int(bool(independent)), *tail))
+            _lib.check(lib.drrt_gen_rays_f32(int(kind), _p(u), _p(rots), nv, spp, p0, p1, float(width), float(sensor_dist),
+                                             int(bool(circle)), int(bool(independent)), *tail))
         if kind == 2 or not circle:
             # no rejection (only the disc mask drops samples, csrc/drrt_source.hip): the counts are known on the host,
             # so the call returns without waiting for the device

@@ -339,6 +339,151 @@ def test_invalid_calls_are_refused_by_the_same_check(lib):
         assert h.drrt_order_hint_pending() == 0, (entry, row)
 
 
+# ---- the operators around the march: sensor, rays -> plane, up-sampling, Adam, ray generation ---------------------------
+# Argument names in call order (include/drrt_hip.h).  The sensor entries are one family of rays, a frame (host vectors, or
+# `frame12` for the *_dframe twins) and a tail per direction; `span` stands for the far field's `ang_cut` too.
+_SENSOR = {       # family: (rays, host frame, forward tail, backward tail)
+    "splat": ("n x v e e_scalar", "plane_p plane_n t1 t2", "res span image flags", "res span grad_image grad_x grad_v"),
+    "far_splat": ("n v e e_scalar", "t1 t2", "res span image flags", "res span grad_image grad_x grad_v"),
+    "tex_get": ("n x v", "plane_p plane_n t1 t2", "tex res span mode f_out", "tex res span mode grad_f grad_x grad_v"),
+}
+_GEN_TAIL = " ic_rot span x v planes view_counts workspace workspace_bytes stream"
+_OP_ARGS = {f"drrt_sensor_{fam}{d}{b}_f32": f"{rays} {'frame12' if d else frame} {bwd if b else fwd} stream"
+            for fam, (rays, frame, fwd, bwd) in _SENSOR.items() for d in ("", "_dframe") for b in ("", "_bwd")}
+_OP_ARGS.update({
+    "drrt_rays_to_plane_f32": "n x v plane_p plane_n plane_stride x_out stream",
+    "drrt_rays_to_plane_bwd_f32": "n x v plane_p plane_n plane_stride grad_x_out grad_x grad_v stream",
+    "drrt_upres_volume_f32": "src src_shape dst dst_shape stream",
+    "drrt_adam_step_f32": "param grad exp_avg exp_avg_sq shape step lr beta1 beta2 eps weight_decay clamp_min flags stream",
+    "drrt_gen_workspace_bytes": "n_views spp p0 p1",
+    "drrt_gen_rays_f32": "kind u view_rot n_views spp p0 p1 width sensor_dist circle independent" + _GEN_TAIL,
+    "drrt_gen_cone_rays_f32": "u view_rot n_views spp p0 p1 width sensor_dist cone_cos" + _GEN_TAIL,
+})
+_HOST_VEC3 = ("plane_p", "plane_n", "t1", "t2")        # host float[3] of the sensor entries: read once the checks pass
+_SHAPES = ("src_shape", "dst_shape", "shape")          # host int[3]
+_NAN = float("nan")
+_GEN_WS = {(1, 1, 1, 1): 8, (2, 1, 4, 4): 12, (1, 1, 1024, 1): 8, (1, 1, 1025, 1): 12, (3, 2, 33, 31): 28,
+           (6, 1, 512, 512): 6148, (0, 1, 4, 4): 0, (2, 0, 4, 4): 0, (2, 1, -1, 4): 0, (2, 1, 4, 0): 0}
+
+
+def _operator_calls():
+    """[(entry, row name, overrides)]: operator calls that are answered before the first HIP call -- refused, or
+    DRRT_OK for nothing to do (the `ok_` rows).  Rows with two faults pin which check answers."""
+    rows = []
+    for e, names in _OP_ARGS.items():
+        if "_sensor_" not in e:
+            continue
+        names = names.split()
+        first_ray = "x" if "x" in names else "v"        # (the far field hands `v` on as `x`: a null `v` is a "null pointer")
+        out = [k for k in ("image", "grad_x", "f_out") if k in names][0]
+        mine = [("null_ray", {first_ray: None, "res": 0, out: None}), ("null_v", dict(v=None, span=0.0)),
+                ("null_t1", dict(t1=None, res=0)), ("null_t2", dict(t2=None, span=0.0)),
+                ("null_frame12", dict(frame12=None, res=0)), ("null_frame12_first", {"frame12": None, first_ray: None, "v": None}),
+                ("res0", {"res": 0, out: None, "n": 0}), ("res32769", dict(res=32769)),
+                ("span0", {"span": 0.0, out: None}), ("span_nan", dict(span=_NAN, n=0)), ("span_neg", dict(span=-1.0)),
+                ("null_grad_v", dict(grad_v=None))]
+        if "tex_get" in e:          # n == 0 returns DRRT_OK after the texture and the mode, before the outputs
+            mine += [("null_tex", dict(tex=None, mode=2, n=0)), ("mode2", {"mode": 2, "n": 0, out: None}),
+                     ("mode_neg", dict(mode=-1)), ("null_" + out, {out: None}),
+                     ("ok_n0", dict({k: None for k in ("f_out", "grad_f", "grad_x", "grad_v") if k in names}, n=0))]
+        else:                       # the splats look at their outputs BEFORE the n == 0 return
+            mine += [("null_" + out, {out: None, "n": 0}), ("null_grad_image", dict(grad_image=None, n=0)),
+                     ("ok_n0", dict(n=0))]                              # (flags: DRRT_FLAG_NO_ZERO, so no fill either)
+        rows += [(e, row, o) for row, o in mine if set(o) <= set(names)]
+    for e in ("drrt_rays_to_plane_f32", "drrt_rays_to_plane_bwd_f32"):
+        out = "grad_x" if e.endswith("_bwd_f32") else "x_out"
+        rows += [(e, "stride1", dict(plane_stride=1, n=0)), (e, "stride_first", dict(plane_stride=6, x=None)),
+                 (e, "null_x", dict(x=None)), (e, "null_plane_n", dict(plane_n=None)), (e, "null_out", {out: None}),
+                 (e, "ok_n0", {"n": 0, "x": None, "v": None, "plane_p": None, "plane_n": None, out: None}),
+                 (e, "ok_n0_stride3", dict(n=0, plane_stride=3))]
+    e = "drrt_upres_volume_f32"
+    rows += [(e, "null_src", dict(src=None, src_shape=(4, 5, 4))), (e, "null_shape", dict(dst_shape=None)),
+             (e, "non_cubic", dict(src_shape=(4, 4, 5))), (e, "zero_src_shape", dict(src_shape=(4, 0, 5))),
+             (e, "zero_dst_shape", dict(dst_shape=(8, 8, 0), src_shape=(4, 5, 4)))]
+    e = "drrt_adam_step_f32"
+    rows += [(e, "null_param", dict(param=None, shape=(4, 0, 4))), (e, "null_moment", dict(exp_avg_sq=None, step=0.5)),
+             (e, "null_shape", dict(shape=None)), (e, "zero_shape", dict(shape=(4, 4, 0), step=0.5)),
+             (e, "step_half", dict(step=0.5)), (e, "step0", dict(step=0.0)), (e, "step_nan", dict(step=_NAN))]
+    e = "drrt_gen_rays_f32"
+    rows += [(e, "kind2", dict(kind=2, u=None)), (e, "kind_neg", dict(kind=-1))]
+    rows += [("drrt_gen_cone_rays_f32", "cone_cos_1p5", dict(cone_cos=1.5, u=None)),
+             ("drrt_gen_cone_rays_f32", "cone_cos_nan", dict(cone_cos=_NAN))]
+    for e in ("drrt_gen_rays_f32", "drrt_gen_cone_rays_f32"):
+        rows += [(e, "null_u", dict(u=None, n_views=0)), (e, "null_counts", dict(view_counts=None)),
+                 (e, "null_workspace", dict(workspace=None, width=0.0)),
+                 (e, "views0", dict(n_views=0, width=0.0)), (e, "views65536", dict(n_views=65536)),
+                 (e, "spp0", dict(spp=0)), (e, "p1_neg", dict(p1=-4)),
+                 (e, "cand_2p31", dict(spp=1024, p0=1024, p1=1024, width=0.0)),
+                 (e, "width0", dict(width=0.0, workspace_bytes=0)), (e, "width_nan", dict(width=_NAN)),
+                 (e, "ws_one_short", dict(workspace_bytes=_GEN_WS[2, 1, 4, 4] - 1))]
+    return rows
+
+
+def _invoke_operator(h, entry, overrides):
+    import ctypes as C
+    names = _OP_ARGS[entry].split()
+    # defaults: a valid call of 128 rays / 2 views of 4 x 4 pixels; 0x1000 for every device pointer (never dereferenced)
+    vals = dict(n=128, e=None, e_scalar=1.0, res=8, span=1.0, mode=0, flags=_NO_ZERO, stream=None, plane_stride=0,
+                src_shape=(4, 4, 4), dst_shape=(8, 8, 8), shape=(4, 4, 4), step=1.0, lr=1e-3, beta1=0.9, beta2=0.999,
+                eps=1e-8, weight_decay=0.0, clamp_min=1.0, kind=0, n_views=2, spp=1, p0=4, p1=4, width=1.0,
+                sensor_dist=1.0, circle=0, independent=0, cone_cos=0.5, ic_rot=None, workspace_bytes=1 << 20)
+    assert set(overrides) <= set(names), (entry, set(overrides) - set(names))
+    args = []
+    for k in names:
+        v = overrides[k] if k in overrides else vals.get(k, 0x1000)
+        if k in _SHAPES and v is not None:
+            v = (C.c_int * 3)(*v)
+        elif k in _HOST_VEC3 and "_sensor_" in entry and v is not None:
+            v = (C.c_float * 3)(0.0, 1.0, 0.0)
+        args.append(v)
+    return getattr(h, entry)(*args)
+
+
+# (return code, drrt_last_error()) of every row, as the library answered while each operator entry carried its own checks
+_NULL, _SPAN = (-3, 'null pointer'), (-3, 'bad sensor resolution / span')
+_NULL_GRAD, _MODE = (-3, 'null gradient pointer'), (-3, 'mode must be 0 (near) or 1 (far)')
+_STRIDE, _COUNTS = (-3, 'plane_stride must be 0 or 3'), (-3, 'bad view / pixel counts')
+_STEP = (-3, "step must be >= 1 (the value AFTER the increment, like torch's)")
+_OP_BY_ROW = {
+    'null_ray': _NULL, 'null_v': _NULL, 'null_t1': _NULL, 'null_t2': _NULL,
+    'null_frame12': (-3, 'null frame pointer'), 'null_frame12_first': (-3, 'null frame pointer'),
+    'res0': _SPAN, 'res32769': _SPAN, 'span0': _SPAN, 'span_nan': _SPAN, 'span_neg': _SPAN,
+    'null_image': (-3, 'null image pointer'), 'null_grad_image': _NULL_GRAD, 'null_grad_x': _NULL_GRAD, 'null_grad_v': _NULL_GRAD,
+    'null_tex': (-3, 'null texture pointer'), 'mode2': _MODE, 'mode_neg': _MODE, 'null_f_out': (-3, 'null output pointer'),
+    'ok_n0': 0, 'ok_n0_stride3': 0,
+    'stride1': _STRIDE, 'stride_first': _STRIDE, 'null_x': _NULL, 'null_plane_n': _NULL, 'null_out': _NULL,
+    'null_src': _NULL, 'null_shape': _NULL, 'zero_src_shape': (-3, 'bad shape'), 'zero_dst_shape': (-3, 'bad shape'),
+    'non_cubic': (-3, 'upres_volume expects a cubic source volume (the reference clips all axes with res[0])'),
+    'null_param': _NULL, 'null_moment': _NULL, 'zero_shape': (-3, 'bad shape'), 'step_half': _STEP, 'step0': _STEP, 'step_nan': _STEP,
+    'kind2': (-3, 'source kind must be 0 (plane) or 1 (point)'), 'kind_neg': (-3, 'source kind must be 0 (plane) or 1 (point)'),
+    'cone_cos_1p5': (-3, 'cone_cos must lie in [-1, 1]'), 'cone_cos_nan': (-3, 'cone_cos must lie in [-1, 1]'),
+    'null_u': _NULL, 'null_counts': _NULL, 'null_workspace': _NULL,
+    'views0': _COUNTS, 'views65536': _COUNTS, 'spp0': _COUNTS, 'p1_neg': _COUNTS,
+    'cand_2p31': (-3, 'too many candidate rays (>= 2^31)'), 'width0': (-3, 'width must be positive'),
+    'width_nan': (-3, 'width must be positive'), 'ws_one_short': (-3, 'workspace too small'),
+}
+
+
+def test_operator_calls_are_answered_by_the_same_check(lib):
+    """The operator entries' counterpart of test_invalid_calls_are_refused_by_the_same_check: every call of
+    _operator_calls() returns the code and the message it returned before the operators shared their host call path.
+    The present order is deliberate: tex_get and rays_to_plane return DRRT_OK for n == 0 before they look at their
+    outputs, the splats check theirs first.  Nothing here reaches a HIP call, so this runs without a GPU."""
+    h = lib.load()
+    rows = _operator_calls()
+    assert len({(e, r) for e, r, _ in rows}) == len(rows) == 206
+    assert {e for e, _, _ in rows} == set(_OP_ARGS) - {"drrt_gen_workspace_bytes"}
+    assert {r for _, r, _ in rows} == set(_OP_BY_ROW)
+    for entry, row, overrides in rows:
+        want = _OP_BY_ROW[row]
+        assert (want == 0) == row.startswith("ok_"), (entry, row)
+        rc = _invoke_operator(h, entry, overrides)
+        got = 0 if rc == 0 else (rc, h.drrt_last_error().decode())      # (a call that succeeds leaves the message alone)
+        assert got == want, (entry, row)
+    for sizes, nbytes in _GEN_WS.items():
+        assert _invoke_operator(h, "drrt_gen_workspace_bytes", dict(zip("n_views spp p0 p1".split(), sizes))) == nbytes, sizes
+
+
 def test_q16_params_host_side(lib):
     """drrt_q16_params is host-only: q_min = -E/16, q_step = 1.125 E / 65535 with E the largest box extent, 2^-14."""
     import ctypes as C

@@ -386,3 +386,47 @@ def test_sdf_vals_refuse_what_they_cannot_differentiate(gpu):
     with pytest.raises(RuntimeError, match="one plane"):
         sensor.get_sdf_vals_near((x, v), tex, (pp, n.repeat(N, 1)), 1.0)
     assert torch.equal(sensor.get_sdf_vals_near((x, v), tex, (p.repeat(N, 1), n.repeat(N, 1)), 1.0), f)   # equal rows are fine
+
+
+@pytest.mark.gpu
+def test_splat_without_rays_and_without_zeroing(gpu):
+    """The two corners of the splat entries that the Python operators never take: a call of no rays still zeroes its
+    image, and DRRT_FLAG_NO_ZERO adds onto what the image holds.  64 rays onto 8 x 8 pixels, near and far field.  The
+    second statement is checked ray by ray: one ray's taps reach a pixel as ONE fp32 add each, so pre-fill + splat has no
+    summation order and must equal the plain splat added to the pre-fill bit for bit."""
+    import ctypes as C
+    from adjointnonlinearraytracing_amd import _lib
+    from adjointnonlinearraytracing_amd._lib import _p, _stream
+    h, s = _lib.load(), _stream(gpu)
+    torch.manual_seed(11)
+    n, res = 64, 8
+    x = torch.rand(n, 3, device=gpu) * 0.8 + 0.1
+    x[:, 1] = 0.0
+    v = torch.randn(n, 3, device=gpu) * 0.15
+    v[:, 1] = 1.0
+    vec = lambda *a: (C.c_float * 3)(*a)
+    p, nrm, t1, t2 = vec(0.5, 1.1, 0.5), vec(0.0, 1.0, 0.0), vec(1.0, 0.0, 0.0), vec(0.0, 0.0, 1.0)
+
+    def near(k, img, flags):
+        _lib.check(h.drrt_sensor_splat_f32(k, _p(x), _p(v), None, 1.0, p, nrm, t1, t2, res, 1.0, _p(img), flags, s))
+
+    def far(k, img, flags):
+        _lib.check(h.drrt_sensor_far_splat_f32(k, _p(v), None, 1.0, t1, t2, res, 0.5, _p(img), flags, s))
+
+    for splat in (near, far):
+        img = torch.ones(res, res, device=gpu)
+        splat(0, img, 0)
+        assert not img.any(), "no rays: the image is still zeroed"
+        img.fill_(1.0)
+        splat(0, img, _lib.FLAG_NO_ZERO)
+        assert torch.equal(img, torch.ones_like(img)), "no rays, DRRT_FLAG_NO_ZERO: the image is left alone"
+    pre = torch.rand(2, n, res, res, device=gpu)
+    plain, filled = torch.full_like(pre, 7.0), pre.clone()
+    for f, (entry, rays) in enumerate(((h.drrt_sensor_splat_f32, (x, v)), (h.drrt_sensor_far_splat_f32, (v,)))):
+        frame = (p, nrm, t1, t2) if f == 0 else (t1, t2)
+        for k in range(n):
+            head = (1, *(_p(r[k:k + 1]) for r in rays), None, 1.0, *frame, res, (1.0, 0.5)[f])
+            _lib.check(entry(*head, _p(plain[f, k]), 0, s))
+            _lib.check(entry(*head, _p(filled[f, k]), _lib.FLAG_NO_ZERO, s))
+        assert (plain[f].sum(dim=(1, 2)) > 0).sum() >= n // 2, "most rays land on the image"
+    assert torch.equal(filled, pre + plain)
