@@ -12,7 +12,9 @@ torch tensors instead of enoki arrays and backed by the hand-written HIP kernels
 
 All methods ``detach()`` / ``contiguous()`` / cast to fp32 exactly where the reference narrows
 (``core/tracer.py:299-301``, ``include/tracer.h:20-21``); ``res`` may be any 3-sequence
-(``torch.Size`` is what the scripts pass, ``core/tracer.py:298,307``).
+(``torch.Size`` is what the scripts pass, ``core/tracer.py:298,307``).  Ray tensors of any floating-point dtype are
+converted to fp32 by value; integer ray tensors are codes of the 16-bit ray state and are refused wherever the call does not
+select it (``_rays``).
 """
 from __future__ import annotations
 
@@ -232,6 +234,12 @@ def decode_rays16(res: Sequence[int], h: float, pos_q: Optional[torch.Tensor] = 
 
 
 def _rays(t: torch.Tensor, device: torch.device, n: Optional[int] = None, half: bool = False, q16: bool = False) -> torch.Tensor:
+    if q16 != (t.dtype == torch.int16) or not (q16 or t.dtype.is_floating_point):
+        # integer tensors are codes, not numbers: converting them to fp32 would march code 16384 as 16384.0
+        raise RuntimeError(
+            f"{t.dtype} ray tensor where this call takes {'int16 codes' if q16 else 'floating-point values'}: codes of the "
+            "16-bit ray state (encode_rays16) go to trace / backtrace only, as int16 positions with int16 or floating-point "
+            "directions; decode_rays16 turns them into fp32 for every other call")
     if q16:
         t = t.detach().to(device=device).contiguous()
     else:

@@ -230,3 +230,33 @@ EXPORT int stop_raygrad_host_backtrace_rays(int mode, const float* rif, const fl
   else return 1;
   return 0;
 }
+
+// ---- 16-bit ray state: the codecs ld3 / st3 call, array in / array out, on the Vol that vol_finish builds ------------
+// out: q_min, q_step, q_inv_step
+EXPORT int hostcheck_q16_params(const int* res, float h, float* out) {
+  const Vol V = make_vol(nullptr, res, h);
+  out[0] = V.q_min; out[1] = V.q_step; out[2] = V.q_inv_step;
+  return 0;
+}
+EXPORT int hostcheck_q16_pos_enc(const int* res, float h, size_t n, const float* x, uint16_t* code) {
+  const Vol V = make_vol(nullptr, res, h);
+  for (size_t i = 0; i < n; ++i) code[i] = q16_pos_enc(V, x[i]);
+  return 0;
+}
+EXPORT int hostcheck_q16_pos_dec(const int* res, float h, size_t n, const uint16_t* code, float* x) {
+  const Vol V = make_vol(nullptr, res, h);
+  for (size_t i = 0; i < n; ++i) x[i] = q16_pos_dec(V, code[i]);
+  return 0;
+}
+EXPORT int hostcheck_q16_vel_enc(const int* res, float h, size_t n, const float* v, int16_t* code) {
+  const Vol V = make_vol(nullptr, res, h);
+  (void)V;
+  for (size_t i = 0; i < n; ++i) code[i] = q16_vel_enc(v[i]);
+  return 0;
+}
+EXPORT int hostcheck_q16_vel_dec(const int* res, float h, size_t n, const int16_t* code, float* v) {
+  const Vol V = make_vol(nullptr, res, h);
+  (void)V;
+  for (size_t i = 0; i < n; ++i) v[i] = q16_vel_dec(code[i]);
+  return 0;
+}

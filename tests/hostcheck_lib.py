@@ -155,3 +155,34 @@ def backtrace_pln_rays(rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds):
 def backtrace_sdf_rays(rif, sdf, res, pos, vel, dx, dv, h, ds):
     """The same for drrt_backtrace_sdf_rays_f32."""
     return _backtrace_stop_rays(2, rif, sdf, res, pos, vel, None, None, dx, dv, h, ds)
+
+
+# ---- 16-bit ray state: the __host__ __device__ codecs of drrt_device.h -----------------------------------------------
+def q16_params(res, h):
+    """-> float32[3]: q_min, q_step, q_inv_step of the Vol that vol_finish builds."""
+    out = np.empty(3, np.float32)
+    lib().hostcheck_q16_params(_p(_res(res)), C.c_float(h), _p(out))
+    return out
+
+
+def _q16(name, res, h, a, in_dtype, out_dtype):
+    a = np.ascontiguousarray(np.asarray(a, dtype=in_dtype))
+    out = np.empty(a.shape, out_dtype)
+    getattr(lib(), name)(_p(_res(res)), C.c_float(h), C.c_size_t(a.size), _p(a), _p(out))
+    return out
+
+
+def q16_pos_enc(res, h, x):
+    return _q16("hostcheck_q16_pos_enc", res, h, x, np.float32, np.uint16)
+
+
+def q16_pos_dec(res, h, code):
+    return _q16("hostcheck_q16_pos_dec", res, h, code, np.uint16, np.float32)
+
+
+def q16_vel_enc(res, h, v):
+    return _q16("hostcheck_q16_vel_enc", res, h, v, np.float32, np.int16)
+
+
+def q16_vel_dec(res, h, code):
+    return _q16("hostcheck_q16_vel_dec", res, h, code, np.int16, np.float32)

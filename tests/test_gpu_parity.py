@@ -448,6 +448,42 @@ def test_golden_fuel_injection(gpu, oracle, drrt_mod):
     assert unexplained <= 0.002 and bad <= 0.05
 
 
+def test_golden_fuel_injection_adjoint(gpu, oracle, drrt_mod):
+    """The adjoint on the same real 65^3 volume, from the traced exit rays (the forward's visit order handed over), against
+    oracle.backtrace on the oracle's own exit rays: once with dx = dv = 1, once with the seed of a squared-distance loss on
+    sensor.trace_rays_to_plane (each ray's sensor plane faces its input direction one box width past the centre; the
+    target is where the unrefracted ray meets it -- the deflection loss of core/fuel_injection_opt.py).  All 1728 rays of
+    the fixture: the single-thread oracle takes well under a second for them, so no strided subset is taken."""
+    from adjointnonlinearraytracing_amd import sensor
+    z = _golden("fuel_injection.npz")
+    vol, h, ds = z["vol"], float(z["h"]), float(z["ds"])
+    span = h * (vol.shape[0] - 1)
+    T = drrt_mod.TracerC()
+    V = _t(vol, gpu)
+    x, v = _t(z["x"], gpu), _t(z["v"], gpu)
+    with drrt_mod.using(sort_rays=True):
+        xt, vt = T.trace(V, vol.shape, x, v, h, ds)
+        order = drrt_mod.keep_order(drrt_mod.last_order)
+        with oracle.arith("factored"):
+            o32 = oracle.trace(vol, vol.shape, z["x"], z["v"], h, ds, dtype=np.float32)
+        assert np.array_equal(xt.cpu().numpy(), o32["xt"]) and np.array_equal(vt.cpu().numpy(), o32["vt"])
+        n = v / v.norm(dim=1, keepdim=True)
+        plane = (torch.full((1, 3), span / 2, device=gpu) + span * n, n)
+        target = sensor.trace_rays_to_plane((x, v), plane)[0]
+        xl, vl = xt.clone().requires_grad_(True), vt.clone().requires_grad_(True)
+        ((sensor.trace_rays_to_plane((xl, vl), plane)[0] - target) ** 2).sum().backward()
+        assert float(xl.grad.abs().max()) > 0 and bool(torch.isfinite(xl.grad).all() and torch.isfinite(vl.grad).all())
+        for dx, dv in ((torch.ones_like(xt), torch.ones_like(vt)), (xl.grad, vl.grad)):
+            g = T.backtrace(V, vol.shape, xt, vt, dx, dv, h, ds, order=order)
+            st = drrt_mod.read_stats()
+            with oracle.arith("factored"):
+                ob = oracle.backtrace(vol, vol.shape, o32["xt"], o32["vt"], dx.cpu().numpy(), dv.cpu().numpy(), h, ds,
+                                      dtype=np.float32)
+            assert st["ray_steps"] == ob["steps_total"]
+            assert float(np.abs(ob["grad"]).max()) > 1e-20
+            assert cases.grads_agree(g.cpu().numpy(), ob["grad"])
+
+
 def test_non_cubic_grid(gpu, oracle, drrt_mod):
     """res = (W,H,D) all different; flat index (z*H + y)*W + x as src/volume.cpp:134-141 writes it."""
     W, H, D = 20, 14, 9
