@@ -31,9 +31,11 @@ __global__ void __launch_bounds__(256) k_upres(const float* __restrict__ src, in
   int i0[3], i1[3]; double w[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
-    // torch.linspace(0, 1, s): step*i for the first half, 1 - step*(s-1-i) for the second
+    // torch.linspace(0, 1, s): step*i for the first half, 1 - step*(s-1-i) for the second as ONE fused multiply-add
+    // (torch's kernels contract it: one rounding); one step is the start alone.  The last bit matters: where a point
+    // lands on a source node it decides floor(), and one ulp short of the node mixes 1e-16 of the neighbour in.
     const double step = sn[a] > 1 ? 1.0 / (double)(sn[a] - 1) : 0.0;
-    const double x = (idx[a] < sn[a] / 2) ? step * idx[a] : 1.0 - step * (double)(sn[a] - 1 - idx[a]);
+    const double x = (idx[a] < sn[a] / 2 || sn[a] == 1) ? step * idx[a] : fma(-step, (double)(sn[a] - 1 - idx[a]), 1.0);
     const double nx = x / h;                           // grid.py:232
     const double fl = floor(nx);
     double ww = nx - fl; ww = ww < 0.0 ? 0.0 : (ww > 1.0 ? 1.0 : ww);   // :235
@@ -74,7 +76,8 @@ extern "C" int drrt_upres_volume_f32(const float* src, const int src_shape[3], f
 // is ONE pass: 16 B read + 12 B written per voxel.  The update is torch's Adam (torch/optim/adam.py
 // _single_tensor_adam, amsgrad = maximize = False), bias corrections computed by the caller in double:
 //   g     = grad (0 on the boundary layer; written back there like the reference's in-place mask) + weight_decay * p
-//   m    += (g - m) * (1 - beta1)                      (exp_avg.lerp_)
+//   m     = w < 0.5 ? m + (g - m) * w : g - (g - m) * (1 - w)      (exp_avg.lerp_; w = 1 - beta1 rounded to fp32 and
+//                                                                  1 - w its fp32 complement, as in ATen -- not beta1)
 //   v     = beta2 * v + (1 - beta2) * g * g
 //   p    -= step_size * m / (sqrt(v) / sqrt(bias_correction2) + eps),   step_size = lr / bias_correction1
 //   p     = p < clamp_min ? clamp_min : p              (NaN stays NaN, like clamp_)
@@ -98,7 +101,9 @@ __global__ void __launch_bounds__(256) k_adam_masked(AdamArgs a) {
   }
   float p = a.p[i], m = a.m[i], v = a.v[i];
   if (a.weight_decay != 0.f) g = fmaf(a.weight_decay, p, g);
-  m = fmaf(g - m, a.omb1, m);
+  // lerp_ weighs from the nearer end (ATen's lerp: |weight| < 0.5 from m, else from g), so beta1 = 0 gives m = g exactly
+  const float d = g - m;
+  m = (a.omb1 < 0.5f) ? fmaf(d, a.omb1, m) : fmaf(-d, 1.f - a.omb1, g);
   v = fmaf(a.omb2, g * g, a.beta2 * v);
   const float denom = sqrtf(v) / a.bc2_sqrt + a.eps;
   p = fmaf(-a.step_size, m / denom, p);

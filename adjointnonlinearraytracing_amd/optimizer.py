@@ -26,10 +26,10 @@ def upres_scene(n: torch.Tensor, res: int) -> torch.Tensor:
     float64 like the reference, returned in ``n.dtype``).  HIP kernel; cuda tensors only."""
     if not n.is_cuda:
         raise RuntimeError("upres_scene expects a tensor on the cuda (ROCm) device (no CPU path)")
-    src = n.detach().to(torch.float32).contiguous()
-    dst = torch.empty((int(res),) * n.dim(), dtype=torch.float32, device=n.device)
     if n.dim() != 3:
         raise RuntimeError("upres_scene: only 3-D volumes are supported")
+    src = n.detach().to(torch.float32).contiguous()
+    dst = torch.empty((int(res),) * 3, dtype=torch.float32, device=n.device)
     with torch.cuda.device(n.device):
         _lib.check(_lib.load().drrt_upres_volume_f32(_p(src), (C.c_int * 3)(*src.shape), _p(dst), (C.c_int * 3)(*dst.shape),
                                                      _stream(n.device)))
@@ -49,6 +49,14 @@ class MaskedAdam(optim.Optimizer):
             raise ValueError("invalid Adam hyper-parameter")            # torch/optim/adam.py raises the same way
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay,
                                       mask_boundary=mask_boundary, clamp_min=clamp_min))
+
+    def __setstate__(self, state):
+        """``load_state_dict`` replaces the param groups by the saved ones; a checkpoint written by torch.optim.Adam
+        (the reference's) has no ``mask_boundary`` / ``clamp_min``, which then take this optimiser's defaults."""
+        super().__setstate__(state)
+        for group in self.param_groups:
+            for key in _MASKED_HYPER:
+                group.setdefault(key, self.defaults[key])
 
     @torch.no_grad()
     def step(self, closure=None):

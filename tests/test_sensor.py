@@ -94,7 +94,9 @@ def test_upres_matches_reference_run(gpu):
         src, ref = z[f"{tag}_src"], z[f"{tag}_dst"]
         out = optimizer.upres_scene(torch.from_numpy(src).to(gpu), ref.shape[0])
         assert out.shape == ref.shape and out.dtype == torch.float32
-        assert np.abs(out.cpu().numpy() - ref).max() <= 2e-7 * np.abs(ref).max()
+        # per element: the kernel rounds its float64 sum once, the fixture is the reference's float64 result rounded once
+        err = np.abs(out.cpu().numpy().astype(np.float64) - ref)
+        assert (err <= 0.51 * np.spacing(np.abs(ref)).astype(np.float64)).all(), (tag, err.max())
     # Adam-state transfer keeps hyper-parameters and up-samples both moments (core/optimizer.py:13-41)
     n0 = torch.rand(5, 5, 5, device=gpu, requires_grad=True)
     o0 = torch.optim.Adam([n0], lr=3e-3, betas=(0.8, 0.95))
