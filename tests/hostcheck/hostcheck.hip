@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../adjointnonlinearraytracing_amd/csrc/drrt_device.h"
+#include "../../adjointnonlinearraytracing_amd/csrc/drrt_keys.h"
 
 using namespace drrt;
 
@@ -258,5 +259,35 @@ EXPORT int hostcheck_q16_vel_dec(const int* res, float h, size_t n, const int16_
   const Vol V = make_vol(nullptr, res, h);
   (void)V;
   for (size_t i = 0; i < n; ++i) v[i] = q16_vel_dec(code[i]);
+  return 0;
+}
+
+// ---- locality-sort keys: the per-ray functions of drrt_keys.h that k_lightfield_keys / k_chord_keys call ----------------
+EXPORT int hostcheck_hilbert2(size_t n, const uint32_t* x, const uint32_t* y, uint32_t* d) {
+  for (size_t i = 0; i < n; ++i) d[i] = hilbert2(x[i], y[i]);
+  return 0;
+}
+// a, b: n cells in [-15, 15]; c, t1, t2: (n,3)
+EXPORT int hostcheck_lf_cell_frame(size_t n, const int* a, const int* b, float* c, float* t1, float* t2) {
+  for (size_t i = 0; i < n; ++i) lf_cell_frame(a[i], b[i], c + 3 * i, t1 + 3 * i, t2 + 3 * i);
+  return 0;
+}
+// the keys of the fp32 rays (pos, vel) heading along sign * vel, as the kernels form them
+EXPORT int hostcheck_lightfield_keys(const int* res, float h, size_t n, const float* pos, const float* vel, float sign,
+                                     uint32_t* keys) {
+  const Vol V = make_vol(nullptr, res, h);
+  for (size_t i = 0; i < n; ++i) {
+    const float d[3] = {sign * vel[3 * i], sign * vel[3 * i + 1], sign * vel[3 * i + 2]};
+    keys[i] = lightfield_key(V, pos + 3 * i, d);
+  }
+  return 0;
+}
+EXPORT int hostcheck_chord_keys(const int* res, float h, size_t n, const float* pos, const float* vel, float sign,
+                                uint64_t* keys) {
+  const Vol V = make_vol(nullptr, res, h);
+  for (size_t i = 0; i < n; ++i) {
+    const float d[3] = {sign * vel[3 * i], sign * vel[3 * i + 1], sign * vel[3 * i + 2]};
+    keys[i] = chord_key(V, pos + 3 * i, d);
+  }
   return 0;
 }

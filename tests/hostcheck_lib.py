@@ -10,7 +10,8 @@ import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = [os.path.join(_HERE, "hostcheck", "hostcheck.hip")]     # what a build of the library compiles
-_HDR = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc", "drrt_device.h")
+_CSRC = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc")
+_HDRS = [os.path.join(_CSRC, "drrt_device.h"), os.path.join(_CSRC, "drrt_keys.h")]   # what hostcheck.hip includes
 _SO = os.path.join(_HERE, "hostcheck", "_build", "libhostcheck.so")
 _lib = None
 
@@ -19,7 +20,7 @@ def lib():
     global _lib
     if _lib is None:
         os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in SOURCES + [_HDR]):
+        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in SOURCES + _HDRS):
             subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC",
                             "-ffp-contract=off", "-mfma", "-shared", "-fvisibility=hidden", "-o", _SO] + SOURCES,
                            check=True, capture_output=True)
@@ -186,3 +187,39 @@ def q16_vel_enc(res, h, v):
 
 def q16_vel_dec(res, h, code):
     return _q16("hostcheck_q16_vel_dec", res, h, code, np.int16, np.float32)
+
+
+# ---- locality-sort keys: the __host__ __device__ key functions of drrt_keys.h ---------------------------------------
+def hilbert2(x, y):
+    x = np.ascontiguousarray(np.asarray(x, dtype=np.uint32)); y = np.ascontiguousarray(np.asarray(y, dtype=np.uint32))
+    assert x.shape == y.shape
+    d = np.empty(x.shape, np.uint32)
+    lib().hostcheck_hilbert2(C.c_size_t(x.size), _p(x), _p(y), _p(d))
+    return d
+
+
+def lf_cell_frame(a, b):
+    """-> (c, t1, t2), each (n,3) float32: the centre direction and the frame of the direction cells (a, b)."""
+    a = np.ascontiguousarray(np.asarray(a, dtype=np.int32)); b = np.ascontiguousarray(np.asarray(b, dtype=np.int32))
+    assert a.shape == b.shape and a.ndim == 1
+    c, t1, t2 = (np.empty((a.size, 3), np.float32) for _ in range(3))
+    lib().hostcheck_lf_cell_frame(C.c_size_t(a.size), _p(a), _p(b), _p(c), _p(t1), _p(t2))
+    return c, t1, t2
+
+
+def _keys(name, dtype, res, h, pos, vel, sign):
+    pos, vel = _f(pos), _f(vel)
+    assert pos.shape == vel.shape and pos.ndim == 2 and pos.shape[1] == 3
+    out = np.empty(len(pos), dtype)
+    getattr(lib(), name)(_p(_res(res)), C.c_float(h), C.c_size_t(len(pos)), _p(pos), _p(vel), C.c_float(sign), _p(out))
+    return out
+
+
+def lightfield_keys(res, h, pos, vel, sign=1.0):
+    """-> uint32[n]: what k_lightfield_keys writes for the fp32 rays (pos, vel) with dir_sign = sign."""
+    return _keys("hostcheck_lightfield_keys", np.uint32, res, h, pos, vel, sign)
+
+
+def chord_keys(res, h, pos, vel, sign=1.0):
+    """-> uint64[n]: what k_chord_keys writes."""
+    return _keys("hostcheck_chord_keys", np.uint64, res, h, pos, vel, sign)

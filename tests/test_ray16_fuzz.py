@@ -27,6 +27,8 @@ import pytest
 import torch
 
 from oracle import ray16_ref as R16
+from oracle import sortkey_ref as SK
+from test_sort_order import referee
 from test_ray16_ref import MODES, SEEDS, HALF_MIN_NORMAL, options_of, pos_sweep, reference, same_bits, vel_sweep
 
 pytestmark = pytest.mark.gpu
@@ -115,7 +117,7 @@ def test_sort_keys(gpu, mode, seed):
     """With sort_rays on, the visit order of the 16-bit call equals the order of the fp32 call on the widened inputs: same
     keys, same stable sort.  That pins `ldr` of drrt_sort.hip for io 1, 2, 3 in k_lightfield_keys (the default key) and in
     k_chord_keys (chord_key).  The fp32 call repeated returns the same order (the sort is deterministic), which is
-    what makes the comparison meaningful."""
+    what makes the comparison meaningful; which order is RIGHT is the referee's to say (oracle/sortkey_ref.py)."""
     from adjointnonlinearraytracing_amd import drrt
     r = reference(mode, seed)
     T = drrt.TracerC()
@@ -130,6 +132,8 @@ def test_sort_keys(gpu, mode, seed):
         assert np.array_equal(np.sort(orders[0]), np.arange(600)), chord
         assert np.array_equal(orders[0], orders[1]), ("two identical fp32 calls, different orders", chord)
         assert np.array_equal(orders[2], orders[0]), (mode, chord)
+        # ... and the fp32 order is the referee's: a stable sort by the float64 keys on the rays it decides
+        assert SK.order_consistent(orders[0], *referee(r["res"], r["h"], r["wpos"], r["wvel"], 1.0, chord)), ("fp32 order", chord)
 
 
 ADJOINT_SETTINGS = [dict(adjoint_window=w) for w in ("auto", "box", "ring", "ring_sparse", "ring_direct")] + \
