@@ -128,8 +128,8 @@ def allreduce_image(img: torch.Tensor, group=None) -> torch.Tensor:
 def _hip_trace(rif_flat, shape, x, v, h, ds):
     """-> (xt, vt, order): the forward's visit order rides along so the sharded adjoint can reuse it."""
     from . import drrt
-    xt, vt = drrt.TracerC().trace(rif_flat, shape, x, v, h, ds)
-    return xt, vt, drrt.keep_order(drrt.last_order)
+    (xt, vt), order, _ = drrt.TracerC()._trace(rif_flat, shape, x, v, h, ds)
+    return xt, vt, drrt.keep_order(order)
 
 
 def _hip_backtrace(rif_flat, shape, xt, vt, gx, gv, h, ds, order=None):
@@ -143,20 +143,22 @@ class ShardedBackTracerC(torch.autograd.Function):
 
     ``apply(rif, x_local, v_local, h, ds, group=None, overlap_chunks=0)``
 
-    The forward's visit order of the shard (and, riding on it, the per-ray iteration counts) is kept on ``ctx`` and
-    handed to the adjoint exactly as ``tracer.BackTracerC`` does on one GPU, so the sharded adjoint runs the same fast
-    path (no re-sort by exit rays).  The march is the HIP path (module functions ``_hip_trace`` / ``_hip_backtrace``;
+    The forward is ``tracer.BackTracerC``'s own (``tracer._grid_forward``): the visit order of the shard (and, riding on
+    it, the per-ray iteration counts) is kept on ``ctx`` and handed to the adjoint, so the sharded adjoint runs the same
+    fast path (no re-sort by exit rays).  The march is the HIP path (module functions ``_hip_trace`` / ``_hip_backtrace``;
     the CPU tests replace those names with stand-ins -- there is no injection hook in the product signature).
     ``overlap_chunks`` = K > 1: the adjoint runs in K depth chunks and final slabs of the grid are reduced while the later
     chunks march (``backtrace_allreduce_overlapped``); for plane-source sets on small shards."""
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds, group=None, overlap_chunks=0):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds, ctx.group, ctx.chunks = h, ds, group, int(overlap_chunks or 0)
-        outx, outv, ctx.order = _hip_trace(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), h, ds)
-        ctx.save_for_backward(rif, outx, outv)          # version-checked: no silent use of a modified grid
-        return outx, outv
+        from . import tracer
+        ctx.group, ctx.chunks = group, int(overlap_chunks or 0)
+
+        def march(*args):                                # `_hip_trace` is looked up per call: the CPU tests replace it
+            xt, vt, order = _hip_trace(*args)
+            return (xt, vt), order, None
+        return tracer._grid_forward(ctx, march, rif, None, x, v, (), h, ds)[0]
 
     @staticmethod
     def backward(ctx, grad_x, grad_v):

@@ -136,16 +136,16 @@ def _workspace(n: int, flags: int, device: torch.device, nvox: int = 0) -> torch
     if ws is None or ws.numel() < need:
         ws = torch.empty(max(need, 1 << 20), dtype=torch.uint8, device=device)
         _workspaces[key] = ws
-        _quad_tokens.pop(key, None)
+        _pair_tokens.pop(key, None)
     if not (flags & _lib.FLAG_PAIR_GRID):
-        _quad_tokens.pop(key, None)             # this call may overwrite the region a pair copy lived in
+        _pair_tokens.pop(key, None)             # this call may overwrite the region a pair copy lived in
     return ws
 
 
 # What the pair copy in a device's workspace was built from: (rif tensor, key).  Holding the tensor keeps its
 # storage alive, so equal (data_ptr, version counter) means "same contents"; n and the sort bit fix where in
 # the workspace the copy lives.
-_quad_tokens: Dict[tuple, tuple] = {}
+_pair_tokens: Dict[tuple, tuple] = {}
 
 
 def _march_workspace(rif_: torch.Tensor, res, n: int, h: float, ds: float, flags: int, device: torch.device,
@@ -168,16 +168,16 @@ def _march_workspace(rif_: torch.Tensor, res, n: int, h: float, ds: float, flags
     pflags = flags | _lib.FLAG_PAIR_GRID
     key = (rif_.data_ptr(), rif_._version, rif_.numel(), n, flags & _lib.FLAG_SORT_RAYS)
     if auto and adjoint:
-        tok = _quad_tokens.get(_wkey(device))
+        tok = _pair_tokens.get(_wkey(device))
         need = int(_lib.load().drrt_workspace_bytes_grid(n, rif_.numel(), pflags))
         ws = _workspaces.get(_wkey(device))
         if not (paired and tok is not None and tok[1] == key and ws is not None and ws.numel() >= need):
             return flags, _workspace(n, flags, device)
     ws = _workspace(n, pflags, device, rif_.numel())         # may reallocate -> drops the token
-    tok = _quad_tokens.get(_wkey(device))
+    tok = _pair_tokens.get(_wkey(device))
     if paired and tok is not None and tok[1] == key:
         pflags |= _lib.FLAG_PAIR_REUSE
-    _quad_tokens[_wkey(device)] = (rif_, key)
+    _pair_tokens[_wkey(device)] = (rif_, key)
     return pflags, ws
 
 
@@ -256,10 +256,17 @@ def _res3(res: Sequence[int]):
     return (C.c_int * 3)(*r)
 
 
+def _publish(**last) -> None:
+    """The one place that sets the module attributes last_stats / last_order / last_steps / last_bundle_counters: what the
+    call just made left behind, for callers that use the public methods.  The internal path (`_grid_call`) hands order and
+    steps to its own caller as well, which is what tracer.py and dist.py use: a module attribute is shared by all threads."""
+    globals().update(last)
+
+
 def _new_stats(device: torch.device) -> torch.Tensor:
-    global last_stats
-    last_stats = torch.empty(3, dtype=torch.int64, device=device)
-    return last_stats
+    st = torch.empty(3, dtype=torch.int64, device=device)
+    _publish(last_stats=st)
+    return st
 
 
 def read_stats(stats: Optional[torch.Tensor] = None) -> Dict[str, int]:
@@ -294,24 +301,18 @@ def _last_view(fn, n: int, device: torch.device) -> Optional[torch.Tensor]:
     return v
 
 
-def _capture_order(n: int, device: torch.device) -> None:
-    """Hand out the permutation (and the per-ray iteration counts) the library just left in the workspace: views, no
+def _capture_order(n: int, device: torch.device) -> Optional[torch.Tensor]:
+    """The permutation (and, riding on it, the per-ray iteration counts) the library just left in the workspace: views, no
     copies -- see `last_order`."""
-    global last_order
-    last_order = _last_view(_lib.load().drrt_last_order, n, device) if _opt().sort_rays and n >= 2 else None
-    if last_order is not None:
+    order = _last_view(_lib.load().drrt_last_order, n, device) if _opt().sort_rays and n >= 2 else None
+    if order is not None:
         # the forward march's per-ray iteration counts ride along ON the order tensor (attribute `drrt_steps`), so every
         # holder of the order hands both to the paired adjoint: its rays then start on the forward march's clock (step
         # hint, include/drrt_hip.h)
         steps = _last_view(_lib.load().drrt_last_steps, n, device)
         if steps is not None:
-            last_order.drrt_steps = steps
-
-
-def _capture_steps(n: int, device: torch.device) -> None:
-    """Hand out the per-ray iteration counts the forward march just left in the workspace (a view) -> `last_steps`."""
-    global last_steps
-    last_steps = _last_view(_lib.load().drrt_last_steps, n, device)
+            order.drrt_steps = steps
+    return order
 
 
 def keep_steps(steps: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
@@ -349,9 +350,8 @@ last_bundle_counters: Optional[torch.Tensor] = None
 def _capture_counters(ws: torch.Tensor) -> None:
     """The bundle classification of the adjoint call just made (drrt_last_bundle_counters, include/drrt_hip.h): four int32
     copied out of its workspace (device-to-device, async) -> `last_bundle_counters`, or None when the call did not classify."""
-    global last_bundle_counters
     v = _ws_view(_lib.load().drrt_last_bundle_counters(), 32, ws)
-    last_bundle_counters = None if v is None else v.view(torch.int32).clone()
+    _publish(last_bundle_counters=None if v is None else v.view(torch.int32).clone())
 
 
 def read_bundle_counters() -> Optional[Dict[str, int]]:
@@ -421,7 +421,7 @@ def _clear_hint() -> None:
 def _paired_adjoint(rif_, res, n: int, h, ds, device, order, replay: bool = False, flags: int = 0):
     """The call sequence of an adjoint that may be paired with its forward march through `order` (the forward's visit
     order): validate the order, workspace + final flags, a fresh stats block, order / step hint armed -> yields
-    (order, flags, workspace, stats) for the library call -> hint cleared.  The order region of the workspace counts as
+    (flags, workspace, stats, order) for the library call -> hint cleared.  The order region of the workspace counts as
     rewritten when the call sorts for itself (no hint taken), and always for the adjoints that `replay` their forward:
     their second-pass flags go where the forward left its iteration counts, and they march with the forward's flags."""
     order = _valid_order(order)
@@ -430,25 +430,19 @@ def _paired_adjoint(rif_, res, n: int, h, ds, device, order, replay: bool = Fals
     try:
         if not _hint(order, n) or replay:
             _bump_order_gen(device)
-        yield order, fl, ws, st
+        yield fl, ws, st, order
     finally:
         _clear_hint()
 
 
 @contextlib.contextmanager
-def _forward_march(rif_, res, n: int, h, ds, device, flags: int = 0, steps: bool = True, warn: bool = True):
+def _forward_march(rif_, res, n: int, h, ds, device, flags: int = 0):
     """The call sequence of a forward grid march, the twin of `_paired_adjoint`: workspace + final flags, a fresh stats
-    block, the order / state region of the workspace counted as rewritten -> yields (flags, workspace, stats) for the
-    library call -> `last_order` captured, `last_steps` too for the marches that leave iteration counts (`steps`), failed
-    rays reported (`warn`).  Nothing is captured when the call raises."""
+    block, the order / state region of the workspace counted as rewritten -> yields (flags, workspace, stats, None) for
+    the library call.  What the call leaves behind is `_grid_call`'s to collect."""
     (fl, ws), st = _march_workspace(rif_, res, n, h, ds, _flags() | flags, device), _new_stats(device)
     _bump_order_gen(device)
-    yield fl, ws, st
-    _capture_order(n, device)
-    if steps:
-        _capture_steps(n, device)
-    if warn:
-        _warn_failed(st)
+    yield fl, ws, st, None
 
 
 # "failed to exit all rays" (src/tracer.cpp:90) without a host sync per call: the stats block is copied to pinned
@@ -527,76 +521,131 @@ def _cable_call(name: str, rif, radius, length, ds, rays, make_outputs, warn: bo
     return out
 
 
+def _ray_format(pos: torch.Tensor, vel: torch.Tensor, seeds: tuple = ()):
+    """The ray-state format of a trace / backtrace call, from the dtypes of its position and direction tensors (and, for
+    the adjoint, of its `seeds`) -> (entry suffix, extra flag, how `_rays` converts each of (pos, vel, *seeds)).  All
+    float16: the IEEE-half variant (half in, fp32 march, half out).  int16 positions AND directions (codes from
+    ``encode_rays16``): the 16-bit ray state "q16", whose adjoint takes IEEE-half seeds.  int16 positions with
+    floating-point directions: q16 positions only, directions and seeds fp32.  Anything else: fp32."""
+    half, q16 = _is_half(pos, vel, *seeds), _is_q16(pos, vel)
+    qpos = (not q16) and pos.dtype == torch.int16
+    if q16 and seeds and not _is_half(*seeds):
+        raise RuntimeError("q16 exit rays (int16) go with float16 seeds dx, dv")
+    if not (half or q16 or qpos):
+        return "_f32", 0, None
+    how = [dict(half=half, q16=q16 or qpos), dict(half=half, q16=q16)] + [dict(half=half or q16)] * len(seeds)
+    return "_q16io" if q16 or qpos else "_f16io", _lib.FLAG_Q16_POS_ONLY if qpos else 0, how
+
+
+def _grid_inputs(rif, sdf, rays, dev: torch.device, how=None):
+    """The inputs of a grid entry on `dev` -> (flat fp32 grid, flat fp32 SDF or None, the (n,3) ray tensors, n).  The
+    first ray tensor fixes n; `how`: per ray tensor, the format `_rays` converts it to (`_ray_format`; None: all fp32)."""
+    rif_ = _f32(rif, dev).reshape(-1)
+    sdf_ = None if sdf is None else _f32(sdf, dev).reshape(-1)
+    if sdf_ is not None and sdf_.numel() != rif_.numel():
+        raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
+    if how is None:
+        first = _rays(rays[0], dev)
+        return rif_, sdf_, [first] + [_rays(t, dev, first.shape[0]) for t in rays[1:]], first.shape[0]
+    first = _rays(rays[0], dev, **how[0])
+    return rif_, sdf_, [first] + [_rays(t, dev, first.shape[0], **kw) for t, kw in zip(rays[1:], how[1:])], first.shape[0]
+
+
+def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sdf=None, how=None, fwd_steps=None,
+               order=None, replay: bool = False, flags: int = 0, steps: bool = True, warn: bool = False,
+               counters: bool = False) -> tuple:
+    """One call of a grid entry point (they share their shape: grid, [sdf], nvox, res, n, the inputs, h, ds, the outputs,
+    the usual tail) -> (outputs, order, steps): the outputs, made by ``make_outputs(flat grid, ray tensors)``, and what
+    a forward march left behind -- its visit order and per-ray iteration counts, the workspace views that are also
+    published as `last_order` / `last_steps` (None, None for an adjoint).
+    The inputs are the (n,3) tensors `rays` (converted as `_grid_inputs` does) and, for the one entry that takes them,
+    `fwd_steps`: int32[n] behind the fourth ray tensor.  `adjoint`: a forward march, or an adjoint that may be paired
+    with one through `order`; `replay`: an adjoint that marches its forward again (`_paired_adjoint`).  `steps`: the
+    forward leaves iteration counts.  `warn`: failed rays are reported.  `counters`: the adjoint classifies its bundles
+    (`last_bundle_counters`)."""
+    dev = _dev(rif)
+    with torch.cuda.device(dev):
+        rif_, sdf_, rays_, n = _grid_inputs(rif, sdf, rays, dev, how)
+        if fwd_steps is not None:
+            steps_ = fwd_steps.detach().to(device=dev).contiguous()
+            if steps_.dtype != torch.int32 or steps_.numel() != n:
+                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (drrt.last_steps)")
+            rays_.insert(4, steps_)
+        out = make_outputs(rif_, rays_)
+        grids = [_p(rif_)] if sdf_ is None else [_p(rif_), _p(sdf_)]
+        march = _paired_adjoint(rif_, res, n, h, ds, dev, order, replay, flags) if adjoint else \
+            _forward_march(rif_, res, n, h, ds, dev, flags)
+        with march as (fl, ws, st, _):
+            _lib.check(getattr(_lib.load(), name)(
+                *grids, rif_.numel(), _res3(res), n, *map(_p, rays_), float(h), float(ds), *map(_p, out),
+                _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
+            if counters:
+                _capture_counters(ws)
+        left_order = left_steps = None
+        if not adjoint:
+            left_order = _capture_order(n, dev)
+            if steps:
+                left_steps = _last_view(_lib.load().drrt_last_steps, n, dev)
+                _publish(last_order=left_order, last_steps=left_steps)
+            else:
+                _publish(last_order=left_order)
+        if warn:
+            _warn_failed(st)
+    return out, left_order, left_steps
+
+
+def _like_rays(rif_, rays_) -> tuple:
+    """Outputs of the shape and dtype of the call's first two ray tensors: (xt, vt), or (dpos, dvel)."""
+    return torch.empty_like(rays_[0]), torch.empty_like(rays_[1])
+
+
+def _like_grid(rif_, rays_) -> tuple:
+    return (torch.empty_like(rif_),)
+
+
 class TracerC:
-    """GPU tracer without autodiff -- mirror of ``drrt.TracerC`` (``src/drrt.cpp:47-58``)."""
+    """GPU tracer without autodiff -- mirror of ``drrt.TracerC`` (``src/drrt.cpp:47-58``).  The forward grid marches
+    come twice: ``_trace*`` -> (outputs, order, steps) as `_grid_call` returns them, for callers that hand the order to a
+    paired adjoint (tracer.py, dist.py), and the public method, which returns the outputs."""
 
     # ---- forward ------------------------------------------------------------------------
+    def _trace(self, rif, res, pos, vel, h, ds):
+        _dev(rif)
+        suffix, flag, how = _ray_format(pos, vel)
+        return _grid_call("drrt_trace" + suffix, rif, res, [pos, vel], h, ds, _like_rays, adjoint=False, how=how,
+                          flags=flag, warn=True)
+
     def trace(self, rif, res, pos, vel, h, ds) -> Tuple[torch.Tensor, torch.Tensor]:
         """Tracer::trace, src/tracer.cpp:35-100.  float16 pos AND vel select the IEEE-half ray-state variant
         (drrt_trace_f16io: half in, fp32 march, half out); int16 pos AND vel (codes from ``encode_rays16``) select the
         16-bit ray state "q16" (drrt_trace_q16io), which keeps sub-voxel positions -- see include/drrt_hip.h."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            half, q16 = _is_half(pos, vel), _is_q16(pos, vel)
-            qpos = (not q16) and pos.dtype == torch.int16          # q16 positions with fp32 directions
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev, half=half, q16=q16 or qpos)
-            n = pos_.shape[0]
-            vel_ = _rays(vel, dev, n, half=half, q16=q16)
-            xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            q16 = q16 or qpos
-            fn = _lib.load().drrt_trace_q16io if q16 else (_lib.load().drrt_trace_f16io if half else _lib.load().drrt_trace_f32)
-            with _forward_march(rif_, res, n, h, ds, dev, flags=_lib.FLAG_Q16_POS_ONLY if qpos else 0) as (fl, ws, st):
-                _lib.check(fn(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), float(h), float(ds),
-                    _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-        return xt, vt
+        return self._trace(rif, res, pos, vel, h, ds)[0]
+
+    def _trace_pln(self, rif, res, pos, vel, pln_o, pln_d, h, ds):
+        return _grid_call("drrt_trace_pln_f32", rif, res, [pos, vel, pln_o, pln_d], h, ds,
+                          lambda rif_, r: _like_rays(rif_, r) + (torch.empty(r[0].shape[0], dtype=torch.uint8, device=r[0].device),),
+                          adjoint=False, warn=True)
 
     def trace_pln(self, rif, res, pos, vel, pln_o, pln_d, h, ds):
         """Tracer::trace_plane, src/tracer.cpp:102-172 -> (xt, vt, failmask uint8)."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, po, pd = _rays(vel, dev, n), _rays(pln_o, dev, n), _rays(pln_d, dev, n)
-            xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            fm = torch.empty(n, dtype=torch.uint8, device=dev)
-            with _forward_march(rif_, res, n, h, ds, dev) as (fl, ws, st):
-                _lib.check(_lib.load().drrt_trace_pln_f32(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd),
-                    float(h), float(ds), _p(xt), _p(vt), _p(fm), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-        return xt, vt, fm
+        return self._trace_pln(rif, res, pos, vel, pln_o, pln_d, h, ds)[0]
+
+    def _trace_target(self, rif, res, pos, vel, target, h, ds):
+        return _grid_call("drrt_trace_target_f32", rif, res, [pos, vel, target], h, ds,
+                          lambda rif_, r: _like_rays(rif_, r) + (r[0].new_empty(r[0].shape[0]),),
+                          adjoint=False, steps=False, warn=True)
 
     def trace_target(self, rif, res, pos, vel, target, h, ds):
         """Tracer::trace_target, src/tracer.cpp:174-242 -> (xt, vt, dist2)."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, tg = _rays(vel, dev, n), _rays(target, dev, n)
-            xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            d2 = torch.empty(n, dtype=torch.float32, device=dev)
-            with _forward_march(rif_, res, n, h, ds, dev, steps=False) as (fl, ws, st):
-                _lib.check(_lib.load().drrt_trace_target_f32(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(tg),
-                    float(h), float(ds), _p(xt), _p(vt), _p(d2), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-        return xt, vt, d2
+        return self._trace_target(rif, res, pos, vel, target, h, ds)[0]
+
+    def _trace_sdf(self, rif, sdf, res, pos, vel, h, ds):
+        return _grid_call("drrt_trace_sdf_f32", rif, res, [pos, vel], h, ds, _like_rays, adjoint=False, sdf=sdf,
+                          steps=False, warn=False)
 
     def trace_sdf(self, rif, sdf, res, pos, vel, h, ds):
         """Tracer::trace_sdf, src/tracer.cpp:244-310."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, sdf_ = _f32(rif, dev).reshape(-1), _f32(sdf, dev).reshape(-1)
-            if sdf_.numel() != rif_.numel():
-                raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
-            pos_ = _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_ = _rays(vel, dev, n)
-            xt, vt = torch.empty_like(pos_), torch.empty_like(vel_)
-            with _forward_march(rif_, res, n, h, ds, dev, steps=False, warn=False) as (fl, ws, st):
-                _lib.check(_lib.load().drrt_trace_sdf_f32(
-                    _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_),
-                    float(h), float(ds), _p(xt), _p(vt), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-        return xt, vt
+        return self._trace_sdf(rif, sdf, res, pos, vel, h, ds)[0]
 
     def trace_cable(self, rif, radius, length, pos, vel, target, ds):
         """Tracer::trace_cable, src/tracer.cpp:312-382 -> (xt, vt, dist2)."""
@@ -607,27 +656,12 @@ class TracerC:
     def backtrace(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tracer::backtrace, src/tracer.cpp:384-440 -> flat dL/dn (fp32[nvox]).
         `order` (optional, not in the reference): visit order of the paired forward call.
-        float16 xt, vt, dx, dv select the fp16 ray-state variant (fp32 recurrences and accumulation)."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            half = _is_half(xt, vt, dx, dv)
-            q16 = _is_q16(xt, vt)                      # q16 exit rays + IEEE-half seeds (drrt_backtrace_q16io)
-            qpos = (not q16) and xt.dtype == torch.int16           # q16 positions; directions and seeds fp32
-            if q16 and not _is_half(dx, dv):
-                raise RuntimeError("q16 exit rays (int16) go with float16 seeds dx, dv")
-            rif_, xt_ = _f32(rif, dev).reshape(-1), _rays(xt, dev, half=half, q16=q16 or qpos)
-            n = xt_.shape[0]
-            vt_ = _rays(vt, dev, n, half=half, q16=q16)
-            dx_, dv_ = _rays(dx, dev, n, half=half or q16), _rays(dv, dev, n, half=half or q16)
-            grad = torch.empty_like(rif_)
-            q16 = q16 or qpos
-            fn = _lib.load().drrt_backtrace_q16io if q16 else (_lib.load().drrt_backtrace_f16io if half else _lib.load().drrt_backtrace_f32)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order,
-                                 flags=_lib.FLAG_Q16_POS_ONLY if qpos else 0) as (_, fl, ws, st):
-                _lib.check(fn(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(xt_), _p(vt_), _p(dx_), _p(dv_),
-                    float(h), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-                _capture_counters(ws)
+        float16 xt, vt, dx, dv select the fp16 ray-state variant (fp32 recurrences and accumulation); q16 exit rays
+        go with IEEE-half seeds (drrt_backtrace_q16io), q16 positions alone with fp32 directions and seeds."""
+        _dev(rif)
+        suffix, flag, how = _ray_format(xt, vt, (dx, dv))
+        (grad,), _, _ = _grid_call("drrt_backtrace" + suffix, rif, res, [xt, vt, dx, dv], h, ds, _like_grid, adjoint=True,
+                                   how=how, order=order, flags=flag, counters=True)
         return grad
 
     def backtrace_rays(self, rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds,
@@ -637,23 +671,8 @@ class TracerC:
         (``keep_steps(last_steps)`` right after it); `dx`, `dv` the seeds on (xt, vt).  Rays that failed the forward get a
         zero gradient (and the "failed to exit all rays" message).  Not in the reference's C++ Tracer: its ADTracerC gets
         these through enoki autodiff (core/tracer.py:16-66).  fp32 rays only."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, xt_, vt_ = _rays(vel, dev, n), _rays(xt, dev, n), _rays(vt, dev, n)
-            dx_, dv_ = _rays(dx, dev, n), _rays(dv, dev, n)
-            steps_ = steps.detach().to(device=dev).contiguous()
-            if steps_.dtype != torch.int32 or steps_.numel() != n:
-                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (drrt.last_steps)")
-            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (_, fl, ws, st):
-                _lib.check(_lib.load().drrt_backtrace_rays_f32(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
-                    _p(dx_), _p(dv_), float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl,
-                    _stream(dev)))
-            _warn_failed(st)
-        return dpos, dvel
+        return _grid_call("drrt_backtrace_rays_f32", rif, res, [pos, vel, xt, vt, dx, dv], h, ds, _like_rays, adjoint=True,
+                          fwd_steps=steps, order=order, warn=True)[0]
 
     def backtrace_chunked(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None, chunks: int = 4,
                           on_chunk=None) -> torch.Tensor:
@@ -667,9 +686,7 @@ class TracerC:
         used by ``dist`` to reduce final slabs of dL/dn across ranks while the next chunk marches.  fp32 rays only."""
         dev = _dev(rif)
         with torch.cuda.device(dev):
-            rif_, xt_ = _f32(rif, dev).reshape(-1), _rays(xt, dev)
-            n = xt_.shape[0]
-            vt_, dx_, dv_ = _rays(vt, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
+            rif_, _, (xt_, vt_, dx_, dv_), n = _grid_inputs(rif, None, [xt, vt, dx, dv], dev)
             grad = torch.empty_like(rif_)
             lib = _lib.load()
             total = int(lib.drrt_backtrace_max_steps(_res3(res), float(h), float(ds)))
@@ -678,7 +695,7 @@ class TracerC:
             chunks = max(1, min(int(chunks), max(total, 1)))
             state = torch.empty(max(int(lib.drrt_backtrace_chunk_state_bytes(n)), 16), dtype=torch.uint8, device=dev)   # never a null pointer (n = 0)
             bounds = [total * k // chunks for k in range(chunks + 1)]
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (order, fl, ws, st):     # armed for the first chunk
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (fl, ws, st, order):     # armed for the first chunk
                 if n == 1 and order is None and fl & _lib.FLAG_SORT_RAYS:
                     # one ray is not sorted, so the first chunk leaves no order behind (drrt_last_order() is null, or names
                     # an earlier call's): every chunk gets the trivial one, which a resumed chunk of a sorted march asks for
@@ -708,20 +725,8 @@ class TracerC:
 
     def backtrace_sdf(self, rif, sdf, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tracer::backtrace_sdf, src/tracer.cpp:443-509."""
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, sdf_ = _f32(rif, dev).reshape(-1), _f32(sdf, dev).reshape(-1)
-            if sdf_.numel() != rif_.numel():
-                raise RuntimeError("Resolution doesn't match data")
-            xt_ = _rays(xt, dev)
-            n = xt_.shape[0]
-            vt_, dx_, dv_ = _rays(vt, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
-            grad = torch.empty_like(rif_)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order) as (_, fl, ws, st):
-                _lib.check(_lib.load().drrt_backtrace_sdf_f32(
-                    _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(xt_), _p(vt_), _p(dx_), _p(dv_),
-                    float(h), float(ds), _p(grad), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-                _capture_counters(ws)
+        (grad,), _, _ = _grid_call("drrt_backtrace_sdf_f32", rif, res, [xt, vt, dx, dv], h, ds, _like_grid,
+                                   adjoint=True, sdf=sdf, order=order, counters=True)
         return grad
 
     def backtrace_cable(self, rif, radius, length, xt, vt, dx, dv, ds) -> torch.Tensor:
@@ -738,31 +743,6 @@ class TracerC:
         return _cable_call("drrt_backtrace_cable_rays_f32", rif, radius, length, ds, (pos, vel, target, dx, dv),
                            lambda rif_, r: (torch.empty_like(r), torch.empty_like(r)))
 
-    def _backtrace_stop_rays(self, rif, sdf, res, pos, vel, pln, dx, dv, h, ds, order):
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            vel_, dx_, dv_ = _rays(vel, dev, n), _rays(dx, dev, n), _rays(dv, dev, n)
-            if sdf is not None:
-                sdf_ = _f32(sdf, dev).reshape(-1)
-                if sdf_.numel() != rif_.numel():
-                    raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
-            else:
-                po, pd = _rays(pln[0], dev, n), _rays(pln[1], dev, n)
-            dpos, dvel = torch.empty_like(pos_), torch.empty_like(vel_)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order, replay=True) as (_, fl, ws, st):
-                tail = (float(h), float(ds), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev))
-                if sdf is not None:
-                    _lib.check(_lib.load().drrt_backtrace_sdf_rays_f32(
-                        _p(rif_), _p(sdf_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(dx_), _p(dv_), *tail))
-                else:
-                    _lib.check(_lib.load().drrt_backtrace_pln_rays_f32(
-                        _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(po), _p(pd), _p(dx_), _p(dv_), *tail))
-            if sdf is None:
-                _warn_failed(st)
-        return dpos, dvel
-
     def backtrace_pln_rays(self, rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds,
                            order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Ray-state adjoint of ``trace_pln`` (drrt_backtrace_pln_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),
@@ -771,14 +751,17 @@ class TracerC:
         were refracted, so it takes neither (xt, vt) nor a step count.  Rays that failed the forward get a zero gradient
         (and the "failed to exit all rays" message).  Not in the reference's C++ Tracer: it gets these through enoki
         autodiff (core/tracer.py:122-178).  fp32 rays only."""
-        return self._backtrace_stop_rays(rif, None, res, pos, vel, (pln_o, pln_d), dx, dv, h, ds, order)
+        return _grid_call("drrt_backtrace_pln_rays_f32", rif, res, [pos, vel, pln_o, pln_d, dx, dv], h, ds, _like_rays,
+                          adjoint=True, order=order, replay=True, warn=True)[0]
 
     def backtrace_sdf_rays(self, rif, sdf, res, pos, vel, dx, dv, h, ds,
                            order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Ray-state adjoint of ``trace_sdf`` (drrt_backtrace_sdf_rays_f32) -> (dL/dpos, dL/dvel), (n,3) fp32; as
-        ``backtrace_pln_rays``.  A ray that never crosses the surface keeps its input as the record and gets (dx, dv).
+        ``backtrace_pln_rays``, without the message: like ``trace_sdf`` it reports failed rays through its stats block
+        only.  A ray that never crosses the surface keeps its input as the record and gets (dx, dv).
         The reference: enoki autodiff, core/tracer.py:181-234.  fp32 rays only."""
-        return self._backtrace_stop_rays(rif, sdf, res, pos, vel, None, dx, dv, h, ds, order)
+        return _grid_call("drrt_backtrace_sdf_rays_f32", rif, res, [pos, vel, dx, dv], h, ds, _like_rays,
+                          adjoint=True, sdf=sdf, order=order, replay=True, warn=False)[0]
 
     # ---- print-only smoke methods of the reference (src/tracer.cpp:16-33) ------------------
     def test(self) -> torch.Tensor:
@@ -802,28 +785,22 @@ class TracerS:
         self._dev = torch.device(device)
         self._c = TracerC()
 
-    def _up(self, *ts):
-        return [t.to(self._dev) if isinstance(t, torch.Tensor) else t for t in ts]
+    def _staged(self, method, out_dev, *args):
+        """``method(*args)`` of the TracerC with the tensors among `args` staged to the GPU and the results on `out_dev`."""
+        out = method(*(t.to(self._dev) if isinstance(t, torch.Tensor) else t for t in args))
+        return out.to(out_dev) if isinstance(out, torch.Tensor) else tuple(t.to(out_dev) for t in out)
 
     def trace(self, rif, res, pos, vel, h, ds):
-        out_dev = pos.device
-        r, p, v = self._up(rif, pos, vel)
-        return tuple(t.to(out_dev) for t in self._c.trace(r, res, p, v, h, ds))
+        return self._staged(self._c.trace, pos.device, rif, res, pos, vel, h, ds)
 
     def trace_sdf(self, rif, sdf, res, pos, vel, h, ds):
-        out_dev = pos.device
-        r, s, p, v = self._up(rif, sdf, pos, vel)
-        return tuple(t.to(out_dev) for t in self._c.trace_sdf(r, s, res, p, v, h, ds))
+        return self._staged(self._c.trace_sdf, pos.device, rif, sdf, res, pos, vel, h, ds)
 
     def trace_target(self, rif, res, pos, vel, target, h, ds):
-        out_dev = pos.device
-        r, p, v, tg = self._up(rif, pos, vel, target)
-        return tuple(t.to(out_dev) for t in self._c.trace_target(r, res, p, v, tg, h, ds))
+        return self._staged(self._c.trace_target, pos.device, rif, res, pos, vel, target, h, ds)
 
     def backtrace(self, rif, res, xt, vt, dx, dv, h, ds):
-        out_dev = rif.device
-        r, a, b, c, d = self._up(rif, xt, vt, dx, dv)
-        return self._c.backtrace(r, res, a, b, c, d, h, ds).to(out_dev)
+        return self._staged(self._c.backtrace, rif.device, rif, res, xt, vt, dx, dv, h, ds)
 
     test = TracerC.test
     testscale = TracerC.testscale

@@ -24,18 +24,12 @@ import torch
 from . import drrt
 
 
-def _mask_plane_seed(grad_x, outmask):
-    """The plane classes' incoming position seed, zeroed on the rays whose ``outmask`` gradient is set (as written,
-    core/tracer.py:366-367)."""
-    if outmask is not None and outmask.dtype == torch.bool:
-        grad_x = grad_x.clone()
-        grad_x[outmask] = 0
-    return grad_x
-
-
-# Plumbing of the AD*TracerC classes, whose ray inputs x, v sit at positions (ix, iv) of apply().
-def _ray_grad_wanted(ctx, ix, iv, name, x, v):
-    """Whether x or v requires grad; the ray-state adjoints take fp32 rays only."""
+# ---- what the classes of a march family share --------------------------------------------------------------------------
+# A family is one forward march (trace, trace_pln, trace_target, trace_sdf, trace_cable) with its Back* class, its AD* class
+# (ray gradients too) and, for trace, dist.ShardedBackTracerC.  Its forward and its dL/drif are written once, below; a class
+# adds what is its own: the signature of apply(), the mask of the plane march, the ray-state adjoint of an AD* class.
+def _ray_grad_wanted(ctx, name, ix, iv, x, v):
+    """Whether x or v (at positions ix, iv of apply()) requires grad; the ray-state adjoints take fp32 rays only."""
     wanted = ctx.needs_input_grad[ix] or ctx.needs_input_grad[iv]
     if wanted and (x.dtype != torch.float32 or v.dtype != torch.float32):
         raise RuntimeError(f"{name}: gradients w.r.t. x, v need float32 rays")
@@ -48,10 +42,77 @@ def _keep_rays(ctx, x, v, device, *extra):
     ctx.rays = tuple(t.detach().to(device=device, dtype=torch.float32).clone() for t in (x, v) + extra)
 
 
-def _return_ray_grads(ctx, ix, iv, dpos, dvel):
-    """(dL/dx, dL/dv) on the callers' devices, None where not asked for."""
-    return (dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[ix] else None,
-            dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[iv] else None)
+def _grid_forward(ctx, march, rif, sdf, x, v, extra, h, ds, ad=None):
+    """Forward of a grid family: ``march(flat rif, [flat sdf], rif.shape, x, v, *extra, h, ds) -> (outputs, order, steps)``
+    (a ``TracerC._trace*``) on detached inputs -> (outputs, steps).  ``ctx`` gets the shape and the scalars, a private copy
+    of the march's own visit order (the adjoint visits rays in the forward's bundle order; other tracer calls may come
+    before backward) and, saved, ``rif``, the SDF and the exit rays.  `ad` = (class name, positions of x and v in apply())
+    for an AD* class: private copies of (x, v, *extra) are kept when x or v requires grad, and only then."""
+    ctx.shape, ctx.h, ctx.ds = rif.shape, h, ds
+    ray_grad = ad is not None and _ray_grad_wanted(ctx, *ad, x, v)
+    grids = (rif,) if sdf is None else (rif, sdf)
+    out, order, steps = march(*[g.detach().flatten() for g in grids], ctx.shape, x.detach(), v.detach(),
+                              *[t.detach() for t in extra], h, ds)
+    ctx.order = drrt.keep_order(order)
+    if ray_grad:
+        _keep_rays(ctx, x, v, out[0].device, *extra)
+    ctx.save_for_backward(*grids, out[0], out[1])
+    return out, steps
+
+
+def _grid_rif_grad(ctx, grad_x, grad_v):
+    """dL/drif of a grid family from the recorded state: ``backtrace_sdf`` for the SDF march, the generic ``backtrace``
+    for every other (core/tracer.py:376,422), in the forward's visit order."""
+    rif, *sdf, outx, outv = ctx.saved_tensors
+    adjoint = drrt.TracerC().backtrace_sdf if sdf else drrt.TracerC().backtrace
+    return adjoint(rif.detach().flatten(), *[s.detach().flatten() for s in sdf], ctx.shape, outx, outv, grad_x, grad_v,
+                   ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
+
+
+def _cable_forward(ctx, rif, radius, length, x, v, sp, ds, ad=None):
+    """Forward of the fibre family, as `_grid_forward` (the fibre march has no visit order)."""
+    ctx.radius, ctx.length, ctx.ds = radius, length, ds
+    ray_grad = ad is not None and _ray_grad_wanted(ctx, *ad, x, v)
+    out = drrt.TracerC().trace_cable(rif.detach().flatten(), radius, length, x.detach(), v.detach(), sp.detach(), ds)
+    if ray_grad:
+        _keep_rays(ctx, x, v, out[0].device, sp)
+    ctx.save_for_backward(rif, out[0], out[1])
+    return out
+
+
+def _cable_rif_grad(ctx, grad_x, grad_v):
+    rif, outx, outv = ctx.saved_tensors
+    return drrt.TracerC().backtrace_cable(rif.detach().flatten(), ctx.radius, ctx.length, outx, outv,
+                                          grad_x, grad_v, ctx.ds).reshape(rif.shape)
+
+
+def _plane_mask(ctx, out):
+    """(xt, vt, failmask uint8) -> (xt, vt, failmask bool, not differentiable)."""
+    outmask = out[2].to(torch.bool)
+    ctx.mark_non_differentiable(outmask)
+    return out[0], out[1], outmask
+
+
+def _mask_plane_seed(grad_x, outmask):
+    """The plane classes' incoming position seed, zeroed on the rays whose ``outmask`` gradient is set (as written,
+    core/tracer.py:366-367)."""
+    if outmask is not None and outmask.dtype == torch.bool:
+        grad_x = grad_x.clone()
+        grad_x[outmask] = 0
+    return grad_x
+
+
+def _ad_grads(ctx, ix, iv, rif_grad, ray_adjoint, grad_x, grad_v):
+    """(dL/drif, dL/dx, dL/dv) of an AD* class: each adjoint runs only for the inputs that ask for a gradient, so with
+    neither ray input requiring grad the launches are the Back* class's.  ``ray_adjoint() -> (dpos, dvel)``; the ray
+    gradients go back to the callers' devices, None where not asked for."""
+    drif = rif_grad(ctx, grad_x, grad_v) if ctx.needs_input_grad[0] else None
+    dx0 = dv0 = None
+    if ctx.needs_input_grad[ix] or ctx.needs_input_grad[iv]:
+        dpos, dvel = ray_adjoint()
+        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[ix] else None
+        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[iv] else None
+    return drif, dx0, dv0
 
 
 class BackTracerC(torch.autograd.Function):
@@ -59,20 +120,11 @@ class BackTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        outx, outv = drrt.TracerC().trace(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)     # the adjoint visits rays in the forward's bundle order (a private
-        #                                                  copy: other tracer calls may come before backward)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv
+        return _grid_forward(ctx, drrt.TracerC()._trace, rif, None, x, v, (), h, ds)[0]
 
     @staticmethod
     def backward(ctx, grad_x, grad_v):
-        rif, outx, outv = ctx.saved_tensors
-        drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
-                                        ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        return drif, None, None, None, None
+        return _grid_rif_grad(ctx, grad_x, grad_v), None, None, None, None
 
 
 class BackPlaneTracerC(torch.autograd.Function):
@@ -80,23 +132,11 @@ class BackPlaneTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, sp, sn, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        outx, outv, outmask = drrt.TracerC().trace_pln(
-            rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), sp.detach(), sn.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        outmask = outmask.to(torch.bool)
-        ctx.mark_non_differentiable(outmask)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv, outmask
+        return _plane_mask(ctx, _grid_forward(ctx, drrt.TracerC()._trace_pln, rif, None, x, v, (sp, sn), h, ds)[0])
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, outmask):
-        rif, outx, outv = ctx.saved_tensors
-        grad_x = _mask_plane_seed(grad_x, outmask)
-        drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
-                                        ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        return drif, None, None, None, None, None, None
+        return _grid_rif_grad(ctx, _mask_plane_seed(grad_x, outmask), grad_v), None, None, None, None, None, None
 
 
 class BackTargetTracerC(torch.autograd.Function):
@@ -104,20 +144,11 @@ class BackTargetTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, sp, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        outx, outv, dist2 = drrt.TracerC().trace_target(
-            rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), sp.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv, dist2
+        return _grid_forward(ctx, drrt.TracerC()._trace_target, rif, None, x, v, (sp,), h, ds)[0]
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, outdist):
-        rif, outx, outv = ctx.saved_tensors
-        drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
-                                        ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        return drif, None, None, None, None, None
+        return _grid_rif_grad(ctx, grad_x, grad_v), None, None, None, None, None
 
 
 class BackSDFTracerC(torch.autograd.Function):
@@ -125,20 +156,11 @@ class BackSDFTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, sdf, x, v, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        outx, outv = drrt.TracerC().trace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, x.detach(),
-                                              v.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        ctx.save_for_backward(rif, sdf, outx, outv)
-        return outx, outv
+        return _grid_forward(ctx, drrt.TracerC()._trace_sdf, rif, sdf, x, v, (), h, ds)[0]
 
     @staticmethod
     def backward(ctx, grad_x, grad_v):
-        rif, sdf, outx, outv = ctx.saved_tensors
-        drif = drrt.TracerC().backtrace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, outx, outv,
-                                            grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        return drif, None, None, None, None, None
+        return _grid_rif_grad(ctx, grad_x, grad_v), None, None, None, None, None
 
 
 class BackCableTracerC(torch.autograd.Function):
@@ -146,96 +168,63 @@ class BackCableTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, radius, length, x, v, sp, ds):
-        ctx.radius, ctx.length, ctx.ds = radius, length, ds
-        outx, outv, dist2 = drrt.TracerC().trace_cable(
-            rif.detach().flatten(), radius, length, x.detach(), v.detach(), sp.detach(), ds)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv, dist2
+        return _cable_forward(ctx, rif, radius, length, x, v, sp, ds)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, outdist):
-        rif, outx, outv = ctx.saved_tensors
-        drif = drrt.TracerC().backtrace_cable(rif.detach().flatten(), ctx.radius, ctx.length, outx, outv,
-                                              grad_x, grad_v, ctx.ds).reshape(rif.shape)
-        return drif, None, None, None, None, None, None
+        return _cable_rif_grad(ctx, grad_x, grad_v), None, None, None, None, None, None
 
 
 class ADTracerC(torch.autograd.Function):
     """core/tracer.py:16-66 -- ``apply(rif, x, v, h, ds) -> (xt, vt)`` with gradients for ``rif`` AND the rays.
 
-    The reference differentiates its enoki march (``enoki.gradient(ctx.x)``, ``ctx.v``); here the forward is the call
-    BackTracerC makes, dL/drif is the same ``backtrace`` and dL/dx, dL/dv come from the ray-state adjoint
-    ``TracerC.backtrace_rays`` (drrt_backtrace_rays_f32), which needs the forward's inputs and per-ray iteration counts:
-    those are kept (private copies) only when ``x`` or ``v`` requires grad.  Each adjoint runs only for the inputs that
-    ask for a gradient, so with neither ray input requiring grad this launches exactly what BackTracerC launches.
-    Rays that failed the forward (ran out of steps) get a zero ray gradient.  fp32 rays only when ray gradients are
-    asked for."""
+    The reference differentiates its enoki march (``enoki.gradient(ctx.x)``, ``ctx.v``); here the forward and dL/drif are
+    BackTracerC's and dL/dx, dL/dv come from the ray-state adjoint ``TracerC.backtrace_rays`` (drrt_backtrace_rays_f32),
+    which needs the forward's inputs and per-ray iteration counts: those are kept (private copies) only when ``x`` or
+    ``v`` requires grad.  Rays that failed the forward (ran out of steps) get a zero ray gradient.  fp32 rays only when
+    ray gradients are asked for."""
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        ray_grad = _ray_grad_wanted(ctx, 1, 2, "ADTracerC", x, v)
-        outx, outv = drrt.TracerC().trace(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        if ray_grad:
-            steps = drrt.keep_steps(drrt.last_steps)
+        out, steps = _grid_forward(ctx, drrt.TracerC()._trace, rif, None, x, v, (), h, ds, ad=("ADTracerC", 1, 2))
+        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+            steps = drrt.keep_steps(steps)
             if steps is None:
                 raise RuntimeError("ADTracerC: the forward march left no iteration counts")
-            _keep_rays(ctx, x, v, outx.device)
             ctx.rays += (steps,)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv
+        return out
 
     @staticmethod
     def backward(ctx, grad_x, grad_v):
         rif, outx, outv = ctx.saved_tensors
-        drif = dx0 = dv0 = None
-        if ctx.needs_input_grad[0]:
-            drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
-                                            ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
+
+        def ray_adjoint():
             x0, v0, steps = ctx.rays
-            dx0, dv0 = _return_ray_grads(ctx, 1, 2, *drrt.TracerC().backtrace_rays(
-                rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps, grad_x, grad_v, ctx.h, ctx.ds,
-                order=ctx.order))
-        return drif, dx0, dv0, None, None
+            return drrt.TracerC().backtrace_rays(rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps,
+                                                 grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order)
+        return (*_ad_grads(ctx, 1, 2, _grid_rif_grad, ray_adjoint, grad_x, grad_v), None, None)
 
 
 class ADCableTracerC(torch.autograd.Function):
     """core/tracer.py:237-291 -- ``apply(rif (Rr,), radius, length, x, v, sp, ds) -> (xt, vt, dist2)`` with gradients for
     ``rif`` AND the rays that enter the fibre march.
 
-    The reference differentiates its enoki march; here the forward is the call BackCableTracerC makes, dL/drif is the same
-    ``backtrace_cable`` and dL/dx, dL/dv come from the ray-state adjoint ``TracerC.backtrace_cable_rays``
-    (drrt_backtrace_cable_rays_f32).  That call replays the forward from its inputs, so the inputs (x, v, sp) are kept
-    (private copies) only when ``x`` or ``v`` requires grad.  Each adjoint runs only for the inputs that ask for a
-    gradient, so with neither ray input requiring grad this launches exactly what BackCableTracerC launches.  The
-    iteration of the closest-approach record is held fixed, and the gradient arriving on ``dist2`` is ignored, as in the
-    reference (``:268-272``) and in BackCableTracerC; no gradient flows to ``sp``.  A ray that ran out of steps still has
-    a record and a gradient.  fp32 rays only when ray gradients are asked for."""
+    The forward and dL/drif are BackCableTracerC's and dL/dx, dL/dv come from the ray-state adjoint
+    ``TracerC.backtrace_cable_rays`` (drrt_backtrace_cable_rays_f32).  That call replays the forward from its inputs, so
+    the inputs (x, v, sp) are kept (private copies) only when ``x`` or ``v`` requires grad.  The iteration of the
+    closest-approach record is held fixed, and the gradient arriving on ``dist2`` is ignored, as in the reference
+    (``:268-272``) and in BackCableTracerC; no gradient flows to ``sp``.  A ray that ran out of steps still has a record
+    and a gradient.  fp32 rays only when ray gradients are asked for."""
 
     @staticmethod
     def forward(ctx, rif, radius, length, x, v, sp, ds):
-        ctx.radius, ctx.length, ctx.ds = radius, length, ds
-        ray_grad = _ray_grad_wanted(ctx, 3, 4, "ADCableTracerC", x, v)
-        outx, outv, dist2 = drrt.TracerC().trace_cable(
-            rif.detach().flatten(), radius, length, x.detach(), v.detach(), sp.detach(), ds)
-        if ray_grad:
-            _keep_rays(ctx, x, v, outx.device, sp)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv, dist2
+        return _cable_forward(ctx, rif, radius, length, x, v, sp, ds, ad=("ADCableTracerC", 3, 4))
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, outdist):
-        rif, outx, outv = ctx.saved_tensors
-        drif = dx0 = dv0 = None
-        if ctx.needs_input_grad[0]:
-            drif = drrt.TracerC().backtrace_cable(rif.detach().flatten(), ctx.radius, ctx.length, outx, outv,
-                                                  grad_x, grad_v, ctx.ds).reshape(rif.shape)
-        if ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            dx0, dv0 = _return_ray_grads(ctx, 3, 4, *drrt.TracerC().backtrace_cable_rays(
-                rif.detach().flatten(), ctx.radius, ctx.length, *ctx.rays, grad_x, grad_v, ctx.ds))
+        rif = ctx.saved_tensors[0]
+        drif, dx0, dv0 = _ad_grads(ctx, 3, 4, _cable_rif_grad, lambda: drrt.TracerC().backtrace_cable_rays(
+            rif.detach().flatten(), ctx.radius, ctx.length, *ctx.rays, grad_x, grad_v, ctx.ds), grad_x, grad_v)
         return drif, None, None, dx0, dv0, None, None
 
 
@@ -244,77 +233,46 @@ class ADRayPlaneTracerC(torch.autograd.Function):
     reference's ADPlaneTracerC (core/tracer.py:122-178, broken upstream) is meant to be.  The name is new because
     ``ADPlaneTracerC`` stays the alias of BackPlaneTracerC it has always been here.
 
-    The forward is the call BackPlaneTracerC makes, dL/drif is the same generic ``backtrace`` from the recorded state and
-    dL/dx, dL/dv come from the ray-state adjoint ``TracerC.backtrace_pln_rays`` (drrt_backtrace_pln_rays_f32), which replays
-    the forward from its inputs: (x, v, sp, sn) are kept (private copies) only when ``x`` or ``v`` requires grad.  Each
-    adjoint runs only for the inputs that ask for a gradient, so with neither ray input requiring grad this launches
-    exactly what BackPlaneTracerC launches.  The incoming seeds are treated as BackPlaneTracerC.backward treats them and
-    the same seeds go to both adjoints.  Rays that failed the forward get a zero ray gradient; no gradient flows to the
-    plane or to ``failmask``.  fp32 rays only when ray gradients are asked for."""
+    The forward and dL/drif are BackPlaneTracerC's and dL/dx, dL/dv come from the ray-state adjoint
+    ``TracerC.backtrace_pln_rays`` (drrt_backtrace_pln_rays_f32), which replays the forward from its inputs: (x, v, sp, sn)
+    are kept (private copies) only when ``x`` or ``v`` requires grad.  The incoming seeds are treated as
+    BackPlaneTracerC.backward treats them and the same seeds go to both adjoints.  Rays that failed the forward get a zero
+    ray gradient; no gradient flows to the plane or to ``failmask``.  fp32 rays only when ray gradients are asked for."""
 
     @staticmethod
     def forward(ctx, rif, x, v, sp, sn, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        ray_grad = _ray_grad_wanted(ctx, 1, 2, "ADRayPlaneTracerC", x, v)
-        outx, outv, outmask = drrt.TracerC().trace_pln(
-            rif.detach().flatten(), ctx.shape, x.detach(), v.detach(), sp.detach(), sn.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        if ray_grad:
-            _keep_rays(ctx, x, v, outx.device, sp, sn)
-        outmask = outmask.to(torch.bool)
-        ctx.mark_non_differentiable(outmask)
-        ctx.save_for_backward(rif, outx, outv)
-        return outx, outv, outmask
+        return _plane_mask(ctx, _grid_forward(ctx, drrt.TracerC()._trace_pln, rif, None, x, v, (sp, sn), h, ds,
+                                              ad=("ADRayPlaneTracerC", 1, 2))[0])
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, outmask):
-        rif, outx, outv = ctx.saved_tensors
-        grad_x = _mask_plane_seed(grad_x, outmask)                  # as BackPlaneTracerC.backward
-        drif = dx0 = dv0 = None
-        if ctx.needs_input_grad[0]:
-            drif = drrt.TracerC().backtrace(rif.detach().flatten(), ctx.shape, outx, outv, grad_x, grad_v,
-                                            ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        if ctx.needs_input_grad[1] or ctx.needs_input_grad[2]:
-            dx0, dv0 = _return_ray_grads(ctx, 1, 2, *drrt.TracerC().backtrace_pln_rays(
-                rif.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order))
-        return drif, dx0, dv0, None, None, None, None
+        rif = ctx.saved_tensors[0]
+        grad_x = _mask_plane_seed(grad_x, outmask)
+        return (*_ad_grads(ctx, 1, 2, _grid_rif_grad, lambda: drrt.TracerC().backtrace_pln_rays(
+            rif.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order),
+            grad_x, grad_v), None, None, None, None)
 
 
 class ADRaySDFTracerC(torch.autograd.Function):
     """``apply(rif, sdf, x, v, h, ds) -> (xt, vt)`` with gradients for ``rif`` AND the rays (the reference's ADSDFTracerC,
     core/tracer.py:181-234; ``ADSDFTracerC`` stays the alias of BackSDFTracerC here).
 
-    The forward is the call BackSDFTracerC makes, dL/drif is the same ``backtrace_sdf`` and dL/dx, dL/dv come from
-    ``TracerC.backtrace_sdf_rays`` (drrt_backtrace_sdf_rays_f32), which replays the forward from (x, v): private copies
-    of those are kept only when ``x`` or ``v`` requires grad (the SDF is saved anyway).  Each adjoint runs only for the
-    inputs that ask for a gradient.  A ray that never crosses the surface has its input as its record and the identity as
-    its ray gradient; no gradient flows to the SDF.  fp32 rays only when ray gradients are asked for."""
+    The forward and dL/drif are BackSDFTracerC's and dL/dx, dL/dv come from ``TracerC.backtrace_sdf_rays``
+    (drrt_backtrace_sdf_rays_f32), which replays the forward from (x, v): private copies of those are kept only when
+    ``x`` or ``v`` requires grad (the SDF is saved anyway).  A ray that never crosses the surface has its input as its
+    record and the identity as its ray gradient; no gradient flows to the SDF.  fp32 rays only when ray gradients are
+    asked for."""
 
     @staticmethod
     def forward(ctx, rif, sdf, x, v, h, ds):
-        ctx.shape = rif.shape
-        ctx.h, ctx.ds = h, ds
-        ray_grad = _ray_grad_wanted(ctx, 2, 3, "ADRaySDFTracerC", x, v)
-        outx, outv = drrt.TracerC().trace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, x.detach(),
-                                              v.detach(), h, ds)
-        ctx.order = drrt.keep_order(drrt.last_order)
-        if ray_grad:
-            _keep_rays(ctx, x, v, outx.device)
-        ctx.save_for_backward(rif, sdf, outx, outv)
-        return outx, outv
+        return _grid_forward(ctx, drrt.TracerC()._trace_sdf, rif, sdf, x, v, (), h, ds, ad=("ADRaySDFTracerC", 2, 3))[0]
 
     @staticmethod
     def backward(ctx, grad_x, grad_v):
-        rif, sdf, outx, outv = ctx.saved_tensors
-        drif = dx0 = dv0 = None
-        if ctx.needs_input_grad[0]:
-            drif = drrt.TracerC().backtrace_sdf(rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, outx, outv,
-                                                grad_x, grad_v, ctx.h, ctx.ds, order=ctx.order).reshape(*ctx.shape)
-        if ctx.needs_input_grad[2] or ctx.needs_input_grad[3]:
-            dx0, dv0 = _return_ray_grads(ctx, 2, 3, *drrt.TracerC().backtrace_sdf_rays(
-                rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds,
-                order=ctx.order))
+        rif, sdf = ctx.saved_tensors[:2]
+        drif, dx0, dv0 = _ad_grads(ctx, 2, 3, _grid_rif_grad, lambda: drrt.TracerC().backtrace_sdf_rays(
+            rif.detach().flatten(), sdf.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds,
+            order=ctx.order), grad_x, grad_v)
         return drif, None, dx0, dv0, None, None
 
 
