@@ -91,6 +91,7 @@ SIGNATURES = {
     "drrt_backtrace_cable_rays_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp] + _tail),
     "drrt_backtrace_pln_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_backtrace_sdf_rays_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
+    "drrt_backtrace_target_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     **_sensor_signatures(),
     "drrt_rays_to_plane_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "drrt_rays_to_plane_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
@@ -114,7 +115,7 @@ SIGNATURES = {
 }
 
 PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "backtrace_rays",
-              7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays"}
+              7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays", 10: "backtrace_target_rays"}
 
 _lib: Optional[C.CDLL] = None
 

@@ -1,7 +1,7 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
 // utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
@@ -679,6 +679,33 @@ extern "C" int drrt_backtrace_sdf_rays_f32(const float* rif, const float* sdf, l
                                            size_t ws_bytes, unsigned flags, void* stream) {
   return run_backtrace_stop_rays<2>(rif, sdf, nvox, res, n, pos, vel, nullptr, nullptr, dx, dv, h, ds, dpos, dvel, stats,
                                     ws, ws_bytes, flags, stream);
+}
+
+// ray-state adjoint of trace_target: drrt_target_rays.hip.  Keeps nothing per ray between its two launches, so the per-ray
+// slot of the workspace stays untouched and an order hint is used wherever it lives.
+extern "C" int drrt_backtrace_target_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                              const float* pos, const float* vel, const float* target,
+                                              const float* dx, const float* dv, const float* ddist2, float h, float ds,
+                                              float* dpos, float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes,
+                                              unsigned flags, void* stream) {
+  TargetRayGradArgs a{};
+  GridCall c(a.vol, stream);
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
+  if (n == 0) return zero_stats(stats, s);
+  if (!pos || !vel || !target || !dx || !dv) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
+  rc = check_ray_count(n); if (rc) return rc;
+  const WsLayout L = ws_layout(n, nvox, flags, ws_bytes);
+  if (!ws || ws_bytes < L.ray_bytes) return fail(DRRT_ERR_ARG, "workspace too small for backtrace_target_rays (see drrt_workspace_bytes)");
+  if (!stats) { rc = private_stats(&stats); if (rc) return rc; }
+  rc = zero_stats(stats, s); if (rc) return rc;
+  rc = c.place(nvox, n, pos, vel, 1.f, flags, L, ws, ws_bytes); if (rc) return rc;
+  a.pos = pos; a.vel = vel; a.target = target; a.dx = dx; a.dv = dv; a.dd2 = ddist2;
+  a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
+  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(DRRT_PROF_BACKTRACE_TARGET_RAYS, s, "k_backtrace_target_rays", [&] { launch_backtrace_target_rays(a, s); });
 }
 
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }

@@ -1061,6 +1061,138 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
   return g;
 }
 
+// Ray-state adjoint of trace_target for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the closest-approach record
+// (xt, vt) = (x_j, v_j) and the seed dd2 on dist2 = |x_j - t|^2, given only the forward's inputs (p0, v0), its target t and
+// `total`, the call's global loop count (the maximum of the phase-A iteration counts over the call's rays).  j = the iteration
+// count at the LAST record update (strict <, :217; 0: the record is the input); j and the forward's `inside` masks are held
+// fixed (as autograd through a masked select does).
+//   * The forward is replayed from (p0, v0) with its own operations, looped as it loops them: phase A is fwd_init /
+//     fwd_step_c<3> (what target_ray_a's fwd_step_r<3> runs on the taps it fetches) until the ray is flagged escaped, at
+//     most max_steps: `done` iterations; phase B is the straight flight of target_ray_b over the iterations done .. total-1.
+//     Phase A ends at the first cross, so its masks are F^e T^(done-e): e = the index of the first in-box sample (done
+//     when there is none), x_e the position sampled there.
+//   * The effective position seed is gx = dx + 2 dd2 (x_j - t), one fmaf per component.  j = 0: the result is (gx, dv).
+//   * Otherwise the iterations j-1 .. 0 are undone run by run, seeded like adj_init (lambda = gx, mu = dv + ds gx, q = dv:
+//     q is dL/dv_k, mu runs one iteration ahead of it as adj_recur leaves it):
+//       free flight   (the iterations after the escape, done .. j-1, and the prefix 0 .. e-1): m iterations leave lambda
+//                     unchanged and add m ds lambda to mu and q;
+//       sampled run   (e .. min(j, done)-1): reverse iterations of adj_sample<0> / adj_recur with neither the backward-escape
+//                     test nor the adjoint's step bound, started from the record itself, or, for a record written after the
+//                     escape (j > done), from phase A's end state; the last of them samples at the replayed x_e itself
+//                     instead of its reconstruction x_{e+1} - ds v_{e+1} (a start exactly on a face; the sibling routines
+//                     do the same).
+//   * A ray that ran out of steps keeps its record and its gradient (as in the cable routine); `failed` only reports it.
+//   * steps = the forward iterations replayed (done, plus total - done of phase B) + the reverse iterations of the sampled
+//     run; fwd = done.
+// The 1/h of DRRT_FLAG_CORRECTED_H does not enter; dL/dt = -2 dd2 (x_j - t) is a point-wise expression of the forward's
+// outputs and is left to the caller.  `taps(c)` returns the 8 taps of cell c.  `rec` (optional) receives the replayed record.
+struct TargetRecord { float xt[3], vt[3], dist2; unsigned j; };
+struct TargetGrad { float dp[3], dv[3]; unsigned steps, fwd; bool failed; };
+struct TargetReplay {
+  FwdState f;              // phase A's end state: (x, v) is what phase B continues from, (xt, vt, aux3) the record so far
+  unsigned done, j, e;
+  float ex, ey, ez;        // x_e
+};
+
+// phase A of the forward, replayed: also the whole of the first pass, which needs `done` only
+template <typename TapFn>
+DRRT_HD void target_replay_a(const Vol& V, float ds, int max_steps, const float p0[3], const float v0[3], const float tg[3],
+                             TapFn&& taps, TargetReplay& r) {
+  FwdState& f = r.f;
+  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
+  f.aux0 = tg[0]; f.aux1 = tg[1]; f.aux2 = tg[2]; f.aux4 = f.aux5 = 0.f;
+  const float ex = f.x - tg[0], ey = f.y - tg[1], ez = f.z - tg[2];
+  f.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // src/tracer.cpp:200
+  fwd_init(V, f);
+  Cell c = locate(V, f.x, f.y, f.z);
+  unsigned steps = 0, j = 0, e = 0;
+  bool entered = false;
+  r.ex = f.x; r.ey = f.y; r.ez = f.z;
+  for (int it = 0; it < max_steps; ++it) {
+    const bool was = f.inside;
+    if (was & !entered) { entered = true; e = steps; r.ex = f.x; r.ey = f.y; r.ez = f.z; }
+    Taps t = taps_zero();
+    if (was) t = taps(c);
+    const float best = f.aux3;
+    fwd_step_c<3>(V, nullptr, ds, f, c, t);
+    ++steps;
+    if (f.aux3 < best) j = steps;                                         // the record was updated (strict <, :217)
+    if (f.esc) break;
+  }
+  r.done = steps; r.j = j; r.e = entered ? e : steps;
+}
+
+template <typename TapFn>
+DRRT_HD TargetGrad target_backtrace_ray_state(const Vol& V, float ds, int max_steps, unsigned total, const float p0[3],
+                                              const float v0[3], const float tg[3], const float dx[3], const float dv[3],
+                                              float dd2, TapFn&& taps, TargetRecord* rec = nullptr) {
+  TargetReplay r;
+  target_replay_a(V, ds, max_steps, p0, v0, tg, taps, r);
+  const FwdState& f = r.f;
+  const unsigned done = r.done, e = r.e;
+  unsigned j = r.j;
+  float xj[3] = {f.xtx, f.xty, f.xtz}, vj[3] = {f.vtx, f.vty, f.vtz};
+  float best = f.aux3;
+  TargetGrad g;
+  g.failed = !f.esc; g.fwd = done; g.steps = done;
+  if (done < total) {                                                     // phase B, as target_ray_b
+    float x = f.x, y = f.y, z = f.z;
+    bool upd = false;
+    for (unsigned k = done; k < total; ++k) {
+      x = fmaf(ds, f.vx, x); y = fmaf(ds, f.vy, y); z = fmaf(ds, f.vz, z);
+      const float bx = x - tg[0], by = y - tg[1], bz = z - tg[2];
+      const float cur = dot3(bx, by, bz, bx, by, bz);
+      if (cur < best) { best = cur; xj[0] = x; xj[1] = y; xj[2] = z; j = k + 1u; upd = true; }
+    }
+    if (upd) { vj[0] = f.vx; vj[1] = f.vy; vj[2] = f.vz; }
+    g.steps += total - done;
+  }
+  if (rec) {
+    for (int k = 0; k < 3; ++k) { rec->xt[k] = xj[k]; rec->vt[k] = vj[k]; }
+    rec->dist2 = best; rec->j = j;
+  }
+  const float w = dd2 + dd2;
+  const float gx[3] = {fmaf(w, xj[0] - tg[0], dx[0]), fmaf(w, xj[1] - tg[1], dx[1]), fmaf(w, xj[2] - tg[2], dx[2])};
+  g.dp[0] = gx[0]; g.dp[1] = gx[1]; g.dp[2] = gx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+  if (j == 0) return g;
+  AdjState s;
+  s.lx = gx[0]; s.ly = gx[1]; s.lz = gx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, gx[0], dv[0]); s.my = fmaf(ds, gx[1], dv[1]); s.mz = fmaf(ds, gx[2], dv[2]);   // :410
+  s.active = true; s.outside = false;
+  float qx = dv[0], qy = dv[1], qz = dv[2];
+  unsigned hi = j;
+  if (j > done) {                                    // the record was written after the escape: free flight back to phase A's end
+    const float ads = (float)(j - done) * ds;
+    qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
+    s.mx = fmaf(ads, s.lx, s.mx); s.my = fmaf(ads, s.ly, s.my); s.mz = fmaf(ads, s.lz, s.mz);
+    s.x = f.x; s.y = f.y; s.z = f.z; s.vx = f.vx; s.vy = f.vy; s.vz = f.vz;
+    hi = done;
+  } else {
+    s.x = xj[0]; s.y = xj[1]; s.z = xj[2]; s.vx = vj[0]; s.vy = vj[1]; s.vz = vj[2];
+  }
+  if (hi > e) {                                      // the sampled run e .. hi-1
+    for (unsigned k = hi; k > e; --k) {
+      s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+      if (k == e + 1u) { s.x = r.ex; s.y = r.ey; s.z = r.ez; }             // the first in-box sample, as the forward took it
+      const Cell ca = locate(V, s.x, s.y, s.z);
+      AdjSample m;
+      (void)adj_sample<0>(V, nullptr, ds, s, ca, taps(ca), m);              // v_{k-1}; the escape test is not used
+      const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);           // :430
+      qx = s.mx; qy = s.my; qz = s.mz;
+      adj_recur(V, ds, s, m, dn);
+    }
+    g.steps += hi - e;
+    hi = e;
+  }
+  if (hi > 0) {                                      // the free-flight prefix from p0
+    const float ads = (float)hi * ds;
+    qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
+  }
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  return g;
+}
+
 #if defined(__HIPCC__)
 // fp32 atomic add without return: one global_atomic_add_f32 on gfx950 (no CAS loop).
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }

@@ -10,6 +10,8 @@
 //   drrt_adjoint_rays.hip   backtrace_rays: dL/dpos, dL/dvel of trace (ray-state adjoint, no grid writes)
 //   drrt_stop_rays.hip      backtrace_pln_rays / backtrace_sdf_rays: dL/dpos, dL/dvel of trace_plane / trace_sdf (ray-state
 //                           adjoint with the forward replayed, no grid writes)
+//   drrt_target_rays.hip    backtrace_target_rays: dL/dpos, dL/dvel of trace_target (ray-state adjoint with the forward
+//                           replayed over the call's global loop count, no grid writes)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -432,6 +434,21 @@ struct StopRayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// ray-state adjoint of trace_target (drrt_target_rays.hip): takes the forward's inputs only and replays it
+struct TargetRayGradArgs {
+  Vol vol;
+  const float* pos; const float* vel; const float* target;   // the forward's inputs
+  const float* dx; const float* dv;         // seeds on the recorded (xt, vt)
+  const float* dd2;                         // nullable: seed on dist2, n floats
+  float* dpos; float* dvel;
+  const uint32_t* perm;                     // nullable: visit order (both passes)
+  drrt_stats* stats;                        // never null: iters carries the global loop count from the first pass to the second
+  size_t n;
+  float ds;
+  int max_steps;                            // the FORWARD's (steps_fwd)
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -491,6 +508,8 @@ void launch_backtrace_ring_sparse(const BackArgs& a, hipStream_t s, int which); 
 void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
 // ray-state adjoint of trace_plane (mode 1) / trace_sdf (mode 2): first pass, then the flagged rays (drrt_stop_rays.hip)
 void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t s);
+// ray-state adjoint of trace_target: the count of the global loop, then replay and reverse march (drrt_target_rays.hip)
+void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

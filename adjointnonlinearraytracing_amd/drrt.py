@@ -553,13 +553,14 @@ def _grid_inputs(rif, sdf, rays, dev: torch.device, how=None):
 
 def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sdf=None, how=None, fwd_steps=None,
                order=None, replay: bool = False, flags: int = 0, steps: bool = True, warn: bool = False,
-               counters: bool = False) -> tuple:
+               counters: bool = False, per_ray=()) -> tuple:
     """One call of a grid entry point (they share their shape: grid, [sdf], nvox, res, n, the inputs, h, ds, the outputs,
     the usual tail) -> (outputs, order, steps): the outputs, made by ``make_outputs(flat grid, ray tensors)``, and what
     a forward march left behind -- its visit order and per-ray iteration counts, the workspace views that are also
     published as `last_order` / `last_steps` (None, None for an adjoint).
     The inputs are the (n,3) tensors `rays` (converted as `_grid_inputs` does) and, for the one entry that takes them,
-    `fwd_steps`: int32[n] behind the fourth ray tensor.  `adjoint`: a forward march, or an adjoint that may be paired
+    `fwd_steps`: int32[n] behind the fourth ray tensor; `per_ray`: optional fp32[n] inputs behind the ray tensors (None is
+    passed as a null pointer).  `adjoint`: a forward march, or an adjoint that may be paired
     with one through `order`; `replay`: an adjoint that marches its forward again (`_paired_adjoint`).  `steps`: the
     forward leaves iteration counts.  `warn`: failed rays are reported.  `counters`: the adjoint classifies its bundles
     (`last_bundle_counters`)."""
@@ -572,6 +573,11 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
                 raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (drrt.last_steps)")
             rays_.insert(4, steps_)
         out = make_outputs(rif_, rays_)
+        for t in per_ray:
+            t = None if t is None else _f32(t, dev).reshape(-1)
+            if t is not None and t.numel() != n:
+                raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
+            rays_.append(t)
         grids = [_p(rif_)] if sdf_ is None else [_p(rif_), _p(sdf_)]
         march = _paired_adjoint(rif_, res, n, h, ds, dev, order, replay, flags) if adjoint else \
             _forward_march(rif_, res, n, h, ds, dev, flags)
@@ -762,6 +768,18 @@ class TracerC:
         The reference: enoki autodiff, core/tracer.py:181-234.  fp32 rays only."""
         return _grid_call("drrt_backtrace_sdf_rays_f32", rif, res, [pos, vel, dx, dv], h, ds, _like_rays,
                           adjoint=True, sdf=sdf, order=order, replay=True, warn=False)[0]
+
+    def backtrace_target_rays(self, rif, res, pos, vel, target, dx, dv, h, ds, ddist2: Optional[torch.Tensor] = None,
+                              order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """Ray-state adjoint of ``trace_target`` (drrt_backtrace_target_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),
+        (n,3) fp32.  `pos`, `vel`, `target` are the forward call's inputs, `dx`, `dv` the seeds on its (xt, vt) and `ddist2`
+        (n values, optional) the seed on its dist2; the call replays the forward over the call's global iteration count to
+        find the iteration of each ray's closest-approach record, so it takes neither (xt, vt) nor a step count.  A ray that
+        ran out of steps keeps its record and its gradient (and draws the "failed to exit all rays" message).
+        dL/dtarget = -2 ddist2 (xt - target) needs no call.  Not in the reference's C++ Tracer: it binds trace_target on its
+        enoki autodiff tracer (src/drrt.cpp:34).  fp32 rays only."""
+        return _grid_call("drrt_backtrace_target_rays_f32", rif, res, [pos, vel, target, dx, dv], h, ds, _like_rays,
+                          adjoint=True, order=order, replay=True, warn=True, per_ray=(ddist2,))[0]
 
     # ---- print-only smoke methods of the reference (src/tracer.cpp:16-33) ------------------
     def test(self) -> torch.Tensor:

@@ -9,8 +9,8 @@ Contract reproduced from the reference:
     ``ctx.save_for_backward`` -- no copies, and autograd's version check turns an in-place update of ``rif`` (or of
     the returned exit rays) between forward and backward into a RuntimeError instead of a silently wrong gradient;
   * backward returns ``drif`` reshaped to ``rif.shape`` and ``None`` for every other input
-    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC, ADCableTracerC, ADRayPlaneTracerC and
-    ADRaySDFTracerC (below) are the classes with ray gradients;
+    (no gradient w.r.t. ``x``, ``v``: ``:335,386,432,479,526``) -- ADTracerC, ADCableTracerC, ADRayPlaneTracerC,
+    ADRaySDFTracerC and ADRayTargetTracerC (below) are the classes with ray gradients;
   * ``BackPlaneTracerC`` / ``BackTargetTracerC`` backward run the GENERIC ``backtrace`` from the
     recorded state (``:376,422``); ``BackPlaneTracerC.backward`` zeroes ``grad_x`` on
     rays whose ``outmask`` gradient is set, as written (``:366-367``).
@@ -276,12 +276,48 @@ class ADRaySDFTracerC(torch.autograd.Function):
         return drif, None, dx0, dv0, None, None
 
 
+class ADRayTargetTracerC(torch.autograd.Function):
+    """``apply(rif, x, v, sp, h, ds) -> (xt, vt, dist2)`` with all three outputs differentiable w.r.t. ``rif``, the rays AND
+    the target ``sp`` (the reference binds trace_target on its enoki autodiff tracer, src/drrt.cpp:34, and has no class).
+
+    The forward is BackTargetTracerC's.  With ``g`` the gradient arriving on ``dist2 = |xt - sp|^2``, the position seed of
+    both adjoints is ``grad_x + 2 g (xt - sp)``:
+      * dL/drif: the generic ``backtrace`` from the record with that seed and ``grad_v``; with a zero ``g`` it
+        is BackTargetTracerC's gradient.  For a record written after the ray left the box the generic ``backtrace`` samples
+        clamped cells on its way back to the box (Q12 again): that part of dL/drif is not exact, here as there;
+      * dL/dx, dL/dv: ``TracerC.backtrace_target_rays`` (drrt_backtrace_target_rays_f32), which replays the forward from
+        (x, v, sp) -- private copies, kept only when ``x`` or ``v`` requires grad -- and forms the seed itself from
+        ``grad_x`` and ``g``; the iteration of the record is held fixed.  A ray that ran out of steps keeps its record and
+        its gradient;
+      * dL/dsp = ``-2 g (xt - sp)``, without a launch.
+    fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, sp, h, ds):
+        out = _grid_forward(ctx, drrt.TracerC()._trace_target, rif, None, x, v, (sp,), h, ds,
+                            ad=("ADRayTargetTracerC", 1, 2))[0]
+        ctx.sp_like = (sp.device, sp.dtype)
+        ctx.target = sp.detach().to(device=out[0].device, dtype=torch.float32).clone()
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_d):
+        rif, outx, _ = ctx.saved_tensors
+        pull = (2 * grad_d)[:, None] * (outx - ctx.target)               # d(g dist2)/d(xt)
+        drif, dx0, dv0 = _ad_grads(ctx, 1, 2, _grid_rif_grad, lambda: drrt.TracerC().backtrace_target_rays(
+            rif.detach().flatten(), ctx.shape, *ctx.rays, grad_x, grad_v, ctx.h, ctx.ds, ddist2=grad_d, order=ctx.order),
+            grad_x + pull, grad_v)
+        dsp = (-pull).to(device=ctx.sp_like[0], dtype=ctx.sp_like[1]) if ctx.needs_input_grad[3] else None
+        return drif, dx0, dv0, dsp, None, None
+
+
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken
 # upstream, SURVEY Q15) resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working,
 # with the documented difference that no gradient flows to x, v through THESE names.  The classes with ray gradients are
-# ADTracerC, ADCableTracerC, ADRayPlaneTracerC and ADRaySDFTracerC: the ray-state adjoint of trace is exact because its rays
-# end at the sample where they leave the box; the other three replay their forward to find the iteration of the recorded
-# sample (and, for the plane and SDF stops, which iterations were refracted).  trace_target has no AD class in the
-# reference and none here.
+# ADTracerC, ADCableTracerC, ADRayPlaneTracerC, ADRaySDFTracerC and ADRayTargetTracerC: the ray-state adjoint of trace is
+# exact because its rays end at the sample where they leave the box; the other four replay their forward to find the
+# iteration of the recorded sample (and, for the plane, SDF and target marches, which iterations were refracted).
+# trace_target has no AD class in the reference; ADRayTargetTracerC also takes the gradient arriving on dist2 and returns
+# one for the target.  The fibre march's dist2 still has none (ADCableTracerC ignores it, as the reference does).
 ADPlaneTracerC = BackPlaneTracerC
 ADSDFTracerC = BackSDFTracerC

@@ -430,6 +430,39 @@ DRRT_API int drrt_backtrace_sdf_rays_f32(const float* rif, const float* sdf, lon
                              drrt_stats* stats, void* workspace, size_t workspace_bytes,
                              unsigned flags, void* stream);
 
+/* Ray-state adjoint of Tracer::trace_target: dL/dpos, dL/dvel of the rays that entered drrt_trace_target_f32, from seeds on
+ * all three of its outputs (the reference binds trace_target on its autodiff tracer, src/drrt.cpp:34).  No contribution to
+ * dL/dn is formed.
+ *   pos, vel, target   the forward call's inputs, (n,3) fp32
+ *   dx, dv             seeds on its outputs (xt, vt);  ddist2: seed on dist2, fp32[n], or NULL for zero
+ *   dpos, dvel         out: (n,3) fp32
+ * Contract: (xt, vt) is the state (x_j, v_j) of the iteration j with the smallest squared distance to the target (first
+ * minimum; j = 0 is the input itself) over the call's GLOBAL iteration count -- the maximum, over its rays, of the iterations
+ * until a ray is flagged escaped: an escaped ray flies straight on while any ray marches -- and dist2 = |x_j - target|^2.
+ * The forward reports neither j nor which iterations were refracted, so the call replays it from (pos, vel) with the
+ * forward's own fp32 operations: a first launch for the global iteration count, a second for the replay and the reverse
+ * march.  j and the forward's `inside` masks are held fixed.  The effective position seed is gx = dx + 2 ddist2 (x_j - target)
+ * (one fmaf per component); j = 0 gives (gx, dv), which is (dx, dv) bit for bit when ddist2 is zero.  Otherwise the
+ * iterations j-1 .. 0 are undone from the record, seeded like drrt_backtrace_f32 (lambda = gx, mu = dv + ds gx): a refracted
+ * iteration is one reverse iteration of drrt_backtrace_f32 without its backward-escape test and step bound, a masked one --
+ * the prefix before the first in-box sample, and everything after the ray was flagged escaped -- is free flight (lambda
+ * unchanged, mu += ds lambda).  The first refracted sample is taken at the replayed position itself; a record written after
+ * the escape starts the refracted stretch from the replayed state at the escape.  A ray that ran out of steps keeps its
+ * record and its gradient; stats->n_failed counts the rays that never got flagged escaped, as drrt_trace_target_f32's.
+ * stats->ray_steps = replayed forward iterations (second launch) + reverse iterations; stats->iters = the forward's own
+ * stats->iters.  The result does not depend on DRRT_FLAG_CORRECTED_H nor on the visit order; no gradient flows to h or ds.
+ * dL/dtarget = -2 ddist2 (xt - target) is a point-wise expression of the forward's outputs: the caller forms it.
+ * Workspace: drrt_workspace_bytes() (drrt_workspace_bytes_grid() with DRRT_FLAG_PAIR_GRID); the call keeps no per-ray state
+ * in it.  Without a stats block the library's per-device one carries the iteration count, as in drrt_trace_pln_f32.
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE and DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32; the
+ * order hint (normally the paired forward's) is consumed like there, the step hint is ignored.  fp32 only.              */
+DRRT_API int drrt_backtrace_target_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                             const float* pos, const float* vel, const float* target,
+                             const float* dx, const float* dv, const float* ddist2 /* nullable = 0 */,
+                             float h, float ds, float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
 /* ---- sensor image splat (SURVEY.md 8.8 "next" row 1; the reference does this in torch) ----------
  * Forward: core/sensor.py:5-28 generate_sensor = trace_rays_to_plane (:195-202) + sensor frame
  * (t1 = n x t2, t2; get_tan_vecs :219-231 is evaluated by the caller) + foreshortening |v.n| +
@@ -565,6 +598,7 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_CABLE_RAYS 7   /* ray-state adjoint of the cable march (drrt_backtrace_cable_rays_f32) */
 #define DRRT_PROF_BACKTRACE_PLN_RAYS 8   /* ray-state adjoint of trace_plane (drrt_backtrace_pln_rays_f32), both passes */
 #define DRRT_PROF_BACKTRACE_SDF_RAYS 9   /* ray-state adjoint of trace_sdf (drrt_backtrace_sdf_rays_f32), both passes */
+#define DRRT_PROF_BACKTRACE_TARGET_RAYS 10   /* ray-state adjoint of trace_target (drrt_backtrace_target_rays_f32), both launches */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

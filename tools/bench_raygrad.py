@@ -38,7 +38,16 @@ stop    drrt_backtrace_pln_rays_f32 / drrt_backtrace_sdf_rays_f32 (k_backtrace_s
                      backtrace_sdf_rays   TracerC.backtrace_sdf_rays   (the new call, in trace_sdf's visit order)
         usage: bench_raygrad.py stop [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once]
 
-cable and stop time the three calls of a case alternately (one of each per round) with device events around the whole
+target  drrt_backtrace_target_rays_f32 (k_target_rays_count + k_backtrace_target_rays) next to the calls it goes with: 256^3
+        Luneburg ball, 1 048 576 rays of bench.py's plane source, every ray's target the ball's focal point on the far y face.
+            trace_target            TracerC.trace_target            (k_target_a_flat + k_target_b)
+            backtrace               TracerC.backtrace               (dL/dn from the record, in trace_target's visit order)
+            backtrace_target_rays   TracerC.backtrace_target_rays   (the new call, in trace_target's visit order, dist2 seeded)
+        usage: bench_raygrad.py target [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string (source digest), to --out (default
+        profiles/target_raygrad_bench.json).
+
+cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
 over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
 ones.  --once: a single call of each (for a `rocprofv3 --kernel-trace --stats` run of its own)."""
@@ -253,6 +262,31 @@ def stop(a, dev):
     return out
 
 
+# ---- target ---------------------------------------------------------------------------------------------------------
+def target(a, dev):
+    rif, pos, vel, h, ds = bench.make_workload(a.grid, a.rays, dev, seed=0)
+    res = tuple(rif.shape)
+    ext = (a.grid - 1) * h
+    n = pos.shape[0]
+    tg = torch.tensor([[0.5 * ext, ext, 0.5 * ext]], device=dev).expand(n, 3).contiguous()
+    T = drrt.TracerC()
+    xt, vt, _ = T.trace_target(rif, res, pos, vel, tg, h, ds)
+    order = drrt.keep_order(drrt.last_order)
+    one, g = torch.ones_like(xt), torch.ones(n, device=dev)
+    res_ = time_alternately({
+        "trace_target": lambda: T.trace_target(rif, res, pos, vel, tg, h, ds),
+        "backtrace": lambda: T.backtrace(rif, res, xt, vt, one, one, h, ds, order=order),
+        "backtrace_target_rays": lambda: T.backtrace_target_rays(rif, res, pos, vel, tg, one, one, h, ds, ddist2=g, order=order),
+    }, "backtrace_target_rays", a)
+    if res_ is None:
+        return {}
+    out = dict(res_, grid=a.grid, rays=n, h=h, ds=ds, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -269,14 +303,20 @@ def main():
     p_stop.add_argument("--grid", type=int, default=256)
     p_stop.add_argument("--rays", type=int, default=1 << 20)
     p_stop.set_defaults(run=stop)
-    for p in (p_cable, p_stop):
+    p_target = sub.add_parser("target")
+    p_target.add_argument("--grid", type=int, default=256)
+    p_target.add_argument("--rays", type=int, default=1 << 20)
+    p_target.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
+                                                        "target_raygrad_bench.json"))
+    p_target.set_defaults(run=target)
+    for p in (p_cable, p_stop, p_target):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload == "stop" and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
