@@ -83,6 +83,8 @@ SIGNATURES = {
     "drrt_trace_cable_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _f, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail),
     "drrt_backtrace_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
+    "drrt_trace_opl_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_backtrace_opl_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_chunk_state_bytes": (_sz, [_sz]),
     "drrt_backtrace_max_steps": (_i, [_vp, _f, _f]),
     "drrt_backtrace_chunk_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail + [_vp, _sz, _i, _i, _vp]),
@@ -115,7 +117,8 @@ SIGNATURES = {
 }
 
 PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "backtrace_rays",
-              7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays", 10: "backtrace_target_rays"}
+              7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays", 10: "backtrace_target_rays",
+              11: "trace_opl", 12: "backtrace_opl"}
 
 _lib: Optional[C.CDLL] = None
 

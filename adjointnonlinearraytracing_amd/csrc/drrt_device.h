@@ -816,6 +816,103 @@ DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsig
   return g;
 }
 
+// ---- optical path length -------------------------------------------------------------------------------------------
+// The march integrates dx/dsigma = v, dv/dsigma = n grad n, so |v| = n and the optical path length int n dl is
+// int n^2 dsigma: opl = sum_{k<K} ds n_k^2 over the masked samples n_k that fwd_step_c<0> takes at x_k (0 while the ray
+// is not inside: free flight outside the box adds nothing), accumulated in fp32 as opl = fmaf(ds n_k, n_k, opl) in
+// iteration order from 0.f.  Not in the reference.
+
+// trace for ONE ray, with its optical path length.  The state update is fwd_step_c<0> itself on the taps `taps(c)`
+// returns, looped as trace_ray<0> loops it, so (xt, vt, steps) are trace_ray<0>'s bit for bit; the sample is evaluated
+// once more for n_k (the compiler merges the two).  A failed ray returns what it accumulated.
+template <typename TapFn>
+DRRT_HD RayOut trace_opl_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                             float& opl) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
+  fwd_init(V, s);
+  Cell c = locate(V, s.x, s.y, s.z);
+  unsigned steps = 0;
+  float acc = 0.f;
+  for (int it = 0; it < max_steps; ++it) {
+    Taps t = taps_zero();
+    float n = 0.f;
+    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
+      t = taps(c);
+      n = interp<false>(t, c.wx, c.wy, c.wz).n;
+    }
+    acc = fmaf(ds * n, n, acc);
+    fwd_step_c<0>(V, nullptr, ds, s, c, t);
+    ++steps;
+    if (s.esc) break;                                                     // per-ray form of :82
+  }
+  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
+  opl = acc;
+  return o;
+}
+
+// Adjoint of trace_opl_ray for ONE ray: dL/dpos, dL/dvel AND the contributions to dL/dn, from the seeds (dx, dv, dopl) on
+// (xt, vt, opl).  The reverse march is backtrace_ray_state's, unchanged in structure (replayed free-flight prefix, K - e
+// reverse iterations, the last one sampled at the replayed x_e, no backward-escape test, failed rays zero and flagged,
+// never-entered rays (dx, dv) and no contribution).  Each reverse iteration uses
+//   dn = mu . grad n_k + 2 dopl n_k
+// wherever backtrace_ray_state uses mu . grad n_k: d opl / d n_k = 2 ds n_k adds 2 dopl n_k ds to the value weight of
+// the splat, and d opl / d x_k = 2 ds n_k grad n_k adds the same multiple of grad n_k to lambda, which is what adj_recur
+// does with dn.  `sink(c, val, gx, gy, gz)` receives the contribution of the iteration, formed like adj_contrib's with mu
+// BEFORE adj_recur updates it: val = dn ds, g = (n_k ds grad_scale) mu; the caller adds splat_weights(c.wx, c.wy, c.wz,
+// val, gx, gy, gz) at the 8 taps of c.  With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum is the exact discrete
+// derivative; grad_scale does not enter the ray gradients.
+template <typename TapFn, typename Sink>
+DRRT_HD RayGrad opl_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                  const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                  const float dv[3], float dopl, TapFn&& taps, Sink&& sink) {
+  RayGrad g;
+  g.steps = 0; g.failed = false;
+  if (max_steps <= 0 || K >= (unsigned)max_steps) {
+    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    g.failed = true;
+    return g;
+  }
+  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
+  float px = p0[0], py = p0[1], pz = p0[2];
+  unsigned e = 0;
+  while (e < K && !inbounds(V, px, py, pz)) {
+    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
+    ++e;
+  }
+  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, opl = 0
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  const float dopl2 = dopl + dopl;
+  for (unsigned k = K; k > e; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
+    const Cell c = locate(V, s.x, s.y, s.z);
+    AdjSample m;
+    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
+    const float dn = fmaf(dopl2, m.n, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));
+    const float nds = (m.n * ds) * grad_scale;
+    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
+    qx = s.mx; qy = s.my; qz = s.mz;
+    adj_recur(V, ds, s, m, dn);
+  }
+  const float eds = (float)e * ds;
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
+  g.steps = K - e;
+  return g;
+}
+
 // trace_cable for ONE ray (src/tracer.cpp:312-382)
 DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
                                const float tg[3]) {

@@ -12,6 +12,8 @@
 //                           adjoint with the forward replayed, no grid writes)
 //   drrt_target_rays.hip    backtrace_target_rays: dL/dpos, dL/dvel of trace_target (ray-state adjoint with the forward
 //                           replayed over the call's global loop count, no grid writes)
+//   drrt_opl.hip            trace_opl, backtrace_opl: trace with its optical path length, and the adjoint that returns
+//                           dL/dn, dL/dpos and dL/dvel from seeds on (xt, vt, opl) in one march (global atomics, no window)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -449,6 +451,37 @@ struct TargetRayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// optical path length (drrt_opl.hip): trace with opl = sum ds n_k^2, and its adjoint (dL/dn and the ray gradients at once)
+struct OplTraceArgs {
+  Vol vol;
+  const float* pos; const float* vel;
+  float* xt; float* vt; float* opl;
+  uint32_t* steps_out;                      // per-ray iteration counts, caller ray order
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+struct OplBackArgs {
+  Vol vol;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const uint32_t* fsteps;                   // its per-ray iteration counts, caller ray order
+  const float* dx; const float* dv;         // nullable: seeds on (xt, vt), read as zeros
+  const float* dopl;                        // nullable: seed on opl, n floats
+  float* grad;                              // nullable: no scatter
+  float* dpos; float* dvel;                 // both null: no ray outputs
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  float grad_scale;                         // 1 (as written, Q3) or 1/h (DRRT_FLAG_CORRECTED_H)
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -510,6 +543,9 @@ void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
 void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t s);
 // ray-state adjoint of trace_target: the count of the global loop, then replay and reverse march (drrt_target_rays.hip)
 void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
+// optical path length: trace_opl and its adjoint (drrt_opl.hip)
+void launch_trace_opl(const OplTraceArgs& a, hipStream_t s);
+void launch_backtrace_opl(const OplBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

@@ -658,7 +658,57 @@ class TracerC:
         return _cable_call("drrt_trace_cable_f32", rif, radius, length, ds, (pos, vel, target),
                            lambda rif_, r: (torch.empty_like(r), torch.empty_like(r), r.new_empty(r.shape[0])), warn=True)
 
+    def _trace_opl(self, rif, res, pos, vel, h, ds):
+        return _grid_call("drrt_trace_opl_f32", rif, res, [pos, vel], h, ds,
+                          lambda rif_, r: _like_rays(rif_, r) + (r[0].new_empty(r[0].shape[0]),
+                                                                 torch.empty(r[0].shape[0], dtype=torch.int32, device=r[0].device)),
+                          adjoint=False, steps=False, warn=True)
+
+    def trace_opl(self, rif, res, pos, vel, h, ds):
+        """``trace`` with the optical path length of every ray (drrt_trace_opl_f32, include/drrt_hip.h; not in the
+        reference) -> (xt, vt, opl, steps): xt, vt and the per-ray iteration counts `steps` (int32[n], a tensor of the
+        caller's, not a workspace view) are ``trace``'s bit for bit; ``opl = sum ds n_k^2`` over the samples the march takes
+        inside the box (|v| = n, so this is the integral of n along the path).  fp32 rays only."""
+        return self._trace_opl(rif, res, pos, vel, h, ds)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_opl(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dopl, h, ds, grid: bool = True, rays: bool = True,
+                      into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_opl`` (drrt_backtrace_opl_f32, include/drrt_hip.h) -> (grad | None, dpos | None, dvel | None):
+        flat dL/dn (fp32[nvox]), dL/dpos and dL/dvel ((n,3) fp32) from ONE reverse march.  `pos`, `vel` are the forward
+        call's inputs, `xt`, `vt`, `steps` its outputs; `dx`, `dv` ((n,3)) and `dopl` (n values) the seeds on (xt, vt, opl),
+        each optional (None: zeros).  `grid` / `rays`: which outputs are computed (at least one); `into`: a flat fp32[nvox]
+        tensor the grid gradient is ADDED to (DRRT_FLAG_NO_ZERO) and that is returned as grad.  Honours
+        ``options.corrected_h`` (with it the grid gradient is the exact discrete derivative; the ray gradients do not depend
+        on it).  Rays that failed the forward get zeros and contribute nothing.  `order`: the forward's visit order."""
+        if not (grid or rays):
+            raise RuntimeError("backtrace_opl: nothing to compute (grid = rays = False)")
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            rif_, _, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, None, [pos, vel, xt, vt], dev)
+            steps_ = steps.detach().to(device=dev).contiguous()
+            if steps_.dtype != torch.int32 or steps_.numel() != n:
+                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_opl's)")
+            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+            dopl_ = None if dopl is None else _f32(dopl, dev).reshape(-1)
+            if dopl_ is not None and dopl_.numel() != n:
+                raise RuntimeError(f"expected {n} per-ray values, got {dopl_.numel()}")
+            grad, extra = None, 0
+            if grid and into is not None:
+                if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != rif_.numel() or into.device != dev:
+                    raise RuntimeError("backtrace_opl: `into` must be a contiguous fp32 tensor of the grid's size on its device")
+                grad, extra = into.detach().view(-1), _lib.FLAG_NO_ZERO
+            elif grid:
+                grad = torch.empty_like(rif_)
+            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=extra) as (fl, ws, st, _):
+                _lib.check(_lib.load().drrt_backtrace_opl_f32(
+                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_), _p(dx_), _p(dv_),
+                    _p(dopl_), float(h), float(ds), _p(grad), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl,
+                    _stream(dev)))
+            _warn_failed(st)
+        return grad, dpos, dvel
+
     def backtrace(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tracer::backtrace, src/tracer.cpp:384-440 -> flat dL/dn (fp32[nvox]).
         `order` (optional, not in the reference): visit order of the paired forward call.

@@ -19,6 +19,8 @@ torch allocations.
 """
 from __future__ import annotations
 
+import dataclasses
+
 import torch
 
 from . import drrt
@@ -309,6 +311,53 @@ class ADRayTargetTracerC(torch.autograd.Function):
             grad_x + pull, grad_v)
         dsp = (-pull).to(device=ctx.sp_like[0], dtype=ctx.sp_like[1]) if ctx.needs_input_grad[3] else None
         return drif, dx0, dv0, dsp, None, None
+
+
+class OPLTracerC(torch.autograd.Function):
+    """``apply(rif, x, v, h, ds) -> (xt, vt, opl)``: ``trace`` with the optical path length ``opl = sum ds n_k^2`` of every
+    ray (|v| = n along the march, so this is the integral of n along the path), all three outputs differentiable w.r.t.
+    ``rif``, ``x`` and ``v``.  Not in the reference.
+
+    The forward is ``TracerC.trace_opl``; backward is ONE ``TracerC.backtrace_opl`` launch (plus the zero-fill of the grid
+    gradient when ``rif`` requires grad), which returns dL/drif and the ray gradients from the same reverse march and
+    computes only what is asked for.  Unlike the Back* / AD* classes, whose dL/drif is the reference's ``backtrace`` from
+    the exit ray, this adjoint replays the forward's iteration count: with ``drrt.options.corrected_h`` its dL/drif is the
+    exact discrete derivative.  ``sort_rays`` and ``pair_grid`` are honoured as in ADTracerC; the options in effect at the
+    forward (``drrt.options``, or the calling thread's ``drrt.using(...)`` block) are kept and applied to the backward launch,
+    which autograd runs on a thread of its own.  Private copies of (x, v) and the iteration counts are kept whenever any
+    input requires grad.  Rays that failed the forward get zero gradients.  fp32 rays only when ray gradients are asked
+    for."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, h, ds):
+        ctx.set_materialize_grads(False)
+        ctx.shape, ctx.h, ctx.ds = rif.shape, h, ds
+        _ray_grad_wanted(ctx, "OPLTracerC", 1, 2, x, v)
+        (xt, vt, opl, steps), order, _ = drrt.TracerC()._trace_opl(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(),
+                                                                   h, ds)
+        if any(ctx.needs_input_grad[:3]):
+            ctx.options = dataclasses.asdict(drrt._opt())
+            ctx.order = drrt.keep_order(order)
+            _keep_rays(ctx, x, v, xt.device)
+            ctx.rays += (steps,)
+            ctx.save_for_backward(rif, xt, vt)
+        return xt, vt, opl
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_opl):
+        want_rif, want_rays = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
+        if not (want_rif or want_rays):
+            return None, None, None, None, None
+        rif, outx, outv = ctx.saved_tensors
+        x0, v0, steps = ctx.rays
+        with drrt.using(**ctx.options):
+            grad, dpos, dvel = drrt.TracerC().backtrace_opl(rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps,
+                                                            grad_x, grad_v, grad_opl, ctx.h, ctx.ds, grid=want_rif,
+                                                            rays=want_rays, order=ctx.order)
+        drif = grad.reshape(*ctx.shape) if want_rif else None
+        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[1] else None
+        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[2] else None
+        return drif, dx0, dv0, None, None
 
 
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken

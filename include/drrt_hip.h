@@ -322,6 +322,45 @@ DRRT_API int drrt_backtrace_rays_f32(const float* rif, long long nvox, const int
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- optical path length (not in the reference) ------------------------------------------------------------------------
+ * The march integrates dx/dsigma = v, dv/dsigma = n grad n, so |v| = n and the optical path length int n dl is
+ * int n^2 dsigma.  drrt_trace_opl_f32 is drrt_trace_f32 (xt, vt and the per-ray iteration counts K bit for bit) that also
+ * returns  opl = sum_{k<K} ds n_k^2  over the masked samples n_k the march takes at x_k anyway (0 while the ray is not
+ * inside the box: free flight adds nothing), accumulated in fp32 as opl = fmaf(ds n_k, n_k, opl) in iteration order from 0.
+ * A failed ray (K >= max_steps) returns what it accumulated.
+ *   opl        out: fp32[n]
+ *   steps_out  out: uint32[n], required: K per ray, caller ray order (what the adjoint takes as fwd_steps).  The call
+ *              leaves no drrt_last_steps().
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE, DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32.  fp32 only. */
+DRRT_API int drrt_trace_opl_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds,
+                       float* xt, float* vt, float* opl, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_opl_f32: from the seeds dx = dL/dxt, dv = dL/dvt, dopl = dL/dopl (each nullable: read as zeros) ONE
+ * reverse march yields dL/dn (grad), dL/dpos and dL/dvel.  The march is drrt_backtrace_rays_f32's, unchanged in structure
+ * (replayed free-flight prefix, K - e reverse iterations, the last sampled at the replayed x_e, no backward-escape test;
+ * failed rays get zeros, contribute nothing and count in stats->n_failed; never-entered rays get (dx, dv) and contribute
+ * nothing).  Each reverse iteration uses  dn = mu . grad n_k + 2 dopl n_k  where that march uses mu . grad n_k, and adds
+ * splat_weights(w, dn ds, (n_k ds grad_scale) mu), formed with mu before its update, at the 8 taps of the sampled cell.
+ * grad_scale = 1 / h with DRRT_FLAG_CORRECTED_H -- then the result is the exact discrete derivative -- and 1 without, as
+ * for drrt_backtrace_f32 (Q3).
+ *   grad        out, nullable (no scatter at all): fp32[nvox], zeroed by the call unless DRRT_FLAG_NO_ZERO
+ *   dpos, dvel  out, both or neither: (n,3) fp32.  grad, dpos and dvel all null: DRRT_ERR_ARG
+ * The scatter is one global fp32 atomic per tap and per run of samples in one cell (a lane sums in registers while it
+ * stays in a cell): there is no LDS window here, so rays focused into a few voxels run at the memory-side atomic rate.
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE, DRRT_FLAG_DISPATCH_IN_ORDER, DRRT_FLAG_CORRECTED_H,
+ * DRRT_FLAG_NO_ZERO; other adjoint flags are ignored.  The order hint is consumed, the step hint ignored.  fp32 only.      */
+DRRT_API int drrt_backtrace_opl_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, const float* dopl, float h, float ds,
+                       float* grad, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -599,6 +638,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_PLN_RAYS 8   /* ray-state adjoint of trace_plane (drrt_backtrace_pln_rays_f32), both passes */
 #define DRRT_PROF_BACKTRACE_SDF_RAYS 9   /* ray-state adjoint of trace_sdf (drrt_backtrace_sdf_rays_f32), both passes */
 #define DRRT_PROF_BACKTRACE_TARGET_RAYS 10   /* ray-state adjoint of trace_target (drrt_backtrace_target_rays_f32), both launches */
+#define DRRT_PROF_TRACE_OPL 11       /* trace with its optical path length (drrt_trace_opl_f32) */
+#define DRRT_PROF_BACKTRACE_OPL 12   /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_opl_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

@@ -1,0 +1,594 @@
+"""Optical path length: drrt_trace_opl_f32 / drrt_backtrace_opl_f32, TracerC.trace_opl / backtrace_opl, tracer.OPLTracerC.
+
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/opl_rays.hip: trace_opl_ray and opl_backtrace_ray
+of csrc/drrt_device.h) against the product's own trace (bit for bit), against float64 torch.autograd through tests/opl_ad
+(oracle/torch_ad.trace's loop with opl += ds n^2) on the tie-free rays -- those whose fp32 and fp64 marches leave on the same
+iteration with exit samples within TIE_TOL, as in tests/test_raygrad.py::reference --, against closed forms, and the C ABI's
+argument checks.  GPU tier: the kernels of drrt_opl.hip against that host build, the autograd class end to end, its launches,
+and the demo.
+
+On the parent commit every test here fails: tests/hostcheck/opl_rays.hip does not compile (no trace_opl_ray), the library has
+no such C symbols, TracerC no such methods, tracer no such class and examples/ no such demo.
+
+Mutation checks (tried by hand on opl_backtrace_ray, one at a time, each then undone; CPU tier):
+  * the value weight of the splat without the 2 dopl n_k term (dn ds -> (mu . grad n_k) ds): all ten cases of
+    test_adjoint_matches_float64_autograd, test_plane_source_on_host and test_uniform_medium_closed_form fail;
+  * adj_recur called with mu . grad n_k instead of dn (lambda loses 2 dopl ds n_k grad n_k): the same eleven and
+    test_exit_on_first_iteration_closed_form fail."""
+import ctypes as C
+import glob
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import cases
+import hostcheck_lib as HC
+import opl_ad
+import opl_host as OH
+from oracle import torch_ad
+from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grid, ray_sets, rel_err
+
+# Relative error of the fp32 opl against float64 on tie-free rays.  A priori: K 2^-24 for the accumulate (K <= 128) plus
+# TIE_TOL |grad n| / n for the samples taken TIE_TOL apart: <~ 2e-5.  4 x the largest value measured on the host build
+# (4.95e-7, the plane source of test_plane_source_on_host; 4.45e-7 on lens16_h05_half), rounded up to one digit; the margin
+# is for another compiler or libm.  May not exceed 1e-4: more would mean the accumulate is wrong.
+OPL_TOL = 2e-6
+# rel-L2 over the grid of dL/dn against float64 autograd (flag on).  4 x the largest value measured on the host build
+# (4.04e-6, box7x11x5_h05_multi without seeds on the rays), rounded up to one digit; may not exceed GRAD_TOL.
+GRID_TOL = 2e-5
+assert OPL_TOL <= 1e-4 and GRID_TOL <= GRAD_TOL
+ATOMIC_TOL = 2e-5       # grid gradient, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
+KINDS = ("plane", "point", "inside", "face", "never", "graze")
+
+
+# ---- scenes ---------------------------------------------------------------------------------------------------------
+_scenes = {}
+
+
+def scene(name, seed=0):
+    """The box march's scene (raygrad_common) with seeds on all three outputs: <= 672 rays, <= 128 iterations."""
+    if (name, seed) in _scenes:
+        return _scenes[name, seed]
+    kind, h, ds = SCENES[name]
+    rif = grid(kind)
+    D, H, W = rif.shape
+    ext = ((W - 1) * h, (H - 1) * h, (D - 1) * h)
+    sets = ray_sets(ext, ds, seed)
+    pos = np.concatenate([s[0] for s in sets.values()])
+    vel = np.concatenate([s[1] for s in sets.values()])
+    labels = np.concatenate([[k] * len(s[0]) for k, s in sets.items()])
+    rng = np.random.default_rng(seed + 11)
+    s = dict(rif=rif, res=(W, H, D), h=h, ds=ds, pos=pos, vel=vel, labels=labels,
+             dx=rng.normal(size=pos.shape).astype(np.float32), dv=rng.normal(size=pos.shape).astype(np.float32),
+             dopl=rng.normal(size=len(pos)).astype(np.float32))
+    assert len(pos) <= 672 and len(pos) % 256 != 0 and max_steps_fwd(s["res"], h, ds) <= 128
+    _scenes[name, seed] = s
+    return s
+
+
+def max_steps_fwd(res, h, ds):
+    return int(np.float32(4.0) * np.float32(h) * np.float32(max(res)) / np.float32(ds))
+
+
+_refs = {}
+
+
+def reference(oracle, s, key):
+    """Host fp32 forward, fp64 forward, tie-free mask (tests/test_raygrad.py::reference) and the float64 opl; once per `key`."""
+    if key in _refs:
+        return _refs[key]
+    k = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    o64 = oracle.trace(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"], dtype=np.float64)
+    ms = max_steps_fwd(s["res"], s["h"], s["ds"])
+    ok = k["steps"] < ms
+    tie_free = ok & (o64["steps"] == k["steps"]) & \
+        (np.abs(o64["xt"] - k["xt"]).max(1) <= TIE_TOL) & (np.abs(o64["vt"] - k["vt"]).max(1) <= TIE_TOL)
+    T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
+    with torch.no_grad():
+        opl64 = opl_ad.trace_opl(T(s["rif"]), T(s["pos"]), T(s["vel"]), s["h"], s["ds"])[2].numpy()
+    _refs[key] = (k, tie_free, opl64, ms)
+    return _refs[key]
+
+
+def autograd64(s, dx, dv, dopl):
+    """float64 torch.autograd of L = <dx, xt> + <dv, vt> + <dopl, opl> through opl_ad -> (dL/drif, dL/dpos, dL/dvel)."""
+    T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
+    r, p, v = (T(s[k]).requires_grad_(True) for k in ("rif", "pos", "vel"))
+    xt, vt, opl, _ = opl_ad.trace_opl(r, p, v, s["h"], s["ds"])
+    L = (xt * T(dx)).sum() + (vt * T(dv)).sum() + (opl * T(dopl)).sum()
+    gr, gp, gv = torch.autograd.grad(L, (r, p, v))
+    return gr.numpy().reshape(-1), gp.numpy(), gv.numpy()
+
+
+def _bits(a):
+    return np.ascontiguousarray(a).view(np.uint32)
+
+
+# ---- CPU tier -------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(SCENES))
+def test_forward_is_trace(name):
+    """trace_opl_ray's (xt, vt, steps) == the product's trace_ray<0> (tests/hostcheck), bit for bit."""
+    s = scene(name)
+    k = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    t = HC.trace(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    assert np.array_equal(_bits(k["xt"]), _bits(t["xt"])) and np.array_equal(_bits(k["vt"]), _bits(t["vt"]))
+    assert np.array_equal(k["steps"].astype(np.int64), t["steps"].astype(np.int64)) and k["n_failed"] == t["n_failed"] > 0
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+def test_opl_matches_float64(oracle, name):
+    s = scene(name)
+    k, tie_free, opl64, ms = reference(oracle, s, name)
+    lab = s["labels"]
+    for kind in KINDS:
+        assert tie_free[lab == kind].sum() >= 10, kind
+    m = tie_free & (opl64 > 0)
+    err = np.abs(k["opl"].astype(np.float64) - opl64)[m] / opl64[m]
+    print(f"{name}: {tie_free.sum()} tie-free rays, {m.sum()} with opl > 0 (max {opl64[m].max():.3f}); "
+          f"opl rel err max {err.max():.3e} median {np.median(err):.3e}")
+    assert m.sum() >= 40 and err.max() <= OPL_TOL
+    never = (lab == "never") & (k["steps"] < ms)
+    assert never.sum() > 0 and np.array_equal(_bits(k["opl"][never]), np.zeros(never.sum(), np.uint32))
+    assert not opl64[never].any()
+
+
+@pytest.mark.parametrize("rays_seeded", [True, False])
+@pytest.mark.parametrize("name", list(SCENES))
+def test_adjoint_matches_float64_autograd(oracle, name, rays_seeded):
+    """Flag on: (dpos, dvel) per ray and dL/dn over the grid against float64 autograd of L = <dx, xt> + <dv, vt> + <dopl, opl>,
+    and once more with dx = dv = 0; seeds of the rays that are not tie-free zeroed on both sides."""
+    s = scene(name)
+    k, tie_free, _, ms = reference(oracle, s, name)
+    z = (tie_free[:, None] if rays_seeded else np.zeros((len(tie_free), 1), bool))
+    dx, dv, dopl = s["dx"] * z, s["dv"] * z, s["dopl"] * tie_free
+    r = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], dx if rays_seeded else None,
+                         dv if rays_seeded else None, dopl, s["h"], s["ds"], corrected_h=True)
+    gr, gp, gv = autograd64(s, dx, dv, dopl)
+    err = rel_err(r["dpos"], r["dvel"], gp, gv)[tie_free]
+    gerr = cases.rel_l2(r["grad"], gr)
+    print(f"{name} rays_seeded={rays_seeded}: {tie_free.sum()} tie-free rays, ray grad rel err max {err.max():.3e} median "
+          f"{np.median(err):.3e}; grid rel-L2 {gerr:.3e} (|grad| {np.linalg.norm(gr):.3e})")
+    assert np.linalg.norm(gr) > 0.1 and np.abs(gp[tie_free]).max() > 1e-3
+    assert err.max() <= GRAD_TOL
+    assert gerr <= GRID_TOL
+    assert r["n_failed"] == int((k["steps"] >= ms).sum()) == k["n_failed"]
+
+
+def test_plane_source_on_host(oracle):
+    """The scene of the GPU tier's end-to-end test, on the host build: it is part of what OPL_TOL and GRID_TOL were
+    measured on."""
+    s = _plane_case()
+    k, tie_free, opl64, _ = reference(oracle, s, "plane12")
+    oerr = (np.abs(k["opl"] - opl64) / opl64)[tie_free].max()
+    assert tie_free.sum() >= 120 and oerr <= OPL_TOL
+    for seeded in (True, False):
+        z = tie_free[:, None] if seeded else np.zeros((len(tie_free), 1), bool)
+        dx, dv, dopl = s["dx"] * z, s["dv"] * z, s["dopl"] * tie_free
+        r = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], dx, dv, dopl, s["h"], s["ds"])
+        gr, gp, gv = autograd64(s, dx, dv, dopl)
+        err, gerr = rel_err(r["dpos"], r["dvel"], gp, gv)[tie_free].max(), cases.rel_l2(r["grad"], gr)
+        print(f"plane source, rays seeded={seeded}: opl rel err {oerr:.3e}; ray grad rel err max {err:.3e}; grid rel-L2 {gerr:.3e}")
+        assert err <= GRAD_TOL and gerr <= GRID_TOL
+
+
+@pytest.mark.parametrize("name", list(SCENES))
+def test_failed_and_never_entered_rays(oracle, name):
+    """Failed rays: zeros, counted, no grid contribution.  Never-entered rays: (dx, dv) exactly, no grid contribution."""
+    s = scene(name)
+    k, _, _, ms = reference(oracle, s, name)
+    lab = s["labels"]
+    r = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"], s["dopl"],
+                         s["h"], s["ds"])
+    failed = k["steps"] >= ms
+    assert failed[np.where(lab == "zero")[0][:48]].all()
+    assert np.array_equal(r["failed"], failed) and r["n_failed"] == int(failed.sum()) == k["n_failed"] > 0
+    assert not r["dpos"][failed].any() and not r["dvel"][failed].any() and not r["steps"][failed].any()
+    never = (lab == "never") & ~failed
+    assert never.sum() >= 10
+    assert np.array_equal(_bits(r["dpos"][never]), _bits(s["dx"][never])) and np.array_equal(_bits(r["dvel"][never]), _bits(s["dv"][never]))
+    quiet = failed | never
+    q = OH.backtrace_opl(s["rif"], s["res"], s["pos"][quiet], s["vel"][quiet], k["xt"][quiet], k["vt"][quiet], k["steps"][quiet],
+                         s["dx"][quiet], s["dv"][quiet], s["dopl"][quiet], s["h"], s["ds"])
+    assert not q["grad"].any() and q["ray_steps"] == 0
+    assert np.abs(r["grad"]).max() > 0 and r["ray_steps"] == int(r["steps"].astype(np.int64).sum()) > 0
+
+
+def test_uniform_medium_closed_form():
+    """n = c everywhere: opl = ds c^2 (in-box samples), one rounding (<= 1 ulp of the running sum) per term -- every term
+    ds c * c is exact here --, and with dx = dv = 0 the grid gradient sums to sum_rays 2 dopl c ds (samples): the value
+    weights of a splat sum to its value, the gradient splat to zero.  Positions, directions and ds are dyadic, so the
+    fp32 march is exact and the samples can be counted in float64."""
+    res, h, ds, c = (9, 8, 7), 1.0, 0.5, 1.25
+    rif = np.full((res[2], res[1], res[0]), c, np.float32)
+    pos = np.array([(3.25, -1.25, 3.5), (0.0, 2.5, 1.125), (4.5, 3.5, 2.75), (-2.0, 3.0, 3.0), (7.875, 6.75, 5.5)], np.float32)
+    vel = np.array([(0.25, 1.0, 0.125), (1.0, 0.0, 0.0), (-0.5, 0.25, 0.75), (1.0, 0.125, -0.25), (0.125, 0.125, 0.0625)], np.float32)
+    k = OH.trace_opl(rif, res, pos, vel, h, ds)
+    ext = np.array([res[0] - 1, res[1] - 1, res[2] - 1], np.float64) * h
+    m = np.zeros(len(pos), np.int64)
+    for i in range(len(pos)):
+        x = pos[i].astype(np.float64) + ds * np.arange(int(k["steps"][i]))[:, None] * vel[i].astype(np.float64)
+        m[i] = int(((x >= 0) & (x < ext)).all(1).sum())
+    assert (k["steps"] < max_steps_fwd(res, h, ds)).all() and m.min() >= 2 and m.max() >= 12 and len(set(m)) >= 4
+    exact = ds * c * c * m
+    assert (np.abs(k["opl"].astype(np.float64) - exact) <= m * 2.0 ** -24 * exact).all(), (k["opl"], exact)
+    assert np.array_equal(_bits(k["xt"][1]), _bits(np.array([8.0, 2.5, 1.125], np.float32)))
+    dopl = np.array([0.7, -1.3, 0.4, 2.0, -0.6], np.float32)
+    r = OH.backtrace_opl(rif, res, pos, vel, k["xt"], k["vt"], k["steps"], None, None, dopl, h, ds)
+    assert np.array_equal(r["steps"].astype(np.int64), m)
+    np.testing.assert_allclose(r["grad"].sum(), (2.0 * dopl.astype(np.float64) * c * ds * m).sum(), rtol=1e-6)
+    one = OH.backtrace_opl(rif, res, pos[1:2], vel[1:2], k["xt"][1:2], k["vt"][1:2], k["steps"][1:2], None, None, dopl[1:2], h, ds)
+    np.testing.assert_allclose(one["grad"].sum(), 2.0 * float(dopl[1]) * c * ds * m[1], rtol=1e-6)
+    # the uniform medium bends nothing: the ray gradients of opl vanish, those of (xt, vt) are the straight flight's
+    assert not r["dpos"].any() and not r["dvel"].any()
+
+
+def test_exit_on_first_iteration_closed_form():
+    """e = 0, K = 1 (the case of tests/test_raygrad.py::test_exit_on_first_iteration_closed_form):
+    dvel = mu = dv + ds dx, dpos = dx + ds J(x0)^T mu + 2 dopl ds n grad n, J = d(n grad n)/dx at x0; opl = ds n(x0)^2."""
+    rif = cases.luneburg(16)
+    h, ds, res = 1.0, 0.5, (16, 16, 16)
+    pos = np.array([[14.8, 7.3, 6.1]], np.float32)          # half a step from the far x face, heading out
+    vel = np.array([[1.0, 0.1, -0.05]], np.float32)
+    k = OH.trace_opl(rif, res, pos, vel, h, ds)
+    assert k["steps"][0] == 1
+    dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
+    dopl = np.array([1.7], np.float32)
+    r = OH.backtrace_opl(rif, res, pos, vel, k["xt"], k["vt"], k["steps"], dx, dv, dopl, h, ds)
+    R = torch.tensor(rif, dtype=torch.float64)
+    x = torch.tensor(pos[0], dtype=torch.float64)
+    n, g = (t[0].numpy() for t in torch_ad.eval_grad(R, x[None], h, torch.tensor([True])))
+    f = lambda y: (lambda nn, gg: (nn[:, None] * gg)[0])(*torch_ad.eval_grad(R, y[None], h, torch.tensor([True])))   # noqa: E731
+    J = torch.autograd.functional.jacobian(f, x).numpy()
+    mu = dv[0].astype(np.float64) + ds * dx[0]
+    pull = 2.0 * float(dopl[0]) * ds * float(n) * g
+    assert np.abs(pull).max() > 1e-2
+    np.testing.assert_allclose(k["opl"][0], ds * float(n) ** 2, rtol=1e-6)
+    np.testing.assert_allclose(r["dvel"][0], mu, rtol=1e-6)
+    np.testing.assert_allclose(r["dpos"][0], dx[0] + ds * J.T @ mu + pull, rtol=1e-5, atol=1e-6)
+
+
+def test_flag_off_scales_the_gradient_splat(oracle):
+    """h = 0.5: without DRRT_FLAG_CORRECTED_H the grid gradient is the flag-on run's value part plus h times its
+    gradient-splat part.  1 / h = 2 and h are powers of two, so the two splat parts agree bit for bit; what is left is that
+    splat_weights rounds val X -+ g once where the parts round separately: <= 4 roundings of 2^-24 per corner relative to
+    |value part| + |splat part|, 1e-6 over the grid with room."""
+    name = "lens16_h05_half"
+    s = scene(name)
+    assert s["h"] == 0.5
+    k = reference(oracle, s, name)[0]
+    run = lambda **kw: OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"],   # noqa: E731
+                                        s["dopl"], s["h"], s["ds"], **kw)
+    off, on = run(corrected_h=False), run(corrected_h=True)
+    val, spl = run(corrected_h=True, parts=1)["grad"], run(corrected_h=True, parts=2)["grad"]
+    assert np.array_equal(spl * s["h"], run(corrected_h=False, parts=2)["grad"])
+    assert np.array_equal(val, run(corrected_h=False, parts=1)["grad"])
+    assert cases.rel_l2(val + spl, on["grad"]) <= 1e-6
+    err = cases.rel_l2(val + s["h"] * spl, off["grad"])
+    print(f"flag off vs value + h * splat: rel-L2 {err:.3e}; |value| {np.linalg.norm(val):.3e} |splat| {np.linalg.norm(spl):.3e}")
+    assert err <= 1e-6
+    assert cases.rel_l2(off["grad"], on["grad"]) > 0.1 and np.linalg.norm(val) > 0 and np.linalg.norm(spl) > 0
+    # the flag does not enter the ray gradients
+    assert np.array_equal(_bits(off["dpos"]), _bits(on["dpos"])) and np.array_equal(_bits(off["dvel"]), _bits(on["dvel"]))
+
+
+def test_abi_and_python_surface():
+    """The C symbols are exported and bound, the profile ids are appended, the methods and the class exist."""
+    from adjointnonlinearraytracing_amd import _lib, drrt, tracer
+    lib = C.CDLL(_lib.LIB_PATH)
+    for name in ("drrt_trace_opl_f32", "drrt_backtrace_opl_f32"):
+        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
+    assert _lib.PROF_NAMES[11] == "trace_opl" and _lib.PROF_NAMES[12] == "backtrace_opl"
+    assert _lib.PROF_NAMES[10] == "backtrace_target_rays" and _lib.PROF_NAMES[6] == "backtrace_rays"
+    assert callable(drrt.TracerC.trace_opl) and callable(drrt.TracerC.backtrace_opl)
+    assert issubclass(tracer.OPLTracerC, torch.autograd.Function)
+    with open(os.path.join(os.path.dirname(_lib.LIB_PATH), "..", "include", "drrt_hip.h")) as f:
+        hdr = f.read()
+    assert "drrt_trace_opl_f32" in hdr and "drrt_backtrace_opl_f32" in hdr
+    assert "#define DRRT_PROF_TRACE_OPL 11" in hdr and "#define DRRT_PROF_BACKTRACE_OPL 12" in hdr
+
+
+def test_abi_argument_checks():
+    """Null pointers, all outputs null, too many rays and bad steps are refused before anything is launched; n = 0 is fine."""
+    from adjointnonlinearraytracing_amd import _lib
+    lib = _lib.load()
+    rif = np.ones(8 * 8 * 8, np.float32)
+    a = np.zeros((4, 3), np.float32); o = np.zeros(4, np.float32); st = np.zeros(4, np.uint32)
+    P = lambda x: C.c_void_p(x.ctypes.data) if x is not None else None    # noqa: E731 (host pointers: never launched)
+
+    def fwd(rif_=rif, res=(8, 8, 8), n=4, pos=a, xt=a, opl=o, steps=st, h=1.0, ds=0.5):
+        return lib.drrt_trace_opl_f32(P(rif_), rif.size, (C.c_int * 3)(*res), n, P(pos), P(a), h, ds, P(xt), P(a), P(opl),
+                                      P(steps), None, None, 0, 0, None)
+
+    def back(rif_=rif, res=(8, 8, 8), n=4, pos=a, xt=a, steps=st, dx=a, dopl=o, grad=None, dpos=a, dvel=a, h=1.0, ds=0.5):
+        return lib.drrt_backtrace_opl_f32(P(rif_), rif.size, (C.c_int * 3)(*res), n, P(pos), P(a), P(xt), P(a), P(steps), P(dx),
+                                          P(a), P(dopl), h, ds, P(grad), P(dpos), P(dvel), None, None, 0, 0, None)
+    for call, kw, rc, msg in (
+            (fwd, dict(rif_=None), _lib.ERR_ARG, "null rif"), (fwd, dict(res=(8, 8, 7)), _lib.ERR_RES_MISMATCH, "Resolution"),
+            (fwd, dict(pos=None), _lib.ERR_ARG, "null ray"), (fwd, dict(xt=None), _lib.ERR_ARG, "null ray"),
+            (fwd, dict(opl=None), _lib.ERR_ARG, "null ray"), (fwd, dict(steps=None), _lib.ERR_ARG, "steps_out"),
+            (fwd, dict(n=1 << 33), _lib.ERR_ARG, "uint32"), (fwd, dict(ds=0.0), _lib.ERR_ARG, "positive"),
+            (fwd, dict(h=float("nan")), _lib.ERR_ARG, "positive"), (fwd, dict(ds=float("inf")), _lib.ERR_ARG, "positive"),
+            (back, dict(rif_=None), _lib.ERR_ARG, "null rif"), (back, dict(res=(1, 8, 64)), _lib.ERR_BAD_RES, "invalid resolution"),
+            (back, dict(pos=None), _lib.ERR_ARG, "null ray"), (back, dict(xt=None), _lib.ERR_ARG, "null ray"),
+            (back, dict(steps=None), _lib.ERR_ARG, "fwd_steps"), (back, dict(dpos=None, dvel=None), _lib.ERR_ARG, "null output"),
+            (back, dict(dpos=None), _lib.ERR_ARG, "together"), (back, dict(dvel=None), _lib.ERR_ARG, "together"),
+            (back, dict(n=1 << 33), _lib.ERR_ARG, "uint32"), (back, dict(ds=-1.0), _lib.ERR_ARG, "positive"),
+            (back, dict(h=0.0), _lib.ERR_ARG, "positive"), (back, dict(h=float("nan")), _lib.ERR_ARG, "positive")):
+        assert call(**kw) == rc, kw
+        assert msg in _lib.last_error(), (kw, _lib.last_error())
+    # a valid call clears the message (no state left behind); null seeds are not an error
+    assert fwd(n=0) == 0 and _lib.last_error() == ""
+    assert back(ds=0.0) == _lib.ERR_ARG and _lib.last_error() != ""
+    assert back(n=0, dx=None, dopl=None, pos=None) == 0 and _lib.last_error() == ""
+
+
+def test_routines_under_sanitizers(tmp_path):
+    """tests/hostcheck/opl_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
+    as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries."""
+    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
+    if not rt or not os.path.exists(OH.HIPCC):
+        pytest.skip("no clang sanitizer runtime in this image")
+    s = scene(list(SCENES)[1])
+    rng = np.random.default_rng(0)
+    bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0], np.float32)
+    arrs = {}
+    for key in ("pos", "vel", "dx", "dv"):
+        extra = s[key][rng.integers(0, len(s[key]), 96)].copy()
+        extra[rng.integers(0, 96, 60), rng.integers(0, 3, 60)] = rng.choice(bad, 60)
+        arrs[key] = np.concatenate([s[key], extra])
+    dopl = np.concatenate([s["dopl"], rng.choice(bad, 96)])
+    n = len(dopl)
+    path = str(tmp_path / "case.bin")
+    with open(path, "wb") as f:
+        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
+        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
+        f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
+        for key in ("pos", "vel", "dx", "dv"):
+            f.write(np.ascontiguousarray(arrs[key], np.float32).tobytes())
+        f.write(dopl.astype(np.float32).tobytes())
+    exe = str(tmp_path / "opl_rays_sanitize")
+    subprocess.run([OH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DOPL_MAIN",
+                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                    "-o", exe, OH.SOURCE], check=True, capture_output=True)
+    r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert f"{n} rays" in r.stdout
+
+
+# ---- GPU tier -------------------------------------------------------------------------------------------------------
+def _same(got, want):
+    got = got.cpu().numpy()
+    return np.array_equal(np.isfinite(got), np.isfinite(want)) and np.array_equal(got, want, equal_nan=True)
+
+
+def _gpu_forward(T, s, dev):
+    from adjointnonlinearraytracing_amd import drrt
+    xt, vt, opl, steps = T.trace_opl(_t(s["rif"], dev), s["res"], _t(s["pos"], dev), _t(s["vel"], dev), s["h"], s["ds"])
+    return xt, vt, opl, steps, drrt.read_stats(), drrt.keep_order(drrt.last_order)
+
+
+def _gpu_back(T, s, dev, fw, order=None, dx="dx", dv="dv", dopl="dopl", **kw):
+    from adjointnonlinearraytracing_amd import drrt
+    xt, vt, _, steps = fw[:4]
+    seed = lambda k: None if k is None else _t(s[k], dev)      # noqa: E731
+    out = T.backtrace_opl(_t(s["rif"], dev), s["res"], _t(s["pos"], dev), _t(s["vel"], dev), xt, vt, steps, seed(dx), seed(dv),
+                          seed(dopl), s["h"], s["ds"], order=order, **kw)
+    return out, drrt.read_stats()
+
+
+_hosts = {}
+
+
+def host(name):
+    if name not in _hosts:
+        s = scene(name)
+        k = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+        r = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"], s["dopl"],
+                             s["h"], s["ds"], corrected_h=True)
+        _hosts[name] = (k, r)
+    return _hosts[name]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("pair", [False, True])
+@pytest.mark.parametrize("name", list(SCENES))
+def test_kernels_match_host_build(gpu, name, pair):
+    """k_trace_opl and k_backtrace_opl (plain and pair-copy gathers, in the forward's visit order) == the host build: rays
+    and statistics bit for bit, the grid gradient to the order of its atomic sums.  xt, vt, steps are also TracerC.trace's."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = scene(name)
+    k, r = host(name)
+    T = drrt.TracerC()
+    with drrt.using(pair_grid=pair, corrected_h=True):
+        fw = _gpu_forward(T, s, gpu)
+        xt, vt, opl, steps, st, order = fw
+        assert order is not None
+        assert _same(xt, k["xt"]) and _same(vt, k["vt"]) and _same(opl, k["opl"])
+        assert np.array_equal(steps.cpu().numpy().astype(np.int64), k["steps"].astype(np.int64))
+        assert st["n_failed"] == k["n_failed"] > 0 and st["ray_steps"] == int(k["steps"].astype(np.int64).sum())
+        (grad, dpos, dvel), bst = _gpu_back(T, s, gpu, fw, order=order)
+        xt0, vt0 = T.trace(_t(s["rif"], gpu), s["res"], _t(s["pos"], gpu), _t(s["vel"], gpu), s["h"], s["ds"])
+        steps0 = drrt.keep_steps(drrt.last_steps)
+    assert torch.equal(xt0, xt) and torch.equal(vt0, vt) and torch.equal(steps0, steps)
+    assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
+    assert bst["ray_steps"] == r["ray_steps"] and bst["n_failed"] == r["n_failed"] > 0
+    err = cases.rel_l2(grad.cpu().numpy(), r["grad"])
+    print(f"{name} pair={pair}: grid rel-L2 vs host {err:.3e}")
+    assert err <= ATOMIC_TOL
+
+
+@pytest.mark.gpu
+def test_kernel_variants(gpu):
+    """The adjoint with its own sort, accumulating into a pre-filled grid (DRRT_FLAG_NO_ZERO), without the grid, without
+    the ray outputs, and with null seeds: what remains is unchanged bit for bit (rays) or to the order of the sums (grid)."""
+    from adjointnonlinearraytracing_amd import drrt
+    name = "box7x11x5_h05_multi"
+    s = scene(name)
+    k, r = host(name)
+    T = drrt.TracerC()
+    with drrt.using(corrected_h=True, pair_grid=False):
+        fw = _gpu_forward(T, s, gpu)
+        (grad, dpos, dvel), st = _gpu_back(T, s, gpu, fw)                                  # sorts for itself
+        assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"]) and cases.rel_l2(grad.cpu().numpy(), r["grad"]) <= ATOMIC_TOL
+        assert st["ray_steps"] == r["ray_steps"] and st["n_failed"] == r["n_failed"]
+        with drrt.using(sort_rays=False):
+            (grad, dpos, dvel), st = _gpu_back(T, s, gpu, fw)                              # caller order
+        assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"]) and cases.rel_l2(grad.cpu().numpy(), r["grad"]) <= ATOMIC_TOL
+        fill = torch.full((s["rif"].size,), 3.0, device=gpu)
+        (grad, dpos, dvel), _ = _gpu_back(T, s, gpu, fw, order=fw[5], into=fill)
+        assert grad.data_ptr() == fill.data_ptr() and _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
+        assert cases.rel_l2(fill.cpu().numpy().astype(np.float64) - 3.0, r["grad"]) <= ATOMIC_TOL
+        (grad, dpos, dvel), st = _gpu_back(T, s, gpu, fw, order=fw[5], grid=False)
+        assert grad is None and _same(dpos, r["dpos"]) and _same(dvel, r["dvel"]) and st["ray_steps"] == r["ray_steps"]
+        (grad, dpos, dvel), st = _gpu_back(T, s, gpu, fw, order=fw[5], rays=False)
+        assert dpos is None and dvel is None and cases.rel_l2(grad.cpu().numpy(), r["grad"]) <= ATOMIC_TOL
+        assert st["ray_steps"] == r["ray_steps"] and st["n_failed"] == r["n_failed"]
+        # null seeds on the rays == zero seeds
+        r0 = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], None, None, s["dopl"],
+                              s["h"], s["ds"], corrected_h=True)
+        (grad, dpos, dvel), _ = _gpu_back(T, s, gpu, fw, order=fw[5], dx=None, dv=None)
+        assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"]) and cases.rel_l2(grad.cpu().numpy(), r0["grad"]) <= ATOMIC_TOL
+        assert not np.array_equal(r0["dpos"], r["dpos"])
+    # flag off
+    roff = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"], s["dopl"],
+                            s["h"], s["ds"], corrected_h=False)
+    with drrt.using(corrected_h=False, pair_grid=False):
+        (grad, dpos, dvel), _ = _gpu_back(T, s, gpu, fw, order=fw[5])
+    assert _same(dpos, r["dpos"]) and cases.rel_l2(grad.cpu().numpy(), roff["grad"]) <= ATOMIC_TOL
+    assert cases.rel_l2(roff["grad"], r["grad"]) > 0.1
+
+
+@pytest.mark.gpu
+def test_single_ray_and_no_rays(gpu):
+    from adjointnonlinearraytracing_amd import drrt
+    name = "lens16_h1_half"
+    s = scene(name)
+    k, _ = host(name)
+    i = int(np.where((s["labels"] == "inside") & (k["steps"] > 4) & (k["steps"] < 100))[0][0])
+    T = drrt.TracerC()
+    for sl in (slice(i, i + 1), slice(0, 0)):
+        one = dict(s, **{key: s[key][sl] for key in ("pos", "vel", "dx", "dv", "dopl")})
+        with drrt.using(corrected_h=True):
+            fw = _gpu_forward(T, one, gpu)
+            (grad, dpos, dvel), st = _gpu_back(T, one, gpu, fw)
+        k1 = OH.trace_opl(one["rif"], one["res"], one["pos"], one["vel"], one["h"], one["ds"])
+        r1 = OH.backtrace_opl(one["rif"], one["res"], one["pos"], one["vel"], k1["xt"], k1["vt"], k1["steps"], one["dx"],
+                              one["dv"], one["dopl"], one["h"], one["ds"], corrected_h=True)
+        assert _same(fw[0], k1["xt"]) and _same(fw[1], k1["vt"]) and _same(fw[2], k1["opl"])
+        assert np.array_equal(fw[3].cpu().numpy().astype(np.int64), k1["steps"].astype(np.int64))
+        assert _same(dpos, r1["dpos"]) and _same(dvel, r1["dvel"]) and tuple(dpos.shape) == (sl.stop - sl.start, 3)
+        assert st["ray_steps"] == r1["ray_steps"] and st["n_failed"] == 0
+        if sl.stop > sl.start:
+            assert r1["ray_steps"] > 4 and cases.rel_l2(grad.cpu().numpy(), r1["grad"]) <= 1e-6      # one lane: the host's order
+        else:
+            assert not bool(grad.any()) and grad.numel() == s["rif"].size
+
+
+def _plane_case(h=1.0):
+    """A 12^2 plane source outside the y = 0 face of cases.luneburg(16) (tracer.* pass rif.shape as res)."""
+    ds = h / 2
+    rng = np.random.default_rng(3)
+    u = (np.stack(np.meshgrid(np.arange(12), np.arange(12), indexing="ij"), -1).reshape(-1, 2) + rng.random((144, 2))) / 12
+    pos = (np.stack([1.0 + 13.0 * u[:, 0], np.full(144, -0.15), 1.0 + 13.0 * u[:, 1]], -1).astype(np.float32) * np.float32(h))
+    vel = rng.normal(0, 0.05, (144, 3)); vel[:, 1] = 1.0
+    vel = (vel / np.linalg.norm(vel, axis=1, keepdims=True)).astype(np.float32)
+    return dict(rif=cases.luneburg(16), res=(16, 16, 16), h=h, ds=ds, pos=pos, vel=vel,
+                dx=rng.normal(size=pos.shape).astype(np.float32), dv=rng.normal(size=pos.shape).astype(np.float32),
+                dopl=rng.normal(size=144).astype(np.float32))
+
+
+def _ad_grads(s, dev, seeds, rif_grad=True, x_grad=True, v_grad=True, dtype=torch.float32):
+    """OPLTracerC.apply -> L = <dx, xt> + <dv, vt> + <dopl, opl> -> backward -> (rif.grad, x.grad, v.grad, outputs)."""
+    from adjointnonlinearraytracing_amd import tracer
+    rif = _t(s["rif"], dev).requires_grad_(rif_grad)
+    x = _t(s["pos"], dev).to(dtype).requires_grad_(x_grad)
+    v = _t(s["vel"], dev).requires_grad_(v_grad)
+    out = tracer.OPLTracerC.apply(rif, x, v, s["h"], s["ds"])
+    loss = sum((o * _t(np.asarray(w, np.float32), dev)).sum() for o, w in zip(out, seeds) if w is not None)
+    if loss.requires_grad:
+        loss.backward()
+    torch.cuda.synchronize()
+    return rif.grad, x.grad, v.grad, [o.detach() for o in out]
+
+
+@pytest.mark.gpu
+def test_opl_tracer_end_to_end(gpu, oracle):
+    """OPLTracerC.apply -> loss on all three outputs -> backward against float64 autograd on the tie-free rays (the seeds
+    of the others zeroed on both sides); the bounds of the CPU tier."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _plane_case()
+    k, tie_free, opl64, _ = reference(oracle, s, "plane12")
+    assert tie_free.sum() >= 120
+    seeds = (s["dx"] * tie_free[:, None], s["dv"] * tie_free[:, None], s["dopl"] * tie_free)
+    gr, gp, gv = autograd64(s, *seeds)
+    with drrt.using(corrected_h=True):
+        grif, gx, gvel, out = _ad_grads(s, gpu, seeds)
+        assert _same(out[0], k["xt"]) and _same(out[1], k["vt"]) and _same(out[2], k["opl"])
+        err = rel_err(gx.cpu().numpy(), gvel.cpu().numpy(), gp, gv)[tie_free]
+        gerr = cases.rel_l2(grif.cpu().numpy(), gr)
+        oerr = (np.abs(k["opl"] - opl64) / opl64)[tie_free].max()
+        print(f"OPLTracerC: {tie_free.sum()} tie-free rays; opl rel err {oerr:.3e}; ray grad rel err max {err.max():.3e}; grid rel-L2 {gerr:.3e}")
+        assert tuple(grif.shape) == s["rif"].shape and oerr <= OPL_TOL and err.max() <= GRAD_TOL and gerr <= GRID_TOL
+        # a loss on opl alone (the other two outputs unused: their seeds reach the library as null pointers)
+        gr1, gp1, gv1 = autograd64(s, 0 * seeds[0], 0 * seeds[1], seeds[2])
+        grif, gx, gvel, _ = _ad_grads(s, gpu, (None, None, seeds[2]))
+        assert rel_err(gx.cpu().numpy(), gvel.cpu().numpy(), gp1, gv1)[tie_free].max() <= GRAD_TOL
+        assert cases.rel_l2(grif.cpu().numpy(), gr1) <= GRID_TOL
+        # only what is asked for comes back
+        for rg, xg, vg in ((True, False, False), (False, True, False), (False, False, True), (True, False, True)):
+            a, b, c, _ = _ad_grads(s, gpu, seeds, rg, xg, vg)
+            assert ((a is not None), (b is not None), (c is not None)) == (rg, xg, vg)
+        with pytest.raises(RuntimeError, match="float32"):
+            _ad_grads(s, gpu, seeds, True, True, False, dtype=torch.float64)
+    # h = 0.5 (the same rays scaled by a power of two: every fp32 result scales exactly, so the same errors): the options of
+    # the forward's thread reach the backward launch, which autograd runs on a thread of its own
+    s2 = _plane_case(h=0.5)
+    assert np.array_equal(s2["pos"], s["pos"] * np.float32(0.5))
+    gr2 = autograd64(s2, *seeds)[0]
+    with drrt.using(corrected_h=True):
+        on = _ad_grads(s2, gpu, seeds)[0].cpu().numpy()
+    with drrt.using(corrected_h=False):
+        off = _ad_grads(s2, gpu, seeds)[0].cpu().numpy()
+    assert cases.rel_l2(on, gr2) <= GRID_TOL and cases.rel_l2(off, gr2) > 0.1
+
+
+@pytest.mark.gpu
+def test_opl_tracer_launches(gpu):
+    """Forward: ["trace_opl"].  Backward: ONE backtrace_opl launch, plus the zero-fill when rif requires grad; none when
+    nothing requires grad.  (The sort belongs to the forward when options.sort_rays is on: the adjoint takes its order.)"""
+    from adjointnonlinearraytracing_amd import _lib, drrt
+    s = _plane_case()
+    seeds = (s["dx"], s["dv"], s["dopl"])
+    lib = _lib.load()
+
+    def launches(**kw):
+        lib.drrt_profile_begin(256)
+        try:
+            _ad_grads(s, gpu, seeds, **kw)
+            return [name for name, _ in _lib.profile_collect()]
+        finally:
+            lib.drrt_profile_end()
+    for sort, fwd in ((False, ["trace_opl"]), (True, ["sort", "trace_opl"])):
+        with drrt.using(sort_rays=sort, pair_grid=False):
+            assert launches(rif_grad=False, x_grad=False, v_grad=False) == fwd
+            assert launches() == fwd + ["zero", "backtrace_opl"]
+            assert launches(x_grad=False, v_grad=False) == fwd + ["zero", "backtrace_opl"]
+            assert launches(rif_grad=False) == fwd + ["backtrace_opl"]
+            assert launches(rif_grad=False, x_grad=False) == fwd + ["backtrace_opl"]
+
+
+@pytest.mark.gpu
+def test_demo(gpu):
+    """examples/opl_demo.py at 17^3, 3 views of 24^2 rays, 20 iterations: the loss ends below where it began."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    try:
+        import opl_demo
+    finally:
+        sys.path.pop(0)
+    _, _, hist, err = opl_demo.run(res=17, views=3, side=24, iters=20, verbose=False)
+    print(f"opl_demo: loss {hist[0]:.4e} -> {hist[-1]:.4e} (ratio {hist[-1] / hist[0]:.4f}); rms(n - truth) {err[0]:.3e} -> {err[-1]:.3e}")
+    assert len(hist) == 20 and np.isfinite(hist).all() and hist[-1] < hist[0]

@@ -47,6 +47,22 @@ target  drrt_backtrace_target_rays_f32 (k_target_rays_count + k_backtrace_target
         Also writes the JSON, with the library's version string (source digest), to --out (default
         profiles/target_raygrad_bench.json).
 
+opl     drrt_trace_opl_f32 / drrt_backtrace_opl_f32 (k_trace_opl, k_backtrace_opl) next to the calls they go with: 256^3 grid,
+        1 048 576 rays of bench.py's plane source, ds = h / 2, through two media: `luneburg` (the ball: every ray passes the
+        few voxels around the focus, the worst case for the plain atomics k_backtrace_opl scatters with) and `tomo_weak`
+        (bench.make_grid_tomo, n = 1 + 3e-4 U: straight rays, the representative case of a phase measurement).
+            trace               TracerC.trace                      (k_trace_flat)
+            trace_opl           TracerC.trace_opl                  (k_trace_opl)
+            backtrace           TracerC.backtrace                  (dL/dn: classification + window kernel)
+            backtrace_rays      TracerC.backtrace_rays             (dL/dpos, dL/dvel)
+            backtrace_opl_all   TracerC.backtrace_opl              (dL/dn, dL/dpos, dL/dvel from seeds on xt, vt, opl)
+            backtrace_opl_grid  TracerC.backtrace_opl(rays=False)  (dL/dn alone)
+        The six calls are timed alternately like the cases below.  Output per medium and call: median, minimum, maximum ms
+        and stats.ray_steps, and the ratios trace_opl / trace, backtrace_opl_all / (backtrace + backtrace_rays),
+        backtrace_opl_grid / backtrace.
+        usage: bench_raygrad.py opl [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string (source digest), to --out (default profiles/opl_bench.json).
+
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
 over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
@@ -287,6 +303,62 @@ def target(a, dev):
     return out
 
 
+# ---- opl ------------------------------------------------------------------------------------------------------------
+def opl(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # make_workload's rays; the grids are made below
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for medium, make in (("luneburg", bench.make_grid), ("tomo_weak", bench.make_grid_tomo)):
+        rif = make(a.grid, dev)
+        res = tuple(rif.shape)
+        xt, vt, _, steps = T.trace_opl(rif, res, pos, vel, h, ds)
+        order = drrt.keep_order(drrt.last_order)
+        calls = {
+            "trace": lambda: T.trace(rif, res, pos, vel, h, ds),
+            "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
+            "backtrace": lambda: T.backtrace(rif, res, xt, vt, one, one, h, ds, order=order),
+            "backtrace_rays": lambda: T.backtrace_rays(rif, res, pos, vel, xt, vt, steps, one, one, h, ds, order=order),
+            "backtrace_opl_all": lambda: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order),
+            "backtrace_opl_grid": lambda: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, rays=False,
+                                                          order=order),
+        }
+        if a.once:
+            for fn in calls.values():
+                fn()
+            torch.cuda.synchronize()
+            continue
+        rsteps, ms = {}, {k: [] for k in calls}
+        for k, fn in calls.items():
+            for _ in range(max(a.warmup, 1)):
+                fn()
+            rsteps[k] = drrt.read_stats()["ray_steps"]
+        torch.cuda.synchronize()
+        for _ in range(a.rounds):
+            for k, fn in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ms[k].append(e0.elapsed_time(e1))
+        med = {k: statistics.median(v) for k, v in ms.items()}
+        r = {k: dict(median_ms=med[k], min_ms=min(v), max_ms=max(v), ray_steps=rsteps[k]) for k, v in ms.items()}
+        r["trace_opl_over_trace"] = med["trace_opl"] / med["trace"]
+        r["backtrace_opl_all_over_backtrace_plus_backtrace_rays"] = med["backtrace_opl_all"] / (med["backtrace"] + med["backtrace_rays"])
+        r["backtrace_opl_grid_over_backtrace"] = med["backtrace_opl_grid"] / med["backtrace"]
+        out[medium] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -309,14 +381,19 @@ def main():
     p_target.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles",
                                                         "target_raygrad_bench.json"))
     p_target.set_defaults(run=target)
-    for p in (p_cable, p_stop, p_target):
+    p_opl = sub.add_parser("opl")
+    p_opl.add_argument("--grid", type=int, default=256)
+    p_opl.add_argument("--rays", type=int, default=1 << 20)
+    p_opl.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "opl_bench.json"))
+    p_opl.set_defaults(run=opl)
+    for p in (p_cable, p_stop, p_target, p_opl):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
