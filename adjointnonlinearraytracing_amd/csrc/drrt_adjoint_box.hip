@@ -60,6 +60,7 @@ constexpr int kWinX = DRRT_WIN, kWinY = DRRT_WIN, kWinZ = DRRT_WIN;
 constexpr int kWinPX = DRRT_WIN + DRRT_WIN_PAD;           // row pitch
 constexpr int kWinSY = kWinPX, kWinSZ = kWinPX * kWinY;   // LDS strides of y and z
 constexpr int kWinFloats = kWinSZ * kWinZ;                // 810 slots = 6.3 KiB per wave (9^3 window, pitch 10)
+static_assert(kWinFloats < (1 << 16), "win_face_key keeps a window slot in 16 bits");
 
 // Flush the wave's window into the global grid and leave it zeroed.  Called with all 64 lanes.
 // The window's rows (a row = the kWinX slots of one (ly, lz)) are contiguous in LDS at pitch kWinPX, so the flush walks
@@ -93,7 +94,7 @@ __device__ __forceinline__ void win_flush(win_t* win, int ox, int oy, int oz, fl
     }
 #pragma unroll
     for (int b = 0; b < kBatch; ++b)
-      if (v[b] != (win_t)0) atomic_add_f32(grad + g[b], (float)v[b]);
+      if (v[b] != (win_t)0) atomic_add_f32_at(grad, g[b], (float)v[b]);
   }
   wave_lds_fence();
 }
@@ -164,12 +165,49 @@ __device__ __forceinline__ bool flat_emit8(win_t* win, int wsy, int wsz, float* 
     }
     return true;
   }
-  float* g = grad + base;
-  atomic_add_f32(g, p00.x);            atomic_add_f32(g + 1, p00.y);
-  atomic_add_f32(g + sy, p10.x);       atomic_add_f32(g + sy + 1, p10.y);
-  atomic_add_f32(g + sz, p01.x);       atomic_add_f32(g + sz + 1, p01.y);
-  atomic_add_f32(g + sz + sy, p11.x);  atomic_add_f32(g + sz + sy + 1, p11.y);
+  const unsigned g = (unsigned)base, gy = g + (unsigned)sy, gz = g + (unsigned)sz, gzy = gz + (unsigned)sy;
+  atomic_add_f32_at(grad, g, p00.x);    atomic_add_f32_at(grad, g + 1u, p00.y);
+  atomic_add_f32_at(grad, gy, p10.x);   atomic_add_f32_at(grad, gy + 1u, p10.y);
+  atomic_add_f32_at(grad, gz, p01.x);   atomic_add_f32_at(grad, gz + 1u, p01.y);
+  atomic_add_f32_at(grad, gzy, p11.x);  atomic_add_f32_at(grad, gzy + 1u, p11.y);
   return false;
+}
+
+// one face of a regular cell handed to the window: corners e0..e3 go to the slots qi, qi + LP, qi + LQ, qi + LQ + LP, where
+// qi = key & 0xffff: the key names the face (slot of its first corner | axis << 16; win_face_key).
+// Pair / quad pre-reduction: lanes of a quad that hand over the same face (same key; the lanes of a quad that are not in
+// the branch read as -1 / 0) add once, the pair's or the quad's sums.  Returns whether this lane added.
+__device__ __forceinline__ constexpr int win_face_key(int slot_offset, int axis) { return slot_offset | (axis << 16); }
+__device__ __forceinline__ bool win_emit4(win_t* win, int key, int LP, int LQ, float e0, float e1, float e2, float e3) {
+  const int qi = key & 0xffff;
+  const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
+  const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
+  const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
+  const bool psame = k1 == key;
+  const bool same = psame & (k2 == key) & (k3 == key);
+  // the sums are built under the tests (a lane's pair / quad partners pass the same test, so the lanes it reads are enabled):
+  // q = e (+ the pair partner's), then (+ the other pair's) -- four v_add_f32_dpp per level, no selects
+  float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
+  if (psame) {
+    q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
+    q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
+    q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
+    q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
+  }
+  if (same) {
+    q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
+    q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
+    q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
+    q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
+  }
+  const unsigned ql = threadIdx.x & 3u;
+  const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
+  if (add) {
+    win_t* q = win + qi;
+    atomicAdd(q, (win_t)q0);      atomicAdd(q + LP, (win_t)q1);
+    atomicAdd(q + LQ, (win_t)q2); atomicAdd(q + LQ + LP, (win_t)q3);
+  }
+  return add;
 }
 
 __global__ void __launch_bounds__(kBlock) k_bundle_classify(BackArgs a) {
@@ -278,26 +316,29 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
   }
   WinOrg W;                                                    // the wave's window (wave-uniform)
   W.ox = W.oy = W.oz = -(1 << 28);                             // far away = nothing is inside
-  // the cell the ray stands on, located IN PLACE: flat index and coordinates of corner 000, in-cell fractions, strictly
-  // interior / regular (no clamped neighbour), window slot.  A boundary cell's clamp offsets are not carried: the
-  // boundary branch at the top of the step re-derives them from the position (locate()).
+  // the cell the ray stands on, located IN PLACE: flat index and coordinates of corner 000, in-cell fractions, window slot.
+  // A boundary cell's clamp offsets are not carried: the boundary branch at the top of the step re-derives them from the
+  // position (locate()).  The cell's predicates live in the two integers their consumers compare anyway, not in flags:
+  //   strictly interior  <=>  tbase >= 0   (the lane holds the cell's taps, gathered ahead; a boundary cell has tbase = -1)
+  //   regular (no clamped neighbour)  <=>  lidx > kIrregular;  lidx >= 0: window slot, kMiss: regular, outside the window
+  //   (a miss votes for a re-anchor)
+  constexpr int kMiss = -1, kIrregular = -2;
+  constexpr int kNoFace = -(1 << 20);                        // no window slot is that far below kMiss
   int base = 0, ix = 0, iy = 0, iz = 0;
   float wx = 0.f, wy = 0.f, wz = 0.f;
-  bool interior = false, regular = false;
-  int lidx = -1;
+  int lidx = kIrregular;
   f4 q0 = f4{0.f, 0.f, 0.f, 0.f}, q1 = q0;                   // the taps, as gathered (gather_rows)
   int tbase = -1;                                            // cell whose taps the lane holds (-1: none)
   Taps st;                                                   // MODE 1: the sdf taps of that cell, gathered with them
   st.a = st.b = st.e = st.f = f2{0.f, 0.f};
   f2 p00 = f2{0.f, 0.f}, p10 = p00, p01 = p00, p11 = p00;   // accumulators of the cell: x-pairs at (y0,z0) (y1,z0) (y0,z1) (y1,z1)
-  bool miss = false;                                         // the cell just entered lies outside the window
   const TapRows R = tap_rows<PAIR>(V);                       // wave-uniform row pointers + ONE 32-bit byte offset per lane
   // step to the next sample (:420), locate its cell in place and issue its gather unless the lane holds those taps
   auto step_locate = [&](int& nbase, bool& nregular, bool move = true) {      // move = false: locate only (a resumed ray)
     if (move) { s.x = fmaf(-a.ds, s.vx, s.x); s.y = fmaf(-a.ds, s.vy, s.y); s.z = fmaf(-a.ds, s.vz, s.z); }
     const float fx = s.x * V.inv_h, fy = s.y * V.inv_h, fz = s.z * V.inv_h;
     ix = cvt_floor_i32(fx); iy = cvt_floor_i32(fy); iz = cvt_floor_i32(fz);
-    interior = (((unsigned)ix - 1u) < V.lx) & (((unsigned)iy - 1u) < V.ly) & (((unsigned)iz - 1u) < V.lz);
+    const bool interior = (((unsigned)ix - 1u) < V.lx) & (((unsigned)iy - 1u) < V.ly) & (((unsigned)iz - 1u) < V.lz);
     if (interior) {
       // v_fract == f - floor(f) bit for bit for the non-negative coordinates of an interior cell
       wx = __builtin_amdgcn_fractf(fx); wy = __builtin_amdgcn_fractf(fy); wz = __builtin_amdgcn_fractf(fz);
@@ -323,8 +364,8 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     int nbase; bool nregular;
     if (resume) step_locate(nbase, nregular, false);         // the saved position IS the next sample
     else        step_locate(nbase, nregular);                // first sample
-    base = nbase; regular = nregular;
-    miss = regular;                                          // no window yet
+    base = nbase;
+    lidx = nregular ? kMiss : kIrregular;                    // no window yet
   }
   bool dirty = false;
   int cooldown = 0;
@@ -334,8 +375,9 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
   float bx0 = 3.0e38f, by0 = 3.0e38f, bz0 = 3.0e38f, bx1 = -3.0e38f, by1 = -3.0e38f, bz1 = -3.0e38f;
   // event counters of the debug instantiation (a.dbg): [4] one-face leaves handed to the window, [5] of those, lanes that
   // issued the LDS adds after the pair / quad pre-reduction, [6] one-face leaves that went to global atomics (cell outside
-  // the window), [7] leaves that handed over all eight corners, [8] wave-steps, [9] wave-steps with leaves across >= 2 axes
-  unsigned ev_face = 0, ev_add = 0, ev_glob = 0, ev_all8 = 0, ev_wsteps = 0, ev_multi = 0;
+  // the window), [7] leaves that handed over all eight corners, [8] wave-steps, [9] wave-steps with leaves across >= 2 axes,
+  // [15] ray-steps in clamped cells (splat straight to the grid)
+  unsigned ev_face = 0, ev_add = 0, ev_glob = 0, ev_all8 = 0, ev_wsteps = 0, ev_multi = 0, ev_clamp = 0;
 
 #define WSY kWinSY
 #define WSZ kWinSZ
@@ -343,12 +385,13 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     for (int it = 0; it < a.max_steps; ++it) {
       if (!__any(s.active)) break;                                              // wave-uniform exit
       // ---- (re-)anchor the window around the cells the rays stand on (wave-uniform branch) ----
-      const unsigned long long mm = __ballot(s.active & miss);
+      const unsigned long long mm = __ballot(s.active & (lidx == kMiss));
       if (mm != 0ull && cooldown == 0) {
         if (dirty) {
           win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane);
           dirty = false; ++n_flush;
         }
+        const bool regular = lidx > kIrregular;
         const bool ok = s.active & regular;
         const unsigned long long cm = __ballot(ok);
         const int first = __ffsll((long long)cm) - 1, last = 63 - __clzll((long long)cm);
@@ -367,15 +410,15 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
           ox = max(0, min(ox, V.W - kWinX)); oy = max(0, min(oy, V.H - kWinY)); oz = max(0, min(oz, V.D - kWinZ));
           W.ox = __builtin_amdgcn_readfirstlane(ox); W.oy = __builtin_amdgcn_readfirstlane(oy);
           W.oz = __builtin_amdgcn_readfirstlane(oz);
-          lidx = regular ? WIN_INDEX(ix, iy, iz) : -1;                          // every lane's cell, in the new window
-          miss = ok & (lidx < 0);
+          lidx = regular ? WIN_INDEX(ix, iy, iz) : kIrregular;                  // every lane's cell, in the new window
         }
-        cooldown = (__ballot(miss) != 0ull) ? 4 : 0;                            // incoherent wave: do not thrash
+        cooldown = (__ballot(ok & (lidx < 0)) != 0ull) ? 4 : 0;                 // incoherent wave: do not thrash
       } else if (cooldown > 0) {
         --cooldown;
       }
       bool used_lds = false;
       if (s.active) {
+        const bool interior = tbase >= 0, regular = lidx > kIrregular;
         if (!interior) taps_set<PAIR>(fetch(V.data, locate(V, s.x, s.y, s.z)), q0, q1);   // boundary cell (clamped neighbours): fetched here, not ahead
         Cell c;                                              // what adj_sample reads of the cell: fractions, interior
         c.base = 0; c.ix = c.iy = c.iz = 0; c.ox = c.oy = c.oz = 0;
@@ -400,15 +443,15 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
               // clamped boundary cell: taps coincide; straight to the grid
               const Cell cb = locate(V, px, py, pz);
               const Corners w = splat_weights(cb.wx, cb.wy, cb.wz, dn * a.ds, nds * s.mx, nds * s.my, nds * s.mz);
-              float* g = a.grad + cb.base;
-              atomic_add_f32(g, w.c000);                     atomic_add_f32(g + cb.ox, w.c100);
-              atomic_add_f32(g + cb.oy, w.c010);             atomic_add_f32(g + cb.oy + cb.ox, w.c110);
-              atomic_add_f32(g + cb.oz, w.c001);             atomic_add_f32(g + cb.oz + cb.ox, w.c101);
-              atomic_add_f32(g + cb.oz + cb.oy, w.c011);     atomic_add_f32(g + cb.oz + cb.oy + cb.ox, w.c111);
+              const unsigned g = (unsigned)cb.base, gy = g + (unsigned)cb.oy, gz = g + (unsigned)cb.oz, gzy = gz + (unsigned)cb.oy;
+              atomic_add_f32_at(a.grad, g, w.c000);          atomic_add_f32_at(a.grad, g + (unsigned)cb.ox, w.c100);
+              atomic_add_f32_at(a.grad, gy, w.c010);         atomic_add_f32_at(a.grad, gy + (unsigned)cb.ox, w.c110);
+              atomic_add_f32_at(a.grad, gz, w.c001);         atomic_add_f32_at(a.grad, gz + (unsigned)cb.ox, w.c101);
+              atomic_add_f32_at(a.grad, gzy, w.c011);        atomic_add_f32_at(a.grad, gzy + (unsigned)cb.ox, w.c111);
+              if (DBG && a.dbg) ++ev_clamp;
             }
             // step to the next sample and issue its gather (it + 1 == max_steps: located and fetched, never used)
-            const int old_base = base, old_lidx = lidx;
-            const bool old_regular = regular;
+            const int old_base = base;
             int nbase; bool nregular;
             step_locate(nbase, nregular);
             // second half of adj_contrib: lambda / mu (:434-435)
@@ -421,84 +464,85 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
             s.lz = fmaf(a.ds, fmaf(dn, m.gz, m.n * hmz), s.lz);
             s.mx = fmaf(a.ds, s.lx, s.mx); s.my = fmaf(a.ds, s.ly, s.my); s.mz = fmaf(a.ds, s.lz, s.mz);
             // ---- the ray leaves its cell ----
-            if (nbase != old_base || !interior) {
-              base = nbase; regular = nregular;
+            if (nbase != old_base || tbase < 0) {
+              base = nbase;
               const int d = nbase - old_base;
-              if (d != 0 || regular != old_regular) {
-                const bool ax = (d == 1) | (d == -1), ay = (d == V.sy) | (d == -V.sy), az = (d == V.sz) | (d == -V.sz);
-                if (old_regular) {
-                  if (regular & (ax | ay | az)) {
-                    // one face crossed: emit the face left behind, carry the shared one
-                    const bool fwd = d > 0;
-                    if (DBG && a.dbg) {
-                      const int nax = (__ballot(ax) != 0ull) + (__ballot(ay) != 0ull) + (__ballot(az) != 0ull);
-                      if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
-                    }
-                    // emitted corners e0..e3 and carried ones, in (p, q) in-face order; LDS / grid strides of p, q and of the axis
-                    float e0, e1, e2, e3;
-                    int lp, lq, la, gp, gq, ga;
-                    if (ay) {
-                      const f2 ea = fwd ? p00 : p10, eb = fwd ? p01 : p11;
-                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
-                      const f2 ka = fwd ? p10 : p00, kb = fwd ? p11 : p01;
-                      p00 = fwd ? ka : f2{0.f, 0.f}; p01 = fwd ? kb : f2{0.f, 0.f};
-                      p10 = fwd ? f2{0.f, 0.f} : ka; p11 = fwd ? f2{0.f, 0.f} : kb;
-                      lp = 1; lq = WSZ; la = WSY; gp = 1; gq = V.sz; ga = V.sy;
-                    } else if (az) {
-                      const f2 ea = fwd ? p00 : p01, eb = fwd ? p10 : p11;
-                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
-                      const f2 ka = fwd ? p01 : p00, kb = fwd ? p11 : p10;
-                      p00 = fwd ? ka : f2{0.f, 0.f}; p10 = fwd ? kb : f2{0.f, 0.f};
-                      p01 = fwd ? f2{0.f, 0.f} : ka; p11 = fwd ? f2{0.f, 0.f} : kb;
-                      lp = 1; lq = WSY; la = WSZ; gp = 1; gq = V.sy; ga = V.sz;
-                    } else {
+              if (d != 0 || nregular != regular) {
+                if (regular) {
+                  // One face crossed (both cells regular, the flat index moved by one stride): emit the face left behind,
+                  // carry the shared one.  Six cases, axis and direction compile-time in each: a case copies the four
+                  // emitted corners out (e0..e3, in (p, q) in-face order), moves the carried ones once, and names the face's
+                  // window slot and strides; ONE emission follows the cases (wave-steps whose lanes leave across two or more
+                  // axes are the common kind -- over half of the headline's -- so an emission per case would run twice there).
+                  // AX: 0 = x, 1 = y, 2 = z; FWD: towards the higher index.
+                  float e0, e1, e2, e3;
+                  int key = kNoFace, lp, lq;                 // the face (win_face_key; a case sets it), window strides of p and q (slots)
+                  auto face = [&](auto AX, auto FWD) {
+                    constexpr int ax = decltype(AX)::value;
+                    constexpr bool fwd = decltype(FWD)::value;
+                    constexpr f2 zero = f2{0.f, 0.f};
+                    asm volatile("");                          // keeps the case's moves under the case's test (not speculated above it)
+                    key = lidx + win_face_key(fwd ? 0 : (ax == 0 ? 1 : (ax == 1 ? WSY : WSZ)), ax);   // lidx < 2^16: no carry into the axis
+                    lp = ax == 0 ? WSY : 1; lq = ax == 2 ? WSY : WSZ;
+                    if (ax == 0) {
                       e0 = fwd ? p00.x : p00.y; e1 = fwd ? p10.x : p10.y; e2 = fwd ? p01.x : p01.y; e3 = fwd ? p11.x : p11.y;
                       p00 = fwd ? f2{p00.y, 0.f} : f2{0.f, p00.x}; p10 = fwd ? f2{p10.y, 0.f} : f2{0.f, p10.x};
                       p01 = fwd ? f2{p01.y, 0.f} : f2{0.f, p01.x}; p11 = fwd ? f2{p11.y, 0.f} : f2{0.f, p11.x};
-                      lp = WSY; lq = WSZ; la = 1; gp = V.sy; gq = V.sz; ga = 1;
+                    } else if (ax == 1) {
+                      const f2 ea = fwd ? p00 : p10, eb = fwd ? p01 : p11;
+                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
+                      if (fwd) { p00 = p10; p01 = p11; p10 = p11 = zero; } else { p10 = p00; p11 = p01; p00 = p01 = zero; }
+                    } else {
+                      const f2 ea = fwd ? p00 : p01, eb = fwd ? p10 : p11;
+                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
+                      if (fwd) { p00 = p01; p10 = p11; p01 = p11 = zero; } else { p01 = p00; p11 = p10; p00 = p10 = zero; }
                     }
-                    if (old_lidx >= 0) {
-                      const int qi = old_lidx + (fwd ? 0 : la);
-                      // pair / quad pre-reduction (see shift_emit4): lanes of a quad that go to the same four slots
-                      const int key = qi | ((ay ? 1 : (az ? 2 : 0)) << 16);
-                      const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);   // quad_perm [1,0,3,2]
-                      const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);   // quad_perm [2,3,0,1]
-                      const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);   // quad_perm [3,2,1,0]
-                      const bool psame = k1 == key;
-                      const bool same = psame & (k2 == key) & (k3 == key);
-                      float q0 = e0, q1 = e1, q2 = e2, q3 = e3;
-                      q0 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0xB1, 0xF, 0xF, false));
-                      q1 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0xB1, 0xF, 0xF, false));
-                      q2 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0xB1, 0xF, 0xF, false));
-                      q3 += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0xB1, 0xF, 0xF, false));
-                      const float s0 = q0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q0), 0x4E, 0xF, 0xF, false));
-                      const float s1 = q1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q1), 0x4E, 0xF, 0xF, false));
-                      const float s2 = q2 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q2), 0x4E, 0xF, 0xF, false));
-                      const float s3 = q3 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, q3), 0x4E, 0xF, 0xF, false));
-                      const unsigned ql = threadIdx.x & 3u;
-                      const bool add = same ? ql == 0u : (psame ? (ql & 1u) == 0u : true);
-                      if (DBG && a.dbg) { ++ev_face; ev_add += add; }
-                      if (add) {
-                        win_t* q = win + qi;
-                        atomicAdd(q, (win_t)(same ? s0 : (psame ? q0 : e0)));      atomicAdd(q + lp, (win_t)(same ? s1 : (psame ? q1 : e1)));
-                        atomicAdd(q + lq, (win_t)(same ? s2 : (psame ? q2 : e2))); atomicAdd(q + lq + lp, (win_t)(same ? s3 : (psame ? q3 : e3)));
+                  };
+                  using std::integral_constant;
+                  bool one = nregular;
+                  if (nregular) {
+                    if (DBG && a.dbg) {
+                      const bool ax = (d == 1) | (d == -1), ay = (d == V.sy) | (d == -V.sy), az = (d == V.sz) | (d == -V.sz);
+                      if (ax | ay | az) {
+                        const int nax = (__ballot(ax) != 0ull) + (__ballot(ay) != 0ull) + (__ballot(az) != 0ull);
+                        if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
                       }
+                    }
+                    // flat, mutually exclusive tests (a regular cell has 1 < sy < sz), not an else-chain: each case is one
+                    // predicated region
+                    const bool yp = d == V.sy, ym = d == -V.sy, zp = d == V.sz, zm = d == -V.sz, xp = d == 1, xm = d == -1;
+                    if (yp) face(integral_constant<int, 1>{}, integral_constant<bool, true>{});
+                    if (ym) face(integral_constant<int, 1>{}, integral_constant<bool, false>{});
+                    if (zp) face(integral_constant<int, 2>{}, integral_constant<bool, true>{});
+                    if (zm) face(integral_constant<int, 2>{}, integral_constant<bool, false>{});
+                    if (xp) face(integral_constant<int, 0>{}, integral_constant<bool, true>{});
+                    if (xm) face(integral_constant<int, 0>{}, integral_constant<bool, false>{});
+                    one = key != kNoFace;
+                  }
+                  if (one) {
+                    if (lidx >= 0) {
+                      const bool add = win_emit4(win, key, lp, lq, e0, e1, e2, e3);
+                      if (DBG && a.dbg) { ++ev_face; ev_add += add; }
                       used_lds = true;
                     } else {
+                      // the cell lies outside the window: straight to the grid.  |d| is the grid stride of the axis crossed, which
+                      // names the strides of p and q; a face left behind in the negative direction is the cell's far one, |d| on.
                       if (DBG && a.dbg) ++ev_glob;
-                      float* g = a.grad + old_base + (fwd ? 0 : ga);
-                      atomic_add_f32(g, e0); atomic_add_f32(g + gp, e1); atomic_add_f32(g + gq, e2); atomic_add_f32(g + gq + gp, e3);
+                      const int ad = abs(d);
+                      const unsigned gp = ad == 1 ? (unsigned)V.sy : 1u, gq = ad == V.sz ? (unsigned)V.sy : (unsigned)V.sz;
+                      const unsigned g = (unsigned)(old_base + max(-d, 0)), gqq = g + gq;
+                      atomic_add_f32_at(a.grad, g, e0);   atomic_add_f32_at(a.grad, g + gp, e1);
+                      atomic_add_f32_at(a.grad, gqq, e2); atomic_add_f32_at(a.grad, gqq + gp, e3);
                     }
                   } else {
                     // jump over more than one face, or into a clamped cell: hand over all eight
                     if (DBG && a.dbg) ++ev_all8;
                     // (no quad pre-reduction here: two-face crossings are rarely shared by a quad -- 4.87 -> 4.81 ms without it)
-                    used_lds = flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, old_lidx, old_base, p00, p10, p01, p11);
+                    used_lds = flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, old_base, p00, p10, p01, p11);
                     p00 = p10 = p01 = p11 = f2{0.f, 0.f};
                   }
                 }
-                lidx = regular ? WIN_INDEX(ix, iy, iz) : -1;
-                miss = regular & (lidx < 0);
+                lidx = nregular ? WIN_INDEX(ix, iy, iz) : kIrregular;
               }
             }
           }
@@ -508,7 +552,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
       if (DBG && a.dbg) ev_wsteps += lane == 0;
     }
   // rays still marching when max_steps ran out keep what their cell has accumulated: hand it over
-  if (s.active && regular) { if (flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11)) dirty = true; }
+  if (s.active && lidx > kIrregular) { if (flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11)) dirty = true; }
 #undef WSY
 #undef WSZ
 #undef WIN_INDEX
@@ -554,6 +598,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     if (ev_all8) atomicAdd(&a.dbg[7], (unsigned long long)ev_all8);
     if (ev_wsteps) atomicAdd(&a.dbg[8], (unsigned long long)ev_wsteps);
     if (ev_multi) atomicAdd(&a.dbg[9], (unsigned long long)ev_multi);
+    if (ev_clamp) atomicAdd(&a.dbg[15], (unsigned long long)ev_clamp);
   }
   block_stats<kAdjBlock>(a.stats, steps, 0u);
 }

@@ -1293,6 +1293,11 @@ DRRT_HD TargetGrad target_backtrace_ray_state(const Vol& V, float ds, int max_st
 #if defined(__HIPCC__)
 // fp32 atomic add without return: one global_atomic_add_f32 on gfx950 (no CAS loop).
 __device__ __forceinline__ void atomic_add_f32(float* p, float v) { unsafeAtomicAdd(p, v); }
+// The same at element idx of a grid whose base pointer is wave-uniform: ONE 32-bit byte offset per lane against the scalar
+// base (global_atomic_add_f32 ... saddr), no 64-bit address arithmetic.  make_vol keeps byte offsets below 2^31.
+__device__ __forceinline__ void atomic_add_f32_at(float* base, unsigned idx, float v) {
+  unsafeAtomicAdd((float*)((char*)base + (idx << 2)), v);
+}
 
 // ---- wave reductions (64 lanes) -------------------------------------------------------------
 __device__ __forceinline__ unsigned wave_sum_u32(unsigned v) {
