@@ -85,6 +85,8 @@ SIGNATURES = {
     "drrt_backtrace_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_trace_opl_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_opl_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp] + _tail),
+    "drrt_trace_field_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_backtrace_field_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_chunk_state_bytes": (_sz, [_sz]),
     "drrt_backtrace_max_steps": (_i, [_vp, _f, _f]),
     "drrt_backtrace_chunk_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail + [_vp, _sz, _i, _i, _vp]),
@@ -118,7 +120,7 @@ SIGNATURES = {
 
 PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "backtrace_rays",
               7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays", 10: "backtrace_target_rays",
-              11: "trace_opl", 12: "backtrace_opl"}
+              11: "trace_opl", 12: "backtrace_opl", 13: "trace_field", 14: "backtrace_field"}
 
 _lib: Optional[C.CDLL] = None
 

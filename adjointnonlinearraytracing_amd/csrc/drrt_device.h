@@ -913,6 +913,122 @@ DRRT_HD RayGrad opl_backtrace_ray(const Vol& V, float ds, float grad_scale, int 
   return g;
 }
 
+// ---- line integral of a second field ---------------------------------------------------------------------------------
+// tau = int a dl of a second voxel field `a` (absorption, emission, group index) on the grid of n, along the bent ray:
+// |v| = n, so dl = n dsigma and tau = sum_{k<K} ds n_k a_k, a_k the trilinear sample of the field at the cell, the weights
+// and under the mask of n_k (0 while the ray is not inside), accumulated in fp32 as tau = fmaf(ds n_k, a_k, tau) in
+// iteration order from 0.f.  With a = n (the same values) that is trace_opl_ray's opl bit for bit.  Not in the reference.
+
+// The value weights of a splat alone: corner(a,b,c) = val X_a Y_b Z_c (splat_weights without its gradient part).
+DRRT_HD Corners value_weights(float wx, float wy, float wz, float val) {
+  const float x1 = wx, x0 = 1.f - wx, y1 = wy, y0 = 1.f - wy, z1 = wz, z0 = 1.f - wz;
+  const float a0 = val * x0, a1 = val * x1;
+  const float yz00 = y0 * z0, yz10 = y1 * z0, yz01 = y0 * z1, yz11 = y1 * z1;
+  Corners c;
+  c.c000 = yz00 * a0;  c.c100 = yz00 * a1;
+  c.c010 = yz10 * a0;  c.c110 = yz10 * a1;
+  c.c001 = yz01 * a0;  c.c101 = yz01 * a1;
+  c.c011 = yz11 * a0;  c.c111 = yz11 * a1;
+  return c;
+}
+
+// trace for ONE ray, with the line integral of the field whose taps `ftaps(c)` returns (`taps(c)`: those of n).  The loop
+// is trace_opl_ray's, so (xt, vt, steps) are trace_ray<0>'s bit for bit.  A failed ray returns what it accumulated.
+template <typename TapFn, typename FieldTapFn>
+DRRT_HD RayOut trace_field_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                               FieldTapFn&& ftaps, float& tau) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
+  fwd_init(V, s);
+  Cell c = locate(V, s.x, s.y, s.z);
+  unsigned steps = 0;
+  float acc = 0.f;
+  for (int it = 0; it < max_steps; ++it) {
+    Taps t = taps_zero();
+    float n = 0.f, a = 0.f;
+    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
+      t = taps(c);
+      n = interp<false>(t, c.wx, c.wy, c.wz).n;
+      a = interp<false>(ftaps(c), c.wx, c.wy, c.wz).n;
+    }
+    acc = fmaf(ds * n, a, acc);
+    fwd_step_c<0>(V, nullptr, ds, s, c, t);
+    ++steps;
+    if (s.esc) break;                                                     // per-ray form of :82
+  }
+  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
+  tau = acc;
+  return o;
+}
+
+// Adjoint of trace_field_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn AND dL/da, from the seeds
+// (dx, dv, dtau) on (xt, vt, tau).  The reverse march is opl_backtrace_ray's, unchanged in structure.  With a_k, grad a_k
+// the sample of the field at the cell of n_k (grad a_k scaled by 1 / h like grad n_k), each reverse iteration uses
+//   dn = mu . grad n_k + dtau a_k                    (d tau / d n_k = ds a_k)
+// where backtrace_ray_state uses mu . grad n_k, which also puts dtau ds a_k grad n_k into lambda (adj_recur), and adds the
+// term no other march has, the pull of the field's own gradient on the sample position,
+//   lambda += (dtau ds n_k) grad a_k                 (d tau / d x_k = ds (a_k grad n_k + n_k grad a_k))
+// BEFORE adj_recur, whose closing mu += ds lambda must see it.  `sink(c, val, gx, gy, gz)` receives the contribution to
+// dL/dn as opl_backtrace_ray's does (val = dn ds, g = (n_k ds grad_scale) mu, mu before its update: the caller adds
+// splat_weights(...) at the 8 taps of c); `fsink(c, val)` the contribution to dL/da, val = dtau ds n_k: the caller adds
+// value_weights(c.wx, c.wy, c.wz, val) at the same taps (tau is linear in a: no gradient splat, no grad_scale, the exact
+// discrete derivative either way).  grad_scale does not enter the ray gradients.
+template <typename TapFn, typename FieldTapFn, typename Sink, typename FieldSink>
+DRRT_HD RayGrad field_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                    const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                    const float dv[3], float dtau, TapFn&& taps, FieldTapFn&& ftaps, Sink&& sink,
+                                    FieldSink&& fsink) {
+  RayGrad g;
+  g.steps = 0; g.failed = false;
+  if (max_steps <= 0 || K >= (unsigned)max_steps) {
+    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    g.failed = true;
+    return g;
+  }
+  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
+  float px = p0[0], py = p0[1], pz = p0[2];
+  unsigned e = 0;
+  while (e < K && !inbounds(V, px, py, pz)) {
+    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
+    ++e;
+  }
+  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, tau = 0
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  const float dtds = dtau * ds;
+  for (unsigned k = K; k > e; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
+    const Cell c = locate(V, s.x, s.y, s.z);
+    AdjSample m;
+    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
+    const Sample a = interp<false>(ftaps(c), c.wx, c.wy, c.wz);
+    const float dn = fmaf(dtau, a.n, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));
+    const float nds = (m.n * ds) * grad_scale;
+    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
+    const float fv = dtds * m.n;                                          // dtau ds n_k
+    fsink(c, fv);
+    qx = s.mx; qy = s.my; qz = s.mz;
+    s.lx = fmaf(fv, a.gx * V.inv_h, s.lx); s.ly = fmaf(fv, a.gy * V.inv_h, s.ly); s.lz = fmaf(fv, a.gz * V.inv_h, s.lz);
+    adj_recur(V, ds, s, m, dn);
+  }
+  const float eds = (float)e * ds;
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
+  g.steps = K - e;
+  return g;
+}
+
 // trace_cable for ONE ray (src/tracer.cpp:312-382)
 DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
                                const float tg[3]) {

@@ -14,6 +14,8 @@
 //                           replayed over the call's global loop count, no grid writes)
 //   drrt_opl.hip            trace_opl, backtrace_opl: trace with its optical path length, and the adjoint that returns
 //                           dL/dn, dL/dpos and dL/dvel from seeds on (xt, vt, opl) in one march (global atomics, no window)
+//   drrt_field.hip          trace_field, backtrace_field: trace with the line integral tau of a second field along the bent
+//                           ray, and the adjoint that returns dL/dn, dL/dfield, dL/dpos and dL/dvel from seeds on (xt, vt, tau)
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -242,6 +244,51 @@ __device__ __forceinline__ void taps_set(const Taps& t, f4& q0, f4& q1) {
   else      { q0 = f4{t.a.x, t.a.y, t.b.x, t.b.y}; q1 = f4{t.e.x, t.e.y, t.f.x, t.f.y}; }
 }
 template <bool PAIR> __device__ __forceinline__ unsigned tap_offset(int base) { return (unsigned)base << (PAIR ? 3 : 2); }
+
+// ---- one ray per lane with global atomics: drrt_opl.hip, drrt_field.hip ----
+// the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell
+template <bool PAIR>
+struct OplTaps {
+  const Vol& V;
+  const TapRows& R;
+  unsigned off = 0;          // byte offset (tap_offset) of the interior cell whose taps the lane holds
+  bool held = false;
+  f4 q0 = f4{0.f, 0.f, 0.f, 0.f}, q1 = f4{0.f, 0.f, 0.f, 0.f};
+  __device__ __forceinline__ OplTaps(const Vol& v, const TapRows& r) : V(v), R(r) {}
+  __device__ __forceinline__ Taps operator()(const Cell& c) {
+    if (!c.interior) { held = false; return fetch(V.data, c); }
+    const unsigned noff = tap_offset<PAIR>(c.base);
+    if (!(held & (noff == off))) { gather_rows<PAIR>(R, noff, q0, q1); off = noff; held = true; }
+    return taps_of<PAIR>(q0, q1);
+  }
+};
+
+// The eight corner sums of the cell the lane is in.  Two cells with the same corner 000 and the same (clamp) offsets have
+// the same eight addresses, so that is the test for "the same cell".
+struct HeldCorners {
+  float* grad;
+  int base = -1, ox = 0, oy = 0, oz = 0;     // base < 0: nothing held
+  Corners s;
+  __device__ __forceinline__ explicit HeldCorners(float* g) : grad(g) {}
+  __device__ __forceinline__ void flush() {
+    if (base < 0) return;
+    float* g = grad + base;
+    atomic_add_f32(g, s.c000);                atomic_add_f32(g + ox, s.c100);
+    atomic_add_f32(g + oy, s.c010);           atomic_add_f32(g + oy + ox, s.c110);
+    atomic_add_f32(g + oz, s.c001);           atomic_add_f32(g + oz + ox, s.c101);
+    atomic_add_f32(g + oz + oy, s.c011);      atomic_add_f32(g + oz + oy + ox, s.c111);
+    base = -1;
+  }
+  __device__ __forceinline__ void add(const Cell& c, const Corners& w) {
+    if ((c.base == base) & (c.ox == ox) & (c.oy == oy) & (c.oz == oz)) {
+      s.c000 += w.c000; s.c100 += w.c100; s.c010 += w.c010; s.c110 += w.c110;
+      s.c001 += w.c001; s.c101 += w.c101; s.c011 += w.c011; s.c111 += w.c111;
+      return;
+    }
+    flush();
+    s = w; base = c.base; ox = c.ox; oy = c.oy; oz = c.oz;
+  }
+};
 
 struct TargetArgs {
   Vol vol;
@@ -482,6 +529,40 @@ struct OplBackArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// line integral of a second field (drrt_field.hip): trace with tau = sum ds n_k a_k, and its adjoint (both grids and the rays)
+struct FieldTraceArgs {
+  Vol vol;
+  const float* field;                       // the second grid: vol's shape, plain layout (no pair copy)
+  const float* pos; const float* vel;
+  float* xt; float* vt; float* tau;
+  uint32_t* steps_out;                      // per-ray iteration counts, caller ray order
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+struct FieldBackArgs {
+  Vol vol;
+  const float* field;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const uint32_t* fsteps;                   // its per-ray iteration counts, caller ray order
+  const float* dx; const float* dv;         // nullable: seeds on (xt, vt), read as zeros
+  const float* dtau;                        // nullable: seed on tau, n floats
+  float* grad;                              // nullable: no scatter into dL/dn
+  float* grad_field;                        // nullable: no scatter into dL/dfield
+  float* dpos; float* dvel;                 // both null: no ray outputs
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  float grad_scale;                         // 1 (as written, Q3) or 1/h (DRRT_FLAG_CORRECTED_H)
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -546,6 +627,9 @@ void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
 // optical path length: trace_opl and its adjoint (drrt_opl.hip)
 void launch_trace_opl(const OplTraceArgs& a, hipStream_t s);
 void launch_backtrace_opl(const OplBackArgs& a, hipStream_t s);
+// line integral of a second field: trace_field and its adjoint (drrt_field.hip)
+void launch_trace_field(const FieldTraceArgs& a, hipStream_t s);
+void launch_backtrace_field(const FieldBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

@@ -11,26 +11,10 @@
 // cell changes and after its last iteration (with ds = h / 2 that roughly halves the atomics).  There is NO LDS window: the
 // ring kernel's fixed-point window is scaled for backtrace's contributions and a per-step source term does not fit its
 // overflow budget, so this kernel pays the memory-side atomic rate where many rays cross the same voxels.
+// OplTaps and HeldCorners live in drrt_march.h: drrt_field.hip uses them too.
 #include "drrt_march.h"
 
 namespace drrt {
-
-// the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell
-template <bool PAIR>
-struct OplTaps {
-  const Vol& V;
-  const TapRows& R;
-  unsigned off = 0;          // byte offset (tap_offset) of the interior cell whose taps the lane holds
-  bool held = false;
-  f4 q0 = f4{0.f, 0.f, 0.f, 0.f}, q1 = f4{0.f, 0.f, 0.f, 0.f};
-  __device__ __forceinline__ OplTaps(const Vol& v, const TapRows& r) : V(v), R(r) {}
-  __device__ __forceinline__ Taps operator()(const Cell& c) {
-    if (!c.interior) { held = false; return fetch(V.data, c); }
-    const unsigned noff = tap_offset<PAIR>(c.base);
-    if (!(held & (noff == off))) { gather_rows<PAIR>(R, noff, q0, q1); off = noff; held = true; }
-    return taps_of<PAIR>(q0, q1);
-  }
-};
 
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_opl(OplTraceArgs a) {
@@ -53,33 +37,6 @@ __global__ void __launch_bounds__(kBlock) k_trace_opl(OplTraceArgs a) {
   }
   block_stats(a.stats, steps, failed);
 }
-
-// The eight corner sums of the cell the lane is in.  Two cells with the same corner 000 and the same (clamp) offsets have
-// the same eight addresses, so that is the test for "the same cell".
-struct HeldCorners {
-  float* grad;
-  int base = -1, ox = 0, oy = 0, oz = 0;     // base < 0: nothing held
-  Corners s;
-  __device__ __forceinline__ explicit HeldCorners(float* g) : grad(g) {}
-  __device__ __forceinline__ void flush() {
-    if (base < 0) return;
-    float* g = grad + base;
-    atomic_add_f32(g, s.c000);                atomic_add_f32(g + ox, s.c100);
-    atomic_add_f32(g + oy, s.c010);           atomic_add_f32(g + oy + ox, s.c110);
-    atomic_add_f32(g + oz, s.c001);           atomic_add_f32(g + oz + ox, s.c101);
-    atomic_add_f32(g + oz + oy, s.c011);      atomic_add_f32(g + oz + oy + ox, s.c111);
-    base = -1;
-  }
-  __device__ __forceinline__ void add(const Cell& c, const Corners& w) {
-    if ((c.base == base) & (c.ox == ox) & (c.oy == oy) & (c.oz == oz)) {
-      s.c000 += w.c000; s.c100 += w.c100; s.c010 += w.c010; s.c110 += w.c110;
-      s.c001 += w.c001; s.c101 += w.c101; s.c011 += w.c011; s.c111 += w.c111;
-      return;
-    }
-    flush();
-    s = w; base = c.base; ox = c.ox; oy = c.oy; oz = c.oz;
-  }
-};
 
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_backtrace_opl(OplBackArgs a) {

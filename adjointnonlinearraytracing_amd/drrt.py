@@ -671,7 +671,67 @@ class TracerC:
         inside the box (|v| = n, so this is the integral of n along the path).  fp32 rays only."""
         return self._trace_opl(rif, res, pos, vel, h, ds)[0]
 
+    def _trace_field(self, rif, field, res, pos, vel, h, ds):
+        return _grid_call("drrt_trace_field_f32", rif, res, [pos, vel], h, ds,
+                          lambda rif_, r: _like_rays(rif_, r) + (r[0].new_empty(r[0].shape[0]),
+                                                                 torch.empty(r[0].shape[0], dtype=torch.int32, device=r[0].device)),
+                          adjoint=False, sdf=field, steps=False, warn=True)
+
+    def trace_field(self, rif, field, res, pos, vel, h, ds):
+        """``trace`` with the line integral of a second field along every bent ray (drrt_trace_field_f32,
+        include/drrt_hip.h; not in the reference) -> (xt, vt, tau, steps).  `field`: an fp32 grid of `rif`'s shape and axis
+        convention (an absorption or emission coefficient, a group index).  xt, vt and the per-ray iteration counts `steps`
+        (int32[n], a tensor of the caller's, not a workspace view) are ``trace``'s bit for bit; ``tau = sum ds n_k a_k`` over
+        the samples the march takes inside the box, a_k the field at the cell and weights of n_k (|v| = n, so this is the
+        integral of the field along the path; with field = rif it is ``trace_opl``'s opl bit for bit).  fp32 rays only."""
+        return self._trace_field(rif, field, res, pos, vel, h, ds)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_field(self, rif, field, res, pos, vel, xt, vt, steps, dx, dv, dtau, h, ds, grid: bool = True,
+                        field_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,
+                        field_into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_field`` (drrt_backtrace_field_f32, include/drrt_hip.h) -> (grad | None, grad_field | None,
+        dpos | None, dvel | None): flat dL/drif and dL/dfield (fp32[nvox] each), dL/dpos and dL/dvel ((n,3) fp32) from ONE
+        reverse march.  `pos`, `vel` are the forward call's inputs, `xt`, `vt`, `steps` its outputs; `dx`, `dv` ((n,3)) and
+        `dtau` (n values) the seeds on (xt, vt, tau), each optional (None: zeros).  `grid` / `field_grid` / `rays`: which
+        outputs are computed (at least one); `into` / `field_into`: a flat fp32[nvox] tensor that grid's gradient is ADDED to
+        (DRRT_FLAG_NO_ZERO, which covers both grids: where only one of the two is given, the other grid is zeroed here) and
+        that is returned in its place.  Honours ``options.corrected_h`` (with it dL/drif is the exact discrete derivative;
+        dL/dfield and the ray gradients are that either way).  Rays that failed the forward get zeros and contribute
+        nothing.  `order`: the forward's visit order."""
+        if not (grid or field_grid or rays):
+            raise RuntimeError("backtrace_field: nothing to compute (grid = field_grid = rays = False)")
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            rif_, field_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, field, [pos, vel, xt, vt], dev)
+            steps_ = steps.detach().to(device=dev).contiguous()
+            if steps_.dtype != torch.int32 or steps_.numel() != n:
+                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_field's)")
+            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+            dtau_ = None if dtau is None else _f32(dtau, dev).reshape(-1)
+            if dtau_ is not None and dtau_.numel() != n:
+                raise RuntimeError(f"expected {n} per-ray values, got {dtau_.numel()}")
+            no_zero = (grid and into is not None) or (field_grid and field_into is not None)
+            grads = []
+            for want, acc, name in ((grid, into, "into"), (field_grid, field_into, "field_into")):
+                if not want:
+                    grads.append(None)
+                elif acc is not None:
+                    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
+                        raise RuntimeError(f"backtrace_field: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
+                    grads.append(acc.detach().view(-1))
+                else:
+                    grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
+            grad, gfield = grads
+            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
+                _lib.check(_lib.load().drrt_backtrace_field_f32(
+                    _p(rif_), _p(field_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
+                    _p(dx_), _p(dv_), _p(dtau_), float(h), float(ds), _p(grad), _p(gfield), _p(dpos), _p(dvel), _p(st), _p(ws),
+                    ws.numel(), fl, _stream(dev)))
+            _warn_failed(st)
+        return grad, gfield, dpos, dvel
+
     def backtrace_opl(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dopl, h, ds, grid: bool = True, rays: bool = True,
                       into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
         """Adjoint of ``trace_opl`` (drrt_backtrace_opl_f32, include/drrt_hip.h) -> (grad | None, dpos | None, dvel | None):

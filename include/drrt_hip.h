@@ -361,6 +361,54 @@ DRRT_API int drrt_backtrace_opl_f32(const float* rif, long long nvox, const int 
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- line integral of a second field along the bent ray (not in the reference) -------------------------------------------
+ * tau = int a dl of a second voxel field a -- an absorption or emission coefficient, a group index -- along the ray that n
+ * bends.  `field` is an fp32 grid of exactly rif's shape and axis convention (res[0] indexes the fastest axis).  |v| = n
+ * along the march, so dl = n dsigma: drrt_trace_field_f32 is drrt_trace_f32 (xt, vt and the per-ray iteration counts K bit
+ * for bit) that also returns  tau = sum_{k<K} ds n_k a_k,  n_k the masked sample the march takes at x_k anyway (0 while the
+ * ray is not inside the box: free flight adds nothing) and a_k the trilinear sample of `field` at the same cell, with the
+ * same weights and the same mask, accumulated in fp32 as tau = fmaf(ds n_k, a_k, tau) in iteration order from 0.  With
+ * field holding rif's values tau is drrt_trace_opl_f32's opl bit for bit.  A failed ray returns what it accumulated.
+ *   tau        out: fp32[n]
+ *   steps_out  out: uint32[n], required: K per ray, caller ray order (what the adjoint takes as fwd_steps).  The call
+ *              leaves no drrt_last_steps().
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE (the pair copy is of rif; field is gathered as it is),
+ * DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32.  fp32 only. */
+DRRT_API int drrt_trace_field_f32(const float* rif, const float* field, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds,
+                       float* xt, float* vt, float* tau, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_field_f32: from the seeds dx = dL/dxt, dv = dL/dvt, dtau = dL/dtau (each nullable: read as zeros) ONE
+ * reverse march yields dL/drif (grad), dL/dfield (grad_field), dL/dpos and dL/dvel.  The march is drrt_backtrace_opl_f32's,
+ * unchanged in structure (failed rays get zeros, contribute nothing and count in stats->n_failed; never-entered rays get
+ * (dx, dv) and contribute nothing).  Each reverse iteration samples rif (n_k, grad n_k, mixed partials) and field (a_k,
+ * grad a_k, scaled by 1 / h like grad n_k) at the same cell, uses  dn = mu . grad n_k + dtau a_k  where drrt_backtrace_rays_f32
+ * uses mu . grad n_k, adds  (dtau ds n_k) grad a_k  to lambda before the recurrences -- the pull of the field's gradient on
+ * the sample position -- and adds, with mu before its update, at the 8 taps of the sampled cell
+ *   to grad:        splat_weights(w, dn ds, (n_k ds grad_scale) mu),  grad_scale = 1 / h with DRRT_FLAG_CORRECTED_H and 1
+ *                   without, as for drrt_backtrace_f32 (Q3);
+ *   to grad_field:  the value weights alone, w_c (dtau ds n_k): tau is linear in the field, so there is no gradient splat
+ *                   and grad_scale does not enter.
+ * With DRRT_FLAG_CORRECTED_H all four outputs are the exact derivative of the discrete forward; grad_field, dpos and dvel
+ * are that with either setting.
+ *   grad, grad_field  out, each nullable (no scatter into that grid): fp32[nvox], zeroed by the call unless
+ *                     DRRT_FLAG_NO_ZERO, which applies to both
+ *   dpos, dvel        out, both or neither: (n,3) fp32.  All four outputs null: DRRT_ERR_ARG
+ * The scatter is one global fp32 atomic per tap, per grid and per run of samples in one cell, as for drrt_backtrace_opl_f32:
+ * no LDS window, so a call that scatters into both grids pays the memory-side atomic rate twice.
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE, DRRT_FLAG_DISPATCH_IN_ORDER, DRRT_FLAG_CORRECTED_H,
+ * DRRT_FLAG_NO_ZERO; other adjoint flags are ignored.  The order hint is consumed, the step hint ignored.  fp32 only.      */
+DRRT_API int drrt_backtrace_field_f32(const float* rif, const float* field, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, const float* dtau, float h, float ds,
+                       float* grad, float* grad_field, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -640,6 +688,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_TARGET_RAYS 10   /* ray-state adjoint of trace_target (drrt_backtrace_target_rays_f32), both launches */
 #define DRRT_PROF_TRACE_OPL 11       /* trace with its optical path length (drrt_trace_opl_f32) */
 #define DRRT_PROF_BACKTRACE_OPL 12   /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_opl_f32) */
+#define DRRT_PROF_TRACE_FIELD 13     /* trace with the line integral of a second field (drrt_trace_field_f32) */
+#define DRRT_PROF_BACKTRACE_FIELD 14 /* its adjoint: dL/dn, dL/dfield and the ray gradients in one march (drrt_backtrace_field_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

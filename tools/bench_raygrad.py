@@ -63,6 +63,21 @@ opl     drrt_trace_opl_f32 / drrt_backtrace_opl_f32 (k_trace_opl, k_backtrace_op
         usage: bench_raygrad.py opl [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
         Also writes the JSON, with the library's version string (source digest), to --out (default profiles/opl_bench.json).
 
+field   drrt_trace_field_f32 / drrt_backtrace_field_f32 (k_trace_field, k_backtrace_field) next to the optical-path-length calls
+        they are modelled on, on the workloads of `opl` (256^3, 1 048 576 rays, `luneburg` and `tomo_weak`); the second field is
+        1 + 0.5 U, seeded.  All adjoints take seeds on all three outputs and return the ray gradients too.
+            trace                  TracerC.trace
+            trace_opl              TracerC.trace_opl
+            trace_field            TracerC.trace_field
+            backtrace_opl          TracerC.backtrace_opl                          (dL/dn)
+            backtrace_field_rif    TracerC.backtrace_field(field_grid=False)      (dL/dn)
+            backtrace_field_field  TracerC.backtrace_field(grid=False)            (dL/dfield)
+            backtrace_field_both   TracerC.backtrace_field                        (dL/dn and dL/dfield)
+        Timed alternately like `opl`.  Output per medium and call: median, minimum, maximum ms and stats.ray_steps, and the
+        ratios trace_field / trace_opl, trace_field / trace and backtrace_field_* / backtrace_opl.
+        usage: bench_raygrad.py field [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string (source digest), to --out (default profiles/field_bench.json).
+
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
 over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
@@ -303,7 +318,34 @@ def target(a, dev):
     return out
 
 
-# ---- opl ------------------------------------------------------------------------------------------------------------
+# ---- opl, field -----------------------------------------------------------------------------------------------------
+def time_each(calls, a):
+    """`calls` = {name: fn}, timed alternately (one of each per round, device events around the whole call) -> (per call:
+    median, minimum, maximum ms and stats.ray_steps; the medians); (None, None) with --once, which makes a single call of
+    each instead."""
+    if a.once:
+        for fn in calls.values():
+            fn()
+        torch.cuda.synchronize()
+        return None, None
+    rsteps, ms = {}, {k: [] for k in calls}
+    for k, fn in calls.items():
+        for _ in range(max(a.warmup, 1)):
+            fn()
+        rsteps[k] = drrt.read_stats()["ray_steps"]
+    torch.cuda.synchronize()
+    for _ in range(a.rounds):
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms[k].append(e0.elapsed_time(e1))
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {k: dict(median_ms=med[k], min_ms=min(v), max_ms=max(v), ray_steps=rsteps[k]) for k, v in ms.items()}, med
+
+
 def opl(a, dev):
     pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # make_workload's rays; the grids are made below
     h = 1.0 / (a.grid - 1)
@@ -326,30 +368,51 @@ def opl(a, dev):
             "backtrace_opl_grid": lambda: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, rays=False,
                                                           order=order),
         }
-        if a.once:
-            for fn in calls.values():
-                fn()
-            torch.cuda.synchronize()
+        r, med = time_each(calls, a)
+        if r is None:
             continue
-        rsteps, ms = {}, {k: [] for k in calls}
-        for k, fn in calls.items():
-            for _ in range(max(a.warmup, 1)):
-                fn()
-            rsteps[k] = drrt.read_stats()["ray_steps"]
-        torch.cuda.synchronize()
-        for _ in range(a.rounds):
-            for k, fn in calls.items():
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                fn()
-                e1.record()
-                torch.cuda.synchronize()
-                ms[k].append(e0.elapsed_time(e1))
-        med = {k: statistics.median(v) for k, v in ms.items()}
-        r = {k: dict(median_ms=med[k], min_ms=min(v), max_ms=max(v), ray_steps=rsteps[k]) for k, v in ms.items()}
         r["trace_opl_over_trace"] = med["trace_opl"] / med["trace"]
         r["backtrace_opl_all_over_backtrace_plus_backtrace_rays"] = med["backtrace_opl_all"] / (med["backtrace"] + med["backtrace_rays"])
         r["backtrace_opl_grid_over_backtrace"] = med["backtrace_opl_grid"] / med["backtrace"]
+        out[medium] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
+def field(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl`
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
+    fld = (1.0 + 0.5 * torch.rand((a.grid,) * 3, generator=torch.Generator(device="cpu").manual_seed(2))).to(dev)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for medium, make in (("luneburg", bench.make_grid), ("tomo_weak", bench.make_grid_tomo)):
+        rif = make(a.grid, dev)
+        res = tuple(rif.shape)
+        xt, vt, _, steps = T.trace_field(rif, fld, res, pos, vel, h, ds)
+        order = drrt.keep_order(drrt.last_order)
+        back = lambda **kw: T.backtrace_field(rif, fld, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order, **kw)   # noqa: E731
+        r, med = time_each({
+            "trace": lambda: T.trace(rif, res, pos, vel, h, ds),
+            "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
+            "trace_field": lambda: T.trace_field(rif, fld, res, pos, vel, h, ds),
+            "backtrace_opl": lambda: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order),
+            "backtrace_field_rif": lambda: back(field_grid=False),
+            "backtrace_field_field": lambda: back(grid=False),
+            "backtrace_field_both": back,
+        }, a)
+        if r is None:
+            continue
+        r["trace_field_over_trace_opl"] = med["trace_field"] / med["trace_opl"]
+        r["trace_field_over_trace"] = med["trace_field"] / med["trace"]
+        for k in ("rif", "field", "both"):
+            r[f"backtrace_field_{k}_over_backtrace_opl"] = med[f"backtrace_field_{k}"] / med["backtrace_opl"]
         out[medium] = r
     if a.once:
         return {}
@@ -386,14 +449,19 @@ def main():
     p_opl.add_argument("--rays", type=int, default=1 << 20)
     p_opl.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "opl_bench.json"))
     p_opl.set_defaults(run=opl)
-    for p in (p_cable, p_stop, p_target, p_opl):
+    p_field = sub.add_parser("field")
+    p_field.add_argument("--grid", type=int, default=256)
+    p_field.add_argument("--rays", type=int, default=1 << 20)
+    p_field.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "field_bench.json"))
+    p_field.set_defaults(run=field)
+    for p in (p_cable, p_stop, p_target, p_opl, p_field):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target", "opl") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl", "field") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
