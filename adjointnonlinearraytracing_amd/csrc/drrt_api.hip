@@ -1,7 +1,7 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_opl.hip / drrt_field.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_opl.hip / drrt_field.hip / drrt_emission.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
 // utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
@@ -822,6 +822,76 @@ extern "C" int drrt_backtrace_field_f32(const float* rif, const float* field, lo
   a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
   a.perm = c.perm; a.xcd_order = c.xcd_order;
   return timed_launch(DRRT_PROF_BACKTRACE_FIELD, s, "k_backtrace_field", [&] { launch_backtrace_field(a, s); });
+}
+
+// ---- emission with self-absorption: drrt_emission.hip ------------------------------------------------------------------
+extern "C" int drrt_trace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
+                                       const int res[3], size_t n, const float* pos, const float* vel, float h, float ds,
+                                       float* xt, float* vt, float* rad, float* tau, uint32_t* steps_out, drrt_stats* stats,
+                                       void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  EmissionTraceArgs a{};
+  GridCall c(a.vol, stream);
+  g_ts.reset_last_steps();              // this forward march writes its iteration counts to the caller, none to the workspace
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
+  if (!emission) return fail(DRRT_ERR_ARG, "null emission pointer");
+  if (!absorption) return fail(DRRT_ERR_ARG, "null absorption pointer");
+  if (n == 0) return zero_stats(stats, s);
+  if (!pos || !vel || !xt || !vt || !rad || !tau) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!steps_out) return fail(DRRT_ERR_ARG, "null steps_out pointer (the adjoint needs the iteration counts)");
+  rc = check_ray_count(n); if (rc) return rc;
+  rc = zero_stats(stats, s); if (rc) return rc;
+  rc = c.place(nvox, n, pos, vel, 1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
+  a.emission = emission; a.absorption = absorption;
+  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.rad = rad; a.tau = tau; a.steps_out = steps_out; a.stats = stats;
+  a.n = n; a.ds = ds;
+  a.max_steps = steps_fwd(h, res, ds);
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(DRRT_PROF_TRACE_EMISSION, s, "k_trace_emission", [&] { launch_trace_emission(a, s); });
+}
+
+extern "C" int drrt_backtrace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
+                                           const int res[3], size_t n, const float* pos, const float* vel, const float* xt,
+                                           const float* vt, const uint32_t* fwd_steps, const float* tau, const float* dx,
+                                           const float* dv, const float* drad, const float* dtau, float h, float ds,
+                                           float* grad, float* grad_emission, float* grad_absorption, float* dpos,
+                                           float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags,
+                                           void* stream) {
+  EmissionBackArgs a{};
+  GridCall c(a.vol, stream);
+  hipStream_t s = c.s;
+  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
+  if (!emission) return fail(DRRT_ERR_ARG, "null emission pointer");
+  if (!absorption) return fail(DRRT_ERR_ARG, "null absorption pointer");
+  if (!grad && !grad_emission && !grad_absorption && !dpos && !dvel)
+    return fail(DRRT_ERR_ARG, "null output pointers: grad, grad_emission, grad_absorption, or dpos and dvel, or any of these together");
+  if (!dpos != !dvel) return fail(DRRT_ERR_ARG, "dpos and dvel go together");
+  if (n > 0) {
+    if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
+    if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's steps_out)");
+    if (!tau) return fail(DRRT_ERR_ARG, "null tau pointer (the forward's tau)");
+    rc = check_ray_count(n); if (rc) return rc;
+  }
+  if (!(flags & DRRT_FLAG_NO_ZERO)) {
+    for (float* g : {grad, grad_emission, grad_absorption}) {
+      if (!g) continue;
+      ProfScope prof(DRRT_PROF_ZERO, s);
+      hipError_t e = hipMemsetAsync(g, 0, (size_t)nvox * sizeof(float), s);
+      if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
+    }
+  }
+  rc = zero_stats(stats, s); if (rc) return rc;
+  if (n == 0) return DRRT_OK;
+  rc = c.place(nvox, n, xt, vt, -1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
+  a.emission = emission; a.absorption = absorption;
+  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.tau = tau; a.fsteps = fwd_steps;
+  a.dx = dx; a.dv = dv; a.drad = drad; a.dtau = dtau;
+  a.grad = grad; a.grad_emission = grad_emission; a.grad_absorption = grad_absorption; a.dpos = dpos; a.dvel = dvel;
+  a.stats = stats; a.n = n; a.ds = ds;
+  a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
+  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(DRRT_PROF_BACKTRACE_EMISSION, s, "k_backtrace_emission", [&] { launch_backtrace_emission(a, s); });
 }
 
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }

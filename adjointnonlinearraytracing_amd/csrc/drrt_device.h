@@ -1029,6 +1029,159 @@ DRRT_HD RayGrad field_backtrace_ray(const Vol& V, float ds, float grad_scale, in
   return g;
 }
 
+// ---- emission with self-absorption -----------------------------------------------------------------------------------
+// rad = int e(s) exp(-int_0^s a) ds: what a camera sees through a medium that emits (e) and absorbs (a) along the ray that
+// n bends.  Two voxel fields on the grid of n.  With w_k = ds n_k (n_k masked as in trace_opl_ray) and e_k, a_k the
+// trilinear samples of the two fields at the cell and weights of n_k, in fp32 and in iteration order from tau = rad = 0:
+//   T_k       = exp_neg(tau_k)                 transmittance in front of sample k
+//   rad_{k+1} = fmaf(T_k w_k, e_k, rad_k)      emit, then absorb
+//   tau_{k+1} = fmaf(w_k, a_k, tau_k)          trace_field_ray's tau of the field a, bit for bit
+// With a = 0 everywhere T_k = exp_neg(0) = 1.0f exactly and rad is trace_field_ray's tau of the field e bit for bit.  Not
+// in the reference.
+
+// exp(-t) for the transmittance, as an explicit sequence of +, *, fmaf, comparisons, int <-> float conversions of exact
+// integers and one bit cast: no libm call and no device intrinsic, so the host build and the gfx950 kernel agree bit for
+// bit under -ffp-contract=off.  x = -t is clamped to [-87, 87], where the result is a normal fp32 (negative a, i.e. gain,
+// is legal input); NaN in gives NaN out, and the float -> int conversion never sees it.  x = k ln2 + r with k = round(x
+// log2 e), |k| <= 126, and r in about [-ln2 / 2, ln2 / 2] by a two-constant (Cody-Waite) reduction whose first product is
+// exact; exp(r) is the degree-7 Taylor polynomial in Horner form (truncation <= 5.2e-9 relative on that interval), scaled
+// by 2^k through the exponent field.  Relative error against float64 exp over the clamped range and at all reduction
+// boundaries: 7.9e-8 measured (tests/test_emission.py::test_exp_neg); exp_neg(0) == 1.0f exactly.
+DRRT_HD float exp_neg(float t) {
+  float x = -t;
+  x = x < -87.f ? -87.f : x;
+  x = x > 87.f ? 87.f : x;
+  const bool num = (x == x);
+  const float xs = num ? x : 0.f;                                         // what the conversion below sees is in [-87, 87]
+  const float kf0 = xs * 1.44269504088896341f;
+  const int k = (int)(kf0 + (kf0 >= 0.f ? 0.5f : -0.5f));                 // round to nearest, |k| <= 126
+  const float kf = (float)k;
+  float r = fmaf(-kf, 0.693145751953125f, xs);                            // ln2's upper bits: 9 trailing zeros, kf ln2_hi exact
+  r = fmaf(-kf, 1.428606765330187e-06f, r);
+  float p = 1.f / 5040.f;
+  p = fmaf(p, r, 1.f / 720.f);
+  p = fmaf(p, r, 1.f / 120.f);
+  p = fmaf(p, r, 1.f / 24.f);
+  p = fmaf(p, r, 1.f / 6.f);
+  p = fmaf(p, r, 0.5f);
+  p = fmaf(p, r, 1.f);
+  p = fmaf(p, r, 1.f);
+  const float scale = __builtin_bit_cast(float, (uint32_t)(k + 127) << 23);   // 2^k, k + 127 in [1, 253]
+  return num ? p * scale : x;
+}
+
+// trace for ONE ray with the emission integral; `taps(c)`: the taps of n, `etaps(c)` / `ataps(c)`: those of the emission and
+// absorption fields.  The loop is trace_field_ray's, so (xt, vt, steps) are trace_ray<0>'s and tau is trace_field_ray's
+// with the field a, bit for bit.  A failed ray returns what it accumulated; a ray that never samples inside rad = tau = 0.
+template <typename TapFn, typename EmisTapFn, typename AbsTapFn>
+DRRT_HD RayOut trace_emission_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                                  EmisTapFn&& etaps, AbsTapFn&& ataps, float& rad, float& tau) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
+  fwd_init(V, s);
+  Cell c = locate(V, s.x, s.y, s.z);
+  unsigned steps = 0;
+  float acc = 0.f, racc = 0.f;
+  for (int it = 0; it < max_steps; ++it) {
+    Taps t = taps_zero();
+    float n = 0.f, a = 0.f, e = 0.f;
+    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
+      t = taps(c);
+      n = interp<false>(t, c.wx, c.wy, c.wz).n;
+      e = interp<false>(etaps(c), c.wx, c.wy, c.wz).n;
+      a = interp<false>(ataps(c), c.wx, c.wy, c.wz).n;
+    }
+    const float w = ds * n;
+    racc = fmaf(exp_neg(acc) * w, e, racc);                               // emit with the transmittance in front of the sample
+    acc = fmaf(w, a, acc);                                                // then absorb
+    fwd_step_c<0>(V, nullptr, ds, s, c, t);
+    ++steps;
+    if (s.esc) break;                                                     // per-ray form of :82
+  }
+  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
+  rad = racc; tau = acc;
+  return o;
+}
+
+// Adjoint of trace_emission_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn, dL/de AND dL/da, from the
+// seeds (dx, dv, drad, dtau) on (xt, vt, rad, tau) and the forward's tau.  The reverse march is field_backtrace_ray's,
+// unchanged in structure, with two running scalars: t, the optical depth in front of the sample, which starts at the
+// forward's tau and is stepped back by t = fmaf(-w, a_k, t) (tau_k again, to rounding), and
+//   P_{k+1} = dtau - drad sum_{j>k} T_j w_j e_j        (d L / d tau_{k+1}: every later emission is dimmed by this sample)
+// which starts at dtau.  With ce = drad exp_neg(tau_k) each reverse iteration uses
+//   dn = mu . grad n_k + (ce e_k + P a_k)              (d L / d w_k = drad T_k e_k + P_{k+1} a_k)
+// where backtrace_ray_state uses mu . grad n_k, gives `esink(c, ce w)` the contribution to dL/de and `asink(c, P w)` that
+// to dL/da (value weights at the 8 taps of c, as field_backtrace_ray's fsink), adds the pull of both fields' gradients on
+// the sample position, lambda += (ce w) grad e_k + (P w) grad a_k, BEFORE adj_recur, and then P = fmaf(-(ce w), e_k, P).
+// T is always recovered from tau, never by dividing T, so an opaque ray (T at the clamp of exp_neg) gets finite gradients.
+// Because tau_k is recomputed by subtraction, T_k here differs from the forward's by rounding only: dL/de, dL/da and the
+// ray gradients are the derivative of the discrete forward to fp32 rounding, with either setting of grad_scale; dL/dn is
+// the same derivative with grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H).  With drad = 0 this is field_backtrace_ray with the
+// field a: ce = 0, P stays dtau, and nothing reaches dL/de.
+template <typename TapFn, typename EmisTapFn, typename AbsTapFn, typename Sink, typename EmisSink, typename AbsSink>
+DRRT_HD RayGrad emission_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K,
+                                       const float p0[3], const float v0[3], const float xt[3], const float vt[3],
+                                       float tau, const float dx[3], const float dv[3], float drad, float dtau,
+                                       TapFn&& taps, EmisTapFn&& etaps, AbsTapFn&& ataps, Sink&& sink, EmisSink&& esink,
+                                       AbsSink&& asink) {
+  RayGrad g;
+  g.steps = 0; g.failed = false;
+  if (max_steps <= 0 || K >= (unsigned)max_steps) {
+    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    g.failed = true;
+    return g;
+  }
+  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
+  float px = p0[0], py = p0[1], pz = p0[2];
+  unsigned e = 0;
+  while (e < K && !inbounds(V, px, py, pz)) {
+    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
+    ++e;
+  }
+  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, rad = tau = 0
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  float t = tau, P = dtau;
+  for (unsigned k = K; k > e; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
+    const Cell c = locate(V, s.x, s.y, s.z);
+    AdjSample m;
+    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
+    const Sample em = interp<false>(etaps(c), c.wx, c.wy, c.wz);
+    const Sample ab = interp<false>(ataps(c), c.wx, c.wy, c.wz);
+    const float w = ds * m.n;
+    t = fmaf(-w, ab.n, t);                                                // tau_k
+    const float ce = drad * exp_neg(t);
+    const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz) + fmaf(ce, em.n, P * ab.n);
+    const float nds = (m.n * ds) * grad_scale;
+    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
+    const float ev = ce * w, av = P * w;
+    esink(c, ev);
+    asink(c, av);
+    qx = s.mx; qy = s.my; qz = s.mz;
+    s.lx = fmaf(ev, em.gx * V.inv_h, s.lx); s.ly = fmaf(ev, em.gy * V.inv_h, s.ly); s.lz = fmaf(ev, em.gz * V.inv_h, s.lz);
+    s.lx = fmaf(av, ab.gx * V.inv_h, s.lx); s.ly = fmaf(av, ab.gy * V.inv_h, s.ly); s.lz = fmaf(av, ab.gz * V.inv_h, s.lz);
+    adj_recur(V, ds, s, m, dn);
+    P = fmaf(-ev, em.n, P);
+  }
+  const float eds = (float)e * ds;
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
+  g.steps = K - e;
+  return g;
+}
+
 // trace_cable for ONE ray (src/tracer.cpp:312-382)
 DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
                                const float tg[3]) {

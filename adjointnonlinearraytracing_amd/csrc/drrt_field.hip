@@ -11,22 +11,10 @@
 // The adjoint scatters into each grid with HeldCorners (one global fp32 atomic per tap and per run of samples in one
 // cell), one instance per grid.  The kernel is instantiated per set of grids scattered, so that a call asking for one grid
 // does not carry the other's eight corner sums.  No LDS window, as for the optical path length.
+// FieldTaps lives in drrt_march.h: drrt_emission.hip uses it too.
 #include "drrt_march.h"
 
 namespace drrt {
-
-// the taps of the field at cell c: the cell and clamps of n's taps, kept while the lane stays in a strictly interior cell
-struct FieldTaps {
-  const float* d;
-  int base = -1;             // base < 0: nothing held
-  Taps t;
-  __device__ __forceinline__ explicit FieldTaps(const float* f) : d(f), t(taps_zero()) {}
-  __device__ __forceinline__ Taps operator()(const Cell& c) {
-    if (!c.interior) { base = -1; return fetch(d, c); }
-    if (c.base != base) { t = fetch(d, c); base = c.base; }
-    return t;
-  }
-};
 
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_field(FieldTraceArgs a) {

@@ -16,6 +16,9 @@
 //                           dL/dn, dL/dpos and dL/dvel from seeds on (xt, vt, opl) in one march (global atomics, no window)
 //   drrt_field.hip          trace_field, backtrace_field: trace with the line integral tau of a second field along the bent
 //                           ray, and the adjoint that returns dL/dn, dL/dfield, dL/dpos and dL/dvel from seeds on (xt, vt, tau)
+//   drrt_emission.hip       trace_emission, backtrace_emission: trace with the emission integral rad = int e exp(-int a) of two
+//                           further fields along the bent ray, and the adjoint that returns dL/dn, dL/de, dL/da, dL/dpos and
+//                           dL/dvel from seeds on (xt, vt, rad, tau) in one march
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -245,7 +248,7 @@ __device__ __forceinline__ void taps_set(const Taps& t, f4& q0, f4& q1) {
 }
 template <bool PAIR> __device__ __forceinline__ unsigned tap_offset(int base) { return (unsigned)base << (PAIR ? 3 : 2); }
 
-// ---- one ray per lane with global atomics: drrt_opl.hip, drrt_field.hip ----
+// ---- one ray per lane with global atomics: drrt_opl.hip, drrt_field.hip, drrt_emission.hip ----
 // the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell
 template <bool PAIR>
 struct OplTaps {
@@ -287,6 +290,20 @@ struct HeldCorners {
     }
     flush();
     s = w; base = c.base; ox = c.ox; oy = c.oy; oz = c.oz;
+  }
+};
+
+// the taps of a second field at cell c (drrt_field.hip, drrt_emission.hip): the cell and clamps of n's taps, plain gathers
+// of the field itself, kept while the lane stays in a strictly interior cell
+struct FieldTaps {
+  const float* d;
+  int base = -1;             // base < 0: nothing held
+  Taps t;
+  __device__ __forceinline__ explicit FieldTaps(const float* f) : d(f), t(taps_zero()) {}
+  __device__ __forceinline__ Taps operator()(const Cell& c) {
+    if (!c.interior) { base = -1; return fetch(d, c); }
+    if (c.base != base) { t = fetch(d, c); base = c.base; }
+    return t;
   }
 };
 
@@ -563,6 +580,43 @@ struct FieldBackArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// emission with self-absorption (drrt_emission.hip): trace with rad = sum T_k ds n_k e_k, T_k = exp_neg(tau_k), and
+// tau = sum ds n_k a_k; and its adjoint (all three grids and the rays)
+struct EmissionTraceArgs {
+  Vol vol;
+  const float* emission; const float* absorption;   // two more grids: vol's shape, plain layout (no pair copy)
+  const float* pos; const float* vel;
+  float* xt; float* vt; float* rad; float* tau;
+  uint32_t* steps_out;                      // per-ray iteration counts, caller ray order
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+struct EmissionBackArgs {
+  Vol vol;
+  const float* emission; const float* absorption;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const float* tau;                         // its tau: the reverse march recovers every transmittance from it
+  const uint32_t* fsteps;                   // its per-ray iteration counts, caller ray order
+  const float* dx; const float* dv;         // nullable: seeds on (xt, vt), read as zeros
+  const float* drad; const float* dtau;     // nullable: seeds on rad and tau, n floats each
+  float* grad;                              // nullable: no scatter into dL/dn
+  float* grad_emission;                     // nullable: no scatter into dL/de
+  float* grad_absorption;                   // nullable: no scatter into dL/da
+  float* dpos; float* dvel;                 // both null: no ray outputs
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  float grad_scale;                         // 1 (as written, Q3) or 1/h (DRRT_FLAG_CORRECTED_H)
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -630,6 +684,9 @@ void launch_backtrace_opl(const OplBackArgs& a, hipStream_t s);
 // line integral of a second field: trace_field and its adjoint (drrt_field.hip)
 void launch_trace_field(const FieldTraceArgs& a, hipStream_t s);
 void launch_backtrace_field(const FieldBackArgs& a, hipStream_t s);
+// emission with self-absorption: trace_emission and its adjoint (drrt_emission.hip)
+void launch_trace_emission(const EmissionTraceArgs& a, hipStream_t s);
+void launch_backtrace_emission(const EmissionBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

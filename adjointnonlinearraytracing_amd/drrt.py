@@ -551,9 +551,17 @@ def _grid_inputs(rif, sdf, rays, dev: torch.device, how=None):
     return rif_, sdf_, [first] + [_rays(t, dev, first.shape[0], **kw) for t, kw in zip(rays[1:], how[1:])], first.shape[0]
 
 
+def _more_grid(grid, rif_, dev: torch.device) -> torch.Tensor:
+    """A further grid of a grid entry on `dev`: flat fp32, of the first grid's size."""
+    g = _f32(grid, dev).reshape(-1)
+    if g.numel() != rif_.numel():
+        raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
+    return g
+
+
 def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sdf=None, how=None, fwd_steps=None,
                order=None, replay: bool = False, flags: int = 0, steps: bool = True, warn: bool = False,
-               counters: bool = False, per_ray=()) -> tuple:
+               counters: bool = False, per_ray=(), more_grids=()) -> tuple:
     """One call of a grid entry point (they share their shape: grid, [sdf], nvox, res, n, the inputs, h, ds, the outputs,
     the usual tail) -> (outputs, order, steps): the outputs, made by ``make_outputs(flat grid, ray tensors)``, and what
     a forward march left behind -- its visit order and per-ray iteration counts, the workspace views that are also
@@ -563,10 +571,11 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
     passed as a null pointer).  `adjoint`: a forward march, or an adjoint that may be paired
     with one through `order`; `replay`: an adjoint that marches its forward again (`_paired_adjoint`).  `steps`: the
     forward leaves iteration counts.  `warn`: failed rays are reported.  `counters`: the adjoint classifies its bundles
-    (`last_bundle_counters`)."""
+    (`last_bundle_counters`).  `more_grids`: further fp32 grids of the first one's size, passed behind `sdf`."""
     dev = _dev(rif)
     with torch.cuda.device(dev):
         rif_, sdf_, rays_, n = _grid_inputs(rif, sdf, rays, dev, how)
+        more_ = [_more_grid(g, rif_, dev) for g in more_grids]
         if fwd_steps is not None:
             steps_ = fwd_steps.detach().to(device=dev).contiguous()
             if steps_.dtype != torch.int32 or steps_.numel() != n:
@@ -579,6 +588,7 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
                 raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
             rays_.append(t)
         grids = [_p(rif_)] if sdf_ is None else [_p(rif_), _p(sdf_)]
+        grids += [_p(g) for g in more_]
         march = _paired_adjoint(rif_, res, n, h, ds, dev, order, replay, flags) if adjoint else \
             _forward_march(rif_, res, n, h, ds, dev, flags)
         with march as (fl, ws, st, _):
@@ -686,7 +696,81 @@ class TracerC:
         integral of the field along the path; with field = rif it is ``trace_opl``'s opl bit for bit).  fp32 rays only."""
         return self._trace_field(rif, field, res, pos, vel, h, ds)[0]
 
+    def _trace_emission(self, rif, emission, absorption, res, pos, vel, h, ds):
+        def outputs(rif_, r):
+            n = r[0].shape[0]
+            return _like_rays(rif_, r) + (r[0].new_empty(n), r[0].new_empty(n),
+                                          torch.empty(n, dtype=torch.int32, device=r[0].device))
+        return _grid_call("drrt_trace_emission_f32", rif, res, [pos, vel], h, ds, outputs, adjoint=False, sdf=emission,
+                          more_grids=(absorption,), steps=False, warn=True)
+
+    def trace_emission(self, rif, emission, absorption, res, pos, vel, h, ds):
+        """``trace`` with the radiative-transfer line integral of an emitting, self-absorbing medium along every bent ray
+        (drrt_trace_emission_f32, include/drrt_hip.h; not in the reference) -> (xt, vt, rad, tau, steps).  `emission`,
+        `absorption`: fp32 grids of `rif`'s shape and axis convention.  xt, vt and the per-ray iteration counts `steps`
+        (int32[n], a tensor of the caller's, not a workspace view) are ``trace``'s bit for bit.  Over the samples the march
+        takes inside the box, with ``w_k = ds n_k``: ``rad = sum exp_neg(tau_k) w_k e_k`` (emit, then absorb: the
+        transmittance is that in front of the sample) and ``tau = sum w_k a_k``, which is ``trace_field(rif, absorption)``'s
+        tau bit for bit; with absorption = 0, rad is ``trace_field(rif, emission)``'s tau bit for bit.  |v| = n, so these
+        are the integrals along the path.  Negative absorption (gain) is legal; the exponent is clamped to +-87.  fp32 rays
+        only."""
+        return self._trace_emission(rif, emission, absorption, res, pos, vel, h, ds)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_emission(self, rif, emission, absorption, res, pos, vel, xt, vt, steps, tau, dx, dv, drad, dtau, h, ds,
+                           grid: bool = True, emission_grid: bool = True, absorption_grid: bool = True, rays: bool = True,
+                           into: Optional[torch.Tensor] = None, emission_into: Optional[torch.Tensor] = None,
+                           absorption_into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_emission`` (drrt_backtrace_emission_f32, include/drrt_hip.h) -> (grad | None,
+        grad_emission | None, grad_absorption | None, dpos | None, dvel | None): flat dL/drif, dL/demission and
+        dL/dabsorption (fp32[nvox] each), dL/dpos and dL/dvel ((n,3) fp32) from ONE reverse march.  `pos`, `vel` are the
+        forward call's inputs, `xt`, `vt`, `steps`, `tau` its outputs; `dx`, `dv` ((n,3)), `drad` and `dtau` (n values each)
+        the seeds on (xt, vt, rad, tau), each optional (None: zeros).  `grid` / `emission_grid` / `absorption_grid` / `rays`:
+        which outputs are computed (at least one); `into` / `emission_into` / `absorption_into`: a flat fp32[nvox] tensor
+        that grid's gradient is ADDED to (DRRT_FLAG_NO_ZERO, which covers all three grids: those asked for without an
+        accumulator are zeroed here) and that is returned in its place.  The reverse march recovers every transmittance from
+        `tau` by subtraction, so dL/demission, dL/dabsorption and the ray gradients are the derivative of the discrete
+        forward to fp32 rounding; dL/drif is the same derivative with ``options.corrected_h``.  Rays that failed the forward
+        get zeros and contribute nothing.  `order`: the forward's visit order."""
+        if not (grid or emission_grid or absorption_grid or rays):
+            raise RuntimeError("backtrace_emission: nothing to compute (grid = emission_grid = absorption_grid = rays = False)")
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            rif_, emis_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, emission, [pos, vel, xt, vt], dev)
+            absb_ = _more_grid(absorption, rif_, dev)
+            steps_ = steps.detach().to(device=dev).contiguous()
+            if steps_.dtype != torch.int32 or steps_.numel() != n:
+                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_emission's)")
+            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+            tau_, drad_, dtau_ = (None if t is None else _f32(t, dev).reshape(-1) for t in (tau, drad, dtau))
+            if tau_ is None:
+                raise RuntimeError("backtrace_emission: `tau` is the forward call's tau (trace_emission's)")
+            for t in (tau_, drad_, dtau_):
+                if t is not None and t.numel() != n:
+                    raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
+            wanted = ((grid, into, "into"), (emission_grid, emission_into, "emission_into"),
+                      (absorption_grid, absorption_into, "absorption_into"))
+            no_zero = any(want and acc is not None for want, acc, _ in wanted)
+            grads = []
+            for want, acc, name in wanted:
+                if not want:
+                    grads.append(None)
+                elif acc is not None:
+                    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
+                        raise RuntimeError(f"backtrace_emission: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
+                    grads.append(acc.detach().view(-1))
+                else:
+                    grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
+            grad, gemis, gabsb = grads
+            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
+            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
+                _lib.check(_lib.load().drrt_backtrace_emission_f32(
+                    _p(rif_), _p(emis_), _p(absb_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_),
+                    _p(steps_), _p(tau_), _p(dx_), _p(dv_), _p(drad_), _p(dtau_), float(h), float(ds), _p(grad), _p(gemis),
+                    _p(gabsb), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
+            _warn_failed(st)
+        return grad, gemis, gabsb, dpos, dvel
+
     def backtrace_field(self, rif, field, res, pos, vel, xt, vt, steps, dx, dv, dtau, h, ds, grid: bool = True,
                         field_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,
                         field_into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):

@@ -409,6 +409,68 @@ DRRT_API int drrt_backtrace_field_f32(const float* rif, const float* field, long
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- emission with self-absorption along the bent ray (not in the reference) ----------------------------------------------
+ * rad = int e(s) exp(-int_0^s a) ds, the radiative-transfer line integral: what a camera sees through a medium that emits
+ * (e) and absorbs (a) along the ray that n bends.  `emission` and `absorption` are fp32 grids of exactly rif's shape and
+ * axis convention.  drrt_trace_emission_f32 is drrt_trace_f32 (xt, vt and the per-ray iteration counts K bit for bit) that
+ * also returns rad and tau.  With n_k the masked sample the march takes at x_k anyway (0 while the ray is not inside the
+ * box), w_k = ds n_k, and e_k, a_k the trilinear samples of the two fields at the same cell, with the same weights and the
+ * same mask, in fp32 and in iteration order from tau_0 = rad_0 = 0:
+ *   T_k       = exp_neg(tau_k)                 the transmittance in front of sample k
+ *   rad_{k+1} = fmaf(T_k w_k, e_k, rad_k)      emit, then absorb
+ *   tau_{k+1} = fmaf(w_k, a_k, tau_k)          drrt_trace_field_f32's tau of the field a, bit for bit
+ * exp_neg(t) = exp(-t) is the library's own operation sequence (csrc/drrt_device.h: argument clamped to +-87, relative
+ * error 7.9e-8, exp_neg(0) = 1 exactly, NaN in -> NaN out), so with absorption = 0 everywhere rad is
+ * drrt_trace_field_f32's tau of the field e bit for bit.  Negative absorption (gain) is legal.  A failed ray returns what
+ * it accumulated; a ray that never samples inside returns rad = tau = 0.
+ *   rad, tau   out: fp32[n] each
+ *   steps_out  out: uint32[n], required: K per ray, caller ray order (what the adjoint takes as fwd_steps).  The call
+ *              leaves no drrt_last_steps().
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE (the pair copy is of rif; the two fields are gathered as
+ * they are), DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32.  fp32 only. */
+DRRT_API int drrt_trace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
+                       const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds,
+                       float* xt, float* vt, float* rad, float* tau, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_emission_f32: from the seeds dx = dL/dxt, dv = dL/dvt, drad = dL/drad, dtau = dL/dtau (each
+ * nullable: read as zeros) ONE reverse march yields dL/drif (grad), dL/demission (grad_emission), dL/dabsorption
+ * (grad_absorption), dL/dpos and dL/dvel.  `tau` is the forward's tau (required when n > 0).  The march is
+ * drrt_backtrace_field_f32's, unchanged in structure (failed rays get zeros, contribute nothing and count in
+ * stats->n_failed; never-entered rays get (dx, dv) and contribute nothing), with two running scalars: t, from the
+ * forward's tau, stepped back by t = fmaf(-w_k, a_k, t) to tau_k, and P, from dtau, the derivative of L w.r.t. the optical
+ * depth behind the sample.  Each reverse iteration samples rif, emission and absorption at the same cell and, with
+ * ce = drad exp_neg(t), uses  dn = mu . grad n_k + (ce e_k + P a_k)  where drrt_backtrace_rays_f32 uses mu . grad n_k, adds
+ * (ce w_k) grad e_k + (P w_k) grad a_k  to lambda before the recurrences, adds, with mu before its update, at the 8 taps
+ * of the sampled cell
+ *   to grad:             splat_weights(w, dn ds, (n_k ds grad_scale) mu), grad_scale = 1 / h with DRRT_FLAG_CORRECTED_H and
+ *                        1 without, as for drrt_backtrace_f32 (Q3);
+ *   to grad_emission:    the value weights alone, w_c (ce w_k);
+ *   to grad_absorption:  the value weights alone, w_c (P w_k);
+ * and then steps P = fmaf(-(ce w_k), e_k, P).  The transmittance is always recovered from tau, never by dividing it, so an
+ * opaque ray (exp_neg at its clamp) gets finite gradients.  tau_k is recomputed by subtraction, so the transmittance of the
+ * reverse march differs from the forward's by rounding only: grad_emission, grad_absorption, dpos and dvel are the
+ * derivative of the discrete forward to fp32 rounding with either setting; grad is the same derivative with
+ * DRRT_FLAG_CORRECTED_H.  With drad null or zero this is drrt_backtrace_field_f32 with field = absorption.
+ *   grad, grad_emission, grad_absorption  out, each nullable (no scatter into that grid): fp32[nvox], zeroed by the call
+ *                        unless DRRT_FLAG_NO_ZERO, which applies to all three
+ *   dpos, dvel           out, both or neither: (n,3) fp32.  All five outputs null: DRRT_ERR_ARG
+ * The scatter is one global fp32 atomic per tap, per grid and per run of samples in one cell, as for
+ * drrt_backtrace_field_f32: no LDS window, so a call pays the memory-side atomic rate once per grid it scatters into.
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE, DRRT_FLAG_DISPATCH_IN_ORDER, DRRT_FLAG_CORRECTED_H,
+ * DRRT_FLAG_NO_ZERO; other adjoint flags are ignored.  The order hint is consumed, the step hint ignored.  fp32 only.      */
+DRRT_API int drrt_backtrace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
+                       const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps, const float* tau,
+                       const float* dx, const float* dv, const float* drad, const float* dtau, float h, float ds,
+                       float* grad, float* grad_emission, float* grad_absorption, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -690,6 +752,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_OPL 12   /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_opl_f32) */
 #define DRRT_PROF_TRACE_FIELD 13     /* trace with the line integral of a second field (drrt_trace_field_f32) */
 #define DRRT_PROF_BACKTRACE_FIELD 14 /* its adjoint: dL/dn, dL/dfield and the ray gradients in one march (drrt_backtrace_field_f32) */
+#define DRRT_PROF_TRACE_EMISSION 15  /* trace with the emission integral of two further fields (drrt_trace_emission_f32) */
+#define DRRT_PROF_BACKTRACE_EMISSION 16 /* its adjoint: dL/dn, dL/de, dL/da and the ray gradients in one march (drrt_backtrace_emission_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

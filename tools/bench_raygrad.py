@@ -78,6 +78,22 @@ field   drrt_trace_field_f32 / drrt_backtrace_field_f32 (k_trace_field, k_backtr
         usage: bench_raygrad.py field [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
         Also writes the JSON, with the library's version string (source digest), to --out (default profiles/field_bench.json).
 
+emission  drrt_trace_emission_f32 / drrt_backtrace_emission_f32 (k_trace_emission, k_backtrace_emission) next to the field
+        calls they are modelled on, on the workloads of `field`; emission e = 1 + 0.5 U, absorption a = s (1 + 0.5 U) with s
+        such that the median tau of the rays is 1 (found with one trace_field per medium), both seeded.  All adjoints take
+        seeds on all outputs and return the ray gradients too.
+            trace_field               TracerC.trace_field(field = a)
+            trace_emission            TracerC.trace_emission
+            backtrace_field           TracerC.backtrace_field(grid=False)                            (dL/da)
+            backtrace_emission_rif    TracerC.backtrace_emission(emission_grid = absorption_grid = False)   (dL/dn)
+            backtrace_emission_e      TracerC.backtrace_emission(grid = absorption_grid = False)     (dL/de)
+            backtrace_emission_a      TracerC.backtrace_emission(grid = emission_grid = False)       (dL/da)
+            backtrace_emission_all    TracerC.backtrace_emission                                     (all three grids)
+        Timed alternately like `field`.  Output per medium and call: median, minimum, maximum ms and stats.ray_steps, the
+        median tau, and the ratios trace_emission / trace_field and backtrace_emission_* / backtrace_field.
+        usage: bench_raygrad.py emission [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string (source digest), to --out (default profiles/emission_bench.json).
+
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
 over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
@@ -422,6 +438,49 @@ def field(a, dev):
     return out
 
 
+def emission(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl` and `field`
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
+    gen = lambda seed: (1.0 + 0.5 * torch.rand((a.grid,) * 3, generator=torch.Generator(device="cpu").manual_seed(seed))).to(dev)   # noqa: E731
+    emis, unit = gen(2), gen(3)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for medium, make in (("luneburg", bench.make_grid), ("tomo_weak", bench.make_grid_tomo)):
+        rif = make(a.grid, dev)
+        res = tuple(rif.shape)
+        absb = unit / float(T.trace_field(rif, unit, res, pos, vel, h, ds)[2].median())      # median tau = 1
+        xt, vt, _, tau, steps = T.trace_emission(rif, emis, absb, res, pos, vel, h, ds)
+        order = drrt.keep_order(drrt.last_order)
+        back = lambda **kw: T.backtrace_emission(rif, emis, absb, res, pos, vel, xt, vt, steps, tau, one, one, g, g, h, ds,   # noqa: E731
+                                                 order=order, **kw)
+        r, med = time_each({
+            "trace_field": lambda: T.trace_field(rif, absb, res, pos, vel, h, ds),
+            "trace_emission": lambda: T.trace_emission(rif, emis, absb, res, pos, vel, h, ds),
+            "backtrace_field": lambda: T.backtrace_field(rif, absb, res, pos, vel, xt, vt, steps, one, one, g, h, ds, grid=False,
+                                                         order=order),
+            "backtrace_emission_rif": lambda: back(emission_grid=False, absorption_grid=False),
+            "backtrace_emission_e": lambda: back(grid=False, absorption_grid=False),
+            "backtrace_emission_a": lambda: back(grid=False, emission_grid=False),
+            "backtrace_emission_all": back,
+        }, a)
+        if r is None:
+            continue
+        r["median_tau"] = float(tau.median())
+        r["trace_emission_over_trace_field"] = med["trace_emission"] / med["trace_field"]
+        for k in ("rif", "e", "a", "all"):
+            r[f"backtrace_emission_{k}_over_backtrace_field"] = med[f"backtrace_emission_{k}"] / med["backtrace_field"]
+        out[medium] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -454,14 +513,19 @@ def main():
     p_field.add_argument("--rays", type=int, default=1 << 20)
     p_field.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "field_bench.json"))
     p_field.set_defaults(run=field)
-    for p in (p_cable, p_stop, p_target, p_opl, p_field):
+    p_emis = sub.add_parser("emission")
+    p_emis.add_argument("--grid", type=int, default=256)
+    p_emis.add_argument("--rays", type=int, default=1 << 20)
+    p_emis.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "emission_bench.json"))
+    p_emis.set_defaults(run=emission)
+    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target", "opl", "field") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl", "field", "emission") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
