@@ -1,7 +1,7 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_opl.hip / drrt_field.hip / drrt_emission.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
 // utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
@@ -708,26 +708,94 @@ extern "C" int drrt_backtrace_target_rays_f32(const float* rif, long long nvox, 
   return timed_launch(DRRT_PROF_BACKTRACE_TARGET_RAYS, s, "k_backtrace_target_rays", [&] { launch_backtrace_target_rays(a, s); });
 }
 
-// ---- optical path length: drrt_opl.hip --------------------------------------------------------------------------------
+// ---- the integral operators (optical path length, line integral of a second field, emission with self-absorption):
+// drrt_integral.hip -------------------------------------------------------------------------------------------------------
+// The six entry points share one forward and one backward prologue.  An entry point fills the fields of its argument block
+// that are its own (further grids, per-ray inputs and outputs, gradient grids) and names them for the checks.
+struct IntegralCall {              // the arguments every one of the six has
+  const float* rif; long long nvox; const int* res; size_t n;
+  const float* pos; const float* vel;
+  float h, ds;
+  drrt_stats* stats; void* ws; size_t ws_bytes; unsigned flags; void* stream;
+};
+struct Needed { const void* p; const char* error; };      // a pointer that must not be null, and the message when it is
+
+// `grids`: the further input grids; `outs`: the operator's per-ray outputs (checked with the rays)
+template <typename Args>
+static int run_trace_integral(Args& a, const IntegralCall& k, std::initializer_list<Needed> grids,
+                              std::initializer_list<const float*> outs, float* xt, float* vt, uint32_t* steps_out,
+                              int prof_id, const char* where, void (*launch)(const Args&, hipStream_t)) {
+  GridCall c(a.vol, k.stream);
+  g_ts.reset_last_steps();              // this forward march writes its iteration counts to the caller, none to the workspace
+  hipStream_t s = c.s;
+  int rc = c.open(k.rif, k.nvox, k.res, k.h, k.ds); if (rc) return rc;
+  for (const Needed& g : grids) if (!g.p) return fail(DRRT_ERR_ARG, g.error);
+  if (k.n == 0) return zero_stats(k.stats, s);
+  bool rays = k.pos && k.vel && xt && vt;
+  for (const float* o : outs) rays = rays && o;
+  if (!rays) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!steps_out) return fail(DRRT_ERR_ARG, "null steps_out pointer (the adjoint needs the iteration counts)");
+  rc = check_ray_count(k.n); if (rc) return rc;
+  rc = zero_stats(k.stats, s); if (rc) return rc;
+  rc = c.place(k.nvox, k.n, k.pos, k.vel, 1.f, k.flags, ws_layout(k.n, k.nvox, k.flags, k.ws_bytes), k.ws, k.ws_bytes);
+  if (rc) return rc;
+  a.pos = k.pos; a.vel = k.vel; a.xt = xt; a.vt = vt; a.steps_out = steps_out; a.stats = k.stats; a.n = k.n; a.ds = k.ds;
+  a.max_steps = steps_fwd(k.h, k.res, k.ds);
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(prof_id, s, where, [&] { launch(a, s); });
+}
+
+// `grids`: the further input grids; `per_ray`: the operator's per-ray inputs that must be there (checked behind fwd_steps);
+// `grads`: the gradient grids (each nullable, zeroed here unless DRRT_FLAG_NO_ZERO); `no_outputs`: the message when they,
+// dpos and dvel are all null
+template <typename Args>
+static int run_backtrace_integral(Args& a, const IntegralCall& k, std::initializer_list<Needed> grids,
+                                  std::initializer_list<Needed> per_ray, std::initializer_list<float*> grads,
+                                  const char* no_outputs, const float* xt, const float* vt, const uint32_t* fwd_steps,
+                                  const float* dx, const float* dv, float* dpos, float* dvel, int prof_id, const char* where,
+                                  void (*launch)(const Args&, hipStream_t)) {
+  GridCall c(a.vol, k.stream);
+  hipStream_t s = c.s;
+  int rc = c.open(k.rif, k.nvox, k.res, k.h, k.ds); if (rc) return rc;
+  for (const Needed& g : grids) if (!g.p) return fail(DRRT_ERR_ARG, g.error);
+  bool any = dpos || dvel;
+  for (float* g : grads) any = any || g;
+  if (!any) return fail(DRRT_ERR_ARG, no_outputs);
+  if (!dpos != !dvel) return fail(DRRT_ERR_ARG, "dpos and dvel go together");
+  if (k.n > 0) {
+    if (!k.pos || !k.vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
+    if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's steps_out)");
+    for (const Needed& p : per_ray) if (!p.p) return fail(DRRT_ERR_ARG, p.error);
+    rc = check_ray_count(k.n); if (rc) return rc;
+  }
+  if (!(k.flags & DRRT_FLAG_NO_ZERO)) {
+    for (float* g : grads) {
+      if (!g) continue;
+      ProfScope prof(DRRT_PROF_ZERO, s);
+      hipError_t e = hipMemsetAsync(g, 0, (size_t)k.nvox * sizeof(float), s);
+      if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
+    }
+  }
+  rc = zero_stats(k.stats, s); if (rc) return rc;
+  if (k.n == 0) return DRRT_OK;
+  rc = c.place(k.nvox, k.n, xt, vt, -1.f, k.flags, ws_layout(k.n, k.nvox, k.flags, k.ws_bytes), k.ws, k.ws_bytes);
+  if (rc) return rc;
+  a.pos = k.pos; a.vel = k.vel; a.xt = xt; a.vt = vt; a.fsteps = fwd_steps; a.dx = dx; a.dv = dv;
+  a.dpos = dpos; a.dvel = dvel; a.stats = k.stats; a.n = k.n; a.ds = k.ds;
+  a.grad_scale = (k.flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
+  a.max_steps = steps_fwd(k.h, k.res, k.ds);      // the forward's bound: a ray that used all of it failed
+  a.perm = c.perm; a.xcd_order = c.xcd_order;
+  return timed_launch(prof_id, s, where, [&] { launch(a, s); });
+}
+
 extern "C" int drrt_trace_opl_f32(const float* rif, long long nvox, const int res[3], size_t n,
                                   const float* pos, const float* vel, float h, float ds, float* xt, float* vt,
                                   float* opl, uint32_t* steps_out, drrt_stats* stats, void* ws, size_t ws_bytes,
                                   unsigned flags, void* stream) {
   OplTraceArgs a{};
-  GridCall c(a.vol, stream);
-  g_ts.reset_last_steps();              // this forward march writes its iteration counts to the caller, none to the workspace
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (n == 0) return zero_stats(stats, s);
-  if (!pos || !vel || !xt || !vt || !opl) return fail(DRRT_ERR_ARG, "null ray pointer");
-  if (!steps_out) return fail(DRRT_ERR_ARG, "null steps_out pointer (the adjoint needs the iteration counts)");
-  rc = check_ray_count(n); if (rc) return rc;
-  rc = zero_stats(stats, s); if (rc) return rc;
-  rc = c.place(nvox, n, pos, vel, 1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.opl = opl; a.steps_out = steps_out; a.stats = stats; a.n = n; a.ds = ds;
-  a.max_steps = steps_fwd(h, res, ds);
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_TRACE_OPL, s, "k_trace_opl", [&] { launch_trace_opl(a, s); });
+  a.opl = opl;
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {}, {opl}, xt, vt,
+                            steps_out, DRRT_PROF_TRACE_OPL, "k_trace_opl", launch_trace_opl);
 }
 
 extern "C" int drrt_backtrace_opl_f32(const float* rif, long long nvox, const int res[3], size_t n,
@@ -736,54 +804,21 @@ extern "C" int drrt_backtrace_opl_f32(const float* rif, long long nvox, const in
                                       float h, float ds, float* grad, float* dpos, float* dvel, drrt_stats* stats,
                                       void* ws, size_t ws_bytes, unsigned flags, void* stream) {
   OplBackArgs a{};
-  GridCall c(a.vol, stream);
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (!grad && !dpos && !dvel) return fail(DRRT_ERR_ARG, "null output pointers: grad, or dpos and dvel, or all three");
-  if (!dpos != !dvel) return fail(DRRT_ERR_ARG, "dpos and dvel go together");
-  if (n > 0) {
-    if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
-    if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's steps_out)");
-    rc = check_ray_count(n); if (rc) return rc;
-  }
-  if (grad && !(flags & DRRT_FLAG_NO_ZERO)) {
-    ProfScope prof(DRRT_PROF_ZERO, s);
-    hipError_t e = hipMemsetAsync(grad, 0, (size_t)nvox * sizeof(float), s);
-    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
-  }
-  rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  rc = c.place(nvox, n, xt, vt, -1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.fsteps = fwd_steps; a.dx = dx; a.dv = dv; a.dopl = dopl;
-  a.grad = grad; a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
-  a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
-  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_BACKTRACE_OPL, s, "k_backtrace_opl", [&] { launch_backtrace_opl(a, s); });
+  a.dopl = dopl; a.grad = grad;
+  return run_backtrace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {}, {}, {grad},
+                                "null output pointers: grad, or dpos and dvel, or all three", xt, vt, fwd_steps, dx, dv,
+                                dpos, dvel, DRRT_PROF_BACKTRACE_OPL, "k_backtrace_opl", launch_backtrace_opl);
 }
 
-// ---- line integral of a second field: drrt_field.hip -----------------------------------------------------------------
 extern "C" int drrt_trace_field_f32(const float* rif, const float* field, long long nvox, const int res[3], size_t n,
                                     const float* pos, const float* vel, float h, float ds, float* xt, float* vt,
                                     float* tau, uint32_t* steps_out, drrt_stats* stats, void* ws, size_t ws_bytes,
                                     unsigned flags, void* stream) {
   FieldTraceArgs a{};
-  GridCall c(a.vol, stream);
-  g_ts.reset_last_steps();              // this forward march writes its iteration counts to the caller, none to the workspace
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (!field) return fail(DRRT_ERR_ARG, "null field pointer");
-  if (n == 0) return zero_stats(stats, s);
-  if (!pos || !vel || !xt || !vt || !tau) return fail(DRRT_ERR_ARG, "null ray pointer");
-  if (!steps_out) return fail(DRRT_ERR_ARG, "null steps_out pointer (the adjoint needs the iteration counts)");
-  rc = check_ray_count(n); if (rc) return rc;
-  rc = zero_stats(stats, s); if (rc) return rc;
-  rc = c.place(nvox, n, pos, vel, 1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.field = field;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.tau = tau; a.steps_out = steps_out; a.stats = stats; a.n = n; a.ds = ds;
-  a.max_steps = steps_fwd(h, res, ds);
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_TRACE_FIELD, s, "k_trace_field", [&] { launch_trace_field(a, s); });
+  a.field = field; a.tau = tau;
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+                            {{field, "null field pointer"}}, {tau}, xt, vt, steps_out, DRRT_PROF_TRACE_FIELD, "k_trace_field",
+                            launch_trace_field);
 }
 
 extern "C" int drrt_backtrace_field_f32(const float* rif, const float* field, long long nvox, const int res[3], size_t n,
@@ -792,62 +827,23 @@ extern "C" int drrt_backtrace_field_f32(const float* rif, const float* field, lo
                                         float h, float ds, float* grad, float* grad_field, float* dpos, float* dvel,
                                         drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
   FieldBackArgs a{};
-  GridCall c(a.vol, stream);
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (!field) return fail(DRRT_ERR_ARG, "null field pointer");
-  if (!grad && !grad_field && !dpos && !dvel)
-    return fail(DRRT_ERR_ARG, "null output pointers: grad, grad_field, or dpos and dvel, or any of these together");
-  if (!dpos != !dvel) return fail(DRRT_ERR_ARG, "dpos and dvel go together");
-  if (n > 0) {
-    if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
-    if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's steps_out)");
-    rc = check_ray_count(n); if (rc) return rc;
-  }
-  if (!(flags & DRRT_FLAG_NO_ZERO)) {
-    for (float* g : {grad, grad_field}) {
-      if (!g) continue;
-      ProfScope prof(DRRT_PROF_ZERO, s);
-      hipError_t e = hipMemsetAsync(g, 0, (size_t)nvox * sizeof(float), s);
-      if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
-    }
-  }
-  rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  rc = c.place(nvox, n, xt, vt, -1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.field = field;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.fsteps = fwd_steps; a.dx = dx; a.dv = dv; a.dtau = dtau;
-  a.grad = grad; a.grad_field = grad_field; a.dpos = dpos; a.dvel = dvel; a.stats = stats; a.n = n; a.ds = ds;
-  a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
-  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_BACKTRACE_FIELD, s, "k_backtrace_field", [&] { launch_backtrace_field(a, s); });
+  a.field = field; a.dtau = dtau; a.grad = grad; a.grad_field = grad_field;
+  return run_backtrace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+                                {{field, "null field pointer"}}, {}, {grad, grad_field},
+                                "null output pointers: grad, grad_field, or dpos and dvel, or any of these together", xt, vt,
+                                fwd_steps, dx, dv, dpos, dvel, DRRT_PROF_BACKTRACE_FIELD, "k_backtrace_field",
+                                launch_backtrace_field);
 }
 
-// ---- emission with self-absorption: drrt_emission.hip ------------------------------------------------------------------
 extern "C" int drrt_trace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
                                        const int res[3], size_t n, const float* pos, const float* vel, float h, float ds,
                                        float* xt, float* vt, float* rad, float* tau, uint32_t* steps_out, drrt_stats* stats,
                                        void* ws, size_t ws_bytes, unsigned flags, void* stream) {
   EmissionTraceArgs a{};
-  GridCall c(a.vol, stream);
-  g_ts.reset_last_steps();              // this forward march writes its iteration counts to the caller, none to the workspace
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (!emission) return fail(DRRT_ERR_ARG, "null emission pointer");
-  if (!absorption) return fail(DRRT_ERR_ARG, "null absorption pointer");
-  if (n == 0) return zero_stats(stats, s);
-  if (!pos || !vel || !xt || !vt || !rad || !tau) return fail(DRRT_ERR_ARG, "null ray pointer");
-  if (!steps_out) return fail(DRRT_ERR_ARG, "null steps_out pointer (the adjoint needs the iteration counts)");
-  rc = check_ray_count(n); if (rc) return rc;
-  rc = zero_stats(stats, s); if (rc) return rc;
-  rc = c.place(nvox, n, pos, vel, 1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.emission = emission; a.absorption = absorption;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.rad = rad; a.tau = tau; a.steps_out = steps_out; a.stats = stats;
-  a.n = n; a.ds = ds;
-  a.max_steps = steps_fwd(h, res, ds);
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_TRACE_EMISSION, s, "k_trace_emission", [&] { launch_trace_emission(a, s); });
+  a.emission = emission; a.absorption = absorption; a.rad = rad; a.tau = tau;
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+                            {{emission, "null emission pointer"}, {absorption, "null absorption pointer"}}, {rad, tau}, xt,
+                            vt, steps_out, DRRT_PROF_TRACE_EMISSION, "k_trace_emission", launch_trace_emission);
 }
 
 extern "C" int drrt_backtrace_emission_f32(const float* rif, const float* emission, const float* absorption, long long nvox,
@@ -858,40 +854,14 @@ extern "C" int drrt_backtrace_emission_f32(const float* rif, const float* emissi
                                            float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags,
                                            void* stream) {
   EmissionBackArgs a{};
-  GridCall c(a.vol, stream);
-  hipStream_t s = c.s;
-  int rc = c.open(rif, nvox, res, h, ds); if (rc) return rc;
-  if (!emission) return fail(DRRT_ERR_ARG, "null emission pointer");
-  if (!absorption) return fail(DRRT_ERR_ARG, "null absorption pointer");
-  if (!grad && !grad_emission && !grad_absorption && !dpos && !dvel)
-    return fail(DRRT_ERR_ARG, "null output pointers: grad, grad_emission, grad_absorption, or dpos and dvel, or any of these together");
-  if (!dpos != !dvel) return fail(DRRT_ERR_ARG, "dpos and dvel go together");
-  if (n > 0) {
-    if (!pos || !vel || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
-    if (!fwd_steps) return fail(DRRT_ERR_ARG, "null fwd_steps pointer (the forward's steps_out)");
-    if (!tau) return fail(DRRT_ERR_ARG, "null tau pointer (the forward's tau)");
-    rc = check_ray_count(n); if (rc) return rc;
-  }
-  if (!(flags & DRRT_FLAG_NO_ZERO)) {
-    for (float* g : {grad, grad_emission, grad_absorption}) {
-      if (!g) continue;
-      ProfScope prof(DRRT_PROF_ZERO, s);
-      hipError_t e = hipMemsetAsync(g, 0, (size_t)nvox * sizeof(float), s);
-      if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad)");
-    }
-  }
-  rc = zero_stats(stats, s); if (rc) return rc;
-  if (n == 0) return DRRT_OK;
-  rc = c.place(nvox, n, xt, vt, -1.f, flags, ws_layout(n, nvox, flags, ws_bytes), ws, ws_bytes); if (rc) return rc;
-  a.emission = emission; a.absorption = absorption;
-  a.pos = pos; a.vel = vel; a.xt = xt; a.vt = vt; a.tau = tau; a.fsteps = fwd_steps;
-  a.dx = dx; a.dv = dv; a.drad = drad; a.dtau = dtau;
-  a.grad = grad; a.grad_emission = grad_emission; a.grad_absorption = grad_absorption; a.dpos = dpos; a.dvel = dvel;
-  a.stats = stats; a.n = n; a.ds = ds;
-  a.grad_scale = (flags & DRRT_FLAG_CORRECTED_H) ? a.vol.inv_h : 1.0f;
-  a.max_steps = steps_fwd(h, res, ds);      // the forward's bound: a ray that used all of it failed
-  a.perm = c.perm; a.xcd_order = c.xcd_order;
-  return timed_launch(DRRT_PROF_BACKTRACE_EMISSION, s, "k_backtrace_emission", [&] { launch_backtrace_emission(a, s); });
+  a.emission = emission; a.absorption = absorption; a.tau = tau; a.drad = drad; a.dtau = dtau;
+  a.grad = grad; a.grad_emission = grad_emission; a.grad_absorption = grad_absorption;
+  return run_backtrace_integral(
+      a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+      {{emission, "null emission pointer"}, {absorption, "null absorption pointer"}},
+      {{tau, "null tau pointer (the forward's tau)"}}, {grad, grad_emission, grad_absorption},
+      "null output pointers: grad, grad_emission, grad_absorption, or dpos and dvel, or any of these together", xt, vt,
+      fwd_steps, dx, dv, dpos, dvel, DRRT_PROF_BACKTRACE_EMISSION, "k_backtrace_emission", launch_backtrace_emission);
 }
 
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }

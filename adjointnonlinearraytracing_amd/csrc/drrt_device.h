@@ -754,28 +754,84 @@ DRRT_HD unsigned backtrace_ray(const Vol& V, const float* __restrict__ sdf, floa
   return steps;
 }
 
-// Ray-state adjoint of trace for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the exit ray (xt, vt), given
-// the forward's inputs (p0, v0) and its iteration count K (drrt_last_steps).  No contribution to dL/dn is formed.
+// ---- the integral operators: one forward loop, one reverse march -----------------------------------------------------
+// trace_opl, trace_field and trace_emission are trace with a line integral over the samples the march takes anyway; their
+// adjoints, and the ray-state adjoint of trace, are one reverse march.  Both skeletons are written once here; an operator
+// supplies an integrand (forward) and a term (reverse), defined with its mathematics further down.
+struct RayGrad { float dp[3], dv[3]; unsigned steps; bool failed; };
+
+// The forward loop for ONE ray.  The state update is fwd_step_c<0> itself on the taps `taps(c)` returns, looped as
+// trace_ray<0> loops it, so (xt, vt, steps) are trace_ray<0>'s bit for bit; the sample is evaluated once more for n_k (the
+// compiler merges the two).  `q(c, inside, n)` is called once per iteration, before the step, with the mask of
+// fwd_step_c's sample (Q4) and n = n_k under it, 0.f while the ray is not inside (free flight outside the box adds
+// nothing).  The integrand samples its own fields at the cell and weights of c, under the same mask, and owns its
+// accumulators, which start at 0.f and are updated in iteration order.  A failed ray leaves in them what it accumulated.
+template <typename TapFn, typename Integrand>
+DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                                  Integrand&& q) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
+  fwd_init(V, s);
+  Cell c = locate(V, s.x, s.y, s.z);
+  unsigned steps = 0;
+  for (int it = 0; it < max_steps; ++it) {
+    Taps t = taps_zero();
+    float n = 0.f;
+    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
+      t = taps(c);
+      n = interp<false>(t, c.wx, c.wy, c.wz).n;
+    }
+    q(c, s.inside, n);
+    fwd_step_c<0>(V, nullptr, ds, s, c, t);
+    ++steps;
+    if (s.esc) break;                                                     // per-ray form of :82
+  }
+  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
+  return o;
+}
+
+// The reverse march for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the exit ray (xt, vt), given the forward's
+// inputs (p0, v0) and its iteration count K, and the contributions to dL/dn.
 // The forward samples n only while the ray is inside (Q4), so a ray that starts outside flies straight for e
 // iterations first (x_e = x0 + e ds v0) and is refracted by the samples at x_e .. x_{K-1}: K - e iterations.
-//   * K >= max_steps (the forward's Q5 bound): the ray failed (vt is the stale v0, Q6) -> zero gradient, failed = true.
-//     A ray that exits on exactly the last allowed iteration looks the same and is treated the same.
+//   * K >= max_steps (the forward's Q5 bound): the ray failed (vt is the stale v0, Q6) -> zero gradient, failed = true,
+//     no contribution.  A ray that exits on exactly the last allowed iteration looks the same and is treated the same.
 //   * the prefix is replayed from (p0, v0) with the forward's own operations; no in-box sample among x_0 .. x_{K-1}:
-//     the ray never entered, (xt, vt) = (p0, v0) and the gradient is the identity (dx, dv).
+//     the ray never entered, (xt, vt) = (p0, v0), every integral is 0, the gradient is the identity (dx, dv) and there is
+//     no contribution.
 //   * otherwise K - e reverse iterations from (xt, vt) seeded like adj_init (lambda = dx, mu = dv + ds dx), with
 //     neither the backward-escape test nor the adjoint's own step bound; after the last one lambda = dL/dx_e and the
 //     mu it was updated from is dL/dv_e, so dpos = lambda and dvel = mu_prev + (e ds) lambda.  The last reverse
 //     iteration samples at the replayed x_e itself instead of its reconstruction x_{e+1} - ds v_{e+1}: a ray that
 //     starts on a face (x_e on the box boundary, where grad n jumps) would otherwise be sampled a rounding error
 //     outside it.
-// The 1/h of DRRT_FLAG_CORRECTED_H scales only the splat into the grid (Q3): it does not enter here.
 // `taps(c)` returns the 8 taps of cell c (the caller chooses how they are fetched; the floats are the grid's).
-struct RayGrad { float dp[3], dv[3]; unsigned steps; bool failed; };
+// What an operator adds is its `term`, called in this order in every reverse iteration, m the sample (n_k, grad n_k):
+//   dn = term.dn(V, c, m, mu . grad n_k)   the factor of ds grad n_k that adj_recur adds to lambda: d L / d n_k over ds
+//   sink(c, val, gx, gy, gz)               the contribution to dL/dn, formed like adj_contrib's with mu BEFORE adj_recur
+//                                          updates it: val = dn ds, g = (n_k ds grad_scale) mu; the caller adds
+//                                          splat_weights(c.wx, c.wy, c.wz, val, gx, gy, gz) at the 8 taps of c
+//   term.pull(V, c, m, s)                  the term's own pulls on lambda (the gradients of its fields at the sample
+//                                          position) and its contributions to its own grids, BEFORE adj_recur, whose
+//                                          closing mu += ds lambda must see the pulls
+//   adj_recur(V, ds, s, m, dn)
+//   term.after()                           the term's running scalars
+// With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum of the contributions is the exact discrete derivative; the 1/h
+// scales only the splat into the grid (Q3) and does not enter the ray gradients.
+struct NoTerm {                              // trace itself: nothing is integrated
+  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
+  DRRT_HD void after() {}
+};
 
-template <typename TapFn>
-DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsigned K, const float p0[3],
-                                    const float v0[3], const float xt[3], const float vt[3], const float dx[3],
-                                    const float dv[3], TapFn&& taps) {
+template <typename TapFn, typename Sink, typename Term>
+DRRT_HD RayGrad integral_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K,
+                                       const float p0[3], const float v0[3], const float xt[3], const float vt[3],
+                                       const float dx[3], const float dv[3], TapFn&& taps, Sink&& sink, Term&& term) {
   RayGrad g;
   g.steps = 0; g.failed = false;
   if (max_steps <= 0 || K >= (unsigned)max_steps) {
@@ -805,15 +861,29 @@ DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsig
     const Cell c = locate(V, s.x, s.y, s.z);
     AdjSample m;
     (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
-    const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);           // :430
+    const float dn = term.dn(V, c, m, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));         // :430
+    const float nds = (m.n * ds) * grad_scale;
+    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
     qx = s.mx; qy = s.my; qz = s.mz;
+    term.pull(V, c, m, s);
     adj_recur(V, ds, s, m, dn);
+    term.after();
   }
   const float eds = (float)e * ds;
   g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
   g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
   g.steps = K - e;
   return g;
+}
+
+// Ray-state adjoint of trace for ONE ray (drrt_last_steps gives K): the reverse march with no term.  No contribution to
+// dL/dn is formed.
+template <typename TapFn>
+DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsigned K, const float p0[3],
+                                    const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                    const float dv[3], TapFn&& taps) {
+  return integral_backtrace_ray(V, ds, 1.f, max_steps, K, p0, v0, xt, vt, dx, dv, taps,
+                                [](const Cell&, float, float, float, float) {}, NoTerm{});
 }
 
 // ---- optical path length -------------------------------------------------------------------------------------------
@@ -821,96 +891,39 @@ DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsig
 // int n^2 dsigma: opl = sum_{k<K} ds n_k^2 over the masked samples n_k that fwd_step_c<0> takes at x_k (0 while the ray
 // is not inside: free flight outside the box adds nothing), accumulated in fp32 as opl = fmaf(ds n_k, n_k, opl) in
 // iteration order from 0.f.  Not in the reference.
+struct OplIntegrand {
+  float ds, opl = 0.f;
+  DRRT_HD void operator()(const Cell&, bool, float n) { opl = fmaf(ds * n, n, opl); }
+};
 
-// trace for ONE ray, with its optical path length.  The state update is fwd_step_c<0> itself on the taps `taps(c)`
-// returns, looped as trace_ray<0> loops it, so (xt, vt, steps) are trace_ray<0>'s bit for bit; the sample is evaluated
-// once more for n_k (the compiler merges the two).  A failed ray returns what it accumulated.
+// trace for ONE ray, with its optical path length.
 template <typename TapFn>
 DRRT_HD RayOut trace_opl_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
                              float& opl) {
-  FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
-  unsigned steps = 0;
-  float acc = 0.f;
-  for (int it = 0; it < max_steps; ++it) {
-    Taps t = taps_zero();
-    float n = 0.f;
-    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
-      t = taps(c);
-      n = interp<false>(t, c.wx, c.wy, c.wz).n;
-    }
-    acc = fmaf(ds * n, n, acc);
-    fwd_step_c<0>(V, nullptr, ds, s, c, t);
-    ++steps;
-    if (s.esc) break;                                                     // per-ray form of :82
-  }
-  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
-  RayOut o;
-  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
-  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
-  opl = acc;
+  OplIntegrand q{ds};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  opl = q.opl;
   return o;
 }
 
 // Adjoint of trace_opl_ray for ONE ray: dL/dpos, dL/dvel AND the contributions to dL/dn, from the seeds (dx, dv, dopl) on
-// (xt, vt, opl).  The reverse march is backtrace_ray_state's, unchanged in structure (replayed free-flight prefix, K - e
-// reverse iterations, the last one sampled at the replayed x_e, no backward-escape test, failed rays zero and flagged,
-// never-entered rays (dx, dv) and no contribution).  Each reverse iteration uses
+// (xt, vt, opl).  Each reverse iteration uses
 //   dn = mu . grad n_k + 2 dopl n_k
 // wherever backtrace_ray_state uses mu . grad n_k: d opl / d n_k = 2 ds n_k adds 2 dopl n_k ds to the value weight of
 // the splat, and d opl / d x_k = 2 ds n_k grad n_k adds the same multiple of grad n_k to lambda, which is what adj_recur
-// does with dn.  `sink(c, val, gx, gy, gz)` receives the contribution of the iteration, formed like adj_contrib's with mu
-// BEFORE adj_recur updates it: val = dn ds, g = (n_k ds grad_scale) mu; the caller adds splat_weights(c.wx, c.wy, c.wz,
-// val, gx, gy, gz) at the 8 taps of c.  With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum is the exact discrete
-// derivative; grad_scale does not enter the ray gradients.
+// does with dn.
+struct OplTerm {
+  float dopl2;                               // 2 dopl
+  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample& m, float mg) { return fmaf(dopl2, m.n, mg); }
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
+  DRRT_HD void after() {}
+};
+
 template <typename TapFn, typename Sink>
 DRRT_HD RayGrad opl_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
                                   const float v0[3], const float xt[3], const float vt[3], const float dx[3],
                                   const float dv[3], float dopl, TapFn&& taps, Sink&& sink) {
-  RayGrad g;
-  g.steps = 0; g.failed = false;
-  if (max_steps <= 0 || K >= (unsigned)max_steps) {
-    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
-    g.failed = true;
-    return g;
-  }
-  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
-  float px = p0[0], py = p0[1], pz = p0[2];
-  unsigned e = 0;
-  while (e < K && !inbounds(V, px, py, pz)) {
-    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
-    ++e;
-  }
-  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, opl = 0
-    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
-    return g;
-  }
-  AdjState s;
-  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
-  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  const float dopl2 = dopl + dopl;
-  for (unsigned k = K; k > e; --k) {
-    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
-    const Cell c = locate(V, s.x, s.y, s.z);
-    AdjSample m;
-    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
-    const float dn = fmaf(dopl2, m.n, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));
-    const float nds = (m.n * ds) * grad_scale;
-    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
-    qx = s.mx; qy = s.my; qz = s.mz;
-    adj_recur(V, ds, s, m, dn);
-  }
-  const float eds = (float)e * ds;
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
-  g.steps = K - e;
-  return g;
+  return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, OplTerm{dopl + dopl});
 }
 
 // ---- line integral of a second field ---------------------------------------------------------------------------------
@@ -932,101 +945,61 @@ DRRT_HD Corners value_weights(float wx, float wy, float wz, float val) {
   return c;
 }
 
-// trace for ONE ray, with the line integral of the field whose taps `ftaps(c)` returns (`taps(c)`: those of n).  The loop
-// is trace_opl_ray's, so (xt, vt, steps) are trace_ray<0>'s bit for bit.  A failed ray returns what it accumulated.
+template <typename FieldTapFn>
+struct FieldIntegrand {
+  FieldTapFn& ftaps;
+  float ds, tau = 0.f;
+  DRRT_HD void operator()(const Cell& c, bool inside, float n) {
+    float a = 0.f;
+    if (inside) a = interp<false>(ftaps(c), c.wx, c.wy, c.wz).n;
+    tau = fmaf(ds * n, a, tau);
+  }
+};
+
+// trace for ONE ray, with the line integral of the field whose taps `ftaps(c)` returns (`taps(c)`: those of n).
 template <typename TapFn, typename FieldTapFn>
 DRRT_HD RayOut trace_field_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
                                FieldTapFn&& ftaps, float& tau) {
-  FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
-  unsigned steps = 0;
-  float acc = 0.f;
-  for (int it = 0; it < max_steps; ++it) {
-    Taps t = taps_zero();
-    float n = 0.f, a = 0.f;
-    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
-      t = taps(c);
-      n = interp<false>(t, c.wx, c.wy, c.wz).n;
-      a = interp<false>(ftaps(c), c.wx, c.wy, c.wz).n;
-    }
-    acc = fmaf(ds * n, a, acc);
-    fwd_step_c<0>(V, nullptr, ds, s, c, t);
-    ++steps;
-    if (s.esc) break;                                                     // per-ray form of :82
-  }
-  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
-  RayOut o;
-  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
-  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
-  tau = acc;
+  FieldIntegrand<FieldTapFn> q{ftaps, ds};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  tau = q.tau;
   return o;
 }
 
 // Adjoint of trace_field_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn AND dL/da, from the seeds
-// (dx, dv, dtau) on (xt, vt, tau).  The reverse march is opl_backtrace_ray's, unchanged in structure.  With a_k, grad a_k
-// the sample of the field at the cell of n_k (grad a_k scaled by 1 / h like grad n_k), each reverse iteration uses
+// (dx, dv, dtau) on (xt, vt, tau).  With a_k, grad a_k the sample of the field at the cell of n_k (grad a_k scaled by
+// 1 / h like grad n_k), each reverse iteration uses
 //   dn = mu . grad n_k + dtau a_k                    (d tau / d n_k = ds a_k)
 // where backtrace_ray_state uses mu . grad n_k, which also puts dtau ds a_k grad n_k into lambda (adj_recur), and adds the
 // term no other march has, the pull of the field's own gradient on the sample position,
 //   lambda += (dtau ds n_k) grad a_k                 (d tau / d x_k = ds (a_k grad n_k + n_k grad a_k))
-// BEFORE adj_recur, whose closing mu += ds lambda must see it.  `sink(c, val, gx, gy, gz)` receives the contribution to
-// dL/dn as opl_backtrace_ray's does (val = dn ds, g = (n_k ds grad_scale) mu, mu before its update: the caller adds
-// splat_weights(...) at the 8 taps of c); `fsink(c, val)` the contribution to dL/da, val = dtau ds n_k: the caller adds
-// value_weights(c.wx, c.wy, c.wz, val) at the same taps (tau is linear in a: no gradient splat, no grad_scale, the exact
-// discrete derivative either way).  grad_scale does not enter the ray gradients.
+// `fsink(c, val)` receives the contribution to dL/da, val = dtau ds n_k: the caller adds value_weights(c.wx, c.wy, c.wz,
+// val) at the taps of c (tau is linear in a: no gradient splat, no grad_scale, the exact discrete derivative either way).
+template <typename FieldTapFn, typename FieldSink>
+struct FieldTerm {
+  FieldTapFn& ftaps;
+  FieldSink& fsink;
+  float dtau, dtds;                          // dtau, dtau ds
+  Sample a;
+  DRRT_HD float dn(const Vol&, const Cell& c, const AdjSample& m, float mg) {
+    a = interp<false>(ftaps(c), c.wx, c.wy, c.wz);
+    return fmaf(dtau, a.n, mg);
+  }
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample& m, AdjState& s) {
+    const float fv = dtds * m.n;                                          // dtau ds n_k
+    fsink(c, fv);
+    s.lx = fmaf(fv, a.gx * V.inv_h, s.lx); s.ly = fmaf(fv, a.gy * V.inv_h, s.ly); s.lz = fmaf(fv, a.gz * V.inv_h, s.lz);
+  }
+  DRRT_HD void after() {}
+};
+
 template <typename TapFn, typename FieldTapFn, typename Sink, typename FieldSink>
 DRRT_HD RayGrad field_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
                                     const float v0[3], const float xt[3], const float vt[3], const float dx[3],
                                     const float dv[3], float dtau, TapFn&& taps, FieldTapFn&& ftaps, Sink&& sink,
                                     FieldSink&& fsink) {
-  RayGrad g;
-  g.steps = 0; g.failed = false;
-  if (max_steps <= 0 || K >= (unsigned)max_steps) {
-    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
-    g.failed = true;
-    return g;
-  }
-  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
-  float px = p0[0], py = p0[1], pz = p0[2];
-  unsigned e = 0;
-  while (e < K && !inbounds(V, px, py, pz)) {
-    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
-    ++e;
-  }
-  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, tau = 0
-    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
-    return g;
-  }
-  AdjState s;
-  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
-  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  const float dtds = dtau * ds;
-  for (unsigned k = K; k > e; --k) {
-    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
-    const Cell c = locate(V, s.x, s.y, s.z);
-    AdjSample m;
-    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
-    const Sample a = interp<false>(ftaps(c), c.wx, c.wy, c.wz);
-    const float dn = fmaf(dtau, a.n, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));
-    const float nds = (m.n * ds) * grad_scale;
-    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
-    const float fv = dtds * m.n;                                          // dtau ds n_k
-    fsink(c, fv);
-    qx = s.mx; qy = s.my; qz = s.mz;
-    s.lx = fmaf(fv, a.gx * V.inv_h, s.lx); s.ly = fmaf(fv, a.gy * V.inv_h, s.ly); s.lz = fmaf(fv, a.gz * V.inv_h, s.lz);
-    adj_recur(V, ds, s, m, dn);
-  }
-  const float eds = (float)e * ds;
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
-  g.steps = K - e;
-  return g;
+  FieldTerm<FieldTapFn, FieldSink> term{ftaps, fsink, dtau, dtau * ds, {}};
+  return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
 }
 
 // ---- emission with self-absorption -----------------------------------------------------------------------------------
@@ -1070,47 +1043,39 @@ DRRT_HD float exp_neg(float t) {
   return num ? p * scale : x;
 }
 
-// trace for ONE ray with the emission integral; `taps(c)`: the taps of n, `etaps(c)` / `ataps(c)`: those of the emission and
-// absorption fields.  The loop is trace_field_ray's, so (xt, vt, steps) are trace_ray<0>'s and tau is trace_field_ray's
-// with the field a, bit for bit.  A failed ray returns what it accumulated; a ray that never samples inside rad = tau = 0.
-template <typename TapFn, typename EmisTapFn, typename AbsTapFn>
-DRRT_HD RayOut trace_emission_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
-                                  EmisTapFn&& etaps, AbsTapFn&& ataps, float& rad, float& tau) {
-  FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
-  unsigned steps = 0;
-  float acc = 0.f, racc = 0.f;
-  for (int it = 0; it < max_steps; ++it) {
-    Taps t = taps_zero();
-    float n = 0.f, a = 0.f, e = 0.f;
-    if (s.inside) {                                                       // the masked sample of fwd_step_c (Q4)
-      t = taps(c);
-      n = interp<false>(t, c.wx, c.wy, c.wz).n;
+template <typename EmisTapFn, typename AbsTapFn>
+struct EmissionIntegrand {
+  EmisTapFn& etaps;
+  AbsTapFn& ataps;
+  float ds, rad = 0.f, tau = 0.f;
+  DRRT_HD void operator()(const Cell& c, bool inside, float n) {
+    float a = 0.f, e = 0.f;
+    if (inside) {
       e = interp<false>(etaps(c), c.wx, c.wy, c.wz).n;
       a = interp<false>(ataps(c), c.wx, c.wy, c.wz).n;
     }
     const float w = ds * n;
-    racc = fmaf(exp_neg(acc) * w, e, racc);                               // emit with the transmittance in front of the sample
-    acc = fmaf(w, a, acc);                                                // then absorb
-    fwd_step_c<0>(V, nullptr, ds, s, c, t);
-    ++steps;
-    if (s.esc) break;                                                     // per-ray form of :82
+    rad = fmaf(exp_neg(tau) * w, e, rad);                                 // emit with the transmittance in front of the sample
+    tau = fmaf(w, a, tau);                                                // then absorb
   }
-  if (!s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }                  // :95 (vt stays, Q6)
-  RayOut o;
-  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
-  o.dist2 = 0.f; o.esc = s.esc; o.act = !s.esc; o.steps = steps; o.again = false;
-  rad = racc; tau = acc;
+};
+
+// trace for ONE ray with the emission integral; `taps(c)`: the taps of n, `etaps(c)` / `ataps(c)`: those of the emission and
+// absorption fields.  tau is trace_field_ray's with the field a, bit for bit; a ray that never samples inside has
+// rad = tau = 0.
+template <typename TapFn, typename EmisTapFn, typename AbsTapFn>
+DRRT_HD RayOut trace_emission_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                                  EmisTapFn&& etaps, AbsTapFn&& ataps, float& rad, float& tau) {
+  EmissionIntegrand<EmisTapFn, AbsTapFn> q{etaps, ataps, ds};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  rad = q.rad; tau = q.tau;
   return o;
 }
 
 // Adjoint of trace_emission_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn, dL/de AND dL/da, from the
-// seeds (dx, dv, drad, dtau) on (xt, vt, rad, tau) and the forward's tau.  The reverse march is field_backtrace_ray's,
-// unchanged in structure, with two running scalars: t, the optical depth in front of the sample, which starts at the
-// forward's tau and is stepped back by t = fmaf(-w, a_k, t) (tau_k again, to rounding), and
+// seeds (dx, dv, drad, dtau) on (xt, vt, rad, tau) and the forward's tau.  Two running scalars: t, the optical depth in
+// front of the sample, which starts at the forward's tau and is stepped back by t = fmaf(-w, a_k, t) (tau_k again, to
+// rounding), and
 //   P_{k+1} = dtau - drad sum_{j>k} T_j w_j e_j        (d L / d tau_{k+1}: every later emission is dimmed by this sample)
 // which starts at dtau.  With ce = drad exp_neg(tau_k) each reverse iteration uses
 //   dn = mu . grad n_k + (ce e_k + P a_k)              (d L / d w_k = drad T_k e_k + P_{k+1} a_k)
@@ -1122,64 +1087,43 @@ DRRT_HD RayOut trace_emission_ray(const Vol& V, float ds, int max_steps, const f
 // ray gradients are the derivative of the discrete forward to fp32 rounding, with either setting of grad_scale; dL/dn is
 // the same derivative with grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H).  With drad = 0 this is field_backtrace_ray with the
 // field a: ce = 0, P stays dtau, and nothing reaches dL/de.
+template <typename EmisTapFn, typename AbsTapFn, typename EmisSink, typename AbsSink>
+struct EmissionTerm {
+  EmisTapFn& etaps;
+  AbsTapFn& ataps;
+  EmisSink& esink;
+  AbsSink& asink;
+  float ds, drad, t, P;                      // t starts at the forward's tau, P at dtau
+  Sample em, ab;
+  float w, ce, ev;
+  DRRT_HD float dn(const Vol&, const Cell& c, const AdjSample& m, float mg) {
+    em = interp<false>(etaps(c), c.wx, c.wy, c.wz);
+    ab = interp<false>(ataps(c), c.wx, c.wy, c.wz);
+    w = ds * m.n;
+    t = fmaf(-w, ab.n, t);                                                // tau_k
+    ce = drad * exp_neg(t);
+    return mg + fmaf(ce, em.n, P * ab.n);
+  }
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s) {
+    ev = ce * w;
+    const float av = P * w;
+    esink(c, ev);
+    asink(c, av);
+    s.lx = fmaf(ev, em.gx * V.inv_h, s.lx); s.ly = fmaf(ev, em.gy * V.inv_h, s.ly); s.lz = fmaf(ev, em.gz * V.inv_h, s.lz);
+    s.lx = fmaf(av, ab.gx * V.inv_h, s.lx); s.ly = fmaf(av, ab.gy * V.inv_h, s.ly); s.lz = fmaf(av, ab.gz * V.inv_h, s.lz);
+  }
+  DRRT_HD void after() { P = fmaf(-ev, em.n, P); }
+};
+
 template <typename TapFn, typename EmisTapFn, typename AbsTapFn, typename Sink, typename EmisSink, typename AbsSink>
 DRRT_HD RayGrad emission_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K,
                                        const float p0[3], const float v0[3], const float xt[3], const float vt[3],
                                        float tau, const float dx[3], const float dv[3], float drad, float dtau,
                                        TapFn&& taps, EmisTapFn&& etaps, AbsTapFn&& ataps, Sink&& sink, EmisSink&& esink,
                                        AbsSink&& asink) {
-  RayGrad g;
-  g.steps = 0; g.failed = false;
-  if (max_steps <= 0 || K >= (unsigned)max_steps) {
-    g.dp[0] = g.dp[1] = g.dp[2] = g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
-    g.failed = true;
-    return g;
-  }
-  // free-flight prefix: the forward's x = fmaf(ds, v, x) with v = v0 until the first in-box sample
-  float px = p0[0], py = p0[1], pz = p0[2];
-  unsigned e = 0;
-  while (e < K && !inbounds(V, px, py, pz)) {
-    px = fmaf(ds, v0[0], px); py = fmaf(ds, v0[1], py); pz = fmaf(ds, v0[2], pz);
-    ++e;
-  }
-  if (e == K) {                                                           // never sampled inside: xt = p0, vt = v0, rad = tau = 0
-    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
-    return g;
-  }
-  AdjState s;
-  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
-  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  float t = tau, P = dtau;
-  for (unsigned k = K; k > e; --k) {
-    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
-    const Cell c = locate(V, s.x, s.y, s.z);
-    AdjSample m;
-    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
-    const Sample em = interp<false>(etaps(c), c.wx, c.wy, c.wz);
-    const Sample ab = interp<false>(ataps(c), c.wx, c.wy, c.wz);
-    const float w = ds * m.n;
-    t = fmaf(-w, ab.n, t);                                                // tau_k
-    const float ce = drad * exp_neg(t);
-    const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz) + fmaf(ce, em.n, P * ab.n);
-    const float nds = (m.n * ds) * grad_scale;
-    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
-    const float ev = ce * w, av = P * w;
-    esink(c, ev);
-    asink(c, av);
-    qx = s.mx; qy = s.my; qz = s.mz;
-    s.lx = fmaf(ev, em.gx * V.inv_h, s.lx); s.ly = fmaf(ev, em.gy * V.inv_h, s.ly); s.lz = fmaf(ev, em.gz * V.inv_h, s.lz);
-    s.lx = fmaf(av, ab.gx * V.inv_h, s.lx); s.ly = fmaf(av, ab.gy * V.inv_h, s.ly); s.lz = fmaf(av, ab.gz * V.inv_h, s.lz);
-    adj_recur(V, ds, s, m, dn);
-    P = fmaf(-ev, em.n, P);
-  }
-  const float eds = (float)e * ds;
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
-  g.steps = K - e;
-  return g;
+  EmissionTerm<EmisTapFn, AbsTapFn, EmisSink, AbsSink> term{etaps, ataps, esink, asink, ds, drad, tau, dtau, {}, {},
+                                                            0.f, 0.f, 0.f};
+  return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
 }
 
 // trace_cable for ONE ray (src/tracer.cpp:312-382)

@@ -12,13 +12,13 @@
 //                           adjoint with the forward replayed, no grid writes)
 //   drrt_target_rays.hip    backtrace_target_rays: dL/dpos, dL/dvel of trace_target (ray-state adjoint with the forward
 //                           replayed over the call's global loop count, no grid writes)
-//   drrt_opl.hip            trace_opl, backtrace_opl: trace with its optical path length, and the adjoint that returns
-//                           dL/dn, dL/dpos and dL/dvel from seeds on (xt, vt, opl) in one march (global atomics, no window)
-//   drrt_field.hip          trace_field, backtrace_field: trace with the line integral tau of a second field along the bent
-//                           ray, and the adjoint that returns dL/dn, dL/dfield, dL/dpos and dL/dvel from seeds on (xt, vt, tau)
-//   drrt_emission.hip       trace_emission, backtrace_emission: trace with the emission integral rad = int e exp(-int a) of two
-//                           further fields along the bent ray, and the adjoint that returns dL/dn, dL/de, dL/da, dL/dpos and
-//                           dL/dvel from seeds on (xt, vt, rad, tau) in one march
+//   drrt_integral.hip       the integral operators, each a trace with a line integral over its samples and ONE adjoint
+//                           march that returns every gradient from seeds on all outputs (global atomics, no window):
+//                           trace_opl / backtrace_opl (opl = int n dl; dL/dn, dL/dpos, dL/dvel), trace_field /
+//                           backtrace_field (tau = int a dl of a second field; also dL/dfield), trace_emission /
+//                           backtrace_emission (rad = int e exp(-int a), tau; also dL/de, dL/da).  Their per-ray routines
+//                           are instances of one forward loop and one reverse march (drrt_device.h), which
+//                           backtrace_rays shares
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
@@ -248,7 +248,7 @@ __device__ __forceinline__ void taps_set(const Taps& t, f4& q0, f4& q1) {
 }
 template <bool PAIR> __device__ __forceinline__ unsigned tap_offset(int base) { return (unsigned)base << (PAIR ? 3 : 2); }
 
-// ---- one ray per lane with global atomics: drrt_opl.hip, drrt_field.hip, drrt_emission.hip ----
+// ---- one ray per lane with global atomics: drrt_integral.hip ----
 // the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell
 template <bool PAIR>
 struct OplTaps {
@@ -293,7 +293,7 @@ struct HeldCorners {
   }
 };
 
-// the taps of a second field at cell c (drrt_field.hip, drrt_emission.hip): the cell and clamps of n's taps, plain gathers
+// the taps of a second field at cell c (trace_field, trace_emission and their adjoints): the cell and clamps of n's taps, plain gathers
 // of the field itself, kept while the lane stays in a strictly interior cell
 struct FieldTaps {
   const float* d;
@@ -515,7 +515,7 @@ struct TargetRayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
-// optical path length (drrt_opl.hip): trace with opl = sum ds n_k^2, and its adjoint (dL/dn and the ray gradients at once)
+// optical path length (drrt_integral.hip): trace with opl = sum ds n_k^2, and its adjoint (dL/dn and the ray gradients at once)
 struct OplTraceArgs {
   Vol vol;
   const float* pos; const float* vel;
@@ -546,7 +546,7 @@ struct OplBackArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
-// line integral of a second field (drrt_field.hip): trace with tau = sum ds n_k a_k, and its adjoint (both grids and the rays)
+// line integral of a second field (drrt_integral.hip): trace with tau = sum ds n_k a_k, and its adjoint (both grids and the rays)
 struct FieldTraceArgs {
   Vol vol;
   const float* field;                       // the second grid: vol's shape, plain layout (no pair copy)
@@ -580,7 +580,7 @@ struct FieldBackArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
-// emission with self-absorption (drrt_emission.hip): trace with rad = sum T_k ds n_k e_k, T_k = exp_neg(tau_k), and
+// emission with self-absorption (drrt_integral.hip): trace with rad = sum T_k ds n_k e_k, T_k = exp_neg(tau_k), and
 // tau = sum ds n_k a_k; and its adjoint (all three grids and the rays)
 struct EmissionTraceArgs {
   Vol vol;
@@ -678,13 +678,12 @@ void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
 void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t s);
 // ray-state adjoint of trace_target: the count of the global loop, then replay and reverse march (drrt_target_rays.hip)
 void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
-// optical path length: trace_opl and its adjoint (drrt_opl.hip)
+// the integral operators (drrt_integral.hip): optical path length, line integral of a second field, emission with
+// self-absorption, each with its adjoint
 void launch_trace_opl(const OplTraceArgs& a, hipStream_t s);
 void launch_backtrace_opl(const OplBackArgs& a, hipStream_t s);
-// line integral of a second field: trace_field and its adjoint (drrt_field.hip)
 void launch_trace_field(const FieldTraceArgs& a, hipStream_t s);
 void launch_backtrace_field(const FieldBackArgs& a, hipStream_t s);
-// emission with self-absorption: trace_emission and its adjoint (drrt_emission.hip)
 void launch_trace_emission(const EmissionTraceArgs& a, hipStream_t s);
 void launch_backtrace_emission(const EmissionBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)

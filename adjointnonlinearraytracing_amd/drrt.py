@@ -619,6 +619,53 @@ def _like_grid(rif_, rays_) -> tuple:
     return (torch.empty_like(rif_),)
 
 
+def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_out, dx, dv, seeds, wanted, rays: bool, h, ds,
+                        order) -> tuple:
+    """What ``backtrace_opl`` / ``backtrace_field`` / ``backtrace_emission`` share: one call of drrt_backtrace_<op>_f32 ->
+    (the grid gradients in the order of `wanted`, dpos, dvel), None for what is not asked for.  `more`: the operator's
+    further grids; `fwd_out`: (name, tensor) of the forward outputs the adjoint needs besides xt, vt and steps; `seeds`:
+    the per-ray seeds behind dx, dv (None: zeros); `wanted`: per grid gradient (asked for, accumulator or None, the name of
+    the accumulator's argument).  An accumulator means DRRT_FLAG_NO_ZERO, which covers every grid of the call: those asked
+    for without one are zeroed here."""
+    if not (rays or any(want for want, _, _ in wanted)):
+        switches = [name.replace("into", "grid") for _, _, name in wanted] + ["rays"]
+        raise RuntimeError(f"backtrace_{op}: nothing to compute ({' = '.join(switches)} = False)")
+    dev = _dev(rif)
+    with torch.cuda.device(dev):
+        rif_, first_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, more[0] if more else None, [pos, vel, xt, vt], dev)
+        more_ = ([first_] if more else []) + [_more_grid(g, rif_, dev) for g in more[1:]]
+        steps_ = steps.detach().to(device=dev).contiguous()
+        if steps_.dtype != torch.int32 or steps_.numel() != n:
+            raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_{op}'s)")
+        dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+        per_ray = [None if t is None else _f32(t, dev).reshape(-1) for t in (*(t for _, t in fwd_out), *seeds)]
+        for (name, _), t in zip(fwd_out, per_ray):
+            if t is None:
+                raise RuntimeError(f"backtrace_{op}: `{name}` is the forward call's {name} (trace_{op}'s)")
+        for t in per_ray:
+            if t is not None and t.numel() != n:
+                raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
+        no_zero = any(want and acc is not None for want, acc, _ in wanted)
+        grads = []
+        for want, acc, name in wanted:
+            if not want:
+                grads.append(None)
+            elif acc is not None:
+                if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
+                    raise RuntimeError(f"backtrace_{op}: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
+                grads.append(acc.detach().view(-1))
+            else:
+                grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
+        dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
+        with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
+            _lib.check(getattr(_lib.load(), f"drrt_backtrace_{op}_f32")(
+                _p(rif_), *map(_p, more_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
+                *map(_p, per_ray[:len(fwd_out)]), _p(dx_), _p(dv_), *map(_p, per_ray[len(fwd_out):]), float(h), float(ds),
+                *map(_p, grads), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
+        _warn_failed(st)
+    return (*grads, dpos, dvel)
+
+
 class TracerC:
     """GPU tracer without autodiff -- mirror of ``drrt.TracerC`` (``src/drrt.cpp:47-58``).  The forward grid marches
     come twice: ``_trace*`` -> (outputs, order, steps) as `_grid_call` returns them, for callers that hand the order to a
@@ -732,44 +779,9 @@ class TracerC:
         `tau` by subtraction, so dL/demission, dL/dabsorption and the ray gradients are the derivative of the discrete
         forward to fp32 rounding; dL/drif is the same derivative with ``options.corrected_h``.  Rays that failed the forward
         get zeros and contribute nothing.  `order`: the forward's visit order."""
-        if not (grid or emission_grid or absorption_grid or rays):
-            raise RuntimeError("backtrace_emission: nothing to compute (grid = emission_grid = absorption_grid = rays = False)")
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, emis_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, emission, [pos, vel, xt, vt], dev)
-            absb_ = _more_grid(absorption, rif_, dev)
-            steps_ = steps.detach().to(device=dev).contiguous()
-            if steps_.dtype != torch.int32 or steps_.numel() != n:
-                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_emission's)")
-            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
-            tau_, drad_, dtau_ = (None if t is None else _f32(t, dev).reshape(-1) for t in (tau, drad, dtau))
-            if tau_ is None:
-                raise RuntimeError("backtrace_emission: `tau` is the forward call's tau (trace_emission's)")
-            for t in (tau_, drad_, dtau_):
-                if t is not None and t.numel() != n:
-                    raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
-            wanted = ((grid, into, "into"), (emission_grid, emission_into, "emission_into"),
-                      (absorption_grid, absorption_into, "absorption_into"))
-            no_zero = any(want and acc is not None for want, acc, _ in wanted)
-            grads = []
-            for want, acc, name in wanted:
-                if not want:
-                    grads.append(None)
-                elif acc is not None:
-                    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
-                        raise RuntimeError(f"backtrace_emission: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
-                    grads.append(acc.detach().view(-1))
-                else:
-                    grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
-            grad, gemis, gabsb = grads
-            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
-                _lib.check(_lib.load().drrt_backtrace_emission_f32(
-                    _p(rif_), _p(emis_), _p(absb_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_),
-                    _p(steps_), _p(tau_), _p(dx_), _p(dv_), _p(drad_), _p(dtau_), float(h), float(ds), _p(grad), _p(gemis),
-                    _p(gabsb), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
-            _warn_failed(st)
-        return grad, gemis, gabsb, dpos, dvel
+        return _backtrace_integral("emission", rif, (emission, absorption), res, pos, vel, xt, vt, steps, (("tau", tau),), dx, dv,
+                                   (drad, dtau), ((grid, into, "into"), (emission_grid, emission_into, "emission_into"),
+                                                  (absorption_grid, absorption_into, "absorption_into")), rays, h, ds, order)
 
     def backtrace_field(self, rif, field, res, pos, vel, xt, vt, steps, dx, dv, dtau, h, ds, grid: bool = True,
                         field_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,
@@ -783,38 +795,8 @@ class TracerC:
         that is returned in its place.  Honours ``options.corrected_h`` (with it dL/drif is the exact discrete derivative;
         dL/dfield and the ray gradients are that either way).  Rays that failed the forward get zeros and contribute
         nothing.  `order`: the forward's visit order."""
-        if not (grid or field_grid or rays):
-            raise RuntimeError("backtrace_field: nothing to compute (grid = field_grid = rays = False)")
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, field_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, field, [pos, vel, xt, vt], dev)
-            steps_ = steps.detach().to(device=dev).contiguous()
-            if steps_.dtype != torch.int32 or steps_.numel() != n:
-                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_field's)")
-            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
-            dtau_ = None if dtau is None else _f32(dtau, dev).reshape(-1)
-            if dtau_ is not None and dtau_.numel() != n:
-                raise RuntimeError(f"expected {n} per-ray values, got {dtau_.numel()}")
-            no_zero = (grid and into is not None) or (field_grid and field_into is not None)
-            grads = []
-            for want, acc, name in ((grid, into, "into"), (field_grid, field_into, "field_into")):
-                if not want:
-                    grads.append(None)
-                elif acc is not None:
-                    if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
-                        raise RuntimeError(f"backtrace_field: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
-                    grads.append(acc.detach().view(-1))
-                else:
-                    grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
-            grad, gfield = grads
-            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
-                _lib.check(_lib.load().drrt_backtrace_field_f32(
-                    _p(rif_), _p(field_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
-                    _p(dx_), _p(dv_), _p(dtau_), float(h), float(ds), _p(grad), _p(gfield), _p(dpos), _p(dvel), _p(st), _p(ws),
-                    ws.numel(), fl, _stream(dev)))
-            _warn_failed(st)
-        return grad, gfield, dpos, dvel
+        return _backtrace_integral("field", rif, (field,), res, pos, vel, xt, vt, steps, (), dx, dv, (dtau,),
+                                   ((grid, into, "into"), (field_grid, field_into, "field_into")), rays, h, ds, order)
 
     def backtrace_opl(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dopl, h, ds, grid: bool = True, rays: bool = True,
                       into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
@@ -825,33 +807,8 @@ class TracerC:
         tensor the grid gradient is ADDED to (DRRT_FLAG_NO_ZERO) and that is returned as grad.  Honours
         ``options.corrected_h`` (with it the grid gradient is the exact discrete derivative; the ray gradients do not depend
         on it).  Rays that failed the forward get zeros and contribute nothing.  `order`: the forward's visit order."""
-        if not (grid or rays):
-            raise RuntimeError("backtrace_opl: nothing to compute (grid = rays = False)")
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, _, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, None, [pos, vel, xt, vt], dev)
-            steps_ = steps.detach().to(device=dev).contiguous()
-            if steps_.dtype != torch.int32 or steps_.numel() != n:
-                raise RuntimeError(f"steps must be {n} int32 iteration counts of the forward call (trace_opl's)")
-            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
-            dopl_ = None if dopl is None else _f32(dopl, dev).reshape(-1)
-            if dopl_ is not None and dopl_.numel() != n:
-                raise RuntimeError(f"expected {n} per-ray values, got {dopl_.numel()}")
-            grad, extra = None, 0
-            if grid and into is not None:
-                if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != rif_.numel() or into.device != dev:
-                    raise RuntimeError("backtrace_opl: `into` must be a contiguous fp32 tensor of the grid's size on its device")
-                grad, extra = into.detach().view(-1), _lib.FLAG_NO_ZERO
-            elif grid:
-                grad = torch.empty_like(rif_)
-            dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
-            with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=extra) as (fl, ws, st, _):
-                _lib.check(_lib.load().drrt_backtrace_opl_f32(
-                    _p(rif_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_), _p(dx_), _p(dv_),
-                    _p(dopl_), float(h), float(ds), _p(grad), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl,
-                    _stream(dev)))
-            _warn_failed(st)
-        return grad, dpos, dvel
+        return _backtrace_integral("opl", rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (dopl,), ((grid, into, "into"),),
+                                   rays, h, ds, order)
 
     def backtrace(self, rif, res, xt, vt, dx, dv, h, ds, order: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Tracer::backtrace, src/tracer.cpp:384-440 -> flat dL/dn (fp32[nvox]).

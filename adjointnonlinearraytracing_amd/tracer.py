@@ -313,6 +313,46 @@ class ADRayTargetTracerC(torch.autograd.Function):
         return drif, dx0, dv0, dsp, None, None
 
 
+def _integral_forward(ctx, name, march, rif, fields, x, v, h, ds, keep=0):
+    """The forward of the integral operators' classes -> (xt, vt, *integrals): `march` (``TracerC._trace_opl``, ...) on
+    `rif`, the further grids `fields` (((argument name, grid), ...), each of rif's shape) and the rays.  When any input
+    requires grad, what the ONE backward launch needs is kept: the options in effect now (autograd runs backward on a thread
+    of its own), the visit order, private copies of (x, v), the iteration counts and, saved with the grids and the exit
+    rays, the last `keep` integrals."""
+    ctx.set_materialize_grads(False)
+    for fname, field in fields:
+        if field.shape != rif.shape:
+            raise RuntimeError(f"{name}: {fname} has shape {tuple(field.shape)}, rif {tuple(rif.shape)}")
+    ctx.shape, ctx.h, ctx.ds, ctx.n_fields = rif.shape, h, ds, len(fields)
+    _ray_grad_wanted(ctx, name, 1 + len(fields), 2 + len(fields), x, v)
+    (xt, vt, *integrals, steps), order, _ = march(rif.detach().flatten(), *(f.detach().flatten() for _, f in fields),
+                                                  ctx.shape, x.detach(), v.detach(), h, ds)
+    if any(ctx.needs_input_grad[:3 + len(fields)]):
+        ctx.options = dataclasses.asdict(drrt._opt())
+        ctx.order = drrt.keep_order(order)
+        _keep_rays(ctx, x, v, xt.device)
+        ctx.rays += (steps,)
+        ctx.save_for_backward(rif, *(f for _, f in fields), xt, vt, *integrals[len(integrals) - keep:])
+    return (xt, vt, *integrals)
+
+
+def _integral_backward(ctx, back, grad_x, grad_v, *seeds):
+    """-> (drif, *dfields, dx0, dv0) from ONE launch of `back` (``TracerC.backtrace_opl``, ...) under the forward's options,
+    computing only what ``ctx.needs_input_grad`` asks for."""
+    k = ctx.n_fields
+    want_grids, want_rays = ctx.needs_input_grad[:1 + k], ctx.needs_input_grad[1 + k] or ctx.needs_input_grad[2 + k]
+    if not (any(want_grids) or want_rays):
+        return (None,) * (3 + k)
+    grids, (outx, outv, *kept) = ctx.saved_tensors[:1 + k], ctx.saved_tensors[1 + k:]
+    x0, v0, steps = ctx.rays
+    with drrt.using(**ctx.options):
+        *grads, dpos, dvel = back(*(g.detach().flatten() for g in grids), ctx.shape, x0, v0, outx, outv, steps, *kept, grad_x,
+                                  grad_v, *seeds, ctx.h, ctx.ds, *want_grids, want_rays, order=ctx.order)
+    dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[1 + k] else None
+    dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[2 + k] else None
+    return (*(g.reshape(*ctx.shape) if want else None for g, want in zip(grads, want_grids)), dx0, dv0)
+
+
 class OPLTracerC(torch.autograd.Function):
     """``apply(rif, x, v, h, ds) -> (xt, vt, opl)``: ``trace`` with the optical path length ``opl = sum ds n_k^2`` of every
     ray (|v| = n along the march, so this is the integral of n along the path), all three outputs differentiable w.r.t.
@@ -330,34 +370,11 @@ class OPLTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds):
-        ctx.set_materialize_grads(False)
-        ctx.shape, ctx.h, ctx.ds = rif.shape, h, ds
-        _ray_grad_wanted(ctx, "OPLTracerC", 1, 2, x, v)
-        (xt, vt, opl, steps), order, _ = drrt.TracerC()._trace_opl(rif.detach().flatten(), ctx.shape, x.detach(), v.detach(),
-                                                                   h, ds)
-        if any(ctx.needs_input_grad[:3]):
-            ctx.options = dataclasses.asdict(drrt._opt())
-            ctx.order = drrt.keep_order(order)
-            _keep_rays(ctx, x, v, xt.device)
-            ctx.rays += (steps,)
-            ctx.save_for_backward(rif, xt, vt)
-        return xt, vt, opl
+        return _integral_forward(ctx, "OPLTracerC", drrt.TracerC()._trace_opl, rif, (), x, v, h, ds)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_opl):
-        want_rif, want_rays = ctx.needs_input_grad[0], ctx.needs_input_grad[1] or ctx.needs_input_grad[2]
-        if not (want_rif or want_rays):
-            return None, None, None, None, None
-        rif, outx, outv = ctx.saved_tensors
-        x0, v0, steps = ctx.rays
-        with drrt.using(**ctx.options):
-            grad, dpos, dvel = drrt.TracerC().backtrace_opl(rif.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps,
-                                                            grad_x, grad_v, grad_opl, ctx.h, ctx.ds, grid=want_rif,
-                                                            rays=want_rays, order=ctx.order)
-        drif = grad.reshape(*ctx.shape) if want_rif else None
-        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[1] else None
-        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[2] else None
-        return drif, dx0, dv0, None, None
+        return (*_integral_backward(ctx, drrt.TracerC().backtrace_opl, grad_x, grad_v, grad_opl), None, None)
 
 
 class FieldIntegralTracerC(torch.autograd.Function):
@@ -377,38 +394,12 @@ class FieldIntegralTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, field, x, v, h, ds):
-        ctx.set_materialize_grads(False)
-        if field.shape != rif.shape:
-            raise RuntimeError(f"FieldIntegralTracerC: field has shape {tuple(field.shape)}, rif {tuple(rif.shape)}")
-        ctx.shape, ctx.h, ctx.ds = rif.shape, h, ds
-        _ray_grad_wanted(ctx, "FieldIntegralTracerC", 2, 3, x, v)
-        (xt, vt, tau, steps), order, _ = drrt.TracerC()._trace_field(rif.detach().flatten(), field.detach().flatten(),
-                                                                     ctx.shape, x.detach(), v.detach(), h, ds)
-        if any(ctx.needs_input_grad[:4]):
-            ctx.options = dataclasses.asdict(drrt._opt())
-            ctx.order = drrt.keep_order(order)
-            _keep_rays(ctx, x, v, xt.device)
-            ctx.rays += (steps,)
-            ctx.save_for_backward(rif, field, xt, vt)
-        return xt, vt, tau
+        return _integral_forward(ctx, "FieldIntegralTracerC", drrt.TracerC()._trace_field, rif, (("field", field),), x, v, h,
+                                 ds)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_tau):
-        want_rif, want_field = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        want_rays = ctx.needs_input_grad[2] or ctx.needs_input_grad[3]
-        if not (want_rif or want_field or want_rays):
-            return None, None, None, None, None, None
-        rif, field, outx, outv = ctx.saved_tensors
-        x0, v0, steps = ctx.rays
-        with drrt.using(**ctx.options):
-            grad, gfield, dpos, dvel = drrt.TracerC().backtrace_field(
-                rif.detach().flatten(), field.detach().flatten(), ctx.shape, x0, v0, outx, outv, steps, grad_x, grad_v,
-                grad_tau, ctx.h, ctx.ds, grid=want_rif, field_grid=want_field, rays=want_rays, order=ctx.order)
-        drif = grad.reshape(*ctx.shape) if want_rif else None
-        dfield = gfield.reshape(*ctx.shape) if want_field else None
-        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[2] else None
-        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[3] else None
-        return drif, dfield, dx0, dv0, None, None
+        return (*_integral_backward(ctx, drrt.TracerC().backtrace_field, grad_x, grad_v, grad_tau), None, None)
 
 
 class EmissionTracerC(torch.autograd.Function):
@@ -431,42 +422,12 @@ class EmissionTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, emission, absorption, x, v, h, ds):
-        ctx.set_materialize_grads(False)
-        for name, field in (("emission", emission), ("absorption", absorption)):
-            if field.shape != rif.shape:
-                raise RuntimeError(f"EmissionTracerC: {name} has shape {tuple(field.shape)}, rif {tuple(rif.shape)}")
-        ctx.shape, ctx.h, ctx.ds = rif.shape, h, ds
-        _ray_grad_wanted(ctx, "EmissionTracerC", 3, 4, x, v)
-        (xt, vt, rad, tau, steps), order, _ = drrt.TracerC()._trace_emission(
-            rif.detach().flatten(), emission.detach().flatten(), absorption.detach().flatten(), ctx.shape, x.detach(),
-            v.detach(), h, ds)
-        if any(ctx.needs_input_grad[:5]):
-            ctx.options = dataclasses.asdict(drrt._opt())
-            ctx.order = drrt.keep_order(order)
-            _keep_rays(ctx, x, v, xt.device)
-            ctx.rays += (steps,)
-            ctx.save_for_backward(rif, emission, absorption, xt, vt, tau)
-        return xt, vt, rad, tau
+        return _integral_forward(ctx, "EmissionTracerC", drrt.TracerC()._trace_emission, rif,
+                                 (("emission", emission), ("absorption", absorption)), x, v, h, ds, keep=1)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_rad, grad_tau):
-        want_rif, want_e, want_a = ctx.needs_input_grad[:3]
-        want_rays = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        if not (want_rif or want_e or want_a or want_rays):
-            return None, None, None, None, None, None, None
-        rif, emission, absorption, outx, outv, tau = ctx.saved_tensors
-        x0, v0, steps = ctx.rays
-        with drrt.using(**ctx.options):
-            grad, gemis, gabsb, dpos, dvel = drrt.TracerC().backtrace_emission(
-                rif.detach().flatten(), emission.detach().flatten(), absorption.detach().flatten(), ctx.shape, x0, v0, outx,
-                outv, steps, tau, grad_x, grad_v, grad_rad, grad_tau, ctx.h, ctx.ds, grid=want_rif, emission_grid=want_e,
-                absorption_grid=want_a, rays=want_rays, order=ctx.order)
-        drif = grad.reshape(*ctx.shape) if want_rif else None
-        de = gemis.reshape(*ctx.shape) if want_e else None
-        da = gabsb.reshape(*ctx.shape) if want_a else None
-        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[3] else None
-        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[4] else None
-        return drif, de, da, dx0, dv0, None, None
+        return (*_integral_backward(ctx, drrt.TracerC().backtrace_emission, grad_x, grad_v, grad_rad, grad_tau), None, None)
 
 
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken

@@ -8,12 +8,12 @@ import torch
 
 import cases
 import emission_ad
-import emission_host as EH
 import field_ad
-import field_host as FH
 import hostcheck_lib as HC
+import integral_host as EH
+import integral_host as FH
+import integral_host as OH
 import opl_ad
-import opl_host as OH
 import test_field_integral as TF
 import test_opl as TO
 from oracle import torch_ad

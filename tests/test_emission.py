@@ -1,16 +1,16 @@
 """Emission with self-absorption along bent rays: drrt_trace_emission_f32 / drrt_backtrace_emission_f32,
 TracerC.trace_emission / backtrace_emission, tracer.EmissionTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/emission_rays.hip: exp_neg, trace_emission_ray
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: exp_neg, trace_emission_ray
 and emission_backtrace_ray of csrc/drrt_device.h) against the product's own trace and trace_field_ray (bit for bit), against
 float64 torch.autograd through tests/emission_ad (tests/field_ad's loop with rad += exp(-tau) ds n e, then tau += ds n a) on
 the tie-free rays of tests/test_opl.py::reference, against closed forms, against field_backtrace_ray with drad = 0, in an
-opaque medium, and the C ABI's argument checks.  GPU tier: the kernels of drrt_emission.hip against that host build, the
+opaque medium, and the C ABI's argument checks.  GPU tier: the emission kernels of drrt_integral.hip against that host build, the
 autograd class end to end, its launches, and the demo.  The scenes, ray sets and the plane source are tests/test_opl.py's;
 the two fields of a scene are tests/test_field_integral.py::make_field with two different seeds, the absorption scaled so
 that the largest optical depth of a ray that leaves the box is 5.5.
 
-On the parent commit every test here fails: tests/hostcheck/emission_rays.hip does not compile (no exp_neg, no
+On the parent commit every test here fails: tests/hostcheck/integral_rays.hip does not compile (no exp_neg, no
 trace_emission_ray), the library has no such C symbols, TracerC no such methods, tracer no such class and examples/ no such
 demo.
 
@@ -37,9 +37,9 @@ import torch
 
 import cases
 import emission_ad
-import emission_host as EH
-import field_host as FH
 import hostcheck_lib as HC
+import integral_host as EH
+import integral_host as FH
 import test_field_integral as TF
 import test_opl as TO
 from raygrad_common import GRAD_TOL, SCENES, _t, rel_err
@@ -517,7 +517,7 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/emission_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan
+    """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan
     and run as a child process, nothing preloaded: scene 1 plus rays, seeds and values of both fields with NaN, Inf, huge,
     denormal and negative entries; exp_neg sees every seed on tau (NaN, +-Inf, +-3e38 among them)."""
     rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")

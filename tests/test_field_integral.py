@@ -1,15 +1,15 @@
 """Line integral of a second field along bent rays: drrt_trace_field_f32 / drrt_backtrace_field_f32, TracerC.trace_field /
 backtrace_field, tracer.FieldIntegralTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/field_rays.hip: trace_field_ray and
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_field_ray and
 field_backtrace_ray of csrc/drrt_device.h) against the product's own trace and trace_opl_ray (bit for bit), against float64
 torch.autograd through tests/field_ad (tests/opl_ad's loop with tau += ds n a) on the tie-free rays of
 tests/test_opl.py::reference, against closed forms, against opl_backtrace_ray with field = rif, and the C ABI's argument
-checks.  GPU tier: the kernels of drrt_field.hip against that host build, the autograd class end to end, its launches, and
+checks.  GPU tier: the field kernels of drrt_integral.hip against that host build, the autograd class end to end, its launches, and
 the demo.  The scenes, ray sets and the plane source are tests/test_opl.py's; the second field of a scene is seeded, smooth,
 strictly positive and not symmetric under a permutation of the axes.
 
-On the parent commit every test here fails: tests/hostcheck/field_rays.hip does not compile (no trace_field_ray), the
+On the parent commit every test here fails: tests/hostcheck/integral_rays.hip does not compile (no trace_field_ray), the
 library has no such C symbols, TracerC no such methods, tracer no such class and examples/ no such demo.
 
 Mutation checks (tried by hand on field_backtrace_ray, one at a time, each then undone; CPU tier):
@@ -31,9 +31,9 @@ import torch
 
 import cases
 import field_ad
-import field_host as FH
 import hostcheck_lib as HC
-import opl_host as OH
+import integral_host as FH
+import integral_host as OH
 import test_opl as TO
 from oracle import torch_ad
 from raygrad_common import GRAD_TOL, SCENES, _t, rel_err
@@ -429,7 +429,7 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/field_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
+    """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
     run as a child process, nothing preloaded: scene 1 plus rays, seeds and field values with NaN, Inf, huge and denormal
     entries."""
     rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")

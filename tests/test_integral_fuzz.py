@@ -17,7 +17,7 @@ float64, the bound is
 2.4e-7 = 2^-22 is a few fp32 roundings, 8 the room for another, equally valid order of the fp32 operations.  The bound moves
 with the conditioning of the configuration (rough media, long marches) and never with what the code under test gives.
 
-CPU tier (the host build of the per-ray routines: hostcheck_lib, opl_host, field_host, emission_host): forward identities bit
+CPU tier (the host build of the per-ray routines: hostcheck_lib, integral_host): forward identities bit
 for bit, outputs and adjoints under the bound, flag off, failed and never-entered rays.  GPU tier: the kernels against the
 host build with and without the pair copy (the forward sorts on even seeds and the adjoint takes its order; on odd seeds the
 forward runs in caller order and the adjoint sorts for itself), TracerC.trace with the same pair setting, and the three
@@ -40,14 +40,14 @@ large e_prod (seeds 6 and 12: conditioning, not a defect).  The GPU tier's class
 results are the host build's bit for bit and their grids differ from it by the order of the atomic sums.
 
 Mutation checks (tried by hand on the host build, one at a time, each then undone; CPU tier):
-  * tests/hostcheck/field_rays.hip, the value weights of dL/dfield: in every boundary cell (Cell::interior false) the +z
+  * tests/hostcheck/integral_rays.hip, the value weights of dL/dfield: in every boundary cell (Cell::interior false) the +z
     neighbour replaced by the cell itself (oz = 0): all 32 field cases of test_adjoint_matches_float64_autograd fail; of the
     fixed scenes, all ten cases of tests/test_field_integral.py::test_adjoint_matches_float64_autograd, its
     test_plane_source_on_host, test_consistent_with_opl (5) and tests/test_emission.py::test_consistent_with_field_integral
     (5) fail too: their rays cross boundary cells as well.
   * the same on a 2-voxel axis only (oz = 0 where D == 2, oy = 0 where H == 2): the 8 field cases of
     test_adjoint_matches_float64_autograd on seeds 0, 4, 7, 14 fail; no fixed-scene test fails.
-  * tests/hostcheck/opl_rays.hip, grad_scale of the corrected_h path h instead of 1 / h: all 32 opl cases of
+  * tests/hostcheck/integral_rays.hip, grad_scale of the corrected_h path h instead of 1 / h: all 32 opl cases of
     test_adjoint_matches_float64_autograd and all 16 opl cases of test_flag_off_scales_the_gradient_splat fail; of the fixed
     scenes, the four h = 0.5 cases of tests/test_opl.py::test_adjoint_matches_float64_autograd and its
     test_flag_off_scales_the_gradient_splat fail, the six h = 1 cases pass (h = 1 / h).
@@ -60,8 +60,8 @@ import pytest
 import torch
 
 import cases
-import field_host as FH
 import integral_fuzz_common as IF
+import integral_host as FH
 from integral_fuzz_common import MODES, ROUTINES, SEEDS, TWO_VOXEL, config
 from raygrad_common import _t
 
@@ -252,7 +252,7 @@ def _gpu_pair(T, c, routine, dev, fwd_sorts):
 @pytest.mark.parametrize("pair", [False, True])
 @pytest.mark.parametrize("seed", SEEDS)
 def test_kernels_match_host_build(gpu, seed, pair):
-    """k_backtrace_rays and the kernels of drrt_opl.hip, drrt_field.hip and drrt_emission.hip, with plain and pair-copy
+    """k_backtrace_rays and the kernels of drrt_integral.hip, with plain and pair-copy
     gathers of rif == the host build: outputs, steps, ray gradients and statistics bit for bit, every grid gradient to the
     order of its atomic sums.  And TracerC.trace with the same pair setting gives the same (xt, vt, steps): the seeds with
     a 2-voxel axis never ran the pair copy before."""

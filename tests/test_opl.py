@@ -1,13 +1,13 @@
 """Optical path length: drrt_trace_opl_f32 / drrt_backtrace_opl_f32, TracerC.trace_opl / backtrace_opl, tracer.OPLTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/opl_rays.hip: trace_opl_ray and opl_backtrace_ray
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_opl_ray and opl_backtrace_ray
 of csrc/drrt_device.h) against the product's own trace (bit for bit), against float64 torch.autograd through tests/opl_ad
 (oracle/torch_ad.trace's loop with opl += ds n^2) on the tie-free rays -- those whose fp32 and fp64 marches leave on the same
 iteration with exit samples within TIE_TOL, as in tests/test_raygrad.py::reference --, against closed forms, and the C ABI's
-argument checks.  GPU tier: the kernels of drrt_opl.hip against that host build, the autograd class end to end, its launches,
+argument checks.  GPU tier: the opl kernels of drrt_integral.hip against that host build, the autograd class end to end, its launches,
 and the demo.
 
-On the parent commit every test here fails: tests/hostcheck/opl_rays.hip does not compile (no trace_opl_ray), the library has
+On the parent commit every test here fails: tests/hostcheck/integral_rays.hip does not compile (no trace_opl_ray), the library has
 no such C symbols, TracerC no such methods, tracer no such class and examples/ no such demo.
 
 Mutation checks (tried by hand on opl_backtrace_ray, one at a time, each then undone; CPU tier):
@@ -27,8 +27,8 @@ import torch
 
 import cases
 import hostcheck_lib as HC
+import integral_host as OH
 import opl_ad
-import opl_host as OH
 from oracle import torch_ad
 from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grid, ray_sets, rel_err
 
@@ -327,7 +327,7 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/opl_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
+    """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
     as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries."""
     rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
     if not rt or not os.path.exists(OH.HIPCC):
