@@ -67,28 +67,36 @@ static_assert(kWinFloats < (1 << 16), "win_face_key keeps a window slot in 16 bi
 // them linearly: a pass covers 64 / kWinX rows (lane -> row lane / kWinX, slot lane % kWinX), the LDS address advances
 // by a constant and the grid address by a constant plus a wrap from one z-slice to the next.  Passes go in batches of
 // four: the four LDS exchanges are issued before the first result is used, so a flush costs ceil(rows / 7 / 4) LDS
-// round trips (3 for a 9^3 window) instead of one per pass.
+// round trips (3 for a whole 9^3 window) instead of one per pass.
+// Only the z-planes that lanes have held slots in since the last flush are walked: `planes` (wave-uniform, not 0; bit lz =
+// plane lz may have been written, win_index) names them, and the walk goes from the pass that holds the first row of the
+// lowest such plane to the last row of the highest.  The rest of the window holds zeros.  (The headline's bundles are two
+// or three cells across: three or four planes of nine, two batches instead of three.)
 __device__ __forceinline__ void win_flush(win_t* win, int ox, int oy, int oz, float* __restrict__ grad,
-                                          const Vol& V, int lane) {
-  constexpr int kRowsPerPass = kWave / kWinX, kRowsTotal = kWinY * kWinZ;
-  constexpr int kPasses = (kRowsTotal + kRowsPerPass - 1) / kRowsPerPass, kBatch = 4;
+                                          const Vol& V, int lane, unsigned planes) {
+  constexpr int kRowsPerPass = kWave / kWinX, kBatch = 4;
   static_assert(kWinX <= 16 && kRowsPerPass <= kWinY, "win_flush: one pass must not span more than two z-slices");
   wave_lds_fence();
+  const int z_first = __builtin_ctz(planes), z_last = 31 - __builtin_clz(planes);
+  const int p_first = (z_first * kWinY) / kRowsPerPass;                  // the pass of the first row to flush
+  const int r_end = (z_last + 1) * kWinY;                                // one past the last row to flush
   const int rsub = lane / kWinX, lx = lane - rsub * kWinX;
   const bool lane_ok = rsub < kRowsPerPass;
-  int r = rsub, ly = rsub;                                               // row index, its ly (lz = 0: kRowsPerPass <= kWinY)
-  win_t* wl = win + rsub * kWinPX + lx;
-  unsigned go = (unsigned)oz * (unsigned)V.sz + (unsigned)(oy + rsub) * (unsigned)V.sy + (unsigned)(ox + lx);
+  int r = p_first * kRowsPerPass + rsub;                                 // row index, its lz and ly
+  const int lz = (int)((unsigned)r / (unsigned)kWinY);
+  int ly = r - lz * kWinY;
+  win_t* wl = win + r * kWinPX + lx;
+  unsigned go = (unsigned)(oz + lz) * (unsigned)V.sz + (unsigned)(oy + ly) * (unsigned)V.sy + (unsigned)(ox + lx);
   const unsigned step_y = (unsigned)kRowsPerPass * (unsigned)V.sy, wrap = (unsigned)V.sz - (unsigned)kWinY * (unsigned)V.sy;
 #pragma unroll 1
-  for (int p0 = 0; p0 < kPasses; p0 += kBatch) {
+  for (int p0 = p_first; p0 * kRowsPerPass < r_end; p0 += kBatch) {
     win_t v[kBatch];
     unsigned g[kBatch];
 #pragma unroll
     for (int b = 0; b < kBatch; ++b) {
       v[b] = (win_t)0; g[b] = go;
       // ds_wrxchg_rtn_b64: read the accumulated value and reset the slot in one LDS op
-      if (lane_ok & (r < kRowsTotal)) v[b] = __hip_atomic_exchange(wl, (win_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      if (lane_ok & (r < r_end)) v[b] = __hip_atomic_exchange(wl, (win_t)0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
       r += kRowsPerPass; wl += kRowsPerPass * kWinPX; ly += kRowsPerPass; go += step_y;
       if (ly >= kWinY) { ly -= kWinY; go += wrap; }
     }
@@ -132,10 +140,27 @@ __device__ __forceinline__ int wave_max_i32(int v) {
   for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, kWave));
   return v;
 }
-__device__ __forceinline__ int win_index(int wox, int woy, int woz, int cx, int cy, int cz) {
+// OR over the wave, wave-uniform.  Called with all 64 lanes: four row_shr steps leave a row's OR in its last lane (a lane a
+// shift does not reach reads 0), and the four rows meet in scalars -- no LDS.
+__device__ __forceinline__ unsigned wave_or_u32(unsigned v) {
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false);   // row_shr:1
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x112, 0xF, 0xF, false);   // row_shr:2
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x114, 0xF, 0xF, false);   // row_shr:4
+  v |= (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x118, 0xF, 0xF, false);   // row_shr:8
+  return (unsigned)(__builtin_amdgcn_readlane((int)v, 15) | __builtin_amdgcn_readlane((int)v, 31) |
+                    __builtin_amdgcn_readlane((int)v, 47) | __builtin_amdgcn_readlane((int)v, 63));
+}
+// Window slot of the cell (cx, cy, cz), or -1 when it is not inside.  A cell that is inside has its two z-planes marked in the
+// lane's `planes` here, where the lane gets the slot: every add a lane makes to the window goes to the cell whose slot it
+// holds (a face, all eight corners, the hand-over of a ray that ends or is cut off by the step budget), so the marks cover
+// every slot written, and win_flush walks the marked planes only.  (Marking where the slot is handed out costs a shift and
+// an OR per leave; marking in the four places that add would need the plane again there, i.e. a register per lane.)
+static_assert(kWinZ <= 31, "one bit per z-plane of the window");
+__device__ __forceinline__ int win_index(int wox, int woy, int woz, int cx, int cy, int cz, unsigned& planes) {
   const int lx = cx - wox, ly = cy - woy, lz = cz - woz;
   const bool in = ((unsigned)lx < (unsigned)(kWinX - 1)) & ((unsigned)ly < (unsigned)(kWinY - 1)) &
                   ((unsigned)lz < (unsigned)(kWinZ - 1));
+  planes |= (in ? 3u : 0u) << (lz & 31);
   // v_mad_u32_u24 by hand: with constant strides the compiler turns the 24-bit multiply into the quarter-rate
   // v_mul_lo_u32 (lx, ly, lz are small and non-negative whenever the result is used)
   int r;
@@ -367,7 +392,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     base = nbase;
     lidx = nregular ? kMiss : kIrregular;                    // no window yet
   }
-  bool dirty = false;
+  unsigned planes = 0u;                                      // z-planes of the window the lane has held a slot in since the last flush (win_index)
   int cooldown = 0;
   unsigned steps = 0;
   unsigned n_flush = 0;
@@ -381,15 +406,16 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
 
 #define WSY kWinSY
 #define WSZ kWinSZ
-#define WIN_INDEX(cx, cy, cz) win_index(W.ox, W.oy, W.oz, cx, cy, cz)
+#define WIN_INDEX(cx, cy, cz) win_index(W.ox, W.oy, W.oz, cx, cy, cz, planes)
     for (int it = 0; it < a.max_steps; ++it) {
       if (!__any(s.active)) break;                                              // wave-uniform exit
       // ---- (re-)anchor the window around the cells the rays stand on (wave-uniform branch) ----
       const unsigned long long mm = __ballot(s.active & (lidx == kMiss));
       if (mm != 0ull && cooldown == 0) {
-        if (dirty) {
-          win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane);
-          dirty = false; ++n_flush;
+        const unsigned dirty = wave_or_u32(planes);
+        if (dirty != 0u) {
+          win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane, dirty);
+          planes = 0u; ++n_flush;
         }
         const bool regular = lidx > kIrregular;
         const bool ok = s.active & regular;
@@ -410,13 +436,12 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
           ox = max(0, min(ox, V.W - kWinX)); oy = max(0, min(oy, V.H - kWinY)); oz = max(0, min(oz, V.D - kWinZ));
           W.ox = __builtin_amdgcn_readfirstlane(ox); W.oy = __builtin_amdgcn_readfirstlane(oy);
           W.oz = __builtin_amdgcn_readfirstlane(oz);
-          lidx = regular ? WIN_INDEX(ix, iy, iz) : kIrregular;                  // every lane's cell, in the new window
+          if (ok) lidx = WIN_INDEX(ix, iy, iz);                                 // every marching lane's cell, in the new window
         }
         cooldown = (__ballot(ok & (lidx < 0)) != 0ull) ? 4 : 0;                 // incoherent wave: do not thrash
       } else if (cooldown > 0) {
         --cooldown;
       }
-      bool used_lds = false;
       if (s.active) {
         const bool interior = tbase >= 0, regular = lidx > kIrregular;
         if (!interior) taps_set<PAIR>(fetch(V.data, locate(V, s.x, s.y, s.z)), q0, q1);   // boundary cell (clamped neighbours): fetched here, not ahead
@@ -428,7 +453,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
         AdjSample m;
         if (!adj_sample_st<MODE>(V, a.sdf, a.ds, s, c, taps_of<PAIR>(q0, q1), m, st, MODE == 1 && interior)) {
           // the ray has ended (:426-428): it contributes nothing here; hand over what its cell has accumulated
-          if (regular) used_lds = flat_emit8<true>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
+          if (regular) flat_emit8<true>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
         } else {
           ++steps;
           if (CHUNK) { bx0 = fminf(bx0, px); by0 = fminf(by0, py); bz0 = fminf(bz0, pz); bx1 = fmaxf(bx1, px); by1 = fmaxf(by1, py); bz1 = fmaxf(bz1, pz); }
@@ -523,7 +548,6 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
                     if (lidx >= 0) {
                       const bool add = win_emit4(win, key, lp, lq, e0, e1, e2, e3);
                       if (DBG && a.dbg) { ++ev_face; ev_add += add; }
-                      used_lds = true;
                     } else {
                       // the cell lies outside the window: straight to the grid.  |d| is the grid stride of the axis crossed, which
                       // names the strides of p and q; a face left behind in the negative direction is the cell's far one, |d| on.
@@ -538,7 +562,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
                     // jump over more than one face, or into a clamped cell: hand over all eight
                     if (DBG && a.dbg) ++ev_all8;
                     // (no quad pre-reduction here: two-face crossings are rarely shared by a quad -- 4.87 -> 4.81 ms without it)
-                    used_lds = flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, old_base, p00, p10, p01, p11);
+                    flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, old_base, p00, p10, p01, p11);
                     p00 = p10 = p01 = p11 = f2{0.f, 0.f};
                   }
                 }
@@ -548,17 +572,16 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
           }
         }
       }
-      dirty = dirty | (__ballot(used_lds) != 0ull);
       if (DBG && a.dbg) ev_wsteps += lane == 0;
     }
   // rays still marching when max_steps ran out keep what their cell has accumulated: hand it over
-  if (s.active && lidx > kIrregular) { if (flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11)) dirty = true; }
+  if (s.active && lidx > kIrregular) flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
 #undef WSY
 #undef WSZ
 #undef WIN_INDEX
-  dirty = __ballot(dirty) != 0ull;
-  if (dirty) {
-    win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane);
+  const unsigned dirty = wave_or_u32(planes);
+  if (dirty != 0u) {
+    win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane, dirty);
     ++n_flush;
   }
   if (CHUNK) {
