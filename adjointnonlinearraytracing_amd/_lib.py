@@ -90,6 +90,8 @@ SIGNATURES = {
     "drrt_trace_emission_f32": (_i, [_vp, _vp, _vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_emission_f32": (_i, [_vp, _vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f,
                                          _vp, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_trace_vector_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_backtrace_vector_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_chunk_state_bytes": (_sz, [_sz]),
     "drrt_backtrace_max_steps": (_i, [_vp, _f, _f]),
     "drrt_backtrace_chunk_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail + [_vp, _sz, _i, _i, _vp]),
@@ -124,8 +126,10 @@ SIGNATURES = {
 PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "backtrace_rays",
               7: "backtrace_cable_rays", 8: "backtrace_pln_rays", 9: "backtrace_sdf_rays", 10: "backtrace_target_rays",
               11: "trace_opl", 12: "backtrace_opl", 13: "trace_field", 14: "backtrace_field"}
-# the ids added after PROF_NAMES was closed (profile_collect consults both tables)
+# the ids added after PROF_NAMES was closed (profile_collect consults all three tables)
 PROF_NAMES_MORE = {15: "trace_emission", 16: "backtrace_emission"}
+# ... and after PROF_NAMES_MORE was: this table stays open, a later id goes here
+PROF_NAMES_LATER = {17: "trace_vector", 18: "backtrace_vector"}
 
 _lib: Optional[C.CDLL] = None
 
@@ -154,7 +158,8 @@ def profile_collect(max_out: int = 4096):
     ids = (C.c_int * max_out)()
     ms = (C.c_float * max_out)()
     n = load().drrt_profile_collect(ids, ms, max_out)
-    return [(PROF_NAMES.get(ids[i]) or PROF_NAMES_MORE.get(ids[i], str(ids[i])), float(ms[i])) for i in range(n)]
+    names = {**PROF_NAMES, **PROF_NAMES_MORE, **PROF_NAMES_LATER}
+    return [(names.get(ids[i], str(ids[i])), float(ms[i])) for i in range(n)]
 
 
 def last_error() -> str:

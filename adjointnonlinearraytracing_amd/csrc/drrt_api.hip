@@ -708,11 +708,11 @@ extern "C" int drrt_backtrace_target_rays_f32(const float* rif, long long nvox, 
   return timed_launch(DRRT_PROF_BACKTRACE_TARGET_RAYS, s, "k_backtrace_target_rays", [&] { launch_backtrace_target_rays(a, s); });
 }
 
-// ---- the integral operators (optical path length, line integral of a second field, emission with self-absorption):
-// drrt_integral.hip -------------------------------------------------------------------------------------------------------
-// The six entry points share one forward and one backward prologue.  An entry point fills the fields of its argument block
+// ---- the integral operators (optical path length, line integral of a second field, emission with self-absorption, line
+// integral of a vector field): drrt_integral.hip ------------------------------------------------------------------------
+// The eight entry points share one forward and one backward prologue.  An entry point fills the fields of its argument block
 // that are its own (further grids, per-ray inputs and outputs, gradient grids) and names them for the checks.
-struct IntegralCall {              // the arguments every one of the six has
+struct IntegralCall {              // the arguments every one of the eight has
   const float* rif; long long nvox; const int* res; size_t n;
   const float* pos; const float* vel;
   float h, ds;
@@ -862,6 +862,34 @@ extern "C" int drrt_backtrace_emission_f32(const float* rif, const float* emissi
       {{tau, "null tau pointer (the forward's tau)"}}, {grad, grad_emission, grad_absorption},
       "null output pointers: grad, grad_emission, grad_absorption, or dpos and dvel, or any of these together", xt, vt,
       fwd_steps, dx, dv, dpos, dvel, DRRT_PROF_BACKTRACE_EMISSION, "k_backtrace_emission", launch_backtrace_emission);
+}
+
+extern "C" int drrt_trace_vector_f32(const float* rif, const float* vfield, long long nvox, const int res[3], size_t n,
+                                     const float* pos, const float* vel, float h, float ds, float* xt, float* vt,
+                                     float* circ, uint32_t* steps_out, drrt_stats* stats, void* ws, size_t ws_bytes,
+                                     unsigned flags, void* stream) {
+  VectorTraceArgs a{};
+  a.vfield = vfield; a.circ = circ;
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+                            {{vfield, "null vfield pointer"}}, {circ}, xt, vt, steps_out, DRRT_PROF_TRACE_VECTOR,
+                            "k_trace_vector", launch_trace_vector);
+}
+
+extern "C" int drrt_backtrace_vector_f32(const float* rif, const float* vfield, long long nvox, const int res[3], size_t n,
+                                         const float* pos, const float* vel, const float* xt, const float* vt,
+                                         const uint32_t* fwd_steps, const float* dx, const float* dv, const float* dcirc,
+                                         float h, float ds, float* grad, float* grad_vfield, float* dpos, float* dvel,
+                                         drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  VectorBackArgs a{};
+  a.vfield = vfield; a.dcirc = dcirc; a.grad = grad; a.grad_vfield = grad_vfield;
+  // the three planes of grad_vfield are three gradient grids of nvox floats to the prologue, which zeroes each
+  float* const gy = grad_vfield && nvox > 0 ? grad_vfield + nvox : nullptr;
+  float* const gz = grad_vfield && nvox > 0 ? grad_vfield + 2 * nvox : nullptr;
+  return run_backtrace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream},
+                                {{vfield, "null vfield pointer"}}, {}, {grad, grad_vfield, gy, gz},
+                                "null output pointers: grad, grad_vfield, or dpos and dvel, or any of these together", xt, vt,
+                                fwd_steps, dx, dv, dpos, dvel, DRRT_PROF_BACKTRACE_VECTOR, "k_backtrace_vector",
+                                launch_backtrace_vector);
 }
 
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }

@@ -755,7 +755,7 @@ DRRT_HD unsigned backtrace_ray(const Vol& V, const float* __restrict__ sdf, floa
 }
 
 // ---- the integral operators: one forward loop, one reverse march -----------------------------------------------------
-// trace_opl, trace_field and trace_emission are trace with a line integral over the samples the march takes anyway; their
+// trace_opl, trace_field, trace_emission and trace_vector are trace with a line integral over the samples the march takes anyway; their
 // adjoints, and the ray-state adjoint of trace, are one reverse march.  Both skeletons are written once here; an operator
 // supplies an integrand (forward) and a term (reverse), defined with its mathematics further down.
 struct RayGrad { float dp[3], dv[3]; unsigned steps; bool failed; };
@@ -766,6 +766,8 @@ struct RayGrad { float dp[3], dv[3]; unsigned steps; bool failed; };
 // fwd_step_c's sample (Q4) and n = n_k under it, 0.f while the ray is not inside (free flight outside the box adds
 // nothing).  The integrand samples its own fields at the cell and weights of c, under the same mask, and owns its
 // accumulators, which start at 0.f and are updated in iteration order.  A failed ray leaves in them what it accumulated.
+// `q.step(s)` is called once per iteration behind the step, with the state it left: s.v is v_{k+1}, the velocity that
+// carried the ray from x_k to x_{k+1} (an integrand whose summand needs the ray's direction closes its iteration there).
 template <typename TapFn, typename Integrand>
 DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
                                   Integrand&& q) {
@@ -784,6 +786,7 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
     }
     q(c, s.inside, n);
     fwd_step_c<0>(V, nullptr, ds, s, c, t);
+    q.step(s);
     ++steps;
     if (s.esc) break;                                                     // per-ray form of :82
   }
@@ -811,6 +814,10 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
 //     outside it.
 // `taps(c)` returns the 8 taps of cell c (the caller chooses how they are fetched; the floats are the grid's).
 // What an operator adds is its `term`, called in this order in every reverse iteration, m the sample (n_k, grad n_k):
+//   term.enter(V, c, s)                    behind locate and before the sample: c is the cell of x_k and s.v still holds
+//                                          v_{k+1}, the velocity that carried the ray out of x_k; a term whose summand has
+//                                          the ray's direction in it seeds mu (dL/dv_{k+1}) here, so that dn and the
+//                                          contribution to dL/dn below see the seed
 //   dn = term.dn(V, c, m, mu . grad n_k)   the factor of ds grad n_k that adj_recur adds to lambda: d L / d n_k over ds
 //   sink(c, val, gx, gy, gz)               the contribution to dL/dn, formed like adj_contrib's with mu BEFORE adj_recur
 //                                          updates it: val = dn ds, g = (n_k ds grad_scale) mu; the caller adds
@@ -823,6 +830,7 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
 // With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum of the contributions is the exact discrete derivative; the 1/h
 // scales only the splat into the grid (Q3) and does not enter the ray gradients.
 struct NoTerm {                              // trace itself: nothing is integrated
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
   DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
   DRRT_HD void after() {}
@@ -859,6 +867,7 @@ DRRT_HD RayGrad integral_backtrace_ray(const Vol& V, float ds, float grad_scale,
     s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
     if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
     const Cell c = locate(V, s.x, s.y, s.z);
+    term.enter(V, c, s);
     AdjSample m;
     (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
     const float dn = term.dn(V, c, m, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));         // :430
@@ -894,6 +903,7 @@ DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsig
 struct OplIntegrand {
   float ds, opl = 0.f;
   DRRT_HD void operator()(const Cell&, bool, float n) { opl = fmaf(ds * n, n, opl); }
+  DRRT_HD void step(const FwdState&) {}
 };
 
 // trace for ONE ray, with its optical path length.
@@ -914,6 +924,7 @@ DRRT_HD RayOut trace_opl_ray(const Vol& V, float ds, int max_steps, const float 
 // does with dn.
 struct OplTerm {
   float dopl2;                               // 2 dopl
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample& m, float mg) { return fmaf(dopl2, m.n, mg); }
   DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
   DRRT_HD void after() {}
@@ -954,6 +965,7 @@ struct FieldIntegrand {
     if (inside) a = interp<false>(ftaps(c), c.wx, c.wy, c.wz).n;
     tau = fmaf(ds * n, a, tau);
   }
+  DRRT_HD void step(const FwdState&) {}
 };
 
 // trace for ONE ray, with the line integral of the field whose taps `ftaps(c)` returns (`taps(c)`: those of n).
@@ -981,6 +993,7 @@ struct FieldTerm {
   FieldSink& fsink;
   float dtau, dtds;                          // dtau, dtau ds
   Sample a;
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell& c, const AdjSample& m, float mg) {
     a = interp<false>(ftaps(c), c.wx, c.wy, c.wz);
     return fmaf(dtau, a.n, mg);
@@ -1058,6 +1071,7 @@ struct EmissionIntegrand {
     rad = fmaf(exp_neg(tau) * w, e, rad);                                 // emit with the transmittance in front of the sample
     tau = fmaf(w, a, tau);                                                // then absorb
   }
+  DRRT_HD void step(const FwdState&) {}
 };
 
 // trace for ONE ray with the emission integral; `taps(c)`: the taps of n, `etaps(c)` / `ataps(c)`: those of the emission and
@@ -1096,6 +1110,7 @@ struct EmissionTerm {
   float ds, drad, t, P;                      // t starts at the forward's tau, P at dtau
   Sample em, ab;
   float w, ce, ev;
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell& c, const AdjSample& m, float mg) {
     em = interp<false>(etaps(c), c.wx, c.wy, c.wz);
     ab = interp<false>(ataps(c), c.wx, c.wy, c.wz);
@@ -1123,6 +1138,90 @@ DRRT_HD RayGrad emission_backtrace_ray(const Vol& V, float ds, float grad_scale,
                                        AbsSink&& asink) {
   EmissionTerm<EmisTapFn, AbsTapFn, EmisSink, AbsSink> term{etaps, ataps, esink, asink, ds, drad, tau, dtau, {}, {},
                                                             0.f, 0.f, 0.f};
+  return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
+}
+
+// ---- line integral of a vector field ---------------------------------------------------------------------------------
+// circ = int u . dl of a vector field u (flow velocity, n_e B) given as three component planes on the grid of n, along the
+// bent ray: plane c pairs with component c of pos / vel (x, y, z).  With u_k the trilinear sample of the three planes at the
+// cell, the weights and under the mask of n_k (0 while the ray is not inside) and v_{k+1} the velocity BEHIND the update from
+// sample k -- the one that carries the ray from x_k to x_{k+1} --
+//   circ = sum_{k<K} ds (u_k . v_{k+1}) = sum_k u(x_k) . (x_{k+1} - x_k)
+// accumulated in fp32 in iteration order from 0.f as t = ux vx; t = fmaf(uy, vy, t); t = fmaf(uz, vz, t);
+// circ = fmaf(ds, t, circ).  The sum telescopes: for a uniform u, circ = u . (xt - x_e), x_e the first in-box sample.  Not
+// in the reference.
+template <typename VecTapFn>
+struct VectorIntegrand {
+  VecTapFn& vtaps;                           // vtaps(c, k): the 8 taps of plane k at cell c
+  float ds, circ = 0.f;
+  float ux = 0.f, uy = 0.f, uz = 0.f;
+  DRRT_HD void operator()(const Cell& c, bool inside, float) {
+    ux = uy = uz = 0.f;
+    if (inside) {
+      ux = interp<false>(vtaps(c, 0), c.wx, c.wy, c.wz).n;
+      uy = interp<false>(vtaps(c, 1), c.wx, c.wy, c.wz).n;
+      uz = interp<false>(vtaps(c, 2), c.wx, c.wy, c.wz).n;
+    }
+  }
+  DRRT_HD void step(const FwdState& s) {
+    float t = ux * s.vx;
+    t = fmaf(uy, s.vy, t);
+    t = fmaf(uz, s.vz, t);
+    circ = fmaf(ds, t, circ);
+  }
+};
+
+// trace for ONE ray, with the line integral of the vector field whose taps `vtaps(c, k)` returns (`taps(c)`: those of n).
+template <typename TapFn, typename VecTapFn>
+DRRT_HD RayOut trace_vector_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
+                                VecTapFn&& vtaps, float& circ) {
+  VectorIntegrand<VecTapFn> q{vtaps, ds};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  circ = q.circ;
+  return o;
+}
+
+// Adjoint of trace_vector_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn AND the three planes of dL/du,
+// from the seeds (dx, dv, dcirc) on (xt, vt, circ).  The summand ds u(x_k) . v_{k+1} depends on the velocity the reverse
+// march holds when it arrives at x_k, so the term acts in `enter`, before the sample steps v back: with g = dcirc ds,
+//   mu += g u_k                                      (d circ / d v_{k+1} = ds u_k): the seed on v_{k+1}, there before
+//                                                    dn = mu . grad n_k is formed, so the splat into dL/dn sees it
+//   w   = g v_{k+1}                                  kept for pull
+// and in `pull`, `vsink(k, c, w[k])` receives the contribution to plane k of dL/du (value weights at the taps of c: circ
+// is linear in u, no gradient splat, no grad_scale) and
+//   lambda += (grad u_k)^T w                         (d circ / d x_k = ds (grad u_k)^T v_{k+1}, grad u_k scaled by 1 / h)
+// dn, the contribution to dL/dn, adj_recur and the closing dvel = mu_prev + e ds lambda are the skeleton's; mu_prev is taken
+// behind the seed.  With dcirc = 0 this is backtrace_ray_state with the contributions to dL/dn.
+template <typename VecTapFn, typename VecSink>
+struct VectorTerm {
+  VecTapFn& vtaps;
+  VecSink& vsink;
+  float g;                                   // dcirc ds
+  Sample ux, uy, uz;
+  float wx, wy, wz;
+  DRRT_HD void enter(const Vol&, const Cell& c, AdjState& s) {
+    ux = interp<false>(vtaps(c, 0), c.wx, c.wy, c.wz);
+    uy = interp<false>(vtaps(c, 1), c.wx, c.wy, c.wz);
+    uz = interp<false>(vtaps(c, 2), c.wx, c.wy, c.wz);
+    wx = g * s.vx; wy = g * s.vy; wz = g * s.vz;
+    s.mx = fmaf(g, ux.n, s.mx); s.my = fmaf(g, uy.n, s.my); s.mz = fmaf(g, uz.n, s.mz);
+  }
+  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s) {
+    vsink(0, c, wx); vsink(1, c, wy); vsink(2, c, wz);
+    s.lx = fmaf(dot3(ux.gx, uy.gx, uz.gx, wx, wy, wz), V.inv_h, s.lx);
+    s.ly = fmaf(dot3(ux.gy, uy.gy, uz.gy, wx, wy, wz), V.inv_h, s.ly);
+    s.lz = fmaf(dot3(ux.gz, uy.gz, uz.gz, wx, wy, wz), V.inv_h, s.lz);
+  }
+  DRRT_HD void after() {}
+};
+
+template <typename TapFn, typename VecTapFn, typename Sink, typename VecSink>
+DRRT_HD RayGrad vector_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                     const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                     const float dv[3], float dcirc, TapFn&& taps, VecTapFn&& vtaps, Sink&& sink,
+                                     VecSink&& vsink) {
+  VectorTerm<VecTapFn, VecSink> term{vtaps, vsink, dcirc * ds, {}, {}, {}, 0.f, 0.f, 0.f};
   return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
 }
 

@@ -7,8 +7,12 @@
 //   drrt_trace_emission_f32 / drrt_backtrace_emission_f32  rad = sum T_k ds n_k e_k with T_k = exp_neg(tau_k) the
 //                                                          transmittance in front of sample k, and tau = sum ds n_k a_k;
 //                                                          dL/dn, dL/de, dL/da and the ray gradients from (xt, vt, rad, tau)
+//   drrt_trace_vector_f32 / drrt_backtrace_vector_f32      circ = sum ds u_k . v_{k+1}, u_k a vector field (three planes) at
+//                                                          the cell and weights of n_k, v_{k+1} the velocity behind the
+//                                                          step; dL/dn, the three planes of dL/du and the ray gradients
+//                                                          from (xt, vt, circ)
 // Per-ray arithmetic: trace_integral_ray / integral_backtrace_ray of drrt_device.h with each operator's integrand and term
-// (trace_opl_ray ... emission_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
+// (trace_opl_ray ... vector_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
 // drrt_march.h.
 //
 // One ray per lane, everything in registers, as drrt_adjoint_rays.hip: the taps of n go through OplTaps (pair copy or plain
@@ -183,6 +187,46 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_emission(EmissionBackArgs 
   });
 }
 
+// ---- line integral of a vector field -----------------------------------------------------------------------------------
+// the taps of the three component planes: one FieldTaps each, plane k at + k nvox
+struct VectorTaps {
+  FieldTaps x, y, z;
+  __device__ __forceinline__ VectorTaps(const float* u, size_t nvox) : x(u), y(u + nvox), z(u + 2 * nvox) {}
+  __device__ __forceinline__ Taps operator()(const Cell& c, int k) { return k == 0 ? x(c) : k == 1 ? y(c) : z(c); }
+};
+__device__ __forceinline__ size_t plane_size(const Vol& V) { return (size_t)V.sz * (size_t)V.D; }
+
+template <bool PAIR>
+__global__ void __launch_bounds__(kBlock) k_trace_vector(VectorTraceArgs a) {
+  float circ;
+  trace_lanes<PAIR>(a,
+    [&](const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+      VectorTaps vtaps(a.vfield, plane_size(a.vol));
+      return trace_vector_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, vtaps, circ);
+    },
+    [&](size_t i) { a.circ[i] = circ; });
+}
+
+// GRID / VFIELD: dL/dn / the three planes of dL/du are scattered (a.grad / a.grad_vfield is not null)
+template <bool PAIR, bool GRID, bool VFIELD>
+__global__ void __launch_bounds__(kBlock) k_backtrace_vector(VectorBackArgs a) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+    const float dcirc = a.dcirc ? a.dcirc[i] : 0.f;
+    const size_t nvox = plane_size(a.vol);
+    VectorTaps vtaps(a.vfield, nvox);
+    HeldCorners acc(a.grad), xacc(a.grad_vfield), yacc(a.grad_vfield + nvox), zacc(a.grad_vfield + 2 * nvox);
+    SplatSink<GRID> sink{acc};
+    auto vsink = [&](int k, const Cell& c, float val) {
+      if (VFIELD) (k == 0 ? xacc : k == 1 ? yacc : zacc).add(c, value_weights(c.wx, c.wy, c.wz, val));
+    };
+    const RayGrad g = vector_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
+                                           dcirc, taps, vtaps, sink, vsink);
+    if (GRID) acc.flush();
+    if (VFIELD) { xacc.flush(); yacc.flush(); zacc.flush(); }
+    return g;
+  });
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // with_bools(f, b...) calls f(std::bool_constant<b>...) for the runtime booleans b...: which instantiation of a kernel a
 // call gets
@@ -219,6 +263,14 @@ void launch_backtrace_emission(const EmissionBackArgs& a, hipStream_t s) {
     LAUNCH_INTEGRAL((k_backtrace_emission<decltype(pair)::value, decltype(grid)::value, decltype(emis)::value,
                                           decltype(absb)::value>), a, s);
   }, a.vol.pair != nullptr, a.grad != nullptr, a.grad_emission != nullptr, a.grad_absorption != nullptr);
+}
+void launch_trace_vector(const VectorTraceArgs& a, hipStream_t s) {
+  with_bools([&](auto pair) { LAUNCH_INTEGRAL(k_trace_vector<decltype(pair)::value>, a, s); }, a.vol.pair != nullptr);
+}
+void launch_backtrace_vector(const VectorBackArgs& a, hipStream_t s) {
+  with_bools([&](auto pair, auto grid, auto vfield) {
+    LAUNCH_INTEGRAL((k_backtrace_vector<decltype(pair)::value, decltype(grid)::value, decltype(vfield)::value>), a, s);
+  }, a.vol.pair != nullptr, a.grad != nullptr, a.grad_vfield != nullptr);
 }
 
 }  // namespace drrt

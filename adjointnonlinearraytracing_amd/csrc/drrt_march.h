@@ -617,6 +617,41 @@ struct EmissionBackArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
+// line integral of a vector field (drrt_integral.hip): trace with circ = sum ds u_k . v_{k+1}, and its adjoint (dL/dn, the
+// three planes of dL/du and the rays)
+struct VectorTraceArgs {
+  Vol vol;
+  const float* vfield;                      // three component planes of vol's shape, plane c at + c nvox (no pair copy)
+  const float* pos; const float* vel;
+  float* xt; float* vt; float* circ;
+  uint32_t* steps_out;                      // per-ray iteration counts, caller ray order
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+struct VectorBackArgs {
+  Vol vol;
+  const float* vfield;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const uint32_t* fsteps;                   // its per-ray iteration counts, caller ray order
+  const float* dx; const float* dv;         // nullable: seeds on (xt, vt), read as zeros
+  const float* dcirc;                       // nullable: seed on circ, n floats
+  float* grad;                              // nullable: no scatter into dL/dn
+  float* grad_vfield;                       // nullable: no scatter into dL/du (three planes, as vfield)
+  float* dpos; float* dvel;                 // both null: no ray outputs
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  float grad_scale;                         // 1 (as written, Q3) or 1/h (DRRT_FLAG_CORRECTED_H)
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -679,13 +714,15 @@ void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t 
 // ray-state adjoint of trace_target: the count of the global loop, then replay and reverse march (drrt_target_rays.hip)
 void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
 // the integral operators (drrt_integral.hip): optical path length, line integral of a second field, emission with
-// self-absorption, each with its adjoint
+// self-absorption, line integral of a vector field, each with its adjoint
 void launch_trace_opl(const OplTraceArgs& a, hipStream_t s);
 void launch_backtrace_opl(const OplBackArgs& a, hipStream_t s);
 void launch_trace_field(const FieldTraceArgs& a, hipStream_t s);
 void launch_backtrace_field(const FieldBackArgs& a, hipStream_t s);
 void launch_trace_emission(const EmissionTraceArgs& a, hipStream_t s);
 void launch_backtrace_emission(const EmissionBackArgs& a, hipStream_t s);
+void launch_trace_vector(const VectorTraceArgs& a, hipStream_t s);
+void launch_backtrace_vector(const VectorBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip)
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);

@@ -537,12 +537,13 @@ def _ray_format(pos: torch.Tensor, vel: torch.Tensor, seeds: tuple = ()):
     return "_q16io" if q16 or qpos else "_f16io", _lib.FLAG_Q16_POS_ONLY if qpos else 0, how
 
 
-def _grid_inputs(rif, sdf, rays, dev: torch.device, how=None):
+def _grid_inputs(rif, sdf, rays, dev: torch.device, how=None, planes: int = 1):
     """The inputs of a grid entry on `dev` -> (flat fp32 grid, flat fp32 SDF or None, the (n,3) ray tensors, n).  The
-    first ray tensor fixes n; `how`: per ray tensor, the format `_rays` converts it to (`_ray_format`; None: all fp32)."""
+    first ray tensor fixes n; `how`: per ray tensor, the format `_rays` converts it to (`_ray_format`; None: all fp32);
+    `planes`: the second grid is that many component planes of the first one's size (a vector field: 3)."""
     rif_ = _f32(rif, dev).reshape(-1)
     sdf_ = None if sdf is None else _f32(sdf, dev).reshape(-1)
-    if sdf_ is not None and sdf_.numel() != rif_.numel():
+    if sdf_ is not None and sdf_.numel() != planes * rif_.numel():
         raise RuntimeError("Resolution doesn't match data")      # src/volume.cpp:37
     if how is None:
         first = _rays(rays[0], dev)
@@ -561,7 +562,7 @@ def _more_grid(grid, rif_, dev: torch.device) -> torch.Tensor:
 
 def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sdf=None, how=None, fwd_steps=None,
                order=None, replay: bool = False, flags: int = 0, steps: bool = True, warn: bool = False,
-               counters: bool = False, per_ray=(), more_grids=()) -> tuple:
+               counters: bool = False, per_ray=(), more_grids=(), planes: int = 1) -> tuple:
     """One call of a grid entry point (they share their shape: grid, [sdf], nvox, res, n, the inputs, h, ds, the outputs,
     the usual tail) -> (outputs, order, steps): the outputs, made by ``make_outputs(flat grid, ray tensors)``, and what
     a forward march left behind -- its visit order and per-ray iteration counts, the workspace views that are also
@@ -571,10 +572,11 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
     passed as a null pointer).  `adjoint`: a forward march, or an adjoint that may be paired
     with one through `order`; `replay`: an adjoint that marches its forward again (`_paired_adjoint`).  `steps`: the
     forward leaves iteration counts.  `warn`: failed rays are reported.  `counters`: the adjoint classifies its bundles
-    (`last_bundle_counters`).  `more_grids`: further fp32 grids of the first one's size, passed behind `sdf`."""
+    (`last_bundle_counters`).  `more_grids`: further fp32 grids of the first one's size, passed behind `sdf`.  `planes`:
+    `sdf` is that many component planes of the first grid's size."""
     dev = _dev(rif)
     with torch.cuda.device(dev):
-        rif_, sdf_, rays_, n = _grid_inputs(rif, sdf, rays, dev, how)
+        rif_, sdf_, rays_, n = _grid_inputs(rif, sdf, rays, dev, how, planes)
         more_ = [_more_grid(g, rif_, dev) for g in more_grids]
         if fwd_steps is not None:
             steps_ = fwd_steps.detach().to(device=dev).contiguous()
@@ -620,19 +622,21 @@ def _like_grid(rif_, rays_) -> tuple:
 
 
 def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_out, dx, dv, seeds, wanted, rays: bool, h, ds,
-                        order) -> tuple:
-    """What ``backtrace_opl`` / ``backtrace_field`` / ``backtrace_emission`` share: one call of drrt_backtrace_<op>_f32 ->
+                        order, planes: int = 1) -> tuple:
+    """What ``backtrace_opl`` / ``backtrace_field`` / ``backtrace_emission`` / ``backtrace_vector`` share: one call of drrt_backtrace_<op>_f32 ->
     (the grid gradients in the order of `wanted`, dpos, dvel), None for what is not asked for.  `more`: the operator's
     further grids; `fwd_out`: (name, tensor) of the forward outputs the adjoint needs besides xt, vt and steps; `seeds`:
     the per-ray seeds behind dx, dv (None: zeros); `wanted`: per grid gradient (asked for, accumulator or None, the name of
     the accumulator's argument).  An accumulator means DRRT_FLAG_NO_ZERO, which covers every grid of the call: those asked
-    for without one are zeroed here."""
+    for without one are zeroed here.  `planes`: the operator's first further grid, and the gradient behind dL/drif, are that
+    many component planes of the grid's size (a vector field: 3)."""
     if not (rays or any(want for want, _, _ in wanted)):
         switches = [name.replace("into", "grid") for _, _, name in wanted] + ["rays"]
         raise RuntimeError(f"backtrace_{op}: nothing to compute ({' = '.join(switches)} = False)")
     dev = _dev(rif)
     with torch.cuda.device(dev):
-        rif_, first_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, more[0] if more else None, [pos, vel, xt, vt], dev)
+        rif_, first_, (pos_, vel_, xt_, vt_), n = _grid_inputs(rif, more[0] if more else None, [pos, vel, xt, vt], dev,
+                                                               planes=planes)
         more_ = ([first_] if more else []) + [_more_grid(g, rif_, dev) for g in more[1:]]
         steps_ = steps.detach().to(device=dev).contiguous()
         if steps_.dtype != torch.int32 or steps_.numel() != n:
@@ -647,15 +651,17 @@ def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_ou
                 raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
         no_zero = any(want and acc is not None for want, acc, _ in wanted)
         grads = []
-        for want, acc, name in wanted:
+        for k, (want, acc, name) in enumerate(wanted):
+            size = rif_.numel() * (planes if k == 1 else 1)
             if not want:
                 grads.append(None)
             elif acc is not None:
-                if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != rif_.numel() or acc.device != dev:
-                    raise RuntimeError(f"backtrace_{op}: `{name}` must be a contiguous fp32 tensor of the grid's size on its device")
+                if acc.dtype != torch.float32 or not acc.is_contiguous() or acc.numel() != size or acc.device != dev:
+                    what = "the grid's size" if size == rif_.numel() else f"{planes} planes of the grid's size"
+                    raise RuntimeError(f"backtrace_{op}: `{name}` must be a contiguous fp32 tensor of {what} on its device")
                 grads.append(acc.detach().view(-1))
             else:
-                grads.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
+                grads.append(rif_.new_zeros(size) if no_zero else rif_.new_empty(size))
         dpos, dvel = (torch.empty_like(pos_), torch.empty_like(vel_)) if rays else (None, None)
         with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
             _lib.check(getattr(_lib.load(), f"drrt_backtrace_{op}_f32")(
@@ -763,7 +769,40 @@ class TracerC:
         only."""
         return self._trace_emission(rif, emission, absorption, res, pos, vel, h, ds)[0]
 
+    def _trace_vector(self, rif, vfield, res, pos, vel, h, ds):
+        return _grid_call("drrt_trace_vector_f32", rif, res, [pos, vel], h, ds,
+                          lambda rif_, r: _like_rays(rif_, r) + (r[0].new_empty(r[0].shape[0]),
+                                                                 torch.empty(r[0].shape[0], dtype=torch.int32, device=r[0].device)),
+                          adjoint=False, sdf=vfield, steps=False, warn=True, planes=3)
+
+    def trace_vector(self, rif, vfield, res, pos, vel, h, ds):
+        """``trace`` with the line integral of a vector field projected on the ray's own direction, along every bent ray
+        (drrt_trace_vector_f32, include/drrt_hip.h; not in the reference) -> (xt, vt, circ, steps).  `vfield`: fp32 of shape
+        ``(3,) + rif.shape``, three component planes of `rif`'s shape and axis convention; plane c pairs with component c of
+        pos / vel (x, y, z).  xt, vt and the per-ray iteration counts `steps` (int32[n], a tensor of the caller's, not a
+        workspace view) are ``trace``'s bit for bit; ``circ = sum ds u_k . v_{k+1}`` over the samples the march takes inside
+        the box, u_k the field at the cell and weights of n_k and v_{k+1} the velocity behind the step, which carries the
+        ray from x_k to x_{k+1} (so this is ``sum u(x_k) . (x_{k+1} - x_k)``, the integral of u . dl along the path; for a
+        uniform u it telescopes to ``u . (xt - x_e)``).  fp32 rays only."""
+        return self._trace_vector(rif, vfield, res, pos, vel, h, ds)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_vector(self, rif, vfield, res, pos, vel, xt, vt, steps, dx, dv, dcirc, h, ds, grid: bool = True,
+                         vfield_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,
+                         vfield_into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_vector`` (drrt_backtrace_vector_f32, include/drrt_hip.h) -> (grad | None, grad_vfield | None,
+        dpos | None, dvel | None): flat dL/drif (fp32[nvox]) and dL/dvfield (fp32[3 nvox], the three planes as `vfield`),
+        dL/dpos and dL/dvel ((n,3) fp32) from ONE reverse march.  `pos`, `vel` are the forward call's inputs, `xt`, `vt`,
+        `steps` its outputs; `dx`, `dv` ((n,3)) and `dcirc` (n values) the seeds on (xt, vt, circ), each optional (None:
+        zeros).  `grid` / `vfield_grid` / `rays`: which outputs are computed (at least one); `into` (flat fp32[nvox]) /
+        `vfield_into` (flat fp32[3 nvox]): a tensor that gradient is ADDED to (DRRT_FLAG_NO_ZERO, which covers both: where
+        only one of the two is given, the other is zeroed here) and that is returned in its place.  Honours
+        ``options.corrected_h`` (with it dL/drif is the exact discrete derivative; dL/dvfield and the ray gradients are that
+        either way).  Rays that failed the forward get zeros and contribute nothing.  `order`: the forward's visit order."""
+        return _backtrace_integral("vector", rif, (vfield,), res, pos, vel, xt, vt, steps, (), dx, dv, (dcirc,),
+                                   ((grid, into, "into"), (vfield_grid, vfield_into, "vfield_into")), rays, h, ds, order,
+                                   planes=3)
+
     def backtrace_emission(self, rif, emission, absorption, res, pos, vel, xt, vt, steps, tau, dx, dv, drad, dtau, h, ds,
                            grid: bool = True, emission_grid: bool = True, absorption_grid: bool = True, rays: bool = True,
                            into: Optional[torch.Tensor] = None, emission_into: Optional[torch.Tensor] = None,

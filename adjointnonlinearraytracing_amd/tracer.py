@@ -315,15 +315,19 @@ class ADRayTargetTracerC(torch.autograd.Function):
 
 def _integral_forward(ctx, name, march, rif, fields, x, v, h, ds, keep=0):
     """The forward of the integral operators' classes -> (xt, vt, *integrals): `march` (``TracerC._trace_opl``, ...) on
-    `rif`, the further grids `fields` (((argument name, grid), ...), each of rif's shape) and the rays.  When any input
+    `rif`, the further grids `fields` (((argument name, grid), ...), each of rif's shape, or ((argument name, grid, lead),
+    ...) for a grid of shape ``lead + rif.shape``: the component planes of a vector field) and the rays.  When any input
     requires grad, what the ONE backward launch needs is kept: the options in effect now (autograd runs backward on a thread
     of its own), the visit order, private copies of (x, v), the iteration counts and, saved with the grids and the exit
     rays, the last `keep` integrals."""
     ctx.set_materialize_grads(False)
-    for fname, field in fields:
-        if field.shape != rif.shape:
-            raise RuntimeError(f"{name}: {fname} has shape {tuple(field.shape)}, rif {tuple(rif.shape)}")
-    ctx.shape, ctx.h, ctx.ds, ctx.n_fields = rif.shape, h, ds, len(fields)
+    leads = tuple(tuple(f[2]) if len(f) > 2 else () for f in fields)
+    fields = tuple((f[0], f[1]) for f in fields)
+    for (fname, field), lead in zip(fields, leads):
+        if tuple(field.shape) != lead + tuple(rif.shape):
+            want = f"rif {tuple(rif.shape)}" if not lead else f"rif {tuple(rif.shape)} behind {lead}"
+            raise RuntimeError(f"{name}: {fname} has shape {tuple(field.shape)}, {want}")
+    ctx.shape, ctx.h, ctx.ds, ctx.n_fields, ctx.leads = rif.shape, h, ds, len(fields), ((),) + leads
     _ray_grad_wanted(ctx, name, 1 + len(fields), 2 + len(fields), x, v)
     (xt, vt, *integrals, steps), order, _ = march(rif.detach().flatten(), *(f.detach().flatten() for _, f in fields),
                                                   ctx.shape, x.detach(), v.detach(), h, ds)
@@ -350,7 +354,8 @@ def _integral_backward(ctx, back, grad_x, grad_v, *seeds):
                                   grad_v, *seeds, ctx.h, ctx.ds, *want_grids, want_rays, order=ctx.order)
     dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[1 + k] else None
     dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[2 + k] else None
-    return (*(g.reshape(*ctx.shape) if want else None for g, want in zip(grads, want_grids)), dx0, dv0)
+    return (*(g.reshape(*lead, *ctx.shape) if want else None for g, want, lead in zip(grads, want_grids, ctx.leads)),
+            dx0, dv0)
 
 
 class OPLTracerC(torch.autograd.Function):
@@ -428,6 +433,34 @@ class EmissionTracerC(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_rad, grad_tau):
         return (*_integral_backward(ctx, drrt.TracerC().backtrace_emission, grad_x, grad_v, grad_rad, grad_tau), None, None)
+
+
+class VectorIntegralTracerC(torch.autograd.Function):
+    """``apply(rif, vfield, x, v, h, ds) -> (xt, vt, circ)``: ``trace`` with the line integral ``circ = int u . dl`` of a
+    vector field ``u`` projected on the ray's own direction (``vfield``: a flow velocity, n_e B; shape ``(3,) + rif.shape``,
+    component planes of ``rif``'s shape, plane c pairing with component c of x / v) along every bent ray:
+    ``circ = sum ds u_k . v_{k+1}`` over the samples inside the box, v_{k+1} the velocity that carries the ray from x_k to
+    x_{k+1}.  All three outputs are differentiable w.r.t. ``rif``, ``vfield``, ``x`` and ``v``; ``vfield.grad`` has
+    ``vfield``'s shape.  Not in the reference.
+
+    The forward is ``TracerC.trace_vector``; backward is ONE ``TracerC.backtrace_vector`` launch (plus one zero-fill per
+    gradient plane asked for: one for ``rif``, three for ``vfield``), which returns dL/drif, dL/dvfield and the ray gradients
+    from the same reverse march and computes only what is asked for.  Like OPLTracerC this adjoint replays the forward's
+    iteration count: with ``drrt.options.corrected_h`` its dL/drif is the exact discrete derivative; dL/dvfield and the ray
+    gradients are that either way.  ``sort_rays`` and ``pair_grid`` are honoured as in ADTracerC; the options in effect at
+    the forward (``drrt.options``, or the calling thread's ``drrt.using(...)`` block) are kept and applied to the backward
+    launch, which autograd runs on a thread of its own.  Private copies of (x, v) and the iteration counts are kept whenever
+    any input requires grad.  Rays that failed the forward get zero gradients.  fp32 rays only when ray gradients are asked
+    for."""
+
+    @staticmethod
+    def forward(ctx, rif, vfield, x, v, h, ds):
+        return _integral_forward(ctx, "VectorIntegralTracerC", drrt.TracerC()._trace_vector, rif,
+                                 (("vfield", vfield, (3,)),), x, v, h, ds)
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_circ):
+        return (*_integral_backward(ctx, drrt.TracerC().backtrace_vector, grad_x, grad_v, grad_circ), None, None)
 
 
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken

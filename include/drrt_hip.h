@@ -471,6 +471,62 @@ DRRT_API int drrt_backtrace_emission_f32(const float* rif, const float* emission
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- line integral of a vector field along the bent ray (not in the reference) --------------------------------------------
+ * circ = int u . dl of a vector field u projected on the ray's own direction -- a flow velocity (Doppler and time-of-flight
+ * flow tomography), n_e B (Faraday rotation) -- along the ray that n bends.  `vfield` is 3 nvox fp32: three component planes
+ * of exactly rif's shape and axis convention, plane c at vfield + c nvox, and plane c = 0, 1, 2 pairs with component c of
+ * pos / vel (x, y, z).  drrt_trace_vector_f32 is drrt_trace_f32 (xt, vt and the per-ray iteration counts K bit for bit)
+ * that also returns
+ *   circ = sum_{k<K} ds (u_k . v_{k+1})  =  sum_k u(x_k) . (x_{k+1} - x_k)
+ * u_k the trilinear sample of the three planes at the cell the march samples at x_k anyway, with the same weights and the
+ * same mask (0 while the ray is not inside the box: free flight adds nothing), and v_{k+1} the velocity behind the update
+ * from sample k, the one that carries the ray from x_k to x_{k+1}; accumulated in fp32 in iteration order from 0 as
+ * t = ux vx; t = fmaf(uy, vy, t); t = fmaf(uz, vz, t); circ = fmaf(ds, t, circ).  The sum telescopes: for a uniform u,
+ * circ = u . (xt - x_e) with x_e the first in-box sample.  A failed ray returns what it accumulated; a ray that never
+ * samples inside returns circ = 0.
+ *   circ       out: fp32[n]
+ *   steps_out  out: uint32[n], required: K per ray, caller ray order (what the adjoint takes as fwd_steps).  The call
+ *              leaves no drrt_last_steps().
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE (the pair copy is of rif; the three planes are gathered as
+ * they are), DRRT_FLAG_DISPATCH_IN_ORDER as for drrt_trace_f32.  fp32 only. */
+DRRT_API int drrt_trace_vector_f32(const float* rif, const float* vfield, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds,
+                       float* xt, float* vt, float* circ, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_vector_f32: from the seeds dx = dL/dxt, dv = dL/dvt, dcirc = dL/dcirc (each nullable: read as zeros)
+ * ONE reverse march yields dL/drif (grad), dL/du (grad_vfield, three planes laid out as vfield), dL/dpos and dL/dvel.  The
+ * march is drrt_backtrace_field_f32's, unchanged in structure (failed rays get zeros, contribute nothing and count in
+ * stats->n_failed; never-entered rays get (dx, dv) and contribute nothing).  The summand of sample k holds v_{k+1}, the
+ * velocity the reverse march arrives with, so each reverse iteration first samples the three planes (u_k, grad u_k scaled
+ * by 1 / h like grad n_k) at the cell of x_k and, with g = dcirc ds, adds  g u_k  to mu -- the seed on v_{k+1} -- BEFORE
+ * dn = mu . grad n_k is formed and keeps  w = g v_{k+1};  then it samples rif, and adds, with mu before its update, at the
+ * 8 taps of the sampled cell
+ *   to grad:                   splat_weights(w, dn ds, (n_k ds grad_scale) mu),  grad_scale = 1 / h with
+ *                              DRRT_FLAG_CORRECTED_H and 1 without, as for drrt_backtrace_f32 (Q3);
+ *   to plane c of grad_vfield: the value weights alone, w_c-weights of w[c]: circ is linear in u, so there is no gradient
+ *                              splat and grad_scale does not enter;
+ * and adds  (grad u_k)^T w  to lambda before the recurrences -- the pull of the field's gradient on the sample position.
+ * With DRRT_FLAG_CORRECTED_H all outputs are the exact derivative of the discrete forward; grad_vfield, dpos and dvel are
+ * that with either setting.
+ *   grad         out, nullable (no scatter into dL/drif): fp32[nvox]
+ *   grad_vfield  out, nullable (no scatter into dL/du): fp32[3 nvox]; both are zeroed by the call unless DRRT_FLAG_NO_ZERO
+ *   dpos, dvel   out, both or neither: (n,3) fp32.  All four outputs null: DRRT_ERR_ARG
+ * The scatter is one global fp32 atomic per tap, per grid and per run of samples in one cell, as for
+ * drrt_backtrace_field_f32: no LDS window, so a call pays the memory-side atomic rate once per plane it scatters into
+ * (three for grad_vfield, four with grad).
+ * Flags: DRRT_FLAG_SORT_RAYS, DRRT_FLAG_PAIR_GRID / _PAIR_REUSE, DRRT_FLAG_DISPATCH_IN_ORDER, DRRT_FLAG_CORRECTED_H,
+ * DRRT_FLAG_NO_ZERO; other adjoint flags are ignored.  The order hint is consumed, the step hint ignored.  fp32 only.      */
+DRRT_API int drrt_backtrace_vector_f32(const float* rif, const float* vfield, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, const float* dcirc, float h, float ds,
+                       float* grad, float* grad_vfield, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -754,6 +810,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_FIELD 14 /* its adjoint: dL/dn, dL/dfield and the ray gradients in one march (drrt_backtrace_field_f32) */
 #define DRRT_PROF_TRACE_EMISSION 15  /* trace with the emission integral of two further fields (drrt_trace_emission_f32) */
 #define DRRT_PROF_BACKTRACE_EMISSION 16 /* its adjoint: dL/dn, dL/de, dL/da and the ray gradients in one march (drrt_backtrace_emission_f32) */
+#define DRRT_PROF_TRACE_VECTOR 17    /* trace with the line integral of a vector field (drrt_trace_vector_f32) */
+#define DRRT_PROF_BACKTRACE_VECTOR 18 /* its adjoint: dL/dn, dL/du and the ray gradients in one march (drrt_backtrace_vector_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

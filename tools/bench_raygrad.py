@@ -94,6 +94,20 @@ emission  drrt_trace_emission_f32 / drrt_backtrace_emission_f32 (k_trace_emissio
         usage: bench_raygrad.py emission [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
         Also writes the JSON, with the library's version string (source digest), to --out (default profiles/emission_bench.json).
 
+vector  drrt_trace_vector_f32 / drrt_backtrace_vector_f32 (k_trace_vector, k_backtrace_vector) next to the field and emission
+        calls, on the workloads of `field`; the vector field is three planes U - 0.5 (seeded), the second fields those of
+        `emission`.  All adjoints take the forward's visit order, unit seeds on every output:
+            trace_field, trace_emission, backtrace_field (dL/da), backtrace_emission (all three grids)   as in `emission`
+            trace_vector             TracerC.trace_vector
+            backtrace_vector_rif     TracerC.backtrace_vector(vfield_grid=False)              (dL/dn)
+            backtrace_vector_u       TracerC.backtrace_vector(grid=False)                     (the three planes of dL/du)
+            backtrace_vector_both    TracerC.backtrace_vector                                 (all four planes)
+            backtrace_vector_rays    TracerC.backtrace_vector(grid=False, vfield_grid=False)  (dpos, dvel alone)
+        Timed alternately like `field`.  Output per medium and call: median, minimum, maximum ms and stats.ray_steps, and the
+        ratios trace_vector / trace_emission, trace_vector / trace_field and backtrace_vector_* / backtrace_field.
+        usage: bench_raygrad.py vector [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string (source digest), to --out (default profiles/vector_bench.json).
+
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
 over the rounds, the iteration counts (stats.ray_steps), and the ratio of the new call to the sum of the two existing
@@ -481,6 +495,54 @@ def emission(a, dev):
     return out
 
 
+def vector(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl`, `field` and `emission`
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
+    gen = lambda seed, *lead: torch.rand(lead + (a.grid,) * 3, generator=torch.Generator(device="cpu").manual_seed(seed))   # noqa: E731
+    emis, unit = (1.0 + 0.5 * gen(2)).to(dev), (1.0 + 0.5 * gen(3)).to(dev)
+    vf = (gen(4, 3) - 0.5).to(dev)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for medium, make in (("luneburg", bench.make_grid), ("tomo_weak", bench.make_grid_tomo)):
+        rif = make(a.grid, dev)
+        res = tuple(rif.shape)
+        absb = unit / float(T.trace_field(rif, unit, res, pos, vel, h, ds)[2].median())      # median tau = 1
+        tau = T.trace_emission(rif, emis, absb, res, pos, vel, h, ds)[3]
+        xt, vt, _, steps = T.trace_vector(rif, vf, res, pos, vel, h, ds)
+        order = drrt.keep_order(drrt.last_order)
+        back = lambda **kw: T.backtrace_vector(rif, vf, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order, **kw)   # noqa: E731
+        r, med = time_each({
+            "trace_field": lambda: T.trace_field(rif, absb, res, pos, vel, h, ds),
+            "trace_emission": lambda: T.trace_emission(rif, emis, absb, res, pos, vel, h, ds),
+            "trace_vector": lambda: T.trace_vector(rif, vf, res, pos, vel, h, ds),
+            "backtrace_field": lambda: T.backtrace_field(rif, absb, res, pos, vel, xt, vt, steps, one, one, g, h, ds, grid=False,
+                                                         order=order),
+            "backtrace_emission": lambda: T.backtrace_emission(rif, emis, absb, res, pos, vel, xt, vt, steps, tau, one, one, g, g,
+                                                               h, ds, order=order),
+            "backtrace_vector_rif": lambda: back(vfield_grid=False),
+            "backtrace_vector_u": lambda: back(grid=False),
+            "backtrace_vector_both": back,
+            "backtrace_vector_rays": lambda: back(grid=False, vfield_grid=False),
+        }, a)
+        if r is None:
+            continue
+        r["trace_vector_over_trace_emission"] = med["trace_vector"] / med["trace_emission"]
+        r["trace_vector_over_trace_field"] = med["trace_vector"] / med["trace_field"]
+        for k in ("rif", "u", "both", "rays"):
+            r[f"backtrace_vector_{k}_over_backtrace_field"] = med[f"backtrace_vector_{k}"] / med["backtrace_field"]
+        r["backtrace_emission_over_backtrace_field"] = med["backtrace_emission"] / med["backtrace_field"]
+        out[medium] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -518,14 +580,19 @@ def main():
     p_emis.add_argument("--rays", type=int, default=1 << 20)
     p_emis.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "emission_bench.json"))
     p_emis.set_defaults(run=emission)
-    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis):
+    p_vec = sub.add_parser("vector")
+    p_vec.add_argument("--grid", type=int, default=256)
+    p_vec.add_argument("--rays", type=int, default=1 << 20)
+    p_vec.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "vector_bench.json"))
+    p_vec.set_defaults(run=vector)
+    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis, p_vec):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target", "opl", "field", "emission") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl", "field", "emission", "vector") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
