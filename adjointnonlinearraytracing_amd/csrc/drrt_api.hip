@@ -1,8 +1,9 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip / drrt_cable_rays.hip.  Host code, plus the four small
-// utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip / drrt_cable_rays.hip /
+// drrt_cable_opl.hip.  Host code, plus the four small utility kernels that belong to no march (pair copy of the grid, q16
+// encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
 
@@ -928,7 +929,7 @@ extern "C" int drrt_backtrace_sdf_f32(const float* rif, const float* sdf, long l
   return run_backtrace<1>(rif, sdf, nvox, res, n, xt, vt, dx, dv, h, ds, grad, stats, ws, ws_bytes, flags, stream);
 }
 
-// ---- the prologue the three cable entries share, in their common order: the hint (taken, never honoured: the cable kernels
+// ---- the prologue the five cable entries share, in their common order: the hint (taken, never honoured: the cable kernels
 // visit rays in caller order), the profile and step checks, the adjoint's zero fill of `zero_grad` (nullable), the stats,
 // and the head of the argument block.  `null_msg` (nullable) is the entry's complaint about its own grid pointers.
 template <class Args>
@@ -994,4 +995,41 @@ extern "C" int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, floa
   if (!dpos || !dvel) return fail(DRRT_ERR_ARG, "null dpos/dvel pointer");
   a.pos = pos; a.vel = vel; a.target = target; a.dx = dx; a.dv = dv; a.dpos = dpos; a.dvel = dvel;
   return timed_launch(DRRT_PROF_BACKTRACE_CABLE_RAYS, s, "k_backtrace_cable_rays", [&] { launch_backtrace_cable_rays(a, s); });
+}
+
+extern "C" int drrt_trace_cable_opl_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                                        const float* pos, const float* vel, const float* target, float ds,
+                                        float* xt, float* vt, float* dist2, float* opl, uint32_t* rec_steps,
+                                        drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  (void)ws; (void)ws_bytes; (void)flags;
+  hipStream_t s = (hipStream_t)stream;
+  CableOplTraceArgs a{};
+  const int rc = cable_begin(a, rif ? nullptr : "null rif pointer", rif, rres, radius, length, ds, nullptr, stats, n, s);
+  g_ts.reset_last_steps();              // rec_steps is the caller's: no iteration counts are left in the workspace
+  if (rc || n == 0) return rc;
+  if (!pos || !vel || !target || !xt || !vt || !dist2) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!opl || !rec_steps) return fail(DRRT_ERR_ARG, "null opl/rec_steps pointer");
+  a.pos = pos; a.vel = vel; a.target = target; a.xt = xt; a.vt = vt; a.dist2 = dist2; a.opl = opl; a.rec_steps = rec_steps;
+  return timed_launch(DRRT_PROF_TRACE_CABLE_OPL, s, "k_trace_cable_opl", [&] { launch_trace_cable_opl(a, s); });
+}
+
+extern "C" int drrt_backtrace_cable_opl_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                                            const float* pos, const float* xt, const float* vt, const uint32_t* rec_steps,
+                                            const float* dx, const float* dv, const float* dopl, float ds, float* grad,
+                                            float* dpos, float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes,
+                                            unsigned flags, void* stream) {
+  (void)ws; (void)ws_bytes;
+  hipStream_t s = (hipStream_t)stream;
+  CableOplBackArgs a{};
+  const char* refusal = !rif ? "null rif pointer"
+                      : !(grad || dpos || dvel) ? "nothing to compute: grad, dpos and dvel are all null"
+                      : !dpos != !dvel ? "dpos and dvel go together" : nullptr;
+  const int rc = cable_begin(a, refusal, rif, rres, radius, length, ds, (flags & DRRT_FLAG_NO_ZERO) ? nullptr : grad, stats,
+                             n, s);
+  if (rc || n == 0) return rc;
+  if (!pos || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!rec_steps) return fail(DRRT_ERR_ARG, "null rec_steps pointer (the forward's rec_steps)");
+  a.pos = pos; a.xt = xt; a.vt = vt; a.rec_steps = rec_steps; a.dx = dx; a.dv = dv; a.dopl = dopl;
+  a.grad = grad; a.dpos = dpos; a.dvel = dvel;
+  return timed_launch(DRRT_PROF_BACKTRACE_CABLE_OPL, s, "k_backtrace_cable_opl", [&] { launch_backtrace_cable_opl(a, s); });
 }

@@ -1332,6 +1332,90 @@ DRRT_HD RayGrad cable_backtrace_ray_state(const Cyl& C, float ds, int max_steps,
   return g;
 }
 
+// n at (px, pz) as cable_fwd_step samples it (its `f`): the same operations on the same operands, so a caller that
+// evaluates it in front of cable_fwd_step gets the step's own value (the compiler merges the two).
+DRRT_HD float cable_sample_n(const Cyl& C, float px, float pz) {
+  const CylCell c = cyl_locate(C, px, pz);
+  const float v0 = C.data[c.i0], v1 = C.data[c.i1];
+  return fmaf(v1, c.w0, v0 * (1.f - c.w0));                               // :53
+}
+
+// trace_cable for ONE ray, with the optical path length up to its record and the record's iteration.  The loop is
+// cable_trace_ray's, so (xt, vt, dist2, esc, steps) are its bit for bit.  acc = fmaf(ds n_k, n_k, acc) from 0.f in iteration
+// order (OplIntegrand's sequence), n_k the step's own sample at x_k, unmasked like it; `opl` and `j` are latched whenever
+// the record is updated: opl = sum_{k<j} ds n_k^2, j = the iteration count at the last update (0: the record is the input,
+// opl = 0.f).  It is the integral of n along the path when the rays enter with |v| = n.
+DRRT_HD RayOut cable_trace_opl_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
+                                   const float tg[3], float& opl, unsigned& j) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.xtx = s.x; s.xty = s.y; s.xtz = s.z; s.vtx = s.vx; s.vty = s.vy; s.vtz = s.vz;
+  s.aux0 = tg[0]; s.aux1 = tg[1]; s.aux2 = tg[2]; s.aux4 = s.aux5 = 0.f;
+  float ex = s.x - tg[0], ey = s.y - tg[1], ez = s.z - tg[2];
+  s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
+  s.inside = cyl_inbounds(C, s.x, s.y, s.z);                              // :344
+  s.esc = false;
+  unsigned steps = 0;
+  float acc = 0.f;
+  opl = 0.f; j = 0;
+  for (int it = 0; it < max_steps; ++it) {
+    const float best = s.aux3;
+    const float n = cable_sample_n(C, s.x, s.z);
+    acc = fmaf(ds * n, n, acc);
+    cable_fwd_step(C, ds, s);
+    ++steps;
+    if (s.aux3 < best) { opl = acc; j = steps; }                          // the record was updated (strict <, :365)
+    if (s.esc) break;
+  }
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = s.aux3; o.esc = s.esc; o.act = !s.esc; o.steps = steps;
+  return o;
+}
+
+// Adjoint of cable_trace_opl_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/d(profile) from the seeds
+// (dx, dv, dopl) on (xt, vt, opl), given the forward's input position p0, its record (xt, vt) and the record's iteration j.
+// No replay: j reverse iterations from (xt, vt), run as cable_backtrace_ray_state runs them (lambda = dx, mu = dv + ds dx,
+// no escape test, the last sample at p0 itself), with dn = mu . grad n_k + 2 dopl n_k where that routine has
+// mu . grad n_k; every iteration emits cable_adj_step's two profile contributions through sink(i0, i1, a0, a1).  j is held
+// fixed.  j = 0: (dx, dv), no contribution.  j comes from caller memory and is the ONLY loop bound, so a j above
+// max_steps (the forward's own bound: no forward call returns one) does no iterations: zero gradients, failed = true.
+template <typename Sink>
+DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, const float p0[3], const float xt[3],
+                                        const float vt[3], unsigned j, const float dx[3], const float dv[3], float dopl,
+                                        Sink&& sink) {
+  RayGrad g;
+  g.failed = max_steps < 0 || j > (unsigned)max_steps;
+  g.steps = g.failed ? 0u : j;
+  if (g.failed) {
+    g.dp[0] = g.dp[1] = g.dp[2] = 0.f; g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                               // :536
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);  // :537
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  const float dopl2 = 2.f * dopl;
+  for (unsigned k = j; k > 0; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :547
+    if (k == 1u) { s.x = p0[0]; s.y = p0[1]; s.z = p0[2]; }              // the forward's first sample, as it took it
+    const CylAdjSample m = cable_adj_sample(C, ds, s);
+    const CylCell& c = m.c;
+    const float dn = fmaf(dopl2, m.n, fmaf(s.mz, m.gz, s.mx * m.gx));     // :557, plus d(ds n^2)/dn / ds
+    // cylinder_volume::splat (:113-148) as cable_adj_step forms it
+    const float val = dn * ds;
+    const float gv = (m.n * ds) * fmaf(s.mz, c.rhz, s.mx * c.rhx);
+    const float gvh = gv * C.inv_h;
+    sink(c.i0, c.i1, fmaf(val, 1.f - c.w0, -gvh), fmaf(val, c.w0, gvh));
+    qx = s.mx; qy = s.my; qz = s.mz;
+    cable_adj_recur(ds, s, m, dn);
+  }
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  return g;
+}
+
 // Ray-state adjoint of trace_plane (MODE 1) / trace_sdf (MODE 2) for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on
 // the record (xt, vt) = (x_j, v_j), given only the forward's inputs (p0, v0) and its plane / SDF.  j = the iteration count at
 // the LAST cross (fwd_step_c :378-386), 0 when there was none (the record is the input).  Iteration k samples n grad n at x_k

@@ -21,6 +21,7 @@
 //                           backtrace_rays shares
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
+//   drrt_cable_opl.hip      trace_cable_opl, backtrace_cable_opl: the cable march with its optical path length, one adjoint
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
 // The operators before and after the march do not include this header; they share drrt_host.h (error slot, 1-D launch):
 //   drrt_source.hip         ray generation                                       (core/source.py)
@@ -680,6 +681,26 @@ struct CableRayGradArgs {
   size_t n;
 };
 
+// trace_cable with the optical path length up to the record, and its adjoint (drrt_cable_opl.hip)
+struct CableOplTraceArgs {
+  const float* rif; int rres; float radius, length, ds; int max_steps;
+  const float* pos; const float* vel; const float* target;
+  float* xt; float* vt; float* dist2; float* opl; uint32_t* rec_steps;
+  drrt_stats* stats;
+  size_t n;
+};
+
+struct CableOplBackArgs {
+  const float* rif; int rres; float radius, length, ds; int max_steps;   // max_steps: the FORWARD's, bounds rec_steps
+  const float* pos;                                            // the forward's input positions
+  const float* xt; const float* vt; const uint32_t* rec_steps; // its record and the record's iteration
+  const float* dx; const float* dv; const float* dopl;         // nullable: seeds on (xt, vt, opl), read as zeros
+  float* grad;                                                 // PROFILE kernels only
+  float* dpos; float* dvel;                                    // RAYS kernels only
+  drrt_stats* stats;
+  size_t n;
+};
+
 __device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_tot, unsigned steps_max, unsigned fail_tot) {
   if (!stats) return;
   unsigned wm = wave_max_u32(steps_max), ws = wave_sum_u32(steps_tot), wf = wave_sum_u32(fail_tot);
@@ -687,6 +708,45 @@ __device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_to
     if (wm) atomicMax(&stats->iters, wm);
     if (ws) atomicAdd(&stats->ray_steps, (unsigned long long)ws);
     if (wf) atomicAdd(&stats->n_failed, (unsigned long long)wf);
+  }
+}
+
+// One iteration's two contributions to dL/d(profile), shared by the cable adjoints (k_backtrace_cable, k_backtrace_cable_opl):
+// into the block's f64 LDS accumulators `s_grad` (use_lds), or straight into `gacc` for a profile above kCableMaxRes.
+__device__ __forceinline__ void cable_grad_add(double* s_grad, float* gacc, bool use_lds, int i0, int i1, float a0, float a1) {
+  if (use_lds) {
+    // Rays in source-pixel order sit at nearly the same radius as their neighbours: lanes of a pair / quad
+    // then hit the same two bins, and a pair / quad pre-reduction (as in shift_emit4) halves the time.  For
+    // rays in random order it would only cost instructions, so it runs when at least a quarter of the wave's
+    // lanes have a matching partner (wave-uniform decision).
+    const int key = i0 | (i1 << 16);
+    const int k1 = __builtin_amdgcn_update_dpp(-1, key, 0xB1, 0xF, 0xF, false);
+    const bool psame = k1 == key;
+    if (__popcll(__ballot(psame)) >= 16) {
+      const int k2 = __builtin_amdgcn_update_dpp(-1, key, 0x4E, 0xF, 0xF, false);
+      const int k3 = __builtin_amdgcn_update_dpp(-1, key, 0x1B, 0xF, 0xF, false);
+      const bool same = psame & (k2 == key) & (k3 == key);
+      const float p0 = a0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a0), 0xB1, 0xF, 0xF, false));
+      const float p1 = a1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, a1), 0xB1, 0xF, 0xF, false));
+      const float s0 = p0 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p0), 0x4E, 0xF, 0xF, false));
+      const float s1 = p1 + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, p1), 0x4E, 0xF, 0xF, false));
+      const unsigned ql = threadIdx.x & 3u;
+      if (same ? ql == 0u : (psame ? (ql & 1u) == 0u : true)) {
+        atomicAdd(&s_grad[i0], (double)(same ? s0 : (psame ? p0 : a0)));                   // ds_add_f64
+        atomicAdd(&s_grad[i1], (double)(same ? s1 : (psame ? p1 : a1)));
+      }
+    } else {
+      atomicAdd(&s_grad[i0], (double)a0); atomicAdd(&s_grad[i1], (double)a1);
+    }
+  } else { atomic_add_f32(&gacc[i0], a0); atomic_add_f32(&gacc[i1], a1); }
+}
+
+// ... and the block's flush of those accumulators into `grad` (after every lane of the block is done adding)
+__device__ __forceinline__ void cable_grad_flush(const double* s_grad, float* grad, int rres) {
+  __syncthreads();
+  for (int k = threadIdx.x; k < rres; k += kBlock) {
+    double g = s_grad[k];
+    if (g != 0.0) atomic_add_f32(&grad[k], (float)g);
   }
 }
 
@@ -728,5 +788,9 @@ void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);
 // ray-state adjoint of the cable march (drrt_cable_rays.hip)
 void launch_backtrace_cable_rays(const CableRayGradArgs& a, hipStream_t s);
+// the cable march with its optical path length, and its adjoint: grad and/or (dpos, dvel), whichever are non-null
+// (drrt_cable_opl.hip)
+void launch_trace_cable_opl(const CableOplTraceArgs& a, hipStream_t s);
+void launch_backtrace_cable_opl(const CableOplBackArgs& a, hipStream_t s);
 
 }  // namespace drrt

@@ -939,6 +939,60 @@ class TracerC:
         return _cable_call("drrt_backtrace_cable_rays_f32", rif, radius, length, ds, (pos, vel, target, dx, dv),
                            lambda rif_, r: (torch.empty_like(r), torch.empty_like(r)))
 
+    def trace_cable_opl(self, rif, radius, length, pos, vel, target, ds):
+        """``trace_cable`` with the optical path length of every ray up to its record (drrt_trace_cable_opl_f32,
+        include/drrt_hip.h; not in the reference) -> (xt, vt, dist2, opl, rec_steps): xt, vt and dist2 are ``trace_cable``'s
+        bit for bit; ``opl = sum ds n_k^2`` over the iterations in front of the closest-approach record (the integral of n
+        along the path -- the transit time -- when the rays enter with |v| = n; rays scaled otherwise get the same sum, not
+        that integral); `rec_steps` (int32[n]) is the record's iteration, which ``backtrace_cable_opl`` takes.  fp32 rays
+        only."""
+        return _cable_call("drrt_trace_cable_opl_f32", rif, radius, length, ds, (pos, vel, target),
+                           lambda rif_, r: (torch.empty_like(r), torch.empty_like(r), r.new_empty(r.shape[0]),
+                                            r.new_empty(r.shape[0]),
+                                            torch.empty(r.shape[0], dtype=torch.int32, device=r.device)), warn=True)
+
+    def backtrace_cable_opl(self, rif, radius, length, pos, xt, vt, rec_steps, dx, dv, dopl, ds, profile: bool = True,
+                            rays: bool = True, into: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_cable_opl`` (drrt_backtrace_cable_opl_f32, include/drrt_hip.h) -> (grad | None, dpos | None,
+        dvel | None): dL/d(profile) (fp32[rres]), dL/dpos and dL/dvel ((n,3) fp32) from ONE reverse march that replays
+        nothing.  `pos` is the forward call's input, `xt`, `vt`, `rec_steps` its outputs; `dx`, `dv` ((n,3)) and `dopl` (n
+        values) the seeds on (xt, vt, opl), each optional (None: zeros); a seed on dist2 does not enter and nothing flows to
+        the target.  `profile` / `rays`: which outputs are computed (at least one); `into`: a flat fp32[rres] tensor the
+        profile gradient is ADDED to (DRRT_FLAG_NO_ZERO) and that is returned as grad.  The record's iteration is held
+        fixed.  A ray whose `rec_steps` exceeds the forward's step bound gets zero gradients and the "failed to exit all
+        rays" message."""
+        if not (profile or rays):
+            raise RuntimeError("backtrace_cable_opl: nothing to compute (profile = rays = False)")
+        dev = _dev(rif)
+        with torch.cuda.device(dev):
+            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
+            n = pos_.shape[0]
+            xt_, vt_ = _rays(xt, dev, n), _rays(vt, dev, n)
+            rec_ = rec_steps.detach().to(device=dev).contiguous()
+            if rec_.dtype != torch.int32 or rec_.numel() != n:
+                raise RuntimeError(f"rec_steps must be {n} int32 record iterations of the forward call (trace_cable_opl's)")
+            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+            dopl_ = None if dopl is None else _f32(dopl, dev).reshape(-1)
+            if dopl_ is not None and dopl_.numel() != n:
+                raise RuntimeError(f"expected {n} per-ray values, got {dopl_.numel()}")
+            grad = None
+            if profile and into is not None:
+                if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != rif_.numel() or into.device != dev:
+                    raise RuntimeError("backtrace_cable_opl: `into` must be a contiguous fp32 tensor of the profile's size on "
+                                       "its device")
+                grad = into.detach().view(-1)
+            elif profile:
+                grad = torch.empty_like(rif_)
+            # never a null pointer (n = 0): null dpos / dvel means "not asked for"
+            dpos, dvel = (pos_.new_empty((max(n, 1), 3)), pos_.new_empty((max(n, 1), 3))) if rays else (None, None)
+            ws, st = _workspace(n, 0, dev), _new_stats(dev)
+            _lib.check(_lib.load().drrt_backtrace_cable_opl_f32(
+                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(xt_), _p(vt_), _p(rec_), _p(dx_), _p(dv_),
+                _p(dopl_), float(ds), _p(grad), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(),
+                _lib.FLAG_NO_ZERO if profile and into is not None else 0, _stream(dev)))
+            _warn_failed(st)
+        return (grad, dpos[:n], dvel[:n]) if rays else (grad, None, None)
+
     def backtrace_pln_rays(self, rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds,
                            order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
         """Ray-state adjoint of ``trace_pln`` (drrt_backtrace_pln_rays_f32, include/drrt_hip.h) -> (dL/dpos, dL/dvel),

@@ -463,6 +463,50 @@ class VectorIntegralTracerC(torch.autograd.Function):
         return (*_integral_backward(ctx, drrt.TracerC().backtrace_vector, grad_x, grad_v, grad_circ), None, None)
 
 
+class CableOPLTracerC(torch.autograd.Function):
+    """``apply(rif (Rr,), radius, length, x, v, sp, ds) -> (xt, vt, dist2, opl)``: the fibre march with the optical path
+    length ``opl = sum ds n_k^2`` of every ray up to its closest-approach record; xt, vt and opl are differentiable w.r.t.
+    ``rif``, ``x`` and ``v``.  opl is the integral of n along the path (the transit time) when the rays enter with
+    |v| = n; rays scaled otherwise (examples/fiber_demo.py divides by the boundary index) get the same sum, which is not
+    that integral.  Not in the reference.
+
+    The forward is ``TracerC.trace_cable_opl``, which also returns the iteration of every record; backward is ONE
+    ``TracerC.backtrace_cable_opl`` launch (plus the zero-fill of the profile gradient when ``rif`` requires grad) that
+    replays nothing, returns dL/drif and the ray gradients from the same reverse march and computes only what is asked
+    for.  Unlike BackCableTracerC / ADCableTracerC, whose dL/drif is the reference's ``backtrace_cable`` (the continuous
+    adjoint with a backward-escape test and a step bound), this is the derivative of the discrete forward with the
+    record's iteration held fixed.  ``dist2`` is not differentiable and ``sp`` gets no gradient.  A private copy of x and
+    the record iterations are kept whenever any input requires grad.  fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, radius, length, x, v, sp, ds):
+        ctx.set_materialize_grads(False)
+        ctx.radius, ctx.length, ctx.ds = radius, length, ds
+        _ray_grad_wanted(ctx, "CableOPLTracerC", 3, 4, x, v)
+        xt, vt, dist2, opl, rec = drrt.TracerC().trace_cable_opl(rif.detach().flatten(), radius, length, x.detach(),
+                                                                 v.detach(), sp.detach(), ds)
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
+            ctx.ray_devices = (x.device, v.device)
+            # the adjoint replays nothing: of the forward's ray inputs it takes x alone (a private copy, as _keep_rays makes)
+            ctx.rays = (x.detach().to(device=xt.device, dtype=torch.float32).clone(), rec)
+            ctx.save_for_backward(rif, xt, vt)
+        ctx.mark_non_differentiable(dist2)
+        return xt, vt, dist2, opl
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_dist2, grad_opl):
+        want_rif, want_rays = ctx.needs_input_grad[0], ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
+        if not (want_rif or want_rays):
+            return (None,) * 7
+        rif, xt, vt = ctx.saved_tensors
+        x0, rec = ctx.rays
+        grad, dpos, dvel = drrt.TracerC().backtrace_cable_opl(rif.detach().flatten(), ctx.radius, ctx.length, x0, xt, vt, rec,
+                                                              grad_x, grad_v, grad_opl, ctx.ds, want_rif, want_rays)
+        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[3] else None
+        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[4] else None
+        return grad.reshape(rif.shape) if want_rif else None, None, None, dx0, dv0, None, None
+
+
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken
 # upstream, SURVEY Q15) resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working,
 # with the documented difference that no gradient flows to x, v through THESE names.  The classes with ray gradients are

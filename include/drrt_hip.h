@@ -598,6 +598,41 @@ DRRT_API int drrt_backtrace_cable_rays_f32(const float* rif, size_t rres, float 
                              drrt_stats* stats, void* workspace, size_t workspace_bytes,
                              unsigned flags, void* stream);
 
+/* drrt_trace_cable_f32 with the optical path length of every ray up to its record, and the record's iteration (not in
+ * the reference).  xt, vt, dist2 and the statistics are drrt_trace_cable_f32's bit for bit.
+ *   opl        out: fp32[n], sum_{k<j} ds n_k^2 over the iterations in front of the record (x_j, v_j), n_k the march's own
+ *              unmasked sample at x_k, accumulated in fp32 in iteration order (fmaf(ds n_k, n_k, acc) from 0) and latched
+ *              whenever the record is updated; j = 0 (the record is the input) gives 0.  It is the integral of n along the
+ *              path -- the transit time up to the record -- when the rays enter with |v| = n.
+ *   rec_steps  out: uint32[n], j: what drrt_backtrace_cable_opl_f32 takes, so that it replays nothing
+ * The workspace and flags are not used.  fp32 only.                                                                  */
+DRRT_API int drrt_trace_cable_opl_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                             const float* pos, const float* vel, const float* target, float ds,
+                             float* xt, float* vt, float* dist2, float* opl, uint32_t* rec_steps,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
+/* The ONE adjoint of drrt_trace_cable_opl_f32: dL/d(profile), dL/dpos and dL/dvel from seeds on (xt, vt, opl), the exact
+ * derivative of the discrete forward with the record's iteration held fixed.
+ *   pos                the forward call's input positions, (n,3) fp32
+ *   xt, vt, rec_steps  its outputs
+ *   dx, dv, dopl       seeds on (xt, vt) ((n,3) fp32) and on opl (fp32[n]); each may be null: zeros
+ *   grad               out: fp32[rres], zeroed first unless DRRT_FLAG_NO_ZERO (then added into); null: not computed
+ *   dpos, dvel         out: (n,3) fp32; both null: not computed.  grad, or dpos and dvel, must be asked for.
+ * A ray makes rec_steps[i] reverse iterations from (xt, vt), run as drrt_backtrace_cable_rays_f32 runs them (lambda = dx,
+ * mu = dv + ds dx, no backward-escape test, the last sample at pos itself), with dn = mu . grad n_k + 2 dopl n_k; every
+ * iteration adds drrt_backtrace_cable_f32's two contributions for that dn to grad.  rec_steps = 0 gives (dx, dv) bit for
+ * bit and no contribution.  Nothing flows to target, radius, length or ds, and dist2 takes no seed.
+ * rec_steps is the only loop bound: a ray whose count exceeds the forward's own bound (int)(4 length / ds) -- no forward
+ * call returns one -- makes no iterations, gets zero gradients and counts in stats->n_failed.  stats->ray_steps = the
+ * reverse iterations.  n = 0 zeroes grad and returns DRRT_OK.  The workspace is not used.  fp32 only.               */
+DRRT_API int drrt_backtrace_cable_opl_f32(const float* rif, size_t rres, float radius, float length, size_t n,
+                             const float* pos, const float* xt, const float* vt, const uint32_t* rec_steps,
+                             const float* dx, const float* dv, const float* dopl, float ds,
+                             float* grad, float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
 /* Ray-state adjoints of Tracer::trace_plane and Tracer::trace_sdf: dL/dpos, dL/dvel of the rays that entered
  * drrt_trace_pln_f32 / drrt_trace_sdf_f32 (the reference gets them from enoki autodiff through those marches,
  * core/tracer.py:122-234).  No contribution to dL/dn is formed.
@@ -812,6 +847,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_EMISSION 16 /* its adjoint: dL/dn, dL/de, dL/da and the ray gradients in one march (drrt_backtrace_emission_f32) */
 #define DRRT_PROF_TRACE_VECTOR 17    /* trace with the line integral of a vector field (drrt_trace_vector_f32) */
 #define DRRT_PROF_BACKTRACE_VECTOR 18 /* its adjoint: dL/dn, dL/du and the ray gradients in one march (drrt_backtrace_vector_f32) */
+#define DRRT_PROF_TRACE_CABLE_OPL 19 /* the cable march with its optical path length (drrt_trace_cable_opl_f32) */
+#define DRRT_PROF_BACKTRACE_CABLE_OPL 20 /* its adjoint: dL/d(profile) and the ray gradients in one march (drrt_backtrace_cable_opl_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

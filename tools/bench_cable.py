@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """Times the cable (radial profile) adjoint for 4M rays x ~512 steps with rays in random order and in source-pixel
 order (neighbouring rays at nearly the same radius -> same-bin LDS adds, the case the pair / quad pre-reduction
-of k_backtrace_cable is for).  Two JSON lines."""
+of k_backtrace_cable is for).  Two JSON lines.
+
+    python tools/bench_cable.py opl [OUT.json]
+
+times, at the same sizes and for both orders, trace_cable_opl against trace_cable, and backtrace_cable_opl (profile only,
+rays only, both) against backtrace_cable and backtrace_cable_rays: the calls alternate in one session, every figure is the
+median of 7 single calls between device events.  One JSON line, also written to OUT.json."""
 import sys, json, torch, numpy as np
 sys.path.insert(0,'.')
 from adjointnonlinearraytracing_amd import drrt
@@ -25,7 +31,8 @@ def timed(fn,reps=5):
     a.record()
     for _ in range(reps): fn()
     b.record(); torch.cuda.synchronize(); return a.elapsed_time(b)/reps
-print(json.dumps(dict(adj_random_order_ms=timed(lambda: T.backtrace_cable(prof,radius,length,xt,vt,one,one,ds)))))
+mode=sys.argv[1] if len(sys.argv)>1 else 'adjoint'
+if mode=='adjoint': print(json.dumps(dict(adj_random_order_ms=timed(lambda: T.backtrace_cable(prof,radius,length,xt,vt,one,one,ds)))))
 # pixel-ordered source (neighbouring rays at nearly the same radius)
 side=2048
 i=torch.arange(side,device=dev,dtype=torch.float32)
@@ -34,4 +41,32 @@ px=(X.flatten()+0.5)/side*2*radius; pz=(Z.flatten()+0.5)/side*2*radius
 pos2=torch.stack([px, torch.full((n,),0.37*ds,device=dev), pz],-1)
 vel2=torch.zeros(n,3,device=dev); vel2[:,1]=1
 xt2,vt2,_=T.trace_cable(prof,radius,length,pos2,vel2,tg,ds)
-print(json.dumps(dict(adj_pixel_order_ms=timed(lambda: T.backtrace_cable(prof,radius,length,xt2,vt2,one,one,ds)))))
+if mode=='adjoint': print(json.dumps(dict(adj_pixel_order_ms=timed(lambda: T.backtrace_cable(prof,radius,length,xt2,vt2,one,one,ds)))))
+
+def opl_times(pos,vel):
+    """{call: median ms of 7}, the calls taken in turn 7 times over."""
+    xt,vt,_,opl,rec=T.trace_cable_opl(prof,radius,length,pos,vel,tg,ds)
+    dopl=torch.ones_like(opl)
+    calls=dict(
+        trace_cable=lambda: T.trace_cable(prof,radius,length,pos,vel,tg,ds),
+        trace_cable_opl=lambda: T.trace_cable_opl(prof,radius,length,pos,vel,tg,ds),
+        backtrace_cable=lambda: T.backtrace_cable(prof,radius,length,xt,vt,one,one,ds),
+        backtrace_cable_rays=lambda: T.backtrace_cable_rays(prof,radius,length,pos,vel,tg,one,one,ds),
+        backtrace_cable_opl_profile=lambda: T.backtrace_cable_opl(prof,radius,length,pos,xt,vt,rec,one,one,dopl,ds,rays=False),
+        backtrace_cable_opl_rays=lambda: T.backtrace_cable_opl(prof,radius,length,pos,xt,vt,rec,one,one,dopl,ds,profile=False),
+        backtrace_cable_opl_both=lambda: T.backtrace_cable_opl(prof,radius,length,pos,xt,vt,rec,one,one,dopl,ds))
+    for fn in calls.values(): fn()
+    torch.cuda.synchronize()
+    ms={k:[] for k in calls}
+    for _ in range(7):
+        for k,fn in calls.items():
+            a,b=torch.cuda.Event(enable_timing=True),torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); torch.cuda.synchronize(); ms[k].append(a.elapsed_time(b))
+    out={k:float(np.median(v)) for k,v in ms.items()}
+    out['backtrace_cable_plus_rays']=out['backtrace_cable']+out['backtrace_cable_rays']
+    out['mean_record_iteration']=float(rec.float().mean())
+    return out
+if mode=='opl':
+    res=dict(rays=n,rres=rres,random_order_ms=opl_times(pos,vel),pixel_order_ms=opl_times(pos2,vel2))
+    print(json.dumps(res))
+    if len(sys.argv)>2: json.dump(res,open(sys.argv[2],'w'),indent=1)
