@@ -100,6 +100,9 @@ SIGNATURES = {
     "drrt_backtrace_cable_rays_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp] + _tail),
     "drrt_trace_cable_opl_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_cable_opl_f32": (_i, [_vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp] + _tail),
+    "drrt_trace_cable_field_f32": (_i, [_vp, _vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_backtrace_cable_field_f32": (_i, [_vp, _vp, _sz, _f, _f, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _vp, _vp, _vp, _vp]
+                                       + _tail),
     "drrt_backtrace_pln_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_backtrace_sdf_rays_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_backtrace_target_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
@@ -131,7 +134,8 @@ PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "b
 # the ids added after PROF_NAMES was closed (profile_collect consults all three tables)
 PROF_NAMES_MORE = {15: "trace_emission", 16: "backtrace_emission"}
 # ... and after PROF_NAMES_MORE was: this table stays open, a later id goes here
-PROF_NAMES_LATER = {17: "trace_vector", 18: "backtrace_vector", 19: "trace_cable_opl", 20: "backtrace_cable_opl"}
+PROF_NAMES_LATER = {17: "trace_vector", 18: "backtrace_vector", 19: "trace_cable_opl", 20: "backtrace_cable_opl",
+                    21: "trace_cable_field", 22: "backtrace_cable_field"}
 
 _lib: Optional[C.CDLL] = None
 

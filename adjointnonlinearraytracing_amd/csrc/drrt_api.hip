@@ -2,7 +2,7 @@
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
 // drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip / drrt_cable_rays.hip /
-// drrt_cable_opl.hip.  Host code, plus the four small utility kernels that belong to no march (pair copy of the grid, q16
+// drrt_cable_opl.hip / drrt_cable_field.hip.  Host code, plus the four small utility kernels that belong to no march (pair copy of the grid, q16
 // encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
@@ -929,7 +929,7 @@ extern "C" int drrt_backtrace_sdf_f32(const float* rif, const float* sdf, long l
   return run_backtrace<1>(rif, sdf, nvox, res, n, xt, vt, dx, dv, h, ds, grad, stats, ws, ws_bytes, flags, stream);
 }
 
-// ---- the prologue the five cable entries share, in their common order: the hint (taken, never honoured: the cable kernels
+// ---- the prologue the seven cable entries share, in their common order: the hint (taken, never honoured: the cable kernels
 // visit rays in caller order), the profile and step checks, the adjoint's zero fill of `zero_grad` (nullable), the stats,
 // and the head of the argument block.  `null_msg` (nullable) is the entry's complaint about its own grid pointers.
 template <class Args>
@@ -1032,4 +1032,51 @@ extern "C" int drrt_backtrace_cable_opl_f32(const float* rif, size_t rres, float
   a.pos = pos; a.xt = xt; a.vt = vt; a.rec_steps = rec_steps; a.dx = dx; a.dv = dv; a.dopl = dopl;
   a.grad = grad; a.dpos = dpos; a.dvel = dvel;
   return timed_launch(DRRT_PROF_BACKTRACE_CABLE_OPL, s, "k_backtrace_cable_opl", [&] { launch_backtrace_cable_opl(a, s); });
+}
+
+extern "C" int drrt_trace_cable_field_f32(const float* rif, const float* field, size_t rres, float radius, float length,
+                                          size_t n, const float* pos, const float* vel, const float* target, float ds,
+                                          float* xt, float* vt, float* dist2, float* tau, uint32_t* rec_steps,
+                                          drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  (void)ws; (void)ws_bytes; (void)flags;
+  hipStream_t s = (hipStream_t)stream;
+  CableFieldTraceArgs a{};
+  const int rc = cable_begin(a, !rif ? "null rif pointer" : !field ? "null field pointer" : nullptr, rif, rres, radius, length,
+                             ds, nullptr, stats, n, s);
+  g_ts.reset_last_steps();              // rec_steps is the caller's: no iteration counts are left in the workspace
+  if (rc || n == 0) return rc;
+  if (!pos || !vel || !target || !xt || !vt || !dist2) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!tau || !rec_steps) return fail(DRRT_ERR_ARG, "null tau/rec_steps pointer");
+  a.field = field;
+  a.pos = pos; a.vel = vel; a.target = target; a.xt = xt; a.vt = vt; a.dist2 = dist2; a.tau = tau; a.rec_steps = rec_steps;
+  return timed_launch(DRRT_PROF_TRACE_CABLE_FIELD, s, "k_trace_cable_field", [&] { launch_trace_cable_field(a, s); });
+}
+
+extern "C" int drrt_backtrace_cable_field_f32(const float* rif, const float* field, size_t rres, float radius, float length,
+                                              size_t n, const float* pos, const float* xt, const float* vt,
+                                              const uint32_t* rec_steps, const float* dx, const float* dv, const float* dtau,
+                                              float ds, float* grad, float* grad_field, float* dpos, float* dvel,
+                                              drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  (void)ws; (void)ws_bytes;
+  hipStream_t s = (hipStream_t)stream;
+  CableFieldBackArgs a{};
+  const char* refusal = !rif ? "null rif pointer"
+                      : !field ? "null field pointer"
+                      : !(grad || grad_field || dpos || dvel) ? "nothing to compute: grad, grad_field, dpos and dvel are all null"
+                      : !dpos != !dvel ? "dpos and dvel go together"
+                      : grad && grad == grad_field ? "grad and grad_field must be two arrays" : nullptr;
+  const bool zero = !(flags & DRRT_FLAG_NO_ZERO);
+  const int rc = cable_begin(a, refusal, rif, rres, radius, length, ds, zero ? grad : nullptr, stats, n, s);
+  if (rc) return rc;
+  if (zero && grad_field) {
+    hipError_t e = hipMemsetAsync(grad_field, 0, rres * sizeof(float), s);
+    if (e != hipSuccess) return fail_hip(e, "hipMemsetAsync(grad_field)");
+  }
+  if (n == 0) return rc;
+  if (!pos || !xt || !vt) return fail(DRRT_ERR_ARG, "null ray pointer");
+  if (!rec_steps) return fail(DRRT_ERR_ARG, "null rec_steps pointer (the forward's rec_steps)");
+  a.field = field;
+  a.pos = pos; a.xt = xt; a.vt = vt; a.rec_steps = rec_steps; a.dx = dx; a.dv = dv; a.dtau = dtau;
+  a.grad = grad; a.grad_field = grad_field; a.dpos = dpos; a.dvel = dvel;
+  return timed_launch(DRRT_PROF_BACKTRACE_CABLE_FIELD, s, "k_backtrace_cable_field", [&] { launch_backtrace_cable_field(a, s); });
 }

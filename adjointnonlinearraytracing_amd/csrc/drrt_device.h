@@ -1416,6 +1416,96 @@ DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, c
   return g;
 }
 
+// trace_cable for ONE ray, with the line integral of a second radial profile `fa` (C.rres samples on C's knots; it may be
+// C.data itself, both are only read) up to its record, and the record's iteration.  The loop is cable_trace_opl_ray's, so
+// (xt, vt, dist2, esc, steps) and j are its bit for bit.  a_k = cable_sample_n's operations on `fa` in the cell of the
+// step's own sample n_k (unmasked, clamped beyond the radius like it); acc = fmaf(ds n_k, a_k, acc) from 0.f in iteration
+// order; `tau` and `j` are latched whenever the record is updated: tau = sum_{k<j} ds n_k a_k (j = 0: 0.f).  With fa = C.data
+// it is cable_trace_opl_ray's opl bit for bit.  It is the integral of a along the path when the rays enter with |v| = n.
+DRRT_HD RayOut cable_trace_field_ray(const Cyl& C, const float* fa, float ds, int max_steps, const float p[3],
+                                     const float v[3], const float tg[3], float& tau, unsigned& j) {
+  FwdState s;
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.xtx = s.x; s.xty = s.y; s.xtz = s.z; s.vtx = s.vx; s.vty = s.vy; s.vtz = s.vz;
+  s.aux0 = tg[0]; s.aux1 = tg[1]; s.aux2 = tg[2]; s.aux4 = s.aux5 = 0.f;
+  float ex = s.x - tg[0], ey = s.y - tg[1], ez = s.z - tg[2];
+  s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
+  s.inside = cyl_inbounds(C, s.x, s.y, s.z);                              // :344
+  s.esc = false;
+  unsigned steps = 0;
+  float acc = 0.f;
+  tau = 0.f; j = 0;
+  for (int it = 0; it < max_steps; ++it) {
+    const float best = s.aux3;
+    const CylCell c = cyl_locate(C, s.x, s.z);
+    const float n = fmaf(C.data[c.i1], c.w0, C.data[c.i0] * (1.f - c.w0));    // cable_sample_n
+    const float ak = fmaf(fa[c.i1], c.w0, fa[c.i0] * (1.f - c.w0));           // ... on the other profile
+    acc = fmaf(ds * n, ak, acc);
+    cable_fwd_step(C, ds, s);
+    ++steps;
+    if (s.aux3 < best) { tau = acc; j = steps; }                          // the record was updated (strict <, :365)
+    if (s.esc) break;
+  }
+  RayOut o;
+  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
+  o.dist2 = s.aux3; o.esc = s.esc; o.act = !s.esc; o.steps = steps;
+  return o;
+}
+
+// Adjoint of cable_trace_field_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/d(profile) and dL/d(fa) from
+// the seeds (dx, dv, dtau) on (xt, vt, tau).  Run as cable_opl_backtrace_ray runs (no replay, j reverse iterations from
+// (xt, vt), lambda = dx, mu = dv + ds dx, no escape test, the last sample at p0 itself, j the ONLY loop bound and refused
+// above max_steps), with, per iteration, in the cell (i0, i1, w0) of the sample:
+//   dn = mu . grad n_k + dtau a_k                (d tau / d n_k = ds a_k); cable_adj_step's two contributions for that dn
+//                                                go through sink(i0, i1, a0, a1)
+//   fv = (dtau ds) n_k                           (d tau / d a_k); fsink(i0, i1, fv (1 - w0), fv w0)
+//   lambda += fv a'_k rhat, a'_k = (fa[i1] - fa[i0]) / h   (a_k moves with x_k along fa's own radial slope), before
+//                                                cable_adj_recur carries lambda into mu
+// a' follows grad n's conventions by construction: rhat = 0 where cyl_locate says tiny, and i0 = i1 beyond the radius.
+// dtau = 0 leaves cable_opl_backtrace_ray's iteration with dopl = 0 and sends zeros to fsink.
+template <typename Sink, typename FieldSink>
+DRRT_HD RayGrad cable_field_backtrace_ray(const Cyl& C, const float* fa, float ds, int max_steps, const float p0[3],
+                                          const float xt[3], const float vt[3], unsigned j, const float dx[3],
+                                          const float dv[3], float dtau, Sink&& sink, FieldSink&& fsink) {
+  RayGrad g;
+  g.failed = max_steps < 0 || j > (unsigned)max_steps;
+  g.steps = g.failed ? 0u : j;
+  if (g.failed) {
+    g.dp[0] = g.dp[1] = g.dp[2] = 0.f; g.dv[0] = g.dv[1] = g.dv[2] = 0.f;
+    return g;
+  }
+  AdjState s;
+  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
+  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                               // :536
+  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);  // :537
+  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
+  const float gds = dtau * ds;
+  for (unsigned k = j; k > 0; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :547
+    if (k == 1u) { s.x = p0[0]; s.y = p0[1]; s.z = p0[2]; }              // the forward's first sample, as it took it
+    const CylAdjSample m = cable_adj_sample(C, ds, s);
+    const CylCell& c = m.c;
+    const float f0 = fa[c.i0], f1 = fa[c.i1];
+    const float w1 = 1.f - c.w0;
+    const float ak = fmaf(f1, c.w0, f0 * w1);
+    const float dn = fmaf(dtau, ak, fmaf(s.mz, m.gz, s.mx * m.gx));       // :557, plus d(ds n a)/dn / ds
+    // cylinder_volume::splat (:113-148) as cable_adj_step forms it
+    const float val = dn * ds;
+    const float gv = (m.n * ds) * fmaf(s.mz, c.rhz, s.mx * c.rhx);
+    const float gvh = gv * C.inv_h;
+    sink(c.i0, c.i1, fmaf(val, w1, -gvh), fmaf(val, c.w0, gvh));
+    const float fv = gds * m.n;                                           // d(ds n a)/da
+    fsink(c.i0, c.i1, fv * w1, fv * c.w0);
+    const float fp = fv * ((f1 - f0) * C.inv_h);                          // ... and through a's own radial slope
+    s.lx = fmaf(fp, c.rhx, s.lx); s.lz = fmaf(fp, c.rhz, s.lz);
+    qx = s.mx; qy = s.my; qz = s.mz;
+    cable_adj_recur(ds, s, m, dn);
+  }
+  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
+  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  return g;
+}
+
 // Ray-state adjoint of trace_plane (MODE 1) / trace_sdf (MODE 2) for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on
 // the record (xt, vt) = (x_j, v_j), given only the forward's inputs (p0, v0) and its plane / SDF.  j = the iteration count at
 // the LAST cross (fwd_step_c :378-386), 0 when there was none (the record is the input).  Iteration k samples n grad n at x_k

@@ -22,6 +22,8 @@
 //   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
 //   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
 //   drrt_cable_opl.hip      trace_cable_opl, backtrace_cable_opl: the cable march with its optical path length, one adjoint
+//   drrt_cable_field.hip    trace_cable_field, backtrace_cable_field: the cable march with the line integral of a second
+//                           radial profile, one adjoint (dL/dprofile, dL/dfield, dL/dpos, dL/dvel)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
 // The operators before and after the march do not include this header; they share drrt_host.h (error slot, 1-D launch):
 //   drrt_source.hip         ray generation                                       (core/source.py)
@@ -701,6 +703,39 @@ struct CableOplBackArgs {
   size_t n;
 };
 
+// trace_cable with the line integral of a second radial profile up to the record, and its adjoint (drrt_cable_field.hip)
+struct CableFieldTraceArgs {
+  const float* rif; int rres; float radius, length, ds; int max_steps;
+  const float* field;                                          // rres samples on rif's knots; may be rif itself
+  const float* pos; const float* vel; const float* target;
+  float* xt; float* vt; float* dist2; float* tau; uint32_t* rec_steps;
+  drrt_stats* stats;
+  size_t n;
+};
+
+struct CableFieldBackArgs {
+  const float* rif; int rres; float radius, length, ds; int max_steps;   // max_steps: the FORWARD's, bounds rec_steps
+  const float* field;
+  const float* pos;                                            // the forward's input positions
+  const float* xt; const float* vt; const uint32_t* rec_steps; // its record and the record's iteration
+  const float* dx; const float* dv; const float* dtau;         // nullable: seeds on (xt, vt, tau), read as zeros
+  float* grad;                                                 // PROFILE kernels only
+  float* grad_field;                                           // FIELD kernels only
+  float* dpos; float* dvel;                                    // RAYS kernels only
+  drrt_stats* stats;
+  size_t n;
+};
+
+// The LDS rule of the two kernels of drrt_cable_field.hip, for launcher and kernel alike: the block's dynamic LDS in bytes
+// -- both profiles (floats) and one f64 accumulator array per requested gradient -- or 0 when everything goes to global
+// memory: above kCableMaxRes, or when the need passes the 48 KiB that k_backtrace_cable_opl already launches with at
+// kCableMaxRes (so rres <= 2048 with both gradients, <= 3072 with one, <= 4096 with none and in the forward).
+constexpr size_t kCableFieldMaxLds = 49152;
+__host__ __device__ inline size_t cable_field_lds_bytes(int rres, bool profile, bool field) {
+  const size_t need = (size_t)rres * (2 * sizeof(float) + (profile ? sizeof(double) : 0) + (field ? sizeof(double) : 0));
+  return rres <= kCableMaxRes && need <= kCableFieldMaxLds ? need : 0;
+}
+
 __device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_tot, unsigned steps_max, unsigned fail_tot) {
   if (!stats) return;
   unsigned wm = wave_max_u32(steps_max), ws = wave_sum_u32(steps_tot), wf = wave_sum_u32(fail_tot);
@@ -792,5 +827,9 @@ void launch_backtrace_cable_rays(const CableRayGradArgs& a, hipStream_t s);
 // (drrt_cable_opl.hip)
 void launch_trace_cable_opl(const CableOplTraceArgs& a, hipStream_t s);
 void launch_backtrace_cable_opl(const CableOplBackArgs& a, hipStream_t s);
+// the cable march with the line integral of a second radial profile, and its adjoint: grad, grad_field and/or (dpos, dvel),
+// whichever are non-null (drrt_cable_field.hip)
+void launch_trace_cable_field(const CableFieldTraceArgs& a, hipStream_t s);
+void launch_backtrace_cable_field(const CableFieldBackArgs& a, hipStream_t s);
 
 }  // namespace drrt

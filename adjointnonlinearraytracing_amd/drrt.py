@@ -503,22 +503,77 @@ def _warn_failed(stats: torch.Tensor) -> None:
         _drain_warnings(block=True)
 
 
-def _cable_call(name: str, rif, radius, length, ds, rays, make_outputs, warn: bool = False) -> tuple:
+def _cable_profiles(rif, field, dev: torch.device) -> list:
+    """The flat fp32 profile(s) of a cable entry on `dev`: [rif], or [rif, field] for the entries that integrate a second
+    radial profile, which must have rif's number of samples."""
+    profs = [_f32(rif, dev).reshape(-1)]
+    if field is not None:
+        profs.append(_f32(field, dev).reshape(-1))
+        if profs[1].numel() != profs[0].numel():
+            raise RuntimeError(f"the second profile must have the {profs[0].numel()} samples of rif, got {profs[1].numel()}")
+    return profs
+
+
+def _cable_call(name: str, rif, radius, length, ds, rays, make_outputs, warn: bool = False, field=None) -> tuple:
     """One call of a cable entry point (they share their shape: profile, radius, length, n, the (n,3) ray tensors `rays`, ds,
-    the outputs, the usual tail) -> the outputs, made by ``make_outputs(profile, first ray tensor)``."""
+    the outputs, the usual tail) -> the outputs, made by ``make_outputs(profile, first ray tensor)``.  `field`: the second
+    radial profile of the entries that take one, right after the first."""
     dev = _dev(rif)
     with torch.cuda.device(dev):
-        rif_, first = _f32(rif, dev).reshape(-1), _rays(rays[0], dev)
+        profs, first = _cable_profiles(rif, field, dev), _rays(rays[0], dev)
+        rif_ = profs[0]
         n = first.shape[0]
         rays_ = [first] + [_rays(t, dev, n) for t in rays[1:]]
         out = make_outputs(rif_, first)
         ws, st = _workspace(n, 0, dev), _new_stats(dev)
         _lib.check(getattr(_lib.load(), name)(
-            _p(rif_), rif_.numel(), float(radius), float(length), n, *map(_p, rays_), float(ds), *map(_p, out),
+            *map(_p, profs), rif_.numel(), float(radius), float(length), n, *map(_p, rays_), float(ds), *map(_p, out),
             _p(st), _p(ws), ws.numel(), 0, _stream(dev)))
         if warn:
             _warn_failed(st)
     return out
+
+
+def _backtrace_cable_integral(op: str, rif, field, radius, length, pos, xt, vt, rec_steps, dx, dv, dint, ds, grads, rays):
+    """One call of drrt_backtrace_cable_<op>_f32, the adjoint of a cable march with an integral (they share their shape: the
+    profile(s), radius, length, n, pos, xt, vt, rec_steps, the three optional seeds, ds, one gradient per profile, dpos,
+    dvel, the usual tail) -> ([grad | None per profile], dpos | None, dvel | None).  `grads`: per profile gradient (wanted,
+    the tensor it is added to or None, that argument's name); with any such tensor the call runs under DRRT_FLAG_NO_ZERO,
+    which covers every gradient, so a wanted one without a tensor is added to fresh zeros."""
+    who = f"backtrace_cable_{op}"
+    dev = _dev(rif)
+    with torch.cuda.device(dev):
+        profs, pos_ = _cable_profiles(rif, field, dev), _rays(pos, dev)
+        rif_ = profs[0]
+        n = pos_.shape[0]
+        xt_, vt_ = _rays(xt, dev, n), _rays(vt, dev, n)
+        rec_ = rec_steps.detach().to(device=dev).contiguous()
+        if rec_.dtype != torch.int32 or rec_.numel() != n:
+            raise RuntimeError(f"rec_steps must be {n} int32 record iterations of the forward call (trace_cable_{op}'s)")
+        dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
+        dint_ = None if dint is None else _f32(dint, dev).reshape(-1)
+        if dint_ is not None and dint_.numel() != n:
+            raise RuntimeError(f"expected {n} per-ray values, got {dint_.numel()}")
+        no_zero = any(want and into is not None for want, into, _ in grads)
+        out = []
+        for want, into, arg in grads:
+            if want and into is not None:
+                if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != rif_.numel() or into.device != dev:
+                    raise RuntimeError(f"{who}: `{arg}` must be a contiguous fp32 tensor of the profile's size on its device")
+                out.append(into.detach().view(-1))
+            elif want:
+                out.append(torch.zeros_like(rif_) if no_zero else torch.empty_like(rif_))
+            else:
+                out.append(None)
+        # never a null pointer (n = 0): null dpos / dvel means "not asked for"
+        dpos, dvel = (pos_.new_empty((max(n, 1), 3)), pos_.new_empty((max(n, 1), 3))) if rays else (None, None)
+        ws, st = _workspace(n, 0, dev), _new_stats(dev)
+        _lib.check(getattr(_lib.load(), f"drrt_{who}_f32")(
+            *map(_p, profs), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(xt_), _p(vt_), _p(rec_), _p(dx_),
+            _p(dv_), _p(dint_), float(ds), *map(_p, out), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(),
+            _lib.FLAG_NO_ZERO if no_zero else 0, _stream(dev)))
+        _warn_failed(st)
+    return (out, dpos[:n], dvel[:n]) if rays else (out, None, None)
 
 
 def _ray_format(pos: torch.Tensor, vel: torch.Tensor, seeds: tuple = ()):
@@ -963,35 +1018,42 @@ class TracerC:
         rays" message."""
         if not (profile or rays):
             raise RuntimeError("backtrace_cable_opl: nothing to compute (profile = rays = False)")
-        dev = _dev(rif)
-        with torch.cuda.device(dev):
-            rif_, pos_ = _f32(rif, dev).reshape(-1), _rays(pos, dev)
-            n = pos_.shape[0]
-            xt_, vt_ = _rays(xt, dev, n), _rays(vt, dev, n)
-            rec_ = rec_steps.detach().to(device=dev).contiguous()
-            if rec_.dtype != torch.int32 or rec_.numel() != n:
-                raise RuntimeError(f"rec_steps must be {n} int32 record iterations of the forward call (trace_cable_opl's)")
-            dx_, dv_ = (None if t is None else _rays(t, dev, n) for t in (dx, dv))
-            dopl_ = None if dopl is None else _f32(dopl, dev).reshape(-1)
-            if dopl_ is not None and dopl_.numel() != n:
-                raise RuntimeError(f"expected {n} per-ray values, got {dopl_.numel()}")
-            grad = None
-            if profile and into is not None:
-                if into.dtype != torch.float32 or not into.is_contiguous() or into.numel() != rif_.numel() or into.device != dev:
-                    raise RuntimeError("backtrace_cable_opl: `into` must be a contiguous fp32 tensor of the profile's size on "
-                                       "its device")
-                grad = into.detach().view(-1)
-            elif profile:
-                grad = torch.empty_like(rif_)
-            # never a null pointer (n = 0): null dpos / dvel means "not asked for"
-            dpos, dvel = (pos_.new_empty((max(n, 1), 3)), pos_.new_empty((max(n, 1), 3))) if rays else (None, None)
-            ws, st = _workspace(n, 0, dev), _new_stats(dev)
-            _lib.check(_lib.load().drrt_backtrace_cable_opl_f32(
-                _p(rif_), rif_.numel(), float(radius), float(length), n, _p(pos_), _p(xt_), _p(vt_), _p(rec_), _p(dx_), _p(dv_),
-                _p(dopl_), float(ds), _p(grad), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(),
-                _lib.FLAG_NO_ZERO if profile and into is not None else 0, _stream(dev)))
-            _warn_failed(st)
-        return (grad, dpos[:n], dvel[:n]) if rays else (grad, None, None)
+        (grad,), dpos, dvel = _backtrace_cable_integral("opl", rif, None, radius, length, pos, xt, vt, rec_steps, dx, dv, dopl,
+                                                        ds, ((profile, into, "into"),), rays)
+        return grad, dpos, dvel
+
+    def trace_cable_field(self, rif, field, radius, length, pos, vel, target, ds):
+        """``trace_cable`` with the line integral of a second radial profile `field` (rif's number of samples, same radius)
+        along every ray up to its record (drrt_trace_cable_field_f32, include/drrt_hip.h; not in the reference) -> (xt, vt,
+        dist2, tau, rec_steps): xt, vt and dist2 are ``trace_cable``'s bit for bit; ``tau = sum ds n_k a_k`` over the
+        iterations in front of the closest-approach record, a_k the lerp of `field` in the cell of the march's own sample
+        n_k (the integral of a along the path -- a group delay, an attenuation -- when the rays enter with |v| = n; rays
+        scaled otherwise get the same sum, not that integral; with ``field = rif`` it is ``trace_cable_opl``'s opl bit for
+        bit); `rec_steps` (int32[n]) is the record's iteration, which ``backtrace_cable_field`` takes.  fp32 rays only."""
+        return _cable_call("drrt_trace_cable_field_f32", rif, radius, length, ds, (pos, vel, target),
+                           lambda rif_, r: (torch.empty_like(r), torch.empty_like(r), r.new_empty(r.shape[0]),
+                                            r.new_empty(r.shape[0]),
+                                            torch.empty(r.shape[0], dtype=torch.int32, device=r.device)), warn=True,
+                           field=field)
+
+    def backtrace_cable_field(self, rif, field, radius, length, pos, xt, vt, rec_steps, dx, dv, dtau, ds,
+                              want_rif: bool = True, want_field: bool = True, want_rays: bool = True,
+                              into: Optional[torch.Tensor] = None, into_field: Optional[torch.Tensor] = None):
+        """Adjoint of ``trace_cable_field`` (drrt_backtrace_cable_field_f32, include/drrt_hip.h) -> (grad | None,
+        grad_field | None, dpos | None, dvel | None): dL/d(profile) and dL/d(field) (fp32[rres] each), dL/dpos and dL/dvel
+        ((n,3) fp32) from ONE reverse march that replays nothing.  `pos` is the forward call's input, `xt`, `vt`,
+        `rec_steps` its outputs; `dx`, `dv` ((n,3)) and `dtau` (n values) the seeds on (xt, vt, tau), each optional (None:
+        zeros); a seed on dist2 does not enter and nothing flows to the target.  `want_rif` / `want_field` / `want_rays`:
+        which outputs are computed (at least one).  `into` / `into_field`: flat fp32[rres] tensors the two gradients are
+        ADDED to and that are returned; DRRT_FLAG_NO_ZERO covers both gradients, so with either given a requested gradient
+        without one is added to fresh zeros.  The record's iteration is held fixed.  A ray whose `rec_steps` exceeds the
+        forward's step bound gets zero gradients and the "failed to exit all rays" message."""
+        if not (want_rif or want_field or want_rays):
+            raise RuntimeError("backtrace_cable_field: nothing to compute (want_rif = want_field = want_rays = False)")
+        (grad, grad_field), dpos, dvel = _backtrace_cable_integral(
+            "field", rif, field, radius, length, pos, xt, vt, rec_steps, dx, dv, dtau, ds,
+            ((want_rif, into, "into"), (want_field, into_field, "into_field")), want_rays)
+        return grad, grad_field, dpos, dvel
 
     def backtrace_pln_rays(self, rif, res, pos, vel, pln_o, pln_d, dx, dv, h, ds,
                            order: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:

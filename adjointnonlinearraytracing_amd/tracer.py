@@ -507,6 +507,56 @@ class CableOPLTracerC(torch.autograd.Function):
         return grad.reshape(rif.shape) if want_rif else None, None, None, dx0, dv0, None, None
 
 
+class CableFieldTracerC(torch.autograd.Function):
+    """``apply(rif (Rr,), a (Rr,), radius, length, x, v, sp, ds) -> (xt, vt, dist2, tau)``: the fibre march with the line
+    integral ``tau = sum ds n_k a_k`` of a second radial profile ``a`` (``rif``'s samples, same radius: a group index, an
+    attenuation or a gain) along every ray up to its closest-approach record; xt, vt and tau are differentiable w.r.t.
+    ``rif``, ``a``, ``x`` and ``v``.  tau is the integral of a along the path when the rays enter with |v| = n; rays scaled
+    otherwise (examples/fiber_demo.py divides by the boundary index) get the same sum, which is not that integral.  With
+    ``a = rif`` tau is CableOPLTracerC's opl bit for bit.  Not in the reference.
+
+    The forward is ``TracerC.trace_cable_field``, which also returns the iteration of every record; backward is ONE
+    ``TracerC.backtrace_cable_field`` launch (plus one zero-fill per profile gradient asked for) that replays nothing,
+    returns dL/drif, dL/da and the ray gradients from the same reverse march and computes only what is asked for.  It is
+    the derivative of the discrete forward with the record's iteration held fixed.  ``dist2`` is not differentiable and
+    ``sp`` gets no gradient.  A private copy of x and the record iterations are kept whenever any input requires grad.
+    fp32 rays only when ray gradients are asked for."""
+
+    @staticmethod
+    def forward(ctx, rif, a, radius, length, x, v, sp, ds):
+        ctx.set_materialize_grads(False)
+        ctx.radius, ctx.length, ctx.ds = radius, length, ds
+        if a.numel() != rif.numel():
+            raise RuntimeError(f"CableFieldTracerC: the second profile must have the {rif.numel()} samples of rif, got "
+                               f"{a.numel()}")
+        _ray_grad_wanted(ctx, "CableFieldTracerC", 4, 5, x, v)
+        xt, vt, dist2, tau, rec = drrt.TracerC().trace_cable_field(rif.detach().flatten(), a.detach().flatten(), radius,
+                                                                   length, x.detach(), v.detach(), sp.detach(), ds)
+        if any(ctx.needs_input_grad[i] for i in (0, 1, 4, 5)):
+            ctx.ray_devices = (x.device, v.device)
+            # the adjoint replays nothing: of the forward's ray inputs it takes x alone (a private copy, as _keep_rays makes)
+            ctx.rays = (x.detach().to(device=xt.device, dtype=torch.float32).clone(), rec)
+            ctx.save_for_backward(rif, a, xt, vt)
+        ctx.mark_non_differentiable(dist2)
+        return xt, vt, dist2, tau
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_dist2, grad_tau):
+        want_rif, want_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        want_rays = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
+        if not (want_rif or want_a or want_rays):
+            return (None,) * 8
+        rif, a, xt, vt = ctx.saved_tensors
+        x0, rec = ctx.rays
+        grad, grad_a, dpos, dvel = drrt.TracerC().backtrace_cable_field(
+            rif.detach().flatten(), a.detach().flatten(), ctx.radius, ctx.length, x0, xt, vt, rec, grad_x, grad_v, grad_tau,
+            ctx.ds, want_rif, want_a, want_rays)
+        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[4] else None
+        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[5] else None
+        return (grad.reshape(rif.shape) if want_rif else None, grad_a.reshape(a.shape) if want_a else None, None, None,
+                dx0, dv0, None, None)
+
+
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken
 # upstream, SURVEY Q15) resolve to the adjoint classes so that `autodiff=True` (core/luneburg_opt.py:80-83) keeps working,
 # with the documented difference that no gradient flows to x, v through THESE names.  The classes with ray gradients are

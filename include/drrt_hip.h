@@ -633,6 +633,52 @@ DRRT_API int drrt_backtrace_cable_opl_f32(const float* rif, size_t rres, float r
                              drrt_stats* stats, void* workspace, size_t workspace_bytes,
                              unsigned flags, void* stream);
 
+/* drrt_trace_cable_f32 with the line integral of a second radial profile along every ray up to its record, and the
+ * record's iteration (not in the reference): the group delay int N_g dl, an attenuation or gain int alpha dl.  xt, vt,
+ * dist2 and the statistics are drrt_trace_cable_f32's bit for bit, rec_steps is drrt_trace_cable_opl_f32's.
+ *   field      fp32[rres], the profile a on rif's knots (same radius); it may be rif itself (both are only read)
+ *   tau        out: fp32[n], sum_{k<j} ds n_k a_k over the iterations in front of the record (x_j, v_j); n_k is the march's
+ *              own unmasked sample at x_k and a_k the same lerp of `field` in the same cell (clamped beyond the radius
+ *              like it), accumulated in fp32 in iteration order (fmaf(ds n_k, a_k, acc) from 0) and latched whenever the
+ *              record is updated; j = 0 gives 0.  With field = rif it is drrt_trace_cable_opl_f32's opl bit for bit.  It is
+ *              the integral of a along the path when the rays enter with |v| = n; rays scaled otherwise get the same sum,
+ *              which is not that integral.
+ *   rec_steps  out: uint32[n], j: what drrt_backtrace_cable_field_f32 takes, so that it replays nothing
+ * The workspace and flags are not used.  fp32 only.                                                                  */
+DRRT_API int drrt_trace_cable_field_f32(const float* rif, const float* field, size_t rres, float radius, float length,
+                             size_t n, const float* pos, const float* vel, const float* target, float ds,
+                             float* xt, float* vt, float* dist2, float* tau, uint32_t* rec_steps,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
+/* The ONE adjoint of drrt_trace_cable_field_f32: dL/d(profile), dL/d(field), dL/dpos and dL/dvel from seeds on
+ * (xt, vt, tau), the exact derivative of the discrete forward with the record's iteration held fixed.
+ *   pos                the forward call's input positions, (n,3) fp32
+ *   xt, vt, rec_steps  its outputs
+ *   dx, dv, dtau       seeds on (xt, vt) ((n,3) fp32) and on tau (fp32[n]); each may be null: zeros
+ *   grad, grad_field   out: fp32[rres] each, zeroed first unless DRRT_FLAG_NO_ZERO (then both are added into); null: not
+ *                      computed; they must be two arrays
+ *   dpos, dvel         out: (n,3) fp32; both null: not computed.  grad, grad_field, or dpos and dvel, must be asked for.
+ * A ray makes rec_steps[i] reverse iterations from (xt, vt), run as drrt_backtrace_cable_opl_f32 runs them (lambda = dx,
+ * mu = dv + ds dx, no backward-escape test, the last sample at pos itself).  In the cell (i0, i1, w0) of its sample an
+ * iteration has dn = mu . grad n_k + dtau a_k and adds drrt_backtrace_cable_f32's two contributions for that dn to grad;
+ * with fv = dtau ds n_k it adds fv (1 - w0) to grad_field[i0] and fv w0 to grad_field[i1], and lambda takes
+ * fv a'_k rhat, a'_k = (field[i1] - field[i0]) / h, before it is carried into mu (a' is zero where grad n is: within
+ * 1e-6 of the axis and beyond the radius).  With dtau null, grad, dpos and dvel are drrt_backtrace_cable_opl_f32's with
+ * dopl null and grad_field is zero.  rec_steps = 0 gives (dx, dv) bit for bit and no contribution.  Nothing flows to
+ * target, radius, length or ds, and dist2 takes no seed.
+ * rec_steps is the only loop bound: a ray whose count exceeds the forward's own bound (int)(4 length / ds) -- no forward
+ * call returns one -- makes no iterations, gets zero gradients and counts in stats->n_failed.  stats->ray_steps = the
+ * reverse iterations.  n = 0 zeroes the requested gradients and returns DRRT_OK.  The workspace is not used.  fp32 only.
+ * Up to 2048 profile samples with both gradients, 3072 with one and 4096 with none the block keeps the profiles and its
+ * f64 gradient accumulators in LDS; above, it reads global memory and adds with global atomics.                      */
+DRRT_API int drrt_backtrace_cable_field_f32(const float* rif, const float* field, size_t rres, float radius, float length,
+                             size_t n, const float* pos, const float* xt, const float* vt, const uint32_t* rec_steps,
+                             const float* dx, const float* dv, const float* dtau, float ds,
+                             float* grad, float* grad_field, float* dpos, float* dvel,
+                             drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                             unsigned flags, void* stream);
+
 /* Ray-state adjoints of Tracer::trace_plane and Tracer::trace_sdf: dL/dpos, dL/dvel of the rays that entered
  * drrt_trace_pln_f32 / drrt_trace_sdf_f32 (the reference gets them from enoki autodiff through those marches,
  * core/tracer.py:122-234).  No contribution to dL/dn is formed.
@@ -849,6 +895,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_VECTOR 18 /* its adjoint: dL/dn, dL/du and the ray gradients in one march (drrt_backtrace_vector_f32) */
 #define DRRT_PROF_TRACE_CABLE_OPL 19 /* the cable march with its optical path length (drrt_trace_cable_opl_f32) */
 #define DRRT_PROF_BACKTRACE_CABLE_OPL 20 /* its adjoint: dL/d(profile) and the ray gradients in one march (drrt_backtrace_cable_opl_f32) */
+#define DRRT_PROF_TRACE_CABLE_FIELD 21 /* the cable march with the line integral of a second radial profile (drrt_trace_cable_field_f32) */
+#define DRRT_PROF_BACKTRACE_CABLE_FIELD 22 /* its adjoint: dL/d(profile), dL/d(field) and the ray gradients in one march (drrt_backtrace_cable_field_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

@@ -1,0 +1,771 @@
+"""The fibre march with the line integral of a second radial profile and its one exact adjoint
+(drrt_trace_cable_field_f32, drrt_backtrace_cable_field_f32, TracerC.trace_cable_field / backtrace_cable_field,
+tracer.CableFieldTracerC).
+
+CPU tier: the host build of the product's two per-ray routines (tests/cable_field_host, cable_trace_field_ray and
+cable_field_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through
+tests/cable_field_ad.trace_cable_field (cable_opl_ad.trace_cable_opl with acc += ds n_k a_k), on the scenes, ray sets and
+tie-free mask of tests/test_cable_raygrad.py, within the bound of the integral fuzz suite (tests/integral_fuzz_common.py:
+FLOOR, MARGIN times the error of the same restatement run in float32, never above CAPS); closed forms, identities against
+the existing cable routines, the refusals of the two entry points, and a stand-alone sanitizer build of the two routines.
+GPU tier: the kernels against that host build (per-ray results bit for bit, both profile gradients within ATOMIC_TOL) on
+both sides of every LDS limit, the grid-stride loop, CableFieldTracerC end to end and examples/fiber_group_delay_demo.py.
+
+On the parent commit every test here fails: tests/cable_field_host does not compile (drrt_device.h has neither
+cable_trace_field_ray nor cable_field_backtrace_ray), the library has neither drrt_trace_cable_field_f32 nor
+drrt_backtrace_cable_field_f32, _lib.PROF_NAMES_LATER has no ids 21 and 22, TracerC has no trace_cable_field and tracer no
+CableFieldTracerC, and there is no examples/fiber_group_delay_demo.py."""
+import ctypes as C
+import glob
+import itertools
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+import torch
+
+import cable_ad
+import cable_field_ad
+import cable_field_host as H
+import cable_opl_host as HO
+import cases
+import hostcheck_lib as HC
+import test_cable_raygrad as CR
+from integral_fuzz_common import CAPS, FLOOR, bound
+from raygrad_common import TIE_TOL, _t, rel_err
+
+ATOMIC_TOL = 2e-5       # profile gradients, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
+MODES = {"all": (), "dtau": ("dx", "dv"), "rays": ("dtau",)}      # mode: the seeds it leaves out (null pointers / zeros)
+K_BLOCK = 256           # kBlock of csrc/drrt_march.h
+RAY_KEYS = ("pos", "vel", "tg", "dx", "dv", "dtau")
+
+_refs = {}
+
+
+# ---- scenes and references ------------------------------------------------------------------------------------------
+def field_profile(rres, seed):
+    """The second profile: positive (0.25 .. 1.05), not monotone, of `rres` samples."""
+    rng = np.random.default_rng(7300 + seed)
+    return (0.6 + 0.3 * np.sin(7.0 * np.linspace(0, 1, rres) + seed) + 0.1 * rng.random(rres) - 0.05).astype(np.float32)
+
+
+def scene(name):
+    """tests/test_cable_raygrad.py::scene(name) with a second profile and a seed on tau from generators of this module's
+    own."""
+    s = CR._fuzz(int(name[4:])) if name.startswith("fuzz") else CR.scene(name)
+    tag = sum(map(ord, name))
+    s["field"] = field_profile(len(s["prof"]), tag)
+    s["dtau"] = np.random.default_rng(5200 + tag).normal(size=len(s["pos"])).astype(np.float32)
+    return s
+
+
+def host_forward(s, field=None):
+    return H.trace_cable_field(s["prof"], s["field"] if field is None else field, s["radius"], s["length"], s["pos"],
+                               s["vel"], s["tg"], s["ds"])
+
+
+def host_back(s, k, mode="all", sel=slice(None), rec=None, field=None):
+    seeds = [None if name in MODES[mode] else s[name][sel] for name in ("dx", "dv", "dtau")]
+    return H.backtrace_cable_field(s["prof"], s["field"] if field is None else field, s["radius"], s["length"],
+                                   s["pos"][sel], k["xt"][sel], k["vt"][sel], (k["rec_steps"] if rec is None else rec)[sel],
+                                   *seeds, s["ds"])
+
+
+def opl_forward(s):
+    return HO.trace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["ds"])
+
+
+def opl_back(s, k, dopl):
+    return HO.backtrace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], k["xt"], k["vt"], k["rec_steps"], s["dx"],
+                                  s["dv"], dopl, s["ds"])
+
+
+def _autograd(s, j, idx, seeds, dtype):
+    """torch.autograd of L = <dx, xt> + <dv, vt> + <dtau, tau> through the restatement on the rays `idx` ->
+    (xt, vt, tau, {mode: (dprof, dfield, dpos, dvel)}), the per-ray results scattered back to every ray (zero rows
+    elsewhere)."""
+    T = lambda a: torch.tensor(np.asarray(a), dtype=dtype)      # noqa: E731
+    n = len(s["pos"])
+
+    def full(a):
+        out = np.zeros((n,) + a.shape[1:], a.dtype)
+        out[idx] = a
+        return out
+    prof, field = T(s["prof"]).requires_grad_(True), T(s["field"]).requires_grad_(True)
+    p, v = T(s["pos"][idx]).requires_grad_(True), T(s["vel"][idx]).requires_grad_(True)
+    xt, vt, tau = cable_field_ad.trace_cable_field(prof, field, s["radius"], s["length"], p, v, j[idx].astype(np.int64),
+                                                   s["ds"])
+    grads = {}
+    for mode, left_out in MODES.items():
+        L = sum((o * T(np.zeros_like(seeds[name][idx]) if name in left_out else seeds[name][idx])).sum()
+                for o, name in ((xt, "dx"), (vt, "dv"), (tau, "dtau")))
+        g = torch.autograd.grad(L, (prof, field, p, v), retain_graph=True, allow_unused=True)
+        g = [torch.zeros_like(w) if t is None else t for t, w in zip(g, (prof, field, p, v))]
+        grads[mode] = (g[0].numpy(), g[1].numpy(), full(g[2].numpy()), full(g[3].numpy()))
+    return full(xt.detach().numpy()), full(vt.detach().numpy()), full(tau.detach().numpy()), grads
+
+
+def reference(name):
+    """Everything the CPU tier compares, computed once per scene and handed out unchanged: the host forward `k`, the
+    tie-free mask of tests/test_cable_raygrad.py (the fp32 record within TIE_TOL of the float64 restatement's at the same
+    iteration: it depends on the existing march's (xt, vt) alone), the seeds with those of the dropped rays zeroed, and the
+    float64 (referee) and float32 (yardstick) autograd runs on the tie-free rays."""
+    if name in _refs:
+        return _refs[name]
+    s = scene(name)
+    k = host_forward(s)
+    j = k["rec_steps"]
+    with torch.no_grad():
+        T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
+        x64, v64 = cable_ad.trace_cable(T(s["prof"]), s["radius"], s["length"], T(s["pos"]), T(s["vel"]),
+                                        j.astype(np.int64), s["ds"])
+    tie_free = (np.abs(x64.numpy() - k["xt"]).max(1) <= TIE_TOL) & (np.abs(v64.numpy() - k["vt"]).max(1) <= TIE_TOL)
+    seeds = {key: (s[key] * (tie_free[:, None] if s[key].ndim == 2 else tie_free)).astype(np.float32)
+             for key in ("dx", "dv", "dtau")}
+    idx = np.nonzero(tie_free)[0]
+    hi = _autograd(s, j, idx, seeds, torch.float64)
+    lo = _autograd(s, j, idx, seeds, torch.float32)
+    _refs[name] = dict(s=dict(s, **seeds), k=k, tie_free=tie_free, hi=hi, lo=lo)
+    return _refs[name]
+
+
+def _report(tag, rows):
+    """rows: (quantity, e_prod, e_ref, cap).  Prints each and -> those that miss bound(e_ref, cap)."""
+    bad = []
+    for what, e_prod, e_ref, cap in rows:
+        b = bound(e_ref, cap)
+        print(f"{tag} {what}: e_prod {e_prod:.3e} e_ref {e_ref:.3e} ratio {e_prod / max(e_ref, FLOOR):.2f} bound {b:.3e}")
+        if not e_prod <= b:
+            bad.append((what, e_prod, e_ref, b))
+    return bad
+
+
+# ---- CPU tier: against float64 autograd -----------------------------------------------------------------------------
+@pytest.mark.parametrize("name", list(CR.SCENES))
+def test_host_forward_matches_float64(name):
+    """tau of the host build against the float64 restatement: per-ray relative error over the tie-free rays with j > 0,
+    within the fuzz bound (cap 1e-4); at most MAX_DROPPED of the rays are dropped, every kind of record and every ray set is
+    among the compared ones.  Measured ratios e_prod / max(e_ref, FLOOR): 1.03, 0.97, 1.00 and 1.00 over the four scenes
+    (the bound allows 8)."""
+    r = reference(name)
+    s, k, tf = r["s"], r["k"], r["tie_free"]
+    j, K = k["rec_steps"], k["steps"]
+    assert 1.0 - tf.mean() <= CR.MAX_DROPPED
+    assert ((j == 0) & tf).sum() >= 10 and ((j > 0) & (j < K) & tf).sum() >= 10 and ((j == K) & tf).sum() >= 10
+    for kind in ("inside", "axis", "beyond", "before", "past"):
+        assert tf[s["labels"] == kind].sum() >= 10, kind
+    m = tf & (j > 0)
+    tau64, tau32 = r["hi"][2], r["lo"][2]
+    assert (tau64[m] > 0).all() and (k["tau"][j == 0] == 0).all()
+    e = lambda a: float((np.abs(a.astype(np.float64) - tau64)[m] / tau64[m]).max())      # noqa: E731
+    assert not _report(name, [("tau", e(k["tau"]), e(tau32), CAPS["out"])])
+
+
+@pytest.mark.parametrize("mode", list(MODES))
+@pytest.mark.parametrize("name", list(CR.SCENES))
+def test_host_adjoint_matches_float64_autograd(name, mode):
+    """(dpos, dvel) per-ray and the two profile gradients rel-L2 of the host build against float64 autograd, within the fuzz
+    bound (caps 1e-3), with every seed set, with dtau alone and with (dx, dv) alone; the seeds of the dropped rays are zero.
+    With (dx, dv) alone the field gradient is exactly zero on both sides.  Largest measured ratio e_prod / max(e_ref, FLOOR)
+    over the twelve cases: 2.83 (dL/dprofile, random33_half/dtau: 2.5e-6 against 8.7e-7); the next is 1.24 (the bound allows
+    8).
+
+    Mutation checks (by hand), each of which fails 15 tests of the CPU tier -- the modes `all` and `dtau` here on all four
+    scenes (8 cases; `rays` cannot see them), test_one_iteration_closed_form and the six cases of
+    test_with_the_profile_as_field_the_two_gradients_sum_to_the_opl_gradient: dropping the dtau a_k term from dn; dropping
+    lambda's pull of a'; swapping the two weights of the field sink."""
+    r = reference(name)
+    s, k, tf = r["s"], r["k"], r["tie_free"]
+    b = host_back(s, k, mode)
+    assert not b["failed"].any() and np.array_equal(b["steps"], k["rec_steps"])
+    (g64, f64, p64, v64), (g32, f32, p32, v32) = r["hi"][3][mode], r["lo"][3][mode]
+    assert np.linalg.norm(g64) > 0
+    rows = [("rays", float(rel_err(b["dpos"], b["dvel"], p64, v64)[tf].max()),
+             float(rel_err(p32, v32, p64, v64)[tf].max()), CAPS["rays"]),
+            ("dL/dprofile", cases.rel_l2(b["grad"], g64), cases.rel_l2(g32, g64), CAPS["grid"])]
+    if mode == "rays":
+        assert not b["grad_field"].any() and not f64.any()
+    else:
+        assert np.linalg.norm(f64) > 0
+        rows.append(("dL/dfield", cases.rel_l2(b["grad_field"], f64), cases.rel_l2(f32, f64), CAPS["grid"]))
+    assert not _report(f"{name}/{mode}", rows)
+
+
+# ---- CPU tier: closed forms -----------------------------------------------------------------------------------------
+def _uniform(n0, a0, name="luneburg65_half"):
+    s = scene(name)
+    s["prof"] = np.full(len(s["prof"]), n0, np.float32)
+    s["field"] = np.full(len(s["prof"]), a0, np.float32)
+    return s
+
+
+@pytest.mark.parametrize("n0,a0", [(1.0, 2.0), (2.0, 0.5), (1.5, 0.75)])
+def test_uniform_profiles_tau_closed_form(n0, a0):
+    """Uniform profiles: tau = j ds n0 a0 to fp32 summation.  With n_k = n0 and a_k = a0 exactly (the lerp of two equal
+    powers of two), ds n0 rounds once and every fmaf once, each at most 2^-24 of a partial sum that never exceeds the final
+    one: (j + 1) 2^-24 relative.  For 1.5 and 0.75 a lerp has two roundings (v (1 - w0), then the fmaf), so n_k and a_k are
+    each within 2^-23 of their value: 4 x 2^-24 more."""
+    s = _uniform(n0, a0)
+    k = host_forward(s)
+    j = k["rec_steps"].astype(np.float64)
+    assert (j > 0).sum() >= 100 and j.max() > 100
+    exact = j * float(np.float32(s["ds"])) * n0 * a0
+    m = j > 0
+    lim = (j[m] + 1 + (0 if n0 in (1.0, 2.0) else 4)) * 2.0 ** -24
+    err = np.abs(k["tau"][m] - exact[m]) / exact[m]
+    print(f"n0 = {n0}, a0 = {a0}: max err / bound = {(err / lim).max():.3f}")
+    assert (err <= lim).all()
+
+
+@pytest.mark.parametrize("name", ["luneburg65_half", "two_samples"])
+def test_a_zero_field_leaves_the_opl_adjoint_without_dopl(name):
+    """a = 0: tau = 0; dn = mu . grad n_k + dtau 0 and a' = 0, so grad, dpos and dvel are backtrace_cable_opl's with
+    dopl = 0 bit for bit whatever dtau is, while the field gradient is not zero (d tau / d a_k = ds n_k)."""
+    s = scene(name)
+    zero = np.zeros_like(s["field"])
+    k = host_forward(s, field=zero)
+    assert not k["tau"].any()
+    b = host_back(s, k, field=zero)
+    o = opl_back(s, k, np.zeros_like(s["dtau"]))
+    assert np.array_equal(b["grad"], o["grad"]) and np.linalg.norm(o["grad"]) > 0
+    assert np.array_equal(b["dpos"], o["dpos"], equal_nan=True) and np.array_equal(b["dvel"], o["dvel"], equal_nan=True)
+    assert np.linalg.norm(b["grad_field"]) > 0
+
+
+def _one_iteration_case():
+    prof, radius, length = CR.profile("luneburg65"), 1.0, 2.0
+    ds = radius / 65 / 2
+    pos = np.array([[1.31, length + 0.4 * ds, 0.82]], np.float32)      # past the far end, heading on: stops at once
+    vel = np.array([[0.1, 1.0, -0.05]], np.float32)
+    return dict(prof=prof, field=field_profile(65, 1), radius=radius, length=length, ds=ds, pos=pos, vel=vel,
+                tg=pos + 5.0 * vel, dx=np.array([[0.3, -1.2, 0.7]], np.float32), dv=np.array([[-0.4, 0.9, 0.2]], np.float32),
+                dtau=np.array([0.8], np.float32))
+
+
+def test_one_iteration_closed_form():
+    """j = K = 1, worked by hand: tau = ds n(x0) a(x0); dvel = mu = dv + ds dx; dpos = dx + ds J(x0)^T mu
+    + dtau ds (a grad n + n grad a)(x0), J = d(n grad n)/dx at x0; the profile gradient is d/dprof of
+    ds mu . (n grad n)(x0) + dtau ds n(x0) a(x0), the field gradient d/dfield of dtau ds n(x0) a(x0): the two lerp weights
+    times dtau ds n(x0)."""
+    s = _one_iteration_case()
+    k = host_forward(s)
+    assert k["rec_steps"][0] == 1 and k["steps"][0] == 1
+    b = host_back(s, k)
+    ds = s["ds"]
+    P = torch.tensor(s["prof"], dtype=torch.float64, requires_grad=True)
+    A = torch.tensor(s["field"], dtype=torch.float64, requires_grad=True)
+    x0 = torch.tensor(s["pos"][0], dtype=torch.float64, requires_grad=True)
+    f = lambda y: cable_ad.sample(P.detach(), s["radius"], y[None])[1][0]            # noqa: E731
+    J = torch.autograd.functional.jacobian(f, x0.detach()).numpy()
+    n0, ngn = cable_ad.sample(P, s["radius"], x0[None])
+    a0 = cable_field_ad.sample_field(A, s["radius"], x0[None])
+    mu = s["dv"][0].astype(np.float64) + ds * s["dx"][0]
+    dtau = float(s["dtau"][0])
+    term = dtau * ds * n0[0] * a0[0]
+    pull, = torch.autograd.grad(term, x0, retain_graph=True)                # dtau ds (a grad n + n grad a)
+    assert np.abs(pull.numpy()).max() > 1e-4
+    np.testing.assert_allclose(k["tau"][0], ds * float(n0.detach()) * float(a0.detach()), rtol=1e-6)
+    np.testing.assert_allclose(b["dvel"][0], mu, rtol=1e-6)
+    np.testing.assert_allclose(b["dpos"][0], s["dx"][0] + ds * J.T @ mu + pull.numpy(), rtol=1e-5, atol=1e-6)
+    g, gf = torch.autograd.grad(ds * (ngn[0] * torch.tensor(mu)).sum() + term, (P, A))
+    assert np.abs(g.numpy()).max() > 0.01 and np.count_nonzero(b["grad"]) == 2
+    np.testing.assert_allclose(b["grad"], g.numpy(), rtol=1e-5, atol=1e-6 * np.abs(g.numpy()).max())
+    # the hand-worked field gradient: the cell and weight of x0, times dtau ds n(x0)
+    r = float(np.hypot(float(s["pos"][0, 0]) - s["radius"], float(s["pos"][0, 2]) - s["radius"])) * 64 / s["radius"]
+    i0, w0 = int(r), r - int(r)
+    want = np.zeros(65); want[i0], want[i0 + 1] = 1 - w0, w0
+    want *= dtau * ds * float(n0.detach())
+    assert np.count_nonzero(b["grad_field"]) == 2 and abs(w0 - 0.5) > 0.05      # the two weights differ: a swap shows
+    np.testing.assert_allclose(b["grad_field"], want, rtol=2e-5, atol=0)
+    np.testing.assert_allclose(gf.numpy(), want, rtol=1e-12, atol=0)
+
+
+# ---- CPU tier: identities -------------------------------------------------------------------------------------------
+IDENTITY_CASES = list(CR.SCENES) + ["fuzz1", "fuzz2"]
+
+
+@pytest.mark.parametrize("name", IDENTITY_CASES)
+def test_forward_is_trace_cable_and_with_the_profile_its_opl(name):
+    """xt, vt, dist2 and the statistics are cable_trace_ray's bit for bit and rec_steps is cable_trace_opl_ray's, whatever
+    the field; with field = rif (a copy, and the same array) tau is cable_trace_opl_ray's opl bit for bit; j = 0 has
+    tau = 0."""
+    s = scene(name)
+    k = host_forward(s)
+    t = HC.trace_cable(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["ds"])
+    o = opl_forward(s)
+    for key in ("xt", "vt", "dist2"):
+        assert np.array_equal(k[key], t[key], equal_nan=True), key
+    assert k["ray_steps"] == t["steps_total"]
+    assert np.array_equal(k["rec_steps"], o["rec_steps"]) and np.array_equal(k["steps"], o["steps"])
+    assert (k["tau"][k["rec_steps"] == 0] == 0).all() and (k["rec_steps"] <= k["steps"]).all()
+    for same in (s["prof"].copy(), s["prof"]):
+        assert np.array_equal(host_forward(s, field=same)["tau"], o["opl"], equal_nan=True)
+    assert not np.array_equal(k["tau"], o["opl"])
+
+
+@pytest.mark.parametrize("name", IDENTITY_CASES)
+def test_with_the_profile_as_field_the_two_gradients_sum_to_the_opl_gradient(name):
+    """field = rif, dopl = dtau: grad + grad_field is backtrace_cable_opl's grad within ATOMIC_TOL (2 dopl n_k is split into
+    dtau a_k here and fv there; the ray gradients carry it through dn there and through a' here), and so are dpos and dvel to
+    rounding."""
+    s = scene(name)
+    k = host_forward(s, field=s["prof"])
+    b = host_back(s, k, field=s["prof"])
+    o = opl_back(s, k, s["dtau"])
+    assert np.linalg.norm(b["grad_field"]) > 0 and np.linalg.norm(o["grad"]) > 0
+    e = cases.rel_l2(b["grad"] + b["grad_field"], o["grad"])
+    print(f"{name}: rel-L2 of the sum against the OPL gradient {e:.3e}")
+    assert e <= ATOMIC_TOL
+    fin = np.isfinite(o["dpos"]).all(1) & np.isfinite(o["dvel"]).all(1)
+    assert fin.mean() > 0.9
+    assert cases.rel_l2(b["dpos"][fin], o["dpos"][fin]) <= ATOMIC_TOL and cases.rel_l2(b["dvel"][fin], o["dvel"][fin]) <= ATOMIC_TOL
+
+
+@pytest.mark.parametrize("name", IDENTITY_CASES)
+def test_without_dtau_it_is_the_opl_adjoint_without_dopl(name):
+    """dtau = 0 (zeros, and a null pointer): dpos and dvel equal cable_backtrace_ray_state's bit for bit, grad equals
+    backtrace_cable_opl's with dopl null bit for bit, and grad_field is exactly zero."""
+    s = scene(name)
+    k = host_forward(s)
+    r = CR.host(s)
+    o = opl_back(s, k, None)
+    for dtau in (np.zeros_like(s["dtau"]), None):
+        b = H.backtrace_cable_field(s["prof"], s["field"], s["radius"], s["length"], s["pos"], k["xt"], k["vt"],
+                                    k["rec_steps"], s["dx"], s["dv"], dtau, s["ds"])
+        assert np.array_equal(b["dpos"], r["dpos"], equal_nan=True) and np.array_equal(b["dvel"], r["dvel"], equal_nan=True)
+        assert np.array_equal(b["grad"], o["grad"], equal_nan=True) and np.linalg.norm(np.nan_to_num(o["grad"])) > 0
+        assert not b["grad_field"].any()
+        assert b["ray_steps"] == int(r["jstar"].astype(np.int64).sum())
+
+
+@pytest.mark.parametrize("name", list(CR.SCENES))
+def test_record_on_the_input_gives_the_identity(name):
+    """j = 0: (dpos, dvel) = (dx, dv) bit for bit whatever dtau, and no contribution to either gradient."""
+    s = scene(name)
+    k = host_forward(s)
+    z = k["rec_steps"] == 0
+    assert z.sum() >= 10
+    b = host_back(s, k, sel=z)
+    assert np.array_equal(b["dpos"], s["dx"][z]) and np.array_equal(b["dvel"], s["dv"][z])
+    assert not b["grad"].any() and not b["grad_field"].any() and b["ray_steps"] == 0 and b["n_failed"] == 0
+
+
+def _poison(k, ms):
+    rec = k["rec_steps"].copy()
+    rec[0::4], rec[1::4] = ms + 1, 0xFFFFFFFF
+    bad = np.zeros(len(rec), bool); bad[0::4] = bad[1::4] = True
+    return rec, bad
+
+
+@pytest.mark.parametrize("name", ["two_samples", "luneburg65_multi"])
+def test_poisoned_rec_steps_are_refused(name):
+    """rec_steps above the forward's bound (max_steps + 1, 0xFFFFFFFF): no iterations, zero gradients, counted failed, and
+    the other rays are untouched; max_steps itself is a count the forward can return and is marched."""
+    s = scene(name)
+    k = host_forward(s)
+    ms = H.max_steps(s["length"], s["ds"])
+    assert k["steps"].max() == ms
+    rec, bad = _poison(k, ms)
+    good = host_back(s, k)
+    b = host_back(s, k, rec=rec)
+    assert np.array_equal(b["failed"], bad) and b["n_failed"] == bad.sum()
+    assert not b["dpos"][bad].any() and not b["dvel"][bad].any() and not b["steps"][bad].any()
+    assert np.array_equal(b["dpos"][~bad], good["dpos"][~bad]) and np.array_equal(b["dvel"][~bad], good["dvel"][~bad])
+    assert b["ray_steps"] == int(k["rec_steps"][~bad].astype(np.int64).sum())
+    only_good = host_back(s, k, sel=~bad)
+    assert np.array_equal(b["grad"], only_good["grad"]) and np.array_equal(b["grad_field"], only_good["grad_field"])
+    edge = H.backtrace_cable_field(s["prof"], s["field"], s["radius"], s["length"], s["pos"][:1], s["pos"][:1], s["vel"][:1],
+                                   np.array([ms], np.uint32), s["dx"][:1], s["dv"][:1], s["dtau"][:1], s["ds"])
+    assert not edge["failed"][0] and edge["steps"][0] == ms
+
+
+# ---- CPU tier: the C ABI (no GPU) and the Python surface ------------------------------------------------------------
+def test_abi_and_python_surface():
+    """The C symbols are exported and bound, the two profile ids are named in the open table and in no other, the header
+    defines them, the methods and the class exist."""
+    from adjointnonlinearraytracing_amd import _lib, drrt, tracer
+    lib = C.CDLL(_lib.LIB_PATH)
+    for name in ("drrt_trace_cable_field_f32", "drrt_backtrace_cable_field_f32"):
+        assert hasattr(lib, name) and name in _lib.SIGNATURES, name
+    assert _lib.PROF_NAMES_LATER[21] == "trace_cable_field" and _lib.PROF_NAMES_LATER[22] == "backtrace_cable_field"
+    for other in (_lib.PROF_NAMES, _lib.PROF_NAMES_MORE):
+        assert 21 not in other and 22 not in other
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "drrt_hip.h")).read()
+    assert "#define DRRT_PROF_TRACE_CABLE_FIELD 21" in hdr and "#define DRRT_PROF_BACKTRACE_CABLE_FIELD 22" in hdr
+    assert callable(drrt.TracerC.trace_cable_field) and callable(drrt.TracerC.backtrace_cable_field)
+    assert issubclass(tracer.CableFieldTracerC, torch.autograd.Function)
+    with pytest.raises(RuntimeError, match="nothing to compute"):
+        drrt.TracerC().backtrace_cable_field(*[None] * 12, want_rif=False, want_field=False, want_rays=False)
+
+
+def _abi_calls():
+    from adjointnonlinearraytracing_amd import _lib
+    lib = _lib.load()
+    one, two = 0x1000, 0x2000    # non-null pointers that are never dereferenced: every row is refused before a HIP call
+    fwd = dict(rif=one, field=one, rres=64, radius=1.0, length=1.0, n=128, pos=one, vel=one, target=one, ds=0.5, xt=one,
+               vt=one, dist2=one, tau=one, rec_steps=one)
+    back = dict(rif=one, field=one, rres=64, radius=1.0, length=1.0, n=128, pos=one, xt=one, vt=one, rec_steps=one, dx=one,
+                dv=one, dtau=one, ds=0.5, grad=None, grad_field=None, dpos=one, dvel=one)
+    tail = (None, None, 0, 0, None)
+
+    def call(entry, **kw):
+        base = dict(fwd if entry == "drrt_trace_cable_field_f32" else back, **kw)
+        flags = base.pop("flags", 0)
+        return getattr(lib, entry)(*base.values(), *tail[:3], flags, tail[4])
+    return _lib, lib, call, two
+
+
+def test_abi_refusals():
+    """What drrt_backtrace_cable_opl_f32 and the other cable entries refuse comes back with their code and message (a null
+    profile, a bad profile length, a bad radius / length / step, null rays, a null rec_steps, lone dpos / dvel); the new
+    refusals -- a null field, nothing asked for, grad == grad_field -- have their own; a refusal consumes an armed order
+    hint; n = 0 is DRRT_OK and clears the message."""
+    _lib, lib, call, two = _abi_calls()
+    A, R = _lib.ERR_ARG, _lib.ERR_BAD_RES
+    F, B = "drrt_trace_cable_field_f32", "drrt_backtrace_cable_field_f32"
+    pos = "radius, length and ds must be positive and finite"
+    shared = [(dict(rif=None, rres=1), A, "null rif pointer"), (dict(field=None, rres=1), A, "null field pointer"),
+              (dict(rif=None, field=None), A, "null rif pointer"),
+              (dict(rres=1, radius=0.0), R, "volume: invalid resolution!"),
+              (dict(rres=1 << 31), R, "volume: invalid resolution!"), (dict(radius=0.0, pos=None, n=1 << 33), A, pos),
+              (dict(length=float("nan")), A, pos), (dict(ds=0.0), A, pos), (dict(ds=float("inf")), A, pos)]
+    rows = [(F, *r) for r in shared] + [(B, *r) for r in shared]
+    rows += [(F, dict(**{key: None}), A, "null ray pointer") for key in ("pos", "vel", "target", "xt", "vt", "dist2")]
+    rows += [(F, dict(tau=None), A, "null tau/rec_steps pointer"), (F, dict(rec_steps=None), A, "null tau/rec_steps pointer"),
+             (F, dict(pos=None, tau=None), A, "null ray pointer")]
+    rows += [(B, dict(**{key: None}), A, "null ray pointer") for key in ("pos", "xt", "vt")]
+    nothing = "nothing to compute: grad, grad_field, dpos and dvel are all null"
+    alias = "grad and grad_field must be two arrays"
+    rows += [(B, dict(rec_steps=None), A, "null rec_steps pointer (the forward's rec_steps)"),
+             (B, dict(dpos=None, dvel=None), A, nothing),
+             (B, dict(dpos=None, dvel=None, rres=1), A, nothing),
+             (B, dict(dpos=None), A, "dpos and dvel go together"),
+             (B, dict(dvel=None, grad=two, flags=_lib.FLAG_NO_ZERO), A, "dpos and dvel go together"),
+             (B, dict(dvel=None, grad_field=two, flags=_lib.FLAG_NO_ZERO), A, "dpos and dvel go together"),
+             (B, dict(grad=two, grad_field=two, flags=_lib.FLAG_NO_ZERO), A, alias),
+             (B, dict(grad=two, grad_field=two, dpos=None, dvel=None, flags=_lib.FLAG_NO_ZERO), A, alias),
+             (B, dict(field=None, dpos=None, dvel=None), A, "null field pointer"),
+             (B, dict(rif=None, dpos=None, dvel=None), A, "null rif pointer")]
+    for entry, kw, rc, msg in rows:
+        lib.drrt_set_order_hint(C.c_void_p(0xDEAD0000), 77)
+        assert lib.drrt_order_hint_pending() == 77
+        assert call(entry, **kw) == rc, (entry, kw)
+        assert _lib.last_error() == msg, (entry, kw, _lib.last_error())
+        assert lib.drrt_order_hint_pending() == 0, (entry, kw)
+    # the seeds are optional: null dx, dv and dtau are no refusal (n = 0: nothing is launched, nothing dereferenced)
+    for entry, kw in ((F, dict(n=0)), (F, dict(n=0, pos=None, tau=None)), (B, dict(n=0, dx=None, dv=None, dtau=None)),
+                      (B, dict(n=0, rec_steps=None))):
+        lib.drrt_set_order_hint(C.c_void_p(0xDEAD0000), 77)
+        assert call(entry, **kw) == 0 and _lib.last_error() == "" and lib.drrt_order_hint_pending() == 0, (entry, kw)
+
+
+# ---- CPU tier: the two routines under sanitizers --------------------------------------------------------------------
+def test_routines_under_sanitizers(tmp_path):
+    """tests/hostcheck/cable_field_rays.hip with -DCABLE_FIELD_MAIN: a stand-alone program over the two routines, compiled
+    for the host with ASan + UBSan and run directly (nothing preloaded): NaN / Inf positions, velocities, targets, seeds and
+    entries of both profiles, a 2-sample pair, the profile as its own field, and the poisoned rec_steps -- no report, every
+    loop ends, the poisoned rays are refused."""
+    hipcc = "/opt/rocm/bin/hipcc"
+    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
+    if not rt or not os.path.exists(hipcc):
+        pytest.skip("no clang sanitizer runtime in this image")
+    exe = str(tmp_path / "cable_field_sanitize")
+    subprocess.run([hipcc, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DCABLE_FIELD_MAIN",
+                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, H.SOURCE],
+                   check=True, capture_output=True)
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
+    assert "1024 poisoned rays refused" in r.stdout
+
+
+# ---- GPU tier -------------------------------------------------------------------------------------------------------
+def _gpu_scene(rres, n=65):
+    """`n` rays of the luneburg65_half ray sets (every set and every kind of record among 65) on profiles of `rres` samples.
+    Above the LDS limit of the outputs asked for (2048 samples with both profile gradients, 3072 with one, 4096 with none and
+    in the forward) the kernels read both profiles from global memory and add to the gradients with global atomics."""
+    s = scene("luneburg65_half")
+    sel = np.random.default_rng(3).choice(len(s["pos"]), 65, replace=False)[:n]
+    for key in RAY_KEYS:
+        s[key] = s[key][sel]
+    if rres == 2:
+        s["prof"] = CR.profile("two")
+    elif rres == 33:
+        s["prof"] = CR.profile("random33")
+    elif rres != 65:
+        s["prof"] = (1.5 - 0.4 * np.linspace(0, 1, rres) ** 2 + 0.01 * np.sin(np.arange(rres))).astype(np.float32)
+    s["field"] = field_profile(rres, rres)
+    return s
+
+
+def _dev_forward(T, s, dev):
+    return T.trace_cable_field(_t(s["prof"], dev), _t(s["field"], dev), s["radius"], s["length"], _t(s["pos"], dev),
+                               _t(s["vel"], dev), _t(s["tg"], dev), s["ds"])
+
+
+def _dev_back(T, s, k, dev, mode="all", **kw):
+    seeds = [None if name in MODES[mode] else _t(s[name], dev) for name in ("dx", "dv", "dtau")]
+    return T.backtrace_cable_field(_t(s["prof"], dev), _t(s["field"], dev), s["radius"], s["length"], _t(s["pos"], dev),
+                                   _t(k["xt"], dev), _t(k["vt"], dev), _t(k["rec_steps"].astype(np.int32), dev), *seeds,
+                                   s["ds"], **kw)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", [65, 1, 0])
+@pytest.mark.parametrize("rres", [2, 33, 65, 4096, 4097])
+def test_forward_kernel_matches_host_bitwise(gpu, rres, n):
+    """k_trace_cable_field == the host build bit for bit (xt, vt, dist2, tau, rec_steps) and in its statistics, with both
+    profiles in LDS (up to 4096 samples) and in global memory (4097); xt, vt, dist2 are also trace_cable's on the device,
+    and with the profile as the field tau is trace_cable_opl's."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(rres, n)
+    k = host_forward(s)
+    T = drrt.TracerC()
+    out = _dev_forward(T, s, gpu)
+    st = drrt.read_stats()
+    assert out[4].dtype == torch.int32
+    for got, key in zip(out, ("xt", "vt", "dist2", "tau", "rec_steps")):
+        assert np.array_equal(got.cpu().numpy().view(k[key].dtype).reshape(k[key].shape), k[key], equal_nan=True), key
+    assert (st["ray_steps"], st["iters"], st["n_failed"]) == (k["ray_steps"], k["iters"], k["n_failed"])
+    if n == 65:
+        assert len(set(k["rec_steps"])) > 10 and (k["rec_steps"] == 0).any() and k["tau"].any()
+    dev = [_t(s[key], gpu) for key in ("pos", "vel", "tg")]
+    ref = T.trace_cable(_t(s["prof"], gpu), s["radius"], s["length"], *dev, s["ds"])
+    assert all(torch.equal(a, b) for a, b in zip(out[:3], ref))
+    prof = _t(s["prof"], gpu)
+    same = T.trace_cable_field(prof, prof, s["radius"], s["length"], *dev, s["ds"])
+    opl = T.trace_cable_opl(prof, s["radius"], s["length"], *dev, s["ds"])
+    assert torch.equal(same[3], opl[3]) and torch.equal(same[4], opl[4])
+
+
+def _repeat(s, k, times):
+    s2 = dict(s)
+    for key in RAY_KEYS:
+        s2[key] = np.repeat(s[key], times, axis=0)
+    k2 = {key: np.repeat(k[key], times, axis=0) for key in ("xt", "vt", "rec_steps")}
+    return s2, k2
+
+
+COMBOS = [c for c in itertools.product((True, False), repeat=3) if any(c)]      # (want_rif, want_field, want_rays): seven
+
+
+def _check_adjoint(T, s, k, gpu, combo, modes):
+    from adjointnonlinearraytracing_amd import drrt
+    want_rif, want_field, want_rays = combo
+    for mode in modes:
+        b = host_back(s, k, mode)
+        grad, gfield, dpos, dvel = _dev_back(T, s, k, gpu, mode, want_rif=want_rif, want_field=want_field,
+                                             want_rays=want_rays)
+        st = drrt.read_stats()
+        assert [t is not None for t in (grad, gfield, dpos, dvel)] == [want_rif, want_field, want_rays, want_rays]
+        if want_rays:
+            assert np.array_equal(dpos.cpu().numpy(), b["dpos"], equal_nan=True)
+            assert np.array_equal(dvel.cpu().numpy(), b["dvel"], equal_nan=True)
+        for got, key in ((grad, "grad"), (gfield, "grad_field")):
+            if got is None:
+                continue
+            g = got.cpu().numpy()
+            assert g.shape == b[key].shape
+            if len(s["pos"]) and not (key == "grad_field" and mode == "rays"):
+                assert np.linalg.norm(b[key]) > 0 and cases.rel_l2(g, b[key]) <= ATOMIC_TOL, (key, mode, cases.rel_l2(g, b[key]))
+            else:
+                assert not g.any()
+        assert (st["ray_steps"], st["iters"], st["n_failed"]) == (b["ray_steps"], b["iters"], 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("combo", COMBOS, ids=lambda c: "".join(ch for ch, on in zip("pfr", c) if on))
+@pytest.mark.parametrize("order", ["random", "quad", "pair", "one", "none"])
+def test_adjoint_kernel_matches_host(gpu, order, combo):
+    """k_backtrace_cable_field<PROFILE, FIELD, RAYS> against the host build: dpos and dvel bit for bit, both profile
+    gradients within ATOMIC_TOL, the statistics equal -- with the rays in random order (plain LDS adds), every ray 4x in a
+    row (the quad pre-reduction), 2x in a row (the pair one), one ray and none; all seven output combinations; every seed
+    mode on the runs with every output."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(65, dict(one=1, none=0).get(order, 65))
+    k = host_forward(s)
+    s, k = _repeat(s, k, dict(quad=4, pair=2).get(order, 1))
+    _check_adjoint(drrt.TracerC(), s, k, gpu, combo, MODES if all(combo) else ("all",))
+
+
+LDS_EDGES = [(2048, (True, True, True)), (2049, (True, True, True)), (2048, (True, True, False)), (2049, (True, True, False)),
+             (3072, (True, False, True)), (3073, (True, False, True)), (3072, (False, True, False)),
+             (3073, (False, True, False)), (4096, (False, False, True)), (4097, (False, False, True))]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rres,combo", LDS_EDGES)
+def test_adjoint_kernel_on_both_sides_of_the_lds_limits(gpu, rres, combo):
+    """65 rays on either side of each LDS limit -- 2048 | 2049 samples with both profile gradients (49 152 B of LDS at 2048),
+    3072 | 3073 with one, 4096 | 4097 with the ray gradients alone: on the far side the profiles are read from global memory
+    and the contributions go into global atomics.  Same comparison as test_adjoint_kernel_matches_host."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(rres)
+    k = host_forward(s)
+    _check_adjoint(drrt.TracerC(), s, k, gpu, combo, ("all",))
+
+
+@pytest.mark.gpu
+def test_adjoint_kernel_into_and_poison(gpu):
+    """`into=` / `into_field=` add to the caller's tensors (DRRT_FLAG_NO_ZERO covers both gradients) and return them; with
+    one of them given the other gradient is still the plain one; poisoned rec_steps on the device: zero gradients, n_failed
+    counts them, the other rays and the two gradients are those of the call without them."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(65)
+    k = host_forward(s)
+    T = drrt.TracerC()
+    b = host_back(s, k)
+    fill, fill_f = torch.full((65,), 3.0, device=gpu), torch.full((65,), -2.0, device=gpu)
+    grad, gfield, _, _ = _dev_back(T, s, k, gpu, into=fill, into_field=fill_f)
+    assert grad.data_ptr() == fill.data_ptr() and gfield.data_ptr() == fill_f.data_ptr()
+    assert cases.rel_l2(fill.cpu().numpy().astype(np.float64) - 3.0, b["grad"]) <= ATOMIC_TOL
+    assert cases.rel_l2(fill_f.cpu().numpy().astype(np.float64) + 2.0, b["grad_field"]) <= ATOMIC_TOL
+    fill_f = torch.full((65,), -2.0, device=gpu)
+    grad, gfield, _, _ = _dev_back(T, s, k, gpu, into_field=fill_f, want_rays=False)
+    assert gfield.data_ptr() == fill_f.data_ptr() and cases.rel_l2(grad.cpu().numpy(), b["grad"]) <= ATOMIC_TOL
+    assert cases.rel_l2(fill_f.cpu().numpy().astype(np.float64) + 2.0, b["grad_field"]) <= ATOMIC_TOL
+    with pytest.raises(RuntimeError, match="`into_field` must be"):
+        _dev_back(T, s, k, gpu, into_field=torch.zeros(64, device=gpu))
+    with pytest.raises(RuntimeError, match="second profile must have the 65 samples"):
+        T.trace_cable_field(_t(s["prof"], gpu), _t(s["field"][:64], gpu), s["radius"], s["length"], _t(s["pos"], gpu),
+                            _t(s["vel"], gpu), _t(s["tg"], gpu), s["ds"])
+    rec, bad = _poison(k, H.max_steps(s["length"], s["ds"]))
+    hb = host_back(s, k, rec=rec)
+    old = drrt.options.check_failed
+    drrt.options.check_failed = False
+    try:
+        grad, gfield, dpos, dvel = _dev_back(T, s, dict(k, rec_steps=rec.view(np.int32)), gpu)
+    finally:
+        drrt.options.check_failed = old
+    st = drrt.read_stats()
+    assert st["n_failed"] == bad.sum() and st["ray_steps"] == hb["ray_steps"]
+    assert np.array_equal(dpos.cpu().numpy(), hb["dpos"]) and np.array_equal(dvel.cpu().numpy(), hb["dvel"])
+    assert not dpos.cpu().numpy()[bad].any() and cases.rel_l2(grad.cpu().numpy(), hb["grad"]) <= ATOMIC_TOL
+    assert cases.rel_l2(gfield.cpu().numpy(), hb["grad_field"]) <= ATOMIC_TOL
+
+
+@pytest.mark.gpu
+def test_grid_stride_loop(gpu):
+    """1024 kBlock + 65 rays, the 65-ray set tiled: the launch is capped at 1024 blocks, so every block takes a second
+    trip and one takes a third.  Per-ray outputs equal the small call's bit for bit, each profile gradient is the small
+    call's times the tiling (4033 whole tilings plus the first 64 rays) within ATOMIC_TOL."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(65)
+    T = drrt.TracerC()
+    small = _dev_forward(T, s, gpu)
+    k = {key: small[i].cpu().numpy() for i, key in ((0, "xt"), (1, "vt"), (4, "rec_steps"))}
+    g_small, f_small, dpos_small, dvel_small = _dev_back(T, s, k, gpu)
+    n = 1024 * K_BLOCK + 65
+    idx = np.arange(n) % 65
+    big = dict(s, **{key: s[key][idx] for key in RAY_KEYS})
+    out = _dev_forward(T, big, gpu)
+    tix = torch.as_tensor(idx, device=gpu)
+    for a, b in zip(out, small):
+        assert torch.equal(a, b[tix])
+    kb = {key: out[i].cpu().numpy() for i, key in ((0, "xt"), (1, "vt"), (4, "rec_steps"))}
+    g, f, dpos, dvel = _dev_back(T, big, kb, gpu)
+    assert torch.equal(dpos, dpos_small[tix]) and torch.equal(dvel, dvel_small[tix])
+    # 1024 * 256 + 65 = 4033 * 65 + 64: 4033 whole tilings and the first 64 rays once more
+    tiles = np.bincount(idx, minlength=65)
+    assert tiles.min() == tiles[64] == 4033 and (tiles[:64] == 4034).all()
+    first = dict(s, **{key: s[key][:64] for key in RAY_KEYS})
+    g_first, f_first, _, _ = _dev_back(T, first, {key: k[key][:64] for key in k}, gpu, want_rays=False)
+    for got, one, head in ((g, g_small, g_first), (f, f_small, f_first)):
+        want = one.cpu().numpy().astype(np.float64) * 4033 + head.cpu().numpy().astype(np.float64)
+        assert cases.rel_l2(got.cpu().numpy().astype(np.float64), want) <= ATOMIC_TOL
+
+
+def _tracer_scene():
+    """Every ray of luneburg65_half (480) on 9-sample profiles."""
+    s = scene("luneburg65_half")
+    s["prof"] = np.sqrt(2.0 - np.linspace(0, 1, 9) ** 2).astype(np.float32)
+    s["field"] = field_profile(9, 9)
+    return s
+
+
+def _apply(s, dev, rif_grad=True, a_grad=True, x_grad=True, v_grad=True):
+    from adjointnonlinearraytracing_amd import tracer
+    rif = _t(s["prof"], dev).requires_grad_(rif_grad)
+    a = _t(s["field"], dev).requires_grad_(a_grad)
+    x = _t(s["pos"], dev).requires_grad_(x_grad)
+    v = _t(s["vel"], dev).requires_grad_(v_grad)
+    xt, vt, d2, tau = tracer.CableFieldTracerC.apply(rif, a, s["radius"], s["length"], x, v, _t(s["tg"], dev), s["ds"])
+    assert not d2.requires_grad
+    if rif_grad or a_grad or x_grad or v_grad:
+        loss = (xt * _t(s["dx"], dev)).sum() + (vt * _t(s["dv"], dev)).sum() + (tau * _t(s["dtau"], dev)).sum() + d2.sum()
+        loss.backward()
+    torch.cuda.synchronize()
+    return (xt, vt, d2, tau), (rif.grad, a.grad, x.grad, v.grad)
+
+
+WANTS = [(True, True, True, True), (True, False, False, False), (False, True, False, False), (False, False, True, False),
+         (False, False, False, True), (True, True, False, False), (False, True, True, True)]
+
+
+@pytest.mark.gpu
+def test_cablefieldtracer_end_to_end(gpu):
+    """CableFieldTracerC.apply -> linear loss -> backward on 9 profile samples and 480 rays: the outputs and the gradients
+    are the direct calls' (the ray gradients bit for bit, the profile gradients within ATOMIC_TOL), whichever inputs require
+    grad; dist2 does not require grad; a second profile of another length raises before any launch."""
+    from adjointnonlinearraytracing_amd import _lib, drrt, tracer
+    s = _tracer_scene()
+    T = drrt.TracerC()
+    direct = _dev_forward(T, s, gpu)
+    k = {key: direct[i].cpu().numpy() for i, key in ((0, "xt"), (1, "vt"), (4, "rec_steps"))}
+    grad, gfield, dpos, dvel = _dev_back(T, s, k, gpu)
+    assert float(grad.abs().sum()) > 0 and float(gfield.abs().sum()) > 0 and float(dpos.abs().sum()) > 0
+    for want in WANTS:
+        out, (g, ga, gx, gv) = _apply(s, gpu, *want)
+        assert all(torch.equal(a, b) for a, b in zip(out, direct[:4]))
+        assert [t is not None for t in (g, ga, gx, gv)] == list(want)
+        assert g is None or cases.rel_l2(g.cpu().numpy(), grad.cpu().numpy()) <= ATOMIC_TOL
+        assert ga is None or cases.rel_l2(ga.cpu().numpy(), gfield.cpu().numpy()) <= ATOMIC_TOL
+        assert (gx is None or torch.equal(gx, dpos)) and (gv is None or torch.equal(gv, dvel))
+    args = (s["radius"], s["length"], _t(s["pos"], gpu), _t(s["vel"], gpu), _t(s["tg"], gpu), s["ds"])
+    lib = _lib.load()
+    lib.drrt_profile_begin(16)
+    try:
+        with pytest.raises(RuntimeError, match="second profile must have the 9 samples"):
+            tracer.CableFieldTracerC.apply(_t(s["prof"], gpu), _t(s["field"][:8], gpu), *args)
+        assert _lib.profile_collect() == []
+    finally:
+        lib.drrt_profile_end()
+    with pytest.raises(RuntimeError, match="float32"):
+        tracer.CableFieldTracerC.apply(_t(s["prof"], gpu), _t(s["field"], gpu), s["radius"], s["length"],
+                                       _t(s["pos"], gpu).double().requires_grad_(True), *args[3:])
+
+
+@pytest.mark.gpu
+def test_cablefieldtracer_launches(gpu):
+    """Forward: ["trace_cable_field"].  Backward: exactly ONE backtrace_cable_field launch whatever subset of the inputs
+    requires grad; none when nothing does."""
+    from adjointnonlinearraytracing_amd import _lib
+    s = _tracer_scene()
+    lib = _lib.load()
+
+    def launches(*want):
+        lib.drrt_profile_begin(256)
+        try:
+            _apply(s, gpu, *want)
+            return [name for name, _ in _lib.profile_collect()]
+        finally:
+            lib.drrt_profile_end()
+    assert launches(False, False, False, False) == ["trace_cable_field"]
+    for want in WANTS:
+        assert launches(*want) == ["trace_cable_field", "backtrace_cable_field"], want
+
+
+@pytest.mark.gpu
+def test_group_delay_demo(gpu):
+    """examples/fiber_group_delay_demo.py, three iterations at 9 profile samples: a finite spread and a non-zero profile
+    gradient."""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "examples"))
+    try:
+        import fiber_group_delay_demo
+    finally:
+        sys.path.pop(0)
+    n, hist, gmax = fiber_group_delay_demo.run(res=9, iters=3, n_rays=1024, verbose=False)
+    print(f"group delay demo: rms spread {hist[0]:.6f} -> {hist[-1]:.6f}, max |grad| {gmax}")
+    assert n.shape == (9,) and bool(torch.isfinite(n).all()) and len(hist) == 3
+    assert np.isfinite(hist).all() and np.isfinite(gmax).all() and min(gmax) > 0

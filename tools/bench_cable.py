@@ -7,7 +7,15 @@ of k_backtrace_cable is for).  Two JSON lines.
 
 times, at the same sizes and for both orders, trace_cable_opl against trace_cable, and backtrace_cable_opl (profile only,
 rays only, both) against backtrace_cable and backtrace_cable_rays: the calls alternate in one session, every figure is the
-median of 7 single calls between device events.  One JSON line, also written to OUT.json."""
+median of 7 single calls between device events.  One JSON line, also written to OUT.json.
+
+    python tools/bench_cable.py field [OUT.json]
+
+times, the same way, trace_cable_field against trace_cable_opl, and backtrace_cable_field (profile only, field only, both
+profile gradients, rays only, everything) against backtrace_cable_opl (profile only, rays only, both); the second profile
+is a group index N_g = n + 0.5 (n - n_cladding).  `ratios`: the forward to trace_cable_opl; the adjoint's profile-only,
+field-only and both-gradients runs to backtrace_cable_opl's profile-only run, rays only to its rays-only run, everything to
+its run with both outputs."""
 import sys, json, torch, numpy as np
 sys.path.insert(0,'.')
 from adjointnonlinearraytracing_amd import drrt
@@ -68,5 +76,41 @@ def opl_times(pos,vel):
     return out
 if mode=='opl':
     res=dict(rays=n,rres=rres,random_order_ms=opl_times(pos,vel),pixel_order_ms=opl_times(pos2,vel2))
+    print(json.dumps(res))
+    if len(sys.argv)>2: json.dump(res,open(sys.argv[2],'w'),indent=1)
+
+def field_times(pos,vel):
+    """{call: median ms of 7}, the calls taken in turn 7 times over, and the ratios to the OPL pair."""
+    fld=prof+0.5*(prof-prof[-1])
+    xt,vt,_,tau,rec=T.trace_cable_field(prof,fld,radius,length,pos,vel,tg,ds)
+    dtau=torch.ones_like(tau)
+    bo=lambda **kw: (lambda: T.backtrace_cable_opl(prof,radius,length,pos,xt,vt,rec,one,one,dtau,ds,**kw))
+    bf=lambda r,f,y: (lambda: T.backtrace_cable_field(prof,fld,radius,length,pos,xt,vt,rec,one,one,dtau,ds,r,f,y))
+    calls=dict(
+        trace_cable_opl=lambda: T.trace_cable_opl(prof,radius,length,pos,vel,tg,ds),
+        trace_cable_field=lambda: T.trace_cable_field(prof,fld,radius,length,pos,vel,tg,ds),
+        backtrace_cable_opl_profile=bo(rays=False), backtrace_cable_opl_rays=bo(profile=False), backtrace_cable_opl_both=bo(),
+        backtrace_cable_field_profile=bf(True,False,False), backtrace_cable_field_field=bf(False,True,False),
+        backtrace_cable_field_both_profiles=bf(True,True,False), backtrace_cable_field_rays=bf(False,False,True),
+        backtrace_cable_field_everything=bf(True,True,True))
+    for fn in calls.values(): fn()
+    torch.cuda.synchronize()
+    ms={k:[] for k in calls}
+    for _ in range(7):
+        for k,fn in calls.items():
+            a,b=torch.cuda.Event(enable_timing=True),torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); b.record(); torch.cuda.synchronize(); ms[k].append(a.elapsed_time(b))
+    out={k:float(np.median(v)) for k,v in ms.items()}
+    out['ratios']=dict(
+        forward=out['trace_cable_field']/out['trace_cable_opl'],
+        profile=out['backtrace_cable_field_profile']/out['backtrace_cable_opl_profile'],
+        field=out['backtrace_cable_field_field']/out['backtrace_cable_opl_profile'],
+        both_profiles=out['backtrace_cable_field_both_profiles']/out['backtrace_cable_opl_profile'],
+        rays=out['backtrace_cable_field_rays']/out['backtrace_cable_opl_rays'],
+        everything=out['backtrace_cable_field_everything']/out['backtrace_cable_opl_both'])
+    out['mean_record_iteration']=float(rec.float().mean())
+    return out
+if mode=='field':
+    res=dict(rays=n,rres=rres,random_order_ms=field_times(pos,vel),pixel_order_ms=field_times(pos2,vel2))
     print(json.dumps(res))
     if len(sys.argv)>2: json.dump(res,open(sys.argv[2],'w'),indent=1)
