@@ -1,9 +1,8 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip / drrt_cable_rays.hip /
-// drrt_cable_opl.hip / drrt_cable_field.hip.  Host code, plus the four small utility kernels that belong to no march (pair copy of the grid, q16
-// encode / decode, chunk progress reset).
+// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip.  Host code, plus the
+// four small utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
 

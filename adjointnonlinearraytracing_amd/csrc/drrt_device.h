@@ -1225,9 +1225,38 @@ DRRT_HD RayGrad vector_backtrace_ray(const Vol& V, float ds, float grad_scale, i
   return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
 }
 
-// trace_cable for ONE ray (src/tracer.cpp:312-382)
-DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
-                               const float tg[3]) {
+// ---- the fibre (cable) march: one forward loop, one record-anchored reverse march -------------------------------------
+// trace_cable, with or without a line integral over the samples it takes anyway, is one loop; the adjoints that start
+// from its closest-approach record are one reverse march.  Both skeletons are written once here; an operator supplies an
+// integrand (forward) and a term (reverse), defined with its mathematics further down.  backtrace_cable, the reference's
+// continuous adjoint, is a different march (cable_backtrace_ray).
+
+// The LDS rule of the cable kernels: the block's dynamic LDS in bytes -- `nprof` profiles (floats) and `ngrad` f64
+// accumulator arrays of rres entries each -- or 0 when everything goes to global memory: above kCableMaxRes, or when the
+// need passes 48 KiB (one profile: rres <= 4096 with or without its gradient; two profiles: <= 4096 / 3072 / 2048 with
+// 0 / 1 / 2 gradients).  Nothing to stage (rres, nprof < 1, ngrad < 0) is 0 as well.
+constexpr int kCableMaxRes = 4096;
+constexpr size_t kCableMaxLds = 49152;
+DRRT_HD size_t cable_lds_bytes(int rres, int nprof, int ngrad) {
+  const size_t need = (size_t)rres * (sizeof(float) * (size_t)nprof + sizeof(double) * (size_t)ngrad);
+  return nprof >= 1 && ngrad >= 0 && rres <= kCableMaxRes && need <= kCableMaxLds ? need : 0;
+}
+
+// The forward loop for ONE ray (src/tracer.cpp:312-382): cable_fwd_step from (p, v) until the ray is flagged escaped, at
+// most max_steps times.  `q.sample(C, s)` is called once per iteration in front of the step, s.x / s.z being where the
+// step samples (unmasked, clamped beyond the radius); `q.latch()` whenever the step updated the record (strict <, :365).
+// j is the iteration count at the last update (0: the record is the input).  An integrand owns its accumulator, which
+// starts at 0.f and is updated in iteration order, and the copy it latches with the record (0.f when j = 0).
+struct CableTrace { RayOut o; unsigned j; };
+
+struct CableNoIntegrand {                    // trace_cable itself: nothing is integrated
+  DRRT_HD void sample(const Cyl&, const FwdState&) {}
+  DRRT_HD void latch() {}
+};
+
+template <typename Integrand>
+DRRT_HD CableTrace cable_trace_integral_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
+                                            const float tg[3], Integrand&& q) {
   FwdState s;
   s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
   s.xtx = s.x; s.xty = s.y; s.xtz = s.z; s.vtx = s.vx; s.vty = s.vy; s.vtz = s.vz;
@@ -1236,16 +1265,27 @@ DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const floa
   s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
   s.inside = cyl_inbounds(C, s.x, s.y, s.z);                              // :344
   s.esc = false;
+  CableTrace t;
   unsigned steps = 0;
+  t.j = 0;
   for (int it = 0; it < max_steps; ++it) {
+    const float best = s.aux3;
+    q.sample(C, s);
     cable_fwd_step(C, ds, s);
     ++steps;
+    if (s.aux3 < best) { q.latch(); t.j = steps; }
     if (s.esc) break;          // state is frozen once !active (:353-354): nothing changes later
   }
-  RayOut o;
+  RayOut& o = t.o;
   o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
   o.dist2 = s.aux3; o.esc = s.esc; o.act = !s.esc; o.steps = steps;
-  return o;
+  return t;
+}
+
+// trace_cable for ONE ray
+DRRT_HD RayOut cable_trace_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
+                               const float tg[3]) {
+  return cable_trace_integral_ray(C, ds, max_steps, p, v, tg, CableNoIntegrand{}).o;
 }
 
 // backtrace_cable for ONE ray (src/tracer.cpp:511-567); sink(i0, i1, a0, a1)
@@ -1268,122 +1308,36 @@ DRRT_HD unsigned cable_backtrace_ray(const Cyl& C, float ds, int max_steps, cons
   return steps;
 }
 
-// Ray-state adjoint of trace_cable for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the recorded closest-approach
-// state (xt, vt) = (x_j, v_j), given only the forward's inputs (p0, v0) and its target.  The forward does not report j, so
-//   * the forward is replayed from (p0, v0) with cable_fwd_step itself, looped as cable_trace_ray loops it; j is the
-//     iteration count at the last record update (0: the record is the input) and the replayed record is (xt, vt), so the
-//     caller cannot hand in a mismatched pair;
-//   * j = 0: the gradient is the identity (dx, dv);
-//   * otherwise j reverse iterations from (xt, vt), seeded like cable_backtrace_ray (lambda = dx, mu = dv + ds dx), with
-//     neither its backward-escape test nor its step bound; after the last one lambda = dL/dx_0 and the mu it was updated
-//     from is dL/dv_0.  There is no free-flight prefix (the cable march samples from p0 on, clamped beyond the radius).
+// The reverse march for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the record (xt, vt) = (x_j, v_j), given the
+// forward's input position p0 and the record's iteration j, and the contributions to dL/d(profile).
+//   * The record is held fixed (as autograd through a masked select does); a seed on dist2 does not enter.
+//   * j is the ONLY loop bound and may come from caller memory, so a j above max_steps (the forward's own bound: no
+//     forward call returns one) does no iterations: zero gradients, failed = true.  A ray that ran out of steps still has
+//     a valid record and a gradient.
+//   * j reverse iterations from (xt, vt), seeded like cable_backtrace_ray (lambda = dx, mu = dv + ds dx), with neither its
+//     backward-escape test nor its step bound; after the last one lambda = dL/dx_0 and the mu it was updated from is
+//     dL/dv_0 (j = 0: the identity, no contribution).  There is no free-flight prefix: the cable march samples from p0 on.
 //     The last reverse iteration samples at p0 itself instead of its reconstruction x_1 - ds v_1: a start exactly on a
 //     profile knot or on the axis must see the forward's sample.
-// j is held fixed (as autograd through a masked select does); a seed on dist2 does not enter.  A ray that ran out of
-// steps still has a valid record and a gradient: `failed` stays false.  steps = replay + reverse iterations.
-// `rec` (optional) receives the replayed record.
-struct CableRecord { float xt[3], vt[3]; unsigned j; };
+// What an operator adds is its `term`, called in this order in every reverse iteration, m the sample at x_k:
+//   dn = term.dn(m, mu . grad n_k)        the factor of ds grad n_k that cable_adj_recur adds to lambda: dL / dn_k over ds
+//   sink(i0, i1, a0, a1)                  cable_adj_step's two profile contributions for that dn (cylinder_volume::splat,
+//                                         :113-148), formed with mu BEFORE cable_adj_recur updates it
+//   term.after(C, m, s)                   the term's contributions to its own profile and its pulls on lambda, BEFORE
+//                                         cable_adj_recur, whose closing mu += ds lambda must see them; a term touches
+//                                         nothing else of s.  It may keep what dn() sampled for after(): both are
+//                                         called, in this order, in every iteration
+// A term takes the sample by value, as cable_adj_recur does and for its reason: by reference the compiler schedules the
+// iteration of the rays-only field adjoint differently (measured 2 % slower on MI355X, NOTES.md).
+struct CableNoTerm {                         // trace_cable itself: nothing is integrated
+  DRRT_HD float dn(CylAdjSample, float mg) { return mg; }
+  DRRT_HD void after(const Cyl&, CylAdjSample, AdjState&) {}
+};
 
-DRRT_HD RayGrad cable_backtrace_ray_state(const Cyl& C, float ds, int max_steps, const float p0[3], const float v0[3],
-                                          const float tg[3], const float dx[3], const float dv[3],
-                                          CableRecord* rec = nullptr) {
-  FwdState f;
-  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
-  f.xtx = f.x; f.xty = f.y; f.xtz = f.z; f.vtx = f.vx; f.vty = f.vy; f.vtz = f.vz;
-  f.aux0 = tg[0]; f.aux1 = tg[1]; f.aux2 = tg[2]; f.aux4 = f.aux5 = 0.f;
-  float ex = f.x - tg[0], ey = f.y - tg[1], ez = f.z - tg[2];
-  f.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
-  f.inside = cyl_inbounds(C, f.x, f.y, f.z);                              // :344
-  f.esc = false;
-  unsigned steps = 0, j = 0;
-  for (int it = 0; it < max_steps; ++it) {
-    const float best = f.aux3;
-    cable_fwd_step(C, ds, f);
-    ++steps;
-    if (f.aux3 < best) j = steps;                                         // the record was updated (strict <, :365)
-    if (f.esc) break;
-  }
-  if (rec) {
-    rec->xt[0] = f.xtx; rec->xt[1] = f.xty; rec->xt[2] = f.xtz;
-    rec->vt[0] = f.vtx; rec->vt[1] = f.vty; rec->vt[2] = f.vtz; rec->j = j;
-  }
-  RayGrad g;
-  g.failed = false;
-  g.steps = steps + j;
-  if (j == 0) {
-    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
-    return g;
-  }
-  AdjState s;
-  s.x = f.xtx; s.y = f.xty; s.z = f.xtz; s.vx = f.vtx; s.vy = f.vty; s.vz = f.vtz;
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                               // :536
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);  // :537
-  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  for (unsigned k = j; k > 0; --k) {
-    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :547
-    if (k == 1u) { s.x = p0[0]; s.y = p0[1]; s.z = p0[2]; }              // the forward's first sample, as it took it
-    const CylAdjSample m = cable_adj_sample(C, ds, s);
-    const float dn = fmaf(s.mz, m.gz, s.mx * m.gx);                       // :557
-    qx = s.mx; qy = s.my; qz = s.mz;
-    cable_adj_recur(ds, s, m, dn);
-  }
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
-  return g;
-}
-
-// n at (px, pz) as cable_fwd_step samples it (its `f`): the same operations on the same operands, so a caller that
-// evaluates it in front of cable_fwd_step gets the step's own value (the compiler merges the two).
-DRRT_HD float cable_sample_n(const Cyl& C, float px, float pz) {
-  const CylCell c = cyl_locate(C, px, pz);
-  const float v0 = C.data[c.i0], v1 = C.data[c.i1];
-  return fmaf(v1, c.w0, v0 * (1.f - c.w0));                               // :53
-}
-
-// trace_cable for ONE ray, with the optical path length up to its record and the record's iteration.  The loop is
-// cable_trace_ray's, so (xt, vt, dist2, esc, steps) are its bit for bit.  acc = fmaf(ds n_k, n_k, acc) from 0.f in iteration
-// order (OplIntegrand's sequence), n_k the step's own sample at x_k, unmasked like it; `opl` and `j` are latched whenever
-// the record is updated: opl = sum_{k<j} ds n_k^2, j = the iteration count at the last update (0: the record is the input,
-// opl = 0.f).  It is the integral of n along the path when the rays enter with |v| = n.
-DRRT_HD RayOut cable_trace_opl_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
-                                   const float tg[3], float& opl, unsigned& j) {
-  FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.xtx = s.x; s.xty = s.y; s.xtz = s.z; s.vtx = s.vx; s.vty = s.vy; s.vtz = s.vz;
-  s.aux0 = tg[0]; s.aux1 = tg[1]; s.aux2 = tg[2]; s.aux4 = s.aux5 = 0.f;
-  float ex = s.x - tg[0], ey = s.y - tg[1], ez = s.z - tg[2];
-  s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
-  s.inside = cyl_inbounds(C, s.x, s.y, s.z);                              // :344
-  s.esc = false;
-  unsigned steps = 0;
-  float acc = 0.f;
-  opl = 0.f; j = 0;
-  for (int it = 0; it < max_steps; ++it) {
-    const float best = s.aux3;
-    const float n = cable_sample_n(C, s.x, s.z);
-    acc = fmaf(ds * n, n, acc);
-    cable_fwd_step(C, ds, s);
-    ++steps;
-    if (s.aux3 < best) { opl = acc; j = steps; }                          // the record was updated (strict <, :365)
-    if (s.esc) break;
-  }
-  RayOut o;
-  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
-  o.dist2 = s.aux3; o.esc = s.esc; o.act = !s.esc; o.steps = steps;
-  return o;
-}
-
-// Adjoint of cable_trace_opl_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/d(profile) from the seeds
-// (dx, dv, dopl) on (xt, vt, opl), given the forward's input position p0, its record (xt, vt) and the record's iteration j.
-// No replay: j reverse iterations from (xt, vt), run as cable_backtrace_ray_state runs them (lambda = dx, mu = dv + ds dx,
-// no escape test, the last sample at p0 itself), with dn = mu . grad n_k + 2 dopl n_k where that routine has
-// mu . grad n_k; every iteration emits cable_adj_step's two profile contributions through sink(i0, i1, a0, a1).  j is held
-// fixed.  j = 0: (dx, dv), no contribution.  j comes from caller memory and is the ONLY loop bound, so a j above
-// max_steps (the forward's own bound: no forward call returns one) does no iterations: zero gradients, failed = true.
-template <typename Sink>
-DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, const float p0[3], const float xt[3],
-                                        const float vt[3], unsigned j, const float dx[3], const float dv[3], float dopl,
-                                        Sink&& sink) {
+template <typename Term, typename Sink>
+DRRT_HD RayGrad cable_record_backtrace_ray(const Cyl& C, float ds, int max_steps, const float p0[3], const float xt[3],
+                                           const float vt[3], unsigned j, const float dx[3], const float dv[3],
+                                           Term&& term, Sink&& sink) {
   RayGrad g;
   g.failed = max_steps < 0 || j > (unsigned)max_steps;
   g.steps = g.failed ? 0u : j;
@@ -1396,18 +1350,17 @@ DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, c
   s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                               // :536
   s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);  // :537
   float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  const float dopl2 = 2.f * dopl;
   for (unsigned k = j; k > 0; --k) {
     s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :547
     if (k == 1u) { s.x = p0[0]; s.y = p0[1]; s.z = p0[2]; }              // the forward's first sample, as it took it
     const CylAdjSample m = cable_adj_sample(C, ds, s);
     const CylCell& c = m.c;
-    const float dn = fmaf(dopl2, m.n, fmaf(s.mz, m.gz, s.mx * m.gx));     // :557, plus d(ds n^2)/dn / ds
-    // cylinder_volume::splat (:113-148) as cable_adj_step forms it
+    const float dn = term.dn(m, fmaf(s.mz, m.gz, s.mx * m.gx));           // :557
     const float val = dn * ds;
     const float gv = (m.n * ds) * fmaf(s.mz, c.rhz, s.mx * c.rhx);
     const float gvh = gv * C.inv_h;
     sink(c.i0, c.i1, fmaf(val, 1.f - c.w0, -gvh), fmaf(val, c.w0, gvh));
+    term.after(C, m, s);
     qx = s.mx; qy = s.my; qz = s.mz;
     cable_adj_recur(ds, s, m, dn);
   }
@@ -1416,53 +1369,111 @@ DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, c
   return g;
 }
 
+// Ray-state adjoint of trace_cable for ONE ray, given only the forward's inputs (p0, v0) and its target.  The forward does
+// not report j, so it is replayed with the forward loop itself: the replayed record is (xt, vt), the caller cannot hand in
+// a mismatched pair, and the march's refusal cannot fire.  Then the reverse march with no term and no sink.  j = 0 is the
+// identity whatever max_steps is; `failed` stays false; steps = replay + reverse iterations.  `rec` (optional) receives
+// the replayed record.
+struct CableRecord { float xt[3], vt[3]; unsigned j; };
+
+DRRT_HD RayGrad cable_backtrace_ray_state(const Cyl& C, float ds, int max_steps, const float p0[3], const float v0[3],
+                                          const float tg[3], const float dx[3], const float dv[3],
+                                          CableRecord* rec = nullptr) {
+  const CableTrace t = cable_trace_integral_ray(C, ds, max_steps, p0, v0, tg, CableNoIntegrand{});
+  if (rec) {
+    for (int k = 0; k < 3; ++k) { rec->xt[k] = t.o.xt[k]; rec->vt[k] = t.o.vt[k]; }
+    rec->j = t.j;
+  }
+  RayGrad g;
+  if (t.j == 0) {
+    g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
+  } else {
+    g = cable_record_backtrace_ray(C, ds, max_steps, p0, t.o.xt, t.o.vt, t.j, dx, dv, CableNoTerm{},
+                                   [](int, int, float, float) {});
+  }
+  g.failed = false;
+  g.steps = t.o.steps + t.j;
+  return g;
+}
+
+// n at (px, pz) as cable_fwd_step samples it (its `f`): the same operations on the same operands, so a caller that
+// evaluates it in front of cable_fwd_step gets the step's own value (the compiler merges the two).
+DRRT_HD float cable_sample_n(const Cyl& C, float px, float pz) {
+  const CylCell c = cyl_locate(C, px, pz);
+  const float v0 = C.data[c.i0], v1 = C.data[c.i1];
+  return fmaf(v1, c.w0, v0 * (1.f - c.w0));                               // :53
+}
+
+// trace_cable for ONE ray, with the optical path length up to its record and the record's iteration: acc =
+// fmaf(ds n_k, n_k, acc) (OplIntegrand's sequence), n_k the step's own sample at x_k, so opl = sum_{k<j} ds n_k^2.  It is
+// the integral of n along the path when the rays enter with |v| = n.  Not in the reference.
+struct CableOplIntegrand {
+  float ds, acc = 0.f, opl = 0.f;
+  DRRT_HD void sample(const Cyl& C, const FwdState& s) {
+    const float n = cable_sample_n(C, s.x, s.z);
+    acc = fmaf(ds * n, n, acc);
+  }
+  DRRT_HD void latch() { opl = acc; }
+};
+
+DRRT_HD RayOut cable_trace_opl_ray(const Cyl& C, float ds, int max_steps, const float p[3], const float v[3],
+                                   const float tg[3], float& opl, unsigned& j) {
+  CableOplIntegrand q{ds};
+  const CableTrace t = cable_trace_integral_ray(C, ds, max_steps, p, v, tg, q);
+  opl = q.opl; j = t.j;
+  return t.o;
+}
+
+// Adjoint of cable_trace_opl_ray for ONE ray, from the seeds (dx, dv, dopl) on (xt, vt, opl): the reverse march with
+// dn = mu . grad n_k + 2 dopl n_k (d opl / d n_k = 2 ds n_k) where the ray-state adjoint has mu . grad n_k.
+struct CableOplTerm {
+  float dopl2;                               // 2 dopl
+  DRRT_HD float dn(CylAdjSample m, float mg) { return fmaf(dopl2, m.n, mg); }
+  DRRT_HD void after(const Cyl&, CylAdjSample, AdjState&) {}
+};
+
+template <typename Sink>
+DRRT_HD RayGrad cable_opl_backtrace_ray(const Cyl& C, float ds, int max_steps, const float p0[3], const float xt[3],
+                                        const float vt[3], unsigned j, const float dx[3], const float dv[3], float dopl,
+                                        Sink&& sink) {
+  return cable_record_backtrace_ray(C, ds, max_steps, p0, xt, vt, j, dx, dv, CableOplTerm{2.f * dopl}, sink);
+}
+
 // trace_cable for ONE ray, with the line integral of a second radial profile `fa` (C.rres samples on C's knots; it may be
-// C.data itself, both are only read) up to its record, and the record's iteration.  The loop is cable_trace_opl_ray's, so
-// (xt, vt, dist2, esc, steps) and j are its bit for bit.  a_k = cable_sample_n's operations on `fa` in the cell of the
-// step's own sample n_k (unmasked, clamped beyond the radius like it); acc = fmaf(ds n_k, a_k, acc) from 0.f in iteration
-// order; `tau` and `j` are latched whenever the record is updated: tau = sum_{k<j} ds n_k a_k (j = 0: 0.f).  With fa = C.data
-// it is cable_trace_opl_ray's opl bit for bit.  It is the integral of a along the path when the rays enter with |v| = n.
-DRRT_HD RayOut cable_trace_field_ray(const Cyl& C, const float* fa, float ds, int max_steps, const float p[3],
-                                     const float v[3], const float tg[3], float& tau, unsigned& j) {
-  FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.xtx = s.x; s.xty = s.y; s.xtz = s.z; s.vtx = s.vx; s.vty = s.vy; s.vtz = s.vz;
-  s.aux0 = tg[0]; s.aux1 = tg[1]; s.aux2 = tg[2]; s.aux4 = s.aux5 = 0.f;
-  float ex = s.x - tg[0], ey = s.y - tg[1], ez = s.z - tg[2];
-  s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // :340
-  s.inside = cyl_inbounds(C, s.x, s.y, s.z);                              // :344
-  s.esc = false;
-  unsigned steps = 0;
-  float acc = 0.f;
-  tau = 0.f; j = 0;
-  for (int it = 0; it < max_steps; ++it) {
-    const float best = s.aux3;
+// C.data itself, both are only read) up to its record, and the record's iteration.  a_k = cable_sample_n's operations on
+// `fa` in the cell of the step's own sample n_k (unmasked, clamped beyond the radius like it); acc = fmaf(ds n_k, a_k, acc),
+// so tau = sum_{k<j} ds n_k a_k.  With fa = C.data it is cable_trace_opl_ray's opl bit for bit.  It is the integral of a
+// along the path when the rays enter with |v| = n.  Not in the reference.
+struct CableFieldIntegrand {
+  const float* fa;
+  float ds, acc = 0.f, tau = 0.f;
+  DRRT_HD void sample(const Cyl& C, const FwdState& s) {
     const CylCell c = cyl_locate(C, s.x, s.z);
     const float n = fmaf(C.data[c.i1], c.w0, C.data[c.i0] * (1.f - c.w0));    // cable_sample_n
     const float ak = fmaf(fa[c.i1], c.w0, fa[c.i0] * (1.f - c.w0));           // ... on the other profile
     acc = fmaf(ds * n, ak, acc);
-    cable_fwd_step(C, ds, s);
-    ++steps;
-    if (s.aux3 < best) { tau = acc; j = steps; }                          // the record was updated (strict <, :365)
-    if (s.esc) break;
   }
-  RayOut o;
-  o.xt[0] = s.xtx; o.xt[1] = s.xty; o.xt[2] = s.xtz; o.vt[0] = s.vtx; o.vt[1] = s.vty; o.vt[2] = s.vtz;
-  o.dist2 = s.aux3; o.esc = s.esc; o.act = !s.esc; o.steps = steps;
-  return o;
+  DRRT_HD void latch() { tau = acc; }
+};
+
+DRRT_HD RayOut cable_trace_field_ray(const Cyl& C, const float* fa, float ds, int max_steps, const float p[3],
+                                     const float v[3], const float tg[3], float& tau, unsigned& j) {
+  CableFieldIntegrand q{fa, ds};
+  const CableTrace t = cable_trace_integral_ray(C, ds, max_steps, p, v, tg, q);
+  tau = q.tau; j = t.j;
+  return t.o;
 }
 
-// Adjoint of cable_trace_field_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/d(profile) and dL/d(fa) from
-// the seeds (dx, dv, dtau) on (xt, vt, tau).  Run as cable_opl_backtrace_ray runs (no replay, j reverse iterations from
-// (xt, vt), lambda = dx, mu = dv + ds dx, no escape test, the last sample at p0 itself, j the ONLY loop bound and refused
-// above max_steps), with, per iteration, in the cell (i0, i1, w0) of the sample:
-//   dn = mu . grad n_k + dtau a_k                (d tau / d n_k = ds a_k); cable_adj_step's two contributions for that dn
-//                                                go through sink(i0, i1, a0, a1)
-//   fv = (dtau ds) n_k                           (d tau / d a_k); fsink(i0, i1, fv (1 - w0), fv w0)
-//   lambda += fv a'_k rhat, a'_k = (fa[i1] - fa[i0]) / h   (a_k moves with x_k along fa's own radial slope), before
-//                                                cable_adj_recur carries lambda into mu
+// Adjoint of cable_trace_field_ray for ONE ray, from the seeds (dx, dv, dtau) on (xt, vt, tau): the reverse march with,
+// per iteration, in the cell (i0, i1, w0) of the sample:
+//   dn = mu . grad n_k + dtau a_k                (d tau / d n_k = ds a_k)
+//   fv = (dtau ds) n_k                           (d tau / d a_k); fsink(i0, i1, fv (1 - w0), fv w0), the contributions to
+//                                                dL/d(fa)
+//   lambda += fv a'_k rhat, a'_k = (fa[i1] - fa[i0]) / h   (a_k moves with x_k along fa's own radial slope)
 // a' follows grad n's conventions by construction: rhat = 0 where cyl_locate says tiny, and i0 = i1 beyond the radius.
 // dtau = 0 leaves cable_opl_backtrace_ray's iteration with dopl = 0 and sends zeros to fsink.
+// Written out, not as a term of cable_record_backtrace_ray, whose iteration it restates with the three lines of its own:
+// as a term, the kernels that store no ray gradients compiled differently and measured 0.4-0.8 % slower (NOTES.md).
 template <typename Sink, typename FieldSink>
 DRRT_HD RayGrad cable_field_backtrace_ray(const Cyl& C, const float* fa, float ds, int max_steps, const float p0[3],
                                           const float xt[3], const float vt[3], unsigned j, const float dx[3],

@@ -27,8 +27,6 @@
 // carries only that grid's corner sums.  There is NO LDS window: the ring kernel's fixed-point window is scaled for
 // backtrace's contributions and a per-step source term does not fit its overflow budget, so these kernels pay the
 // memory-side atomic rate where many rays cross the same voxels.
-#include <utility>
-
 #include "drrt_march.h"
 
 namespace drrt {
@@ -228,17 +226,7 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_vector(VectorBackArgs a) {
 }
 
 // ---- launchers ---------------------------------------------------------------------------------------------------------
-// with_bools(f, b...) calls f(std::bool_constant<b>...) for the runtime booleans b...: which instantiation of a kernel a
-// call gets
-template <typename F, bool... Bs>
-static void bools_done(F&& f, std::integer_sequence<bool, Bs...>) { f(std::bool_constant<Bs>{}...); }
-template <typename F, bool... Bs, typename... Rest>
-static void bools_done(F&& f, std::integer_sequence<bool, Bs...>, bool b, Rest... rest) {
-  if (b) bools_done(f, std::integer_sequence<bool, Bs..., true>{}, rest...);
-  else   bools_done(f, std::integer_sequence<bool, Bs..., false>{}, rest...);
-}
-template <typename F, typename... Bools>
-static void with_bools(F&& f, Bools... b) { bools_done(f, std::integer_sequence<bool>{}, b...); }
+// which instantiation of a kernel a call gets: with_bools (drrt_march.h)
 #define LAUNCH_INTEGRAL(kernel, a, s) hipLaunchKernelGGL(kernel, dim3(grid_for((a).n)), dim3(kBlock), 0, s, a)
 
 void launch_trace_opl(const OplTraceArgs& a, hipStream_t s) {

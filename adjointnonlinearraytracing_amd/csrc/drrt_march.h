@@ -19,11 +19,12 @@
 //                           backtrace_emission (rad = int e exp(-int a), tau; also dL/de, dL/da).  Their per-ray routines
 //                           are instances of one forward loop and one reverse march (drrt_device.h), which
 //                           backtrace_rays shares
-//   drrt_cable.hip          trace_cable, backtrace_cable                         (src/tracer.cpp:312-382, 511-567)
-//   drrt_cable_rays.hip     backtrace_cable_rays: dL/dpos, dL/dvel of trace_cable (ray-state adjoint, no profile writes)
-//   drrt_cable_opl.hip      trace_cable_opl, backtrace_cable_opl: the cable march with its optical path length, one adjoint
-//   drrt_cable_field.hip    trace_cable_field, backtrace_cable_field: the cable march with the line integral of a second
-//                           radial profile, one adjoint (dL/dprofile, dL/dfield, dL/dpos, dL/dvel)
+//   drrt_cable.hip          the fibre march: trace_cable, backtrace_cable (src/tracer.cpp:312-382, 511-567);
+//                           backtrace_cable_rays (ray-state adjoint: dL/dpos, dL/dvel, no profile writes); trace_cable_opl /
+//                           backtrace_cable_opl (the march with its optical path length, one adjoint); trace_cable_field /
+//                           backtrace_cable_field (with the line integral of a second radial profile, one adjoint: dL/dprofile,
+//                           dL/dfield, dL/dpos, dL/dvel).  Their per-ray routines are instances of one forward loop and
+//                           one record-anchored reverse march (drrt_device.h)
 //   drrt_api.hip            the C ABI of include/drrt_hip.h (host code only)
 // The operators before and after the march do not include this header; they share drrt_host.h (error slot, 1-D launch):
 //   drrt_source.hip         ray generation                                       (core/source.py)
@@ -52,6 +53,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <type_traits>
+#include <utility>
 
 #include <hip/hip_fp16.h>
 
@@ -659,10 +661,9 @@ struct VectorBackArgs {
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
 // of the gradient profile (ds_add_f64) and flushes it once per block -- millions of rays would
-// otherwise hammer <= 257 global addresses.
+// otherwise hammer <= 257 global addresses.  cable_lds_bytes (drrt_device.h) says when: profiles above
+// kCableMaxRes, or past 48 KiB with their accumulators, fall back to global memory.
 // ---------------------------------------------------------------------------------------------
-constexpr int kCableMaxRes = 4096;   // profiles larger than this fall back to global memory
-
 struct CableArgs {
   const float* rif; int rres; float radius, length, ds; int max_steps;
   const float* pos; const float* vel; const float* target;    // forward
@@ -672,8 +673,7 @@ struct CableArgs {
   size_t n;
 };
 
-// ray-state adjoint of trace_cable (drrt_cable_rays.hip).  Its own argument block: CableArgs keeps the field offsets the
-// two cable kernels were compiled against.
+// ray-state adjoint of trace_cable
 struct CableRayGradArgs {
   const float* rif; int rres; float radius, length, ds; int max_steps;
   const float* pos; const float* vel; const float* target;    // the forward's inputs
@@ -683,7 +683,7 @@ struct CableRayGradArgs {
   size_t n;
 };
 
-// trace_cable with the optical path length up to the record, and its adjoint (drrt_cable_opl.hip)
+// trace_cable with the optical path length up to the record, and its adjoint
 struct CableOplTraceArgs {
   const float* rif; int rres; float radius, length, ds; int max_steps;
   const float* pos; const float* vel; const float* target;
@@ -703,7 +703,7 @@ struct CableOplBackArgs {
   size_t n;
 };
 
-// trace_cable with the line integral of a second radial profile up to the record, and its adjoint (drrt_cable_field.hip)
+// trace_cable with the line integral of a second radial profile up to the record, and its adjoint
 struct CableFieldTraceArgs {
   const float* rif; int rres; float radius, length, ds; int max_steps;
   const float* field;                                          // rres samples on rif's knots; may be rif itself
@@ -725,16 +725,6 @@ struct CableFieldBackArgs {
   drrt_stats* stats;
   size_t n;
 };
-
-// The LDS rule of the two kernels of drrt_cable_field.hip, for launcher and kernel alike: the block's dynamic LDS in bytes
-// -- both profiles (floats) and one f64 accumulator array per requested gradient -- or 0 when everything goes to global
-// memory: above kCableMaxRes, or when the need passes the 48 KiB that k_backtrace_cable_opl already launches with at
-// kCableMaxRes (so rres <= 2048 with both gradients, <= 3072 with one, <= 4096 with none and in the forward).
-constexpr size_t kCableFieldMaxLds = 49152;
-__host__ __device__ inline size_t cable_field_lds_bytes(int rres, bool profile, bool field) {
-  const size_t need = (size_t)rres * (2 * sizeof(float) + (profile ? sizeof(double) : 0) + (field ? sizeof(double) : 0));
-  return rres <= kCableMaxRes && need <= kCableFieldMaxLds ? need : 0;
-}
 
 __device__ __forceinline__ void cable_stats(drrt_stats* stats, unsigned steps_tot, unsigned steps_max, unsigned fail_tot) {
   if (!stats) return;
@@ -792,6 +782,17 @@ static inline unsigned cable_grid(size_t n) {
   const unsigned want = grid_for(n);
   return want < 1024u ? want : 1024u;
 }
+// with_bools(f, b...) calls f(std::bool_constant<b>...) for the runtime booleans b...: which instantiation of a kernel a
+// call gets
+template <typename F, bool... Bs>
+static void bools_done(F&& f, std::integer_sequence<bool, Bs...>) { f(std::bool_constant<Bs>{}...); }
+template <typename F, bool... Bs, typename... Rest>
+static void bools_done(F&& f, std::integer_sequence<bool, Bs...>, bool b, Rest... rest) {
+  if (b) bools_done(f, std::integer_sequence<bool, Bs..., true>{}, rest...);
+  else   bools_done(f, std::integer_sequence<bool, Bs..., false>{}, rest...);
+}
+template <typename F, typename... Bools>
+static void with_bools(F&& f, Bools... b) { bools_done(f, std::integer_sequence<bool>{}, b...); }
 // forward (drrt_forward.hip).  mode: 0 = trace, 1 = trace_plane, 2 = trace_sdf
 void launch_trace(int mode, const TraceArgs& a, hipStream_t s);
 void launch_trace_again(int mode, const TraceArgs& a, hipStream_t s);
@@ -818,17 +819,14 @@ void launch_trace_emission(const EmissionTraceArgs& a, hipStream_t s);
 void launch_backtrace_emission(const EmissionBackArgs& a, hipStream_t s);
 void launch_trace_vector(const VectorTraceArgs& a, hipStream_t s);
 void launch_backtrace_vector(const VectorBackArgs& a, hipStream_t s);
-// cable (drrt_cable.hip)
+// cable (drrt_cable.hip): the march and the reference's adjoint; its ray-state adjoint; the march with its optical path
+// length, and its adjoint: grad and/or (dpos, dvel), whichever are non-null; the march with the line integral of a second
+// radial profile, and its adjoint: grad, grad_field and/or (dpos, dvel), whichever are non-null
 void launch_trace_cable(const CableArgs& a, hipStream_t s);
 void launch_backtrace_cable(const CableArgs& a, hipStream_t s);
-// ray-state adjoint of the cable march (drrt_cable_rays.hip)
 void launch_backtrace_cable_rays(const CableRayGradArgs& a, hipStream_t s);
-// the cable march with its optical path length, and its adjoint: grad and/or (dpos, dvel), whichever are non-null
-// (drrt_cable_opl.hip)
 void launch_trace_cable_opl(const CableOplTraceArgs& a, hipStream_t s);
 void launch_backtrace_cable_opl(const CableOplBackArgs& a, hipStream_t s);
-// the cable march with the line integral of a second radial profile, and its adjoint: grad, grad_field and/or (dpos, dvel),
-// whichever are non-null (drrt_cable_field.hip)
 void launch_trace_cable_field(const CableFieldTraceArgs& a, hipStream_t s);
 void launch_backtrace_cable_field(const CableFieldBackArgs& a, hipStream_t s);
 

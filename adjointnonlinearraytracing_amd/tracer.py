@@ -463,6 +463,44 @@ class VectorIntegralTracerC(torch.autograd.Function):
         return (*_integral_backward(ctx, drrt.TracerC().backtrace_vector, grad_x, grad_v, grad_circ), None, None)
 
 
+def _cable_integral_forward(ctx, name, march, profiles, radius, length, x, v, sp, ds):
+    """Forward of a fibre march with an integral up to the record: ``march(flat profiles..., radius, length, x, v, sp, ds)
+    -> (xt, vt, dist2, integral, rec_steps)`` (``TracerC.trace_cable_opl`` / ``trace_cable_field``) on detached inputs ->
+    (xt, vt, dist2, integral), dist2 not differentiable.  apply() takes (*profiles, radius, length, x, v, sp, ds).  When
+    any input requires grad ``ctx`` gets a private copy of x (the adjoint replays nothing: of the forward's ray inputs it
+    takes x alone; a copy as _keep_rays makes) and the record iterations, and, saved, the profiles and the record."""
+    ctx.set_materialize_grads(False)
+    ctx.radius, ctx.length, ctx.ds = radius, length, ds
+    ix = len(profiles) + 2
+    _ray_grad_wanted(ctx, name, ix, ix + 1, x, v)
+    xt, vt, dist2, integral, rec = march(*[p.detach().flatten() for p in profiles], radius, length, x.detach(), v.detach(),
+                                         sp.detach(), ds)
+    if any(ctx.needs_input_grad[i] for i in (*range(len(profiles)), ix, ix + 1)):
+        ctx.ray_devices = (x.device, v.device)
+        ctx.rays = (x.detach().to(device=xt.device, dtype=torch.float32).clone(), rec)
+        ctx.save_for_backward(*profiles, xt, vt)
+    ctx.mark_non_differentiable(dist2)
+    return xt, vt, dist2, integral
+
+
+def _cable_integral_backward(ctx, nprof, back, grad_x, grad_v, grad_integral):
+    """Backward of the same: ONE ``back(flat profiles..., radius, length, x, xt, vt, rec_steps, grad_x, grad_v,
+    grad_integral, ds, wanted per profile..., rays wanted) -> (gradient | None per profile, dpos | None, dvel | None)``
+    (``TracerC.backtrace_cable_opl`` / ``backtrace_cable_field``) -> the gradients in apply()'s order."""
+    ix = nprof + 2
+    want = [ctx.needs_input_grad[i] for i in range(nprof)]
+    want_rays = ctx.needs_input_grad[ix] or ctx.needs_input_grad[ix + 1]
+    if not (any(want) or want_rays):
+        return (None,) * (nprof + 6)
+    *profiles, xt, vt = ctx.saved_tensors
+    x0, rec = ctx.rays
+    *grads, dpos, dvel = back(*[p.detach().flatten() for p in profiles], ctx.radius, ctx.length, x0, xt, vt, rec, grad_x,
+                              grad_v, grad_integral, ctx.ds, *want, want_rays)
+    dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[ix] else None
+    dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[ix + 1] else None
+    return (*[g.reshape(p.shape) if w else None for g, p, w in zip(grads, profiles, want)], None, None, dx0, dv0, None, None)
+
+
 class CableOPLTracerC(torch.autograd.Function):
     """``apply(rif (Rr,), radius, length, x, v, sp, ds) -> (xt, vt, dist2, opl)``: the fibre march with the optical path
     length ``opl = sum ds n_k^2`` of every ray up to its closest-approach record; xt, vt and opl are differentiable w.r.t.
@@ -480,31 +518,12 @@ class CableOPLTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, radius, length, x, v, sp, ds):
-        ctx.set_materialize_grads(False)
-        ctx.radius, ctx.length, ctx.ds = radius, length, ds
-        _ray_grad_wanted(ctx, "CableOPLTracerC", 3, 4, x, v)
-        xt, vt, dist2, opl, rec = drrt.TracerC().trace_cable_opl(rif.detach().flatten(), radius, length, x.detach(),
-                                                                 v.detach(), sp.detach(), ds)
-        if ctx.needs_input_grad[0] or ctx.needs_input_grad[3] or ctx.needs_input_grad[4]:
-            ctx.ray_devices = (x.device, v.device)
-            # the adjoint replays nothing: of the forward's ray inputs it takes x alone (a private copy, as _keep_rays makes)
-            ctx.rays = (x.detach().to(device=xt.device, dtype=torch.float32).clone(), rec)
-            ctx.save_for_backward(rif, xt, vt)
-        ctx.mark_non_differentiable(dist2)
-        return xt, vt, dist2, opl
+        return _cable_integral_forward(ctx, "CableOPLTracerC", drrt.TracerC().trace_cable_opl, (rif,), radius, length, x, v,
+                                       sp, ds)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_dist2, grad_opl):
-        want_rif, want_rays = ctx.needs_input_grad[0], ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        if not (want_rif or want_rays):
-            return (None,) * 7
-        rif, xt, vt = ctx.saved_tensors
-        x0, rec = ctx.rays
-        grad, dpos, dvel = drrt.TracerC().backtrace_cable_opl(rif.detach().flatten(), ctx.radius, ctx.length, x0, xt, vt, rec,
-                                                              grad_x, grad_v, grad_opl, ctx.ds, want_rif, want_rays)
-        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[3] else None
-        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[4] else None
-        return grad.reshape(rif.shape) if want_rif else None, None, None, dx0, dv0, None, None
+        return _cable_integral_backward(ctx, 1, drrt.TracerC().backtrace_cable_opl, grad_x, grad_v, grad_opl)
 
 
 class CableFieldTracerC(torch.autograd.Function):
@@ -524,37 +543,15 @@ class CableFieldTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, a, radius, length, x, v, sp, ds):
-        ctx.set_materialize_grads(False)
-        ctx.radius, ctx.length, ctx.ds = radius, length, ds
         if a.numel() != rif.numel():
             raise RuntimeError(f"CableFieldTracerC: the second profile must have the {rif.numel()} samples of rif, got "
                                f"{a.numel()}")
-        _ray_grad_wanted(ctx, "CableFieldTracerC", 4, 5, x, v)
-        xt, vt, dist2, tau, rec = drrt.TracerC().trace_cable_field(rif.detach().flatten(), a.detach().flatten(), radius,
-                                                                   length, x.detach(), v.detach(), sp.detach(), ds)
-        if any(ctx.needs_input_grad[i] for i in (0, 1, 4, 5)):
-            ctx.ray_devices = (x.device, v.device)
-            # the adjoint replays nothing: of the forward's ray inputs it takes x alone (a private copy, as _keep_rays makes)
-            ctx.rays = (x.detach().to(device=xt.device, dtype=torch.float32).clone(), rec)
-            ctx.save_for_backward(rif, a, xt, vt)
-        ctx.mark_non_differentiable(dist2)
-        return xt, vt, dist2, tau
+        return _cable_integral_forward(ctx, "CableFieldTracerC", drrt.TracerC().trace_cable_field, (rif, a), radius, length,
+                                       x, v, sp, ds)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_dist2, grad_tau):
-        want_rif, want_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        want_rays = ctx.needs_input_grad[4] or ctx.needs_input_grad[5]
-        if not (want_rif or want_a or want_rays):
-            return (None,) * 8
-        rif, a, xt, vt = ctx.saved_tensors
-        x0, rec = ctx.rays
-        grad, grad_a, dpos, dvel = drrt.TracerC().backtrace_cable_field(
-            rif.detach().flatten(), a.detach().flatten(), ctx.radius, ctx.length, x0, xt, vt, rec, grad_x, grad_v, grad_tau,
-            ctx.ds, want_rif, want_a, want_rays)
-        dx0 = dpos.to(ctx.ray_devices[0]) if ctx.needs_input_grad[4] else None
-        dv0 = dvel.to(ctx.ray_devices[1]) if ctx.needs_input_grad[5] else None
-        return (grad.reshape(rif.shape) if want_rif else None, grad_a.reshape(a.shape) if want_a else None, None, None,
-                dx0, dv0, None, None)
+        return _cable_integral_backward(ctx, 2, drrt.TracerC().backtrace_cable_field, grad_x, grad_v, grad_tau)
 
 
 # The reference's enoki-autodiff names for the plane and SDF marches (core/tracer.py:122-234; its ADPlaneTracerC is broken

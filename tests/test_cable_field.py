@@ -2,7 +2,7 @@
 (drrt_trace_cable_field_f32, drrt_backtrace_cable_field_f32, TracerC.trace_cable_field / backtrace_cable_field,
 tracer.CableFieldTracerC).
 
-CPU tier: the host build of the product's two per-ray routines (tests/cable_field_host, cable_trace_field_ray and
+CPU tier: the host build of the product's two per-ray routines (tests/cable_integral_host, cable_trace_field_ray and
 cable_field_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through
 tests/cable_field_ad.trace_cable_field (cable_opl_ad.trace_cable_opl with acc += ds n_k a_k), on the scenes, ray sets and
 tie-free mask of tests/test_cable_raygrad.py, within the bound of the integral fuzz suite (tests/integral_fuzz_common.py:
@@ -11,7 +11,7 @@ the existing cable routines, the refusals of the two entry points, and a stand-a
 GPU tier: the kernels against that host build (per-ray results bit for bit, both profile gradients within ATOMIC_TOL) on
 both sides of every LDS limit, the grid-stride loop, CableFieldTracerC end to end and examples/fiber_group_delay_demo.py.
 
-On the parent commit every test here fails: tests/cable_field_host does not compile (drrt_device.h has neither
+On the parent commit every test here fails: tests/cable_integral_host does not compile (drrt_device.h has neither
 cable_trace_field_ray nor cable_field_backtrace_ray), the library has neither drrt_trace_cable_field_f32 nor
 drrt_backtrace_cable_field_f32, _lib.PROF_NAMES_LATER has no ids 21 and 22, TracerC has no trace_cable_field and tracer no
 CableFieldTracerC, and there is no examples/fiber_group_delay_demo.py."""
@@ -28,8 +28,7 @@ import torch
 
 import cable_ad
 import cable_field_ad
-import cable_field_host as H
-import cable_opl_host as HO
+import cable_integral_host as H
 import cases
 import hostcheck_lib as HC
 import test_cable_raygrad as CR
@@ -74,11 +73,11 @@ def host_back(s, k, mode="all", sel=slice(None), rec=None, field=None):
 
 
 def opl_forward(s):
-    return HO.trace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["ds"])
+    return H.trace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], s["vel"], s["tg"], s["ds"])
 
 
 def opl_back(s, k, dopl):
-    return HO.backtrace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], k["xt"], k["vt"], k["rec_steps"], s["dx"],
+    return H.backtrace_cable_opl(s["prof"], s["radius"], s["length"], s["pos"], k["xt"], k["vt"], k["rec_steps"], s["dx"],
                                   s["dv"], dopl, s["ds"])
 
 
@@ -463,7 +462,7 @@ def test_abi_refusals():
 
 # ---- CPU tier: the two routines under sanitizers --------------------------------------------------------------------
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/cable_field_rays.hip with -DCABLE_FIELD_MAIN: a stand-alone program over the two routines, compiled
+    """tests/hostcheck/cable_integral_rays.hip with -DCABLE_FIELD_MAIN: a stand-alone program over the two routines, compiled
     for the host with ASan + UBSan and run directly (nothing preloaded): NaN / Inf positions, velocities, targets, seeds and
     entries of both profiles, a 2-sample pair, the profile as its own field, and the poisoned rec_steps -- no report, every
     loop ends, the poisoned rays are refused."""

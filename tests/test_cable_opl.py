@@ -1,7 +1,7 @@
 """The fibre march with its optical path length and its one exact adjoint (drrt_trace_cable_opl_f32,
 drrt_backtrace_cable_opl_f32, TracerC.trace_cable_opl / backtrace_cable_opl, tracer.CableOPLTracerC).
 
-CPU tier: the host build of the product's two per-ray routines (tests/cable_opl_host, cable_trace_opl_ray and
+CPU tier: the host build of the product's two per-ray routines (tests/cable_integral_host, cable_trace_opl_ray and
 cable_opl_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through tests/cable_opl_ad.trace_cable_opl
 (cable_ad.trace_cable plus the latched sum, the record's iteration handed in), on the scenes, ray sets and tie-free mask of
 tests/test_cable_raygrad.py, within the bound of the integral fuzz suite (tests/integral_fuzz_common.py: FLOOR, MARGIN times
@@ -10,7 +10,7 @@ routines, the refusals of the two entry points, and a stand-alone sanitizer buil
 GPU tier: the kernels against that host build (per-ray results bit for bit, the profile gradient within ATOMIC_TOL), the
 grid-stride loop, CableOPLTracerC end to end and examples/fiber_delay_demo.py.
 
-On the parent commit every test here fails: tests/cable_opl_host does not compile (drrt_device.h has neither
+On the parent commit every test here fails: tests/cable_integral_host does not compile (drrt_device.h has neither
 cable_trace_opl_ray nor cable_opl_backtrace_ray), the library has neither drrt_trace_cable_opl_f32 nor
 drrt_backtrace_cable_opl_f32, _lib.PROF_NAMES_LATER has no ids 19 and 20, TracerC has no trace_cable_opl and tracer no
 CableOPLTracerC, and there is no examples/fiber_delay_demo.py."""
@@ -26,7 +26,7 @@ import torch
 
 import cable_ad
 import cable_opl_ad
-import cable_opl_host as H
+import cable_integral_host as H
 import cases
 import hostcheck_lib as HC
 import test_cable_raygrad as CR
@@ -380,7 +380,7 @@ def test_abi_refusals():
 
 # ---- CPU tier: the two routines under sanitizers --------------------------------------------------------------------
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/cable_opl_rays.hip with -DCABLE_OPL_MAIN: a stand-alone program over the two routines, compiled for
+    """tests/hostcheck/cable_integral_rays.hip with -DCABLE_OPL_MAIN: a stand-alone program over the two routines, compiled for
     the host with ASan + UBSan and run directly (nothing preloaded): NaN / Inf positions, velocities, targets, seeds and
     profile entries, a 2-sample profile, and the poisoned rec_steps -- no report, every loop ends, the poisoned rays are
     refused."""
@@ -395,6 +395,17 @@ def test_routines_under_sanitizers(tmp_path):
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert "768 poisoned rays refused" in r.stdout
+
+
+# ---- CPU tier: the LDS rule of the cable kernels --------------------------------------------------------------------
+def test_lds_table():
+    """cable_lds_bytes(rres, nprof, ngrad), the one rule launchers and kernels share: rres (4 nprof + 8 ngrad) bytes up to
+    the largest staged profile, 0 (global memory) from one sample more."""
+    for nprof, ngrad, largest, nbytes in ((1, 0, 4096, 16384), (1, 1, 4096, 49152), (2, 0, 4096, 32768),
+                                          (2, 1, 3072, 49152), (2, 2, 2048, 49152)):
+        assert H.lds_bytes(largest, nprof, ngrad) == nbytes, (nprof, ngrad)
+        assert H.lds_bytes(largest + 1, nprof, ngrad) == 0, (nprof, ngrad)
+        assert H.lds_bytes(2, nprof, ngrad) == 2 * (4 * nprof + 8 * ngrad), (nprof, ngrad)
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
@@ -486,6 +497,31 @@ def test_adjoint_kernel_matches_host(gpu, order, what):
             else:
                 assert not g.any()
         assert (st["ray_steps"], st["iters"], st["n_failed"]) == (b["ray_steps"], b["iters"], 0)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("rres", [4096, 4097])
+def test_single_profile_adjoints_on_both_sides_of_the_lds_limit(gpu, rres):
+    """65 rays at 4096 | 4097 samples: the 49 152 B launch of the single-profile adjoints (profile and f64 accumulators in
+    LDS) on one side, global reads and global atomics on the other.  k_backtrace_cable_opl<true, true> as in
+    test_adjoint_kernel_matches_host; k_backtrace_cable from the same record against its host build
+    (tests/hostcheck_lib.py), the profile gradient within ATOMIC_TOL and the statistics equal."""
+    from adjointnonlinearraytracing_amd import drrt
+    s = _gpu_scene(rres)
+    k = host_forward(s)
+    T = drrt.TracerC()
+    b = host_back(s, k)
+    grad, dpos, dvel = _dev_back(T, s, k, gpu)
+    st = drrt.read_stats()
+    assert np.array_equal(dpos.cpu().numpy(), b["dpos"], equal_nan=True)
+    assert np.array_equal(dvel.cpu().numpy(), b["dvel"], equal_nan=True)
+    assert np.linalg.norm(b["grad"]) > 0 and cases.rel_l2(grad.cpu().numpy(), b["grad"]) <= ATOMIC_TOL
+    assert (st["ray_steps"], st["iters"], st["n_failed"]) == (b["ray_steps"], b["iters"], 0)
+    hb = HC.backtrace_cable(s["prof"], s["radius"], s["length"], k["xt"], k["vt"], s["dx"], s["dv"], s["ds"])
+    g = T.backtrace_cable(_t(s["prof"], gpu), s["radius"], s["length"], _t(k["xt"], gpu), _t(k["vt"], gpu), _t(s["dx"], gpu),
+                          _t(s["dv"], gpu), s["ds"])
+    assert drrt.read_stats()["ray_steps"] == hb["steps_total"] > 0
+    assert np.linalg.norm(hb["grad"]) > 0 and cases.rel_l2(g.cpu().numpy(), hb["grad"]) <= ATOMIC_TOL
 
 
 @pytest.mark.gpu
