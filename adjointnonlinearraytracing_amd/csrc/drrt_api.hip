@@ -892,6 +892,42 @@ extern "C" int drrt_backtrace_vector_f32(const float* rif, const float* vfield, 
                                 launch_backtrace_vector);
 }
 
+// the checks of the two path entries that are their own, in front of the family's prologue
+static int check_path_series(int stride, int samples, size_t n) {
+  if (stride < 1) return fail(DRRT_ERR_ARG, "stride must be at least 1");
+  if (samples < 1) return fail(DRRT_ERR_ARG, "samples must be at least 1");
+  // the kernels index path with size_t: (j n + i) 3 floats, j < samples
+  if (n > 0 && (size_t)samples > SIZE_MAX / (3 * sizeof(float)) / n)
+    return fail(DRRT_ERR_ARG, "samples * n * 3 floats overflow size_t");
+  return DRRT_OK;
+}
+
+extern "C" int drrt_trace_path_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                   const float* pos, const float* vel, float h, float ds, int stride, int samples,
+                                   float* xt, float* vt, float* path, int* count, uint32_t* steps_out, drrt_stats* stats,
+                                   void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  int rc = check_path_series(stride, samples, n); if (rc) return rc;
+  PathTraceArgs a{};
+  a.path = path; a.count = count; a.stride = (unsigned)stride; a.samples = (unsigned)samples;
+  // count rides with the ray pointers: one check, one message
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {},
+                            {path, (const float*)count}, xt, vt, steps_out, DRRT_PROF_TRACE_PATH, "k_trace_path",
+                            launch_trace_path);
+}
+
+extern "C" int drrt_backtrace_path_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                       const float* pos, const float* vel, const float* xt, const float* vt,
+                                       const uint32_t* fwd_steps, const float* dx, const float* dv, const float* dpath,
+                                       float h, float ds, int stride, int samples, float* grad, float* dpos, float* dvel,
+                                       drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  int rc = check_path_series(stride, samples, n); if (rc) return rc;
+  PathBackArgs a{};
+  a.dpath = dpath; a.grad = grad; a.stride = (unsigned)stride; a.samples = (unsigned)samples;
+  return run_backtrace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {}, {}, {grad},
+                                "null output pointers: grad, or dpos and dvel, or all three", xt, vt, fwd_steps, dx, dv,
+                                dpos, dvel, DRRT_PROF_BACKTRACE_PATH, "k_backtrace_path", launch_backtrace_path);
+}
+
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }
 extern "C" int drrt_backtrace_max_steps(const int res[3], float h, float ds) {
   if (!res || !(h > 0.f) || !(ds > 0.f)) return -1;

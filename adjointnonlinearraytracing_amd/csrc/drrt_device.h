@@ -822,9 +822,10 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
 //   sink(c, val, gx, gy, gz)               the contribution to dL/dn, formed like adj_contrib's with mu BEFORE adj_recur
 //                                          updates it: val = dn ds, g = (n_k ds grad_scale) mu; the caller adds
 //                                          splat_weights(c.wx, c.wy, c.wz, val, gx, gy, gz) at the 8 taps of c
-//   term.pull(V, c, m, s)                  the term's own pulls on lambda (the gradients of its fields at the sample
-//                                          position) and its contributions to its own grids, BEFORE adj_recur, whose
-//                                          closing mu += ds lambda must see the pulls
+//   term.pull(V, c, m, s, entry)           the term's own pulls on lambda (the gradients of its fields at the sample
+//                                          position, a direct seed on x_k) and its contributions to its own grids, BEFORE
+//                                          adj_recur, whose closing mu += ds lambda must see the pulls; entry: this is the
+//                                          last reverse iteration, the one that samples the replayed x_e itself
 //   adj_recur(V, ds, s, m, dn)
 //   term.after()                           the term's running scalars
 // With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum of the contributions is the exact discrete derivative; the 1/h
@@ -832,7 +833,7 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
 struct NoTerm {                              // trace itself: nothing is integrated
   DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
-  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&, bool) {}
   DRRT_HD void after() {}
 };
 
@@ -874,7 +875,7 @@ DRRT_HD RayGrad integral_backtrace_ray(const Vol& V, float ds, float grad_scale,
     const float nds = (m.n * ds) * grad_scale;
     sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
     qx = s.mx; qy = s.my; qz = s.mz;
-    term.pull(V, c, m, s);
+    term.pull(V, c, m, s, k == e + 1u);
     adj_recur(V, ds, s, m, dn);
     term.after();
   }
@@ -926,7 +927,7 @@ struct OplTerm {
   float dopl2;                               // 2 dopl
   DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample& m, float mg) { return fmaf(dopl2, m.n, mg); }
-  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&) {}
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&, bool) {}
   DRRT_HD void after() {}
 };
 
@@ -998,7 +999,7 @@ struct FieldTerm {
     a = interp<false>(ftaps(c), c.wx, c.wy, c.wz);
     return fmaf(dtau, a.n, mg);
   }
-  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample& m, AdjState& s) {
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample& m, AdjState& s, bool) {
     const float fv = dtds * m.n;                                          // dtau ds n_k
     fsink(c, fv);
     s.lx = fmaf(fv, a.gx * V.inv_h, s.lx); s.ly = fmaf(fv, a.gy * V.inv_h, s.ly); s.lz = fmaf(fv, a.gz * V.inv_h, s.lz);
@@ -1119,7 +1120,7 @@ struct EmissionTerm {
     ce = drad * exp_neg(t);
     return mg + fmaf(ce, em.n, P * ab.n);
   }
-  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s) {
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s, bool) {
     ev = ce * w;
     const float av = P * w;
     esink(c, ev);
@@ -1207,7 +1208,7 @@ struct VectorTerm {
     s.mx = fmaf(g, ux.n, s.mx); s.my = fmaf(g, uy.n, s.my); s.mz = fmaf(g, uz.n, s.mz);
   }
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
-  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s) {
+  DRRT_HD void pull(const Vol& V, const Cell& c, const AdjSample&, AdjState& s, bool) {
     vsink(0, c, wx); vsink(1, c, wy); vsink(2, c, wz);
     s.lx = fmaf(dot3(ux.gx, uy.gx, uz.gx, wx, wy, wz), V.inv_h, s.lx);
     s.ly = fmaf(dot3(ux.gy, uy.gy, uz.gy, wx, wy, wz), V.inv_h, s.ly);
@@ -1223,6 +1224,110 @@ DRRT_HD RayGrad vector_backtrace_ray(const Vol& V, float ds, float grad_scale, i
                                      VecSink&& vsink) {
   VectorTerm<VecTapFn, VecSink> term{vtaps, vsink, dcirc * ds, {}, {}, {}, 0.f, 0.f, 0.f};
   return integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, taps, sink, term);
+}
+
+// ---- ray paths ---------------------------------------------------------------------------------------------------------
+// Where the ray went: every stride-th marching position, as a series of M entries per ray.  With K the ray's iteration
+// count and x_k the marching position in front of iteration k (x_0 = p, the march's own fp32 values),
+//   count   = min(M, ceil(K / stride))      the strided samples x_{j stride} with j stride < K that fit
+//   path[j] = x_{j stride}   for j < count
+//   path[j] = xt             for count <= j < M   (padding: a series that is long enough ends on the exit position; a
+//                                                  ray that never samples inside the box has xt = p, Q6)
+// M stride < K truncates the series (no padding, no error).  x_K, the position behind the last iteration, is no sample: it
+// is xt for a ray that left through a face.  Not in the reference.
+constexpr unsigned path_count(unsigned K, unsigned stride, unsigned M) {
+  const unsigned all = K ? (K - 1u) / stride + 1u : 0u;
+  return all < M ? all : M;
+}
+
+// `store(j, x, y, z)` writes path[j] of the ray.  The iteration behind which the next sample is due is counted down to
+// (no division in the loop).  The position behind iteration `it` is x_{it+1}: it is written when it + 1 is a multiple of
+// stride, the series has room, and the iteration did not flag the ray (then K = it + 1 and x_K is no sample).  A failed ray
+// (K = max_steps, never flagged) may write x_K when stride divides K; that entry is padding, and xt = x_K for such a ray.
+template <typename StoreFn>
+struct PathIntegrand {
+  StoreFn& store;
+  unsigned stride, M, cd, j;
+  DRRT_HD void operator()(const Cell&, bool, float) {}
+  DRRT_HD void step(const FwdState& s) {
+    if (--cd != 0u) return;
+    cd = stride;
+    if (!s.esc & (j < M)) store(j, s.x, s.y, s.z);
+    ++j;
+  }
+};
+
+// trace for ONE ray, with its path: stride >= 1, M >= 1.  All M entries are written: x_0 in front of the loop, the samples
+// from the loop, the padding behind it.
+template <typename TapFn, typename StoreFn>
+DRRT_HD RayOut trace_path_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], unsigned stride,
+                              unsigned M, TapFn&& taps, StoreFn&& store, unsigned& count) {
+  store(0u, p[0], p[1], p[2]);
+  PathIntegrand<StoreFn> q{store, stride, M, stride, 1u};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  count = path_count(o.steps, stride, M);
+  for (unsigned j = count; j < M; ++j) store(j, o.xt[0], o.xt[1], o.xt[2]);
+  return o;
+}
+
+// Adjoint of trace_path_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn from the seeds (dx, dv) on
+// (xt, vt) and `seed(j, g)`, which writes the seed on path[j] to g[3] (zeros when there is none), with K and count held
+// fixed.  The reverse iteration that arrives at x_k adds the seed on a sample x_k, k > e, to lambda in `pull`, in front of
+// adj_recur, whose closing mu += ds lambda must see it (x_k = x_{k-1} + ds v_k).  The iterations are counted down to the
+// next sample as in the forward.  What the reverse march does not reach is added around it, in this order:
+//   * padding: the seeds on path[count .. M-1] are seeds on xt and are added to dx in ascending j, in fp32, before the march
+//     is initialised, so mu = dv + ds dx sees them;
+//   * prefix: the samples x_k = p + k ds v of the free flight in front of the box, k <= e (x_e included: the reverse march
+//     ends on lambda = dL/dx_e), are added to the result behind the march in ascending j: dpos += g,
+//     dvel = fmaf((float)k * ds, g, dvel), k = j stride -- the way the skeleton forms e ds.
+// A ray that never sampled inside (e = K) returns (dx, dv) with its padding and prefix seeds and contributes nothing; a
+// failed ray returns zeros (no seed is read).
+template <typename SeedFn>
+struct PathTerm {
+  SeedFn& seed;
+  unsigned stride, cd;                       // cd: reverse iterations until one arrives at the sample j
+  int j;                                     // the next sample the march arrives at; < 0: none left
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
+  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState& s, bool entry) {
+    if (cd-- != 0u) return;
+    cd = stride - 1u;
+    if ((j >= 0) & !entry) {
+      float g[3];
+      seed((unsigned)j, g);
+      s.lx += g[0]; s.ly += g[1]; s.lz += g[2];
+    }
+    --j;
+  }
+  DRRT_HD void after() {}
+};
+
+template <typename TapFn, typename SeedFn, typename Sink>
+DRRT_HD RayGrad path_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                   const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                   const float dv[3], unsigned stride, unsigned M, SeedFn&& seed, TapFn&& taps, Sink&& sink) {
+  float dxp[3] = {dx[0], dx[1], dx[2]};
+  unsigned count = 0;
+  const bool failed = max_steps <= 0 || K >= (unsigned)max_steps;
+  if (!failed) {
+    count = path_count(K, stride, M);
+    for (unsigned j = count; j < M; ++j) {
+      float g[3];
+      seed(j, g);
+      dxp[0] += g[0]; dxp[1] += g[1]; dxp[2] += g[2];
+    }
+  }
+  PathTerm<SeedFn> term{seed, stride, count ? (K - 1u) - (count - 1u) * stride : 0u, (int)count - 1};
+  RayGrad r = integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dxp, dv, taps, sink, term);
+  if (r.failed) return r;
+  const unsigned e = K - r.steps;                                         // the skeleton's free-flight prefix
+  for (unsigned j = 0, k = 0; j < count && k <= e; ++j, k += stride) {
+    float g[3];
+    seed(j, g);
+    const float kds = (float)k * ds;
+    for (int a = 0; a < 3; ++a) { r.dp[a] += g[a]; r.dv[a] = fmaf(kds, g[a], r.dv[a]); }
+  }
+  return r;
 }
 
 // ---- the fibre (cable) march: one forward loop, one record-anchored reverse march -------------------------------------

@@ -11,6 +11,9 @@
 //                                                          the cell and weights of n_k, v_{k+1} the velocity behind the
 //                                                          step; dL/dn, the three planes of dL/du and the ray gradients
 //                                                          from (xt, vt, circ)
+//   drrt_trace_path_f32 / drrt_backtrace_path_f32          path = every stride-th marching position, padded with xt: the
+//                                                          first operator whose per-ray output is a series; dL/dn and the
+//                                                          ray gradients from (xt, vt, path)
 // Per-ray arithmetic: trace_integral_ray / integral_backtrace_ray of drrt_device.h with each operator's integrand and term
 // (trace_opl_ray ... vector_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
 // drrt_march.h.
@@ -31,8 +34,8 @@
 
 namespace drrt {
 
-// What the forward kernels share: the lane's ray, its march and its stores.  `march(p0, v0, taps)` -> RayOut runs the
-// operator's routine, `store(i)` writes the operator's own per-ray outputs.
+// What the forward kernels share: the lane's ray, its march and its stores.  `march(i, p0, v0, taps)` -> RayOut runs the
+// operator's routine on ray i, `store(i)` writes the operator's own per-ray outputs.
 template <bool PAIR, typename Args, typename March, typename Store>
 __device__ __forceinline__ void trace_lanes(const Args& a, March&& march, Store&& store) {
   const Vol& V = a.vol;
@@ -44,7 +47,7 @@ __device__ __forceinline__ void trace_lanes(const Args& a, March&& march, Store&
     const Ray3 p = ld3(a.pos, i), u = ld3(a.vel, i);
     const float p0[3] = {p.x, p.y, p.z}, v0[3] = {u.x, u.y, u.z};
     OplTaps<PAIR> taps(V, R);
-    const RayOut r = march(p0, v0, taps);
+    const RayOut r = march(i, p0, v0, taps);
     steps = r.steps; failed = r.act ? 1u : 0u;
     st3(a.xt, i, r.xt[0], r.xt[1], r.xt[2]);
     st3(a.vt, i, r.vt[0], r.vt[1], r.vt[2]);
@@ -104,7 +107,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_opl(OplTraceArgs a) {
   float opl;
   trace_lanes<PAIR>(a,
-    [&](const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
       return trace_opl_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, opl);
     },
     [&](size_t i) { a.opl[i] = opl; });
@@ -130,7 +133,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_field(FieldTraceArgs a) {
   float tau;
   trace_lanes<PAIR>(a,
-    [&](const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
       FieldTaps ftaps(a.field);
       return trace_field_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, ftaps, tau);
     },
@@ -159,7 +162,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_emission(EmissionTraceArgs a) {
   float rad, tau;
   trace_lanes<PAIR>(a,
-    [&](const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
       FieldTaps etaps(a.emission), ataps(a.absorption);
       return trace_emission_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, etaps, ataps, rad, tau);
     },
@@ -198,7 +201,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_vector(VectorTraceArgs a) {
   float circ;
   trace_lanes<PAIR>(a,
-    [&](const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
       VectorTaps vtaps(a.vfield, plane_size(a.vol));
       return trace_vector_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, vtaps, circ);
     },
@@ -221,6 +224,39 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_vector(VectorBackArgs a) {
                                            dcirc, taps, vtaps, sink, vsink);
     if (GRID) acc.flush();
     if (VFIELD) { xacc.flush(); yacc.flush(); zacc.flush(); }
+    return g;
+  });
+}
+
+// ---- ray paths -----------------------------------------------------------------------------------------------------------
+// path is (samples, n, 3), sample-major: entry j of ray i at (j n + i) 3, so that in caller order a wave's 64 stores of one
+// sample are one contiguous run of 768 bytes.  Under a visit order (perm) they are 64 scattered 12-byte stores on 1 / stride
+// of the iterations; they are not staged (DESIGN.md 6 has what that costs).
+template <bool PAIR>
+__global__ void __launch_bounds__(kBlock) k_trace_path(PathTraceArgs a) {
+  unsigned count;
+  trace_lanes<PAIR>(a,
+    [&](size_t i, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+      auto store = [&](unsigned j, float x, float y, float z) { st3(a.path, (size_t)j * a.n + i, x, y, z); };
+      return trace_path_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
+    },
+    [&](size_t i) { a.count[i] = (int)count; });
+}
+
+// GRID: dL/dn is scattered (a.grad is not null)
+template <bool PAIR, bool GRID>
+__global__ void __launch_bounds__(kBlock) k_backtrace_path(PathBackArgs a) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+    auto seed = [&](unsigned j, float* g) {
+      const Ray3 zero{0.f, 0.f, 0.f};
+      const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;
+      g[0] = d.x; g[1] = d.y; g[2] = d.z;
+    };
+    HeldCorners acc(a.grad);
+    SplatSink<GRID> sink{acc};
+    const RayGrad g = path_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
+                                         a.stride, a.samples, seed, taps, sink);
+    if (GRID) acc.flush();
     return g;
   });
 }
@@ -259,6 +295,14 @@ void launch_backtrace_vector(const VectorBackArgs& a, hipStream_t s) {
   with_bools([&](auto pair, auto grid, auto vfield) {
     LAUNCH_INTEGRAL((k_backtrace_vector<decltype(pair)::value, decltype(grid)::value, decltype(vfield)::value>), a, s);
   }, a.vol.pair != nullptr, a.grad != nullptr, a.grad_vfield != nullptr);
+}
+void launch_trace_path(const PathTraceArgs& a, hipStream_t s) {
+  with_bools([&](auto pair) { LAUNCH_INTEGRAL(k_trace_path<decltype(pair)::value>, a, s); }, a.vol.pair != nullptr);
+}
+void launch_backtrace_path(const PathBackArgs& a, hipStream_t s) {
+  with_bools([&](auto pair, auto grid) {
+    LAUNCH_INTEGRAL((k_backtrace_path<decltype(pair)::value, decltype(grid)::value>), a, s);
+  }, a.vol.pair != nullptr, a.grad != nullptr);
 }
 
 }  // namespace drrt

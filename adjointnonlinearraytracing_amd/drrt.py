@@ -617,7 +617,7 @@ def _more_grid(grid, rif_, dev: torch.device) -> torch.Tensor:
 
 def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sdf=None, how=None, fwd_steps=None,
                order=None, replay: bool = False, flags: int = 0, steps: bool = True, warn: bool = False,
-               counters: bool = False, per_ray=(), more_grids=(), planes: int = 1) -> tuple:
+               counters: bool = False, per_ray=(), more_grids=(), planes: int = 1, scalars=()) -> tuple:
     """One call of a grid entry point (they share their shape: grid, [sdf], nvox, res, n, the inputs, h, ds, the outputs,
     the usual tail) -> (outputs, order, steps): the outputs, made by ``make_outputs(flat grid, ray tensors)``, and what
     a forward march left behind -- its visit order and per-ray iteration counts, the workspace views that are also
@@ -628,7 +628,8 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
     with one through `order`; `replay`: an adjoint that marches its forward again (`_paired_adjoint`).  `steps`: the
     forward leaves iteration counts.  `warn`: failed rays are reported.  `counters`: the adjoint classifies its bundles
     (`last_bundle_counters`).  `more_grids`: further fp32 grids of the first one's size, passed behind `sdf`.  `planes`:
-    `sdf` is that many component planes of the first grid's size."""
+    `sdf` is that many component planes of the first grid's size.  `scalars`: further int arguments of the entry, passed
+    behind ds."""
     dev = _dev(rif)
     with torch.cuda.device(dev):
         rif_, sdf_, rays_, n = _grid_inputs(rif, sdf, rays, dev, how, planes)
@@ -650,7 +651,7 @@ def _grid_call(name: str, rif, res, rays, h, ds, make_outputs, adjoint: bool, sd
             _forward_march(rif_, res, n, h, ds, dev, flags)
         with march as (fl, ws, st, _):
             _lib.check(getattr(_lib.load(), name)(
-                *grids, rif_.numel(), _res3(res), n, *map(_p, rays_), float(h), float(ds), *map(_p, out),
+                *grids, rif_.numel(), _res3(res), n, *map(_p, rays_), float(h), float(ds), *map(int, scalars), *map(_p, out),
                 _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
             if counters:
                 _capture_counters(ws)
@@ -677,14 +678,16 @@ def _like_grid(rif_, rays_) -> tuple:
 
 
 def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_out, dx, dv, seeds, wanted, rays: bool, h, ds,
-                        order, planes: int = 1) -> tuple:
+                        order, planes: int = 1, series=(), scalars=()) -> tuple:
     """What ``backtrace_opl`` / ``backtrace_field`` / ``backtrace_emission`` / ``backtrace_vector`` share: one call of drrt_backtrace_<op>_f32 ->
     (the grid gradients in the order of `wanted`, dpos, dvel), None for what is not asked for.  `more`: the operator's
     further grids; `fwd_out`: (name, tensor) of the forward outputs the adjoint needs besides xt, vt and steps; `seeds`:
     the per-ray seeds behind dx, dv (None: zeros); `wanted`: per grid gradient (asked for, accumulator or None, the name of
     the accumulator's argument).  An accumulator means DRRT_FLAG_NO_ZERO, which covers every grid of the call: those asked
     for without one are zeroed here.  `planes`: the operator's first further grid, and the gradient behind dL/drif, are that
-    many component planes of the grid's size (a vector field: 3)."""
+    many component planes of the grid's size (a vector field: 3).  `series`: (seed or None, its shape with None for the ray
+    count) of the seeds on outputs that are a series per ray, passed behind `seeds`; `scalars`: further int arguments of
+    the entry, passed behind ds."""
     if not (rays or any(want for want, _, _ in wanted)):
         switches = [name.replace("into", "grid") for _, _, name in wanted] + ["rays"]
         raise RuntimeError(f"backtrace_{op}: nothing to compute ({' = '.join(switches)} = False)")
@@ -704,6 +707,13 @@ def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_ou
         for t in per_ray:
             if t is not None and t.numel() != n:
                 raise RuntimeError(f"expected {n} per-ray values, got {t.numel()}")
+        series_ = []
+        for t, shape in series:
+            t = None if t is None else _f32(t, dev)
+            want = tuple(n if d is None else d for d in shape)
+            if t is not None and tuple(t.shape) != want:
+                raise RuntimeError(f"backtrace_{op}: expected a seed of shape {want}, got {tuple(t.shape)}")
+            series_.append(t)
         no_zero = any(want and acc is not None for want, acc, _ in wanted)
         grads = []
         for k, (want, acc, name) in enumerate(wanted):
@@ -721,10 +731,17 @@ def _backtrace_integral(op: str, rif, more, res, pos, vel, xt, vt, steps, fwd_ou
         with _paired_adjoint(rif_, res, n, h, ds, dev, order, flags=_lib.FLAG_NO_ZERO if no_zero else 0) as (fl, ws, st, _):
             _lib.check(getattr(_lib.load(), f"drrt_backtrace_{op}_f32")(
                 _p(rif_), *map(_p, more_), rif_.numel(), _res3(res), n, _p(pos_), _p(vel_), _p(xt_), _p(vt_), _p(steps_),
-                *map(_p, per_ray[:len(fwd_out)]), _p(dx_), _p(dv_), *map(_p, per_ray[len(fwd_out):]), float(h), float(ds),
-                *map(_p, grads), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
+                *map(_p, per_ray[:len(fwd_out)]), _p(dx_), _p(dv_), *map(_p, per_ray[len(fwd_out):]), *map(_p, series_),
+                float(h), float(ds), *map(int, scalars), *map(_p, grads), _p(dpos), _p(dvel), _p(st), _p(ws), ws.numel(), fl, _stream(dev)))
         _warn_failed(st)
     return (*grads, dpos, dvel)
+
+
+def path_max_steps(res, h, ds) -> int:
+    """The forward march's iteration bound, (int)(4 h max(res) / ds) in fp32 as the library forms it: what
+    ``trace_path``'s default `samples` is sized by."""
+    f = lambda a: torch.tensor(float(a), dtype=torch.float32)      # noqa: E731
+    return int(f(4.0) * f(h) * f(max(int(r) for r in res)) / f(ds))
 
 
 class TracerC:
@@ -841,7 +858,49 @@ class TracerC:
         uniform u it telescopes to ``u . (xt - x_e)``).  fp32 rays only."""
         return self._trace_vector(rif, vfield, res, pos, vel, h, ds)[0]
 
+    def _trace_path(self, rif, res, pos, vel, h, ds, stride, samples=None):
+        stride = int(stride)
+        if samples is None:
+            samples = -(-max(path_max_steps(res, h, ds), 0) // max(stride, 1)) + 1
+        samples = int(samples)
+
+        def outputs(rif_, r):
+            n, dev = r[0].shape[0], r[0].device
+            return _like_rays(rif_, r) + (r[0].new_empty((max(samples, 0), n, 3)),
+                                          torch.empty(n, dtype=torch.int32, device=dev),
+                                          torch.empty(n, dtype=torch.int32, device=dev))
+        return _grid_call("drrt_trace_path_f32", rif, res, [pos, vel], h, ds, outputs, adjoint=False, steps=False,
+                          warn=True, scalars=(stride, samples))
+
+    def trace_path(self, rif, res, pos, vel, h, ds, stride, samples=None):
+        """``trace`` with the path of every ray (drrt_trace_path_f32, include/drrt_hip.h; not in the reference) ->
+        (xt, vt, path, count, steps).  xt, vt and the per-ray iteration counts `steps` (int32[n]) are ``trace``'s bit for
+        bit.  `path` is fp32 ``(samples, n, 3)``, sample-major: ``path[j]`` is every ray at sample j, ``path[:, i]`` ray i's
+        polyline: the marching positions in front of iterations 0, stride, 2 stride, ... (``path[0] = pos``), `count`
+        (int32[n]) of them, then xt repeated.  A ray that never samples inside the box has xt = pos, so its padding is pos;
+        `count` says where to cut.  ``samples * stride < steps`` truncates a ray's series: no padding, no error.
+        ``samples=None`` is ``ceil(max_steps / stride) + 1``, the smallest that always ends on xt.  fp32 rays only."""
+        return self._trace_path(rif, res, pos, vel, h, ds, stride, samples)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_path(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, h, ds, stride, grid: bool = True,
+                       rays: bool = True, into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+                       samples: Optional[int] = None):
+        """Adjoint of ``trace_path`` (drrt_backtrace_path_f32, include/drrt_hip.h) -> (grad | None, dpos | None, dvel |
+        None): flat dL/dn (fp32[nvox]), dL/dpos and dL/dvel ((n,3) fp32) from ONE reverse march, the derivative of the
+        discrete forward with `steps` and `count` held fixed.  `pos`, `vel` are the forward call's inputs, `xt`, `vt`,
+        `steps` its outputs, `stride` its stride; `dx`, `dv` ((n,3)) and `dpath` ((samples, n, 3)) the seeds on (xt, vt,
+        path), each optional (None: zeros).  `samples` is read off `dpath`; it is needed only when `dpath` is None (then any
+        value gives the same result, and the default is 1).  Seeds on padded entries are seeds on xt, added to dx in
+        ascending j.  `grid` / `rays` / `into` / `order`: as for ``backtrace_opl``.  Honours ``options.corrected_h`` (with it
+        the grid gradient is the exact discrete derivative; the ray gradients do not depend on it).  Rays that failed the
+        forward get zeros and contribute nothing."""
+        if samples is None:
+            samples = 1 if dpath is None else int(dpath.shape[0])
+        return _backtrace_integral("path", rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (), ((grid, into, "into"),),
+                                   rays, h, ds, order, series=((dpath, (int(samples), None, 3)),),
+                                   scalars=(int(stride), int(samples)))
+
     def backtrace_vector(self, rif, vfield, res, pos, vel, xt, vt, steps, dx, dv, dcirc, h, ds, grid: bool = True,
                          vfield_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,
                          vfield_into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None):

@@ -463,6 +463,37 @@ class VectorIntegralTracerC(torch.autograd.Function):
         return (*_integral_backward(ctx, drrt.TracerC().backtrace_vector, grad_x, grad_v, grad_circ), None, None)
 
 
+class PathTracerC(torch.autograd.Function):
+    """``apply(rif, x, v, h, ds, stride, samples) -> (xt, vt, path, count)``: ``trace`` with the path of every ray, ``path``
+    of shape ``(samples, n, 3)`` (``path[j]``: every ray at sample j; ``path[:, i]``: ray i's polyline): the marching
+    positions in front of iterations 0, stride, 2 stride, ..., ``count`` (int32[n], not differentiable) of them per ray, then
+    xt repeated (``samples=None``: ``ceil(max_steps / stride) + 1``, which always ends on xt).  xt, vt and path are
+    differentiable w.r.t. ``rif``, ``x`` and ``v``: a field given in torch (an analytic density, an MLP, a grid of another
+    resolution sampled with ``grid_sample``), a loss on the curve itself or a quadrature of one's own is a few lines of torch
+    on ``path``, and its gradient reaches ``rif`` through the sample positions.  Not in the reference.
+
+    The forward is ``TracerC.trace_path``; backward is ONE ``TracerC.backtrace_path`` launch (plus the zero-fill of the grid
+    gradient when ``rif`` requires grad), the derivative of the discrete forward with the iteration counts and ``count`` held
+    fixed; ``path``'s gradient arrives dense or not at all.  Options, kept copies, failed rays and dtypes: as for
+    OPLTracerC."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, h, ds, stride, samples=None):
+        def march(*a):
+            out, order, left = drrt.TracerC()._trace_path(*a, stride, samples)
+            ctx.stride, ctx.samples = int(stride), int(out[2].shape[0])
+            return out, order, left
+        xt, vt, path, count = _integral_forward(ctx, "PathTracerC", march, rif, (), x, v, h, ds)
+        ctx.mark_non_differentiable(count)
+        return xt, vt, path, count
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_path, _grad_count=None):
+        def back(*a, **kw):             # a: (rif, shape, x0, v0, xt, vt, steps, dx, dv, dpath, h, ds, grid, rays)
+            return drrt.TracerC().backtrace_path(*a[:12], ctx.stride, *a[12:], samples=ctx.samples, **kw)
+        return (*_integral_backward(ctx, back, grad_x, grad_v, grad_path), None, None, None, None)
+
+
 def _cable_integral_forward(ctx, name, march, profiles, radius, length, x, v, sp, ds):
     """Forward of a fibre march with an integral up to the record: ``march(flat profiles..., radius, length, x, v, sp, ds)
     -> (xt, vt, dist2, integral, rec_steps)`` (``TracerC.trace_cable_opl`` / ``trace_cable_field``) on detached inputs ->

@@ -527,6 +527,58 @@ DRRT_API int drrt_backtrace_vector_f32(const float* rif, const float* vfield, lo
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- ray paths: where every bent ray went (not in the reference) ---------------------------------------------------------
+ * drrt_trace_path_f32 is drrt_trace_f32 (xt, vt and the per-ray iteration counts K bit for bit, failed rays included: Q5,
+ * Q6) that also returns every stride-th marching position of every ray.  Per ray, with x_k the marching position in front
+ * of iteration k (x_0 = pos; fp32, the march's own values), stride >= 1 and samples = M >= 1:
+ *   count[i]   = min(M, ceil(K / stride)): the strided samples x_{j stride} with j stride < K that fit
+ *   path[j]    = x_{j stride}  for j < count
+ *   path[j]    = xt            for count <= j < M (padding): a series that is long enough ends on the exit ray's position.
+ *                A ray that never samples inside the box has xt = pos by the march's own convention (Q6), so its padding
+ *                is pos; count says where to cut.
+ * M stride < K truncates the series: no padding, and no error.  M = ceil(max_steps / stride) + 1 is the smallest M that
+ * always ends on xt (max_steps: the forward's bound, (int)(4 h max(res) / ds)).
+ *   path       out: fp32 (M, n, 3), sample-major: entry j of ray i at (j n + i) 3.  path[j] is every ray at sample j; a
+ *              wave stores one contiguous run per sample when the rays are visited in caller order
+ *   count      out: int32[n]
+ *   steps_out  out: uint32[n], required, as for drrt_trace_opl_f32
+ * DRRT_ERR_ARG: stride < 1, samples < 1, samples n 3 floats overflowing size_t (the kernels' index type), and the checks
+ * of drrt_trace_opl_f32 (count is checked with the ray pointers).
+ * Flags: as for drrt_trace_opl_f32.  fp32 only.                                                                         */
+DRRT_API int drrt_trace_path_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds, int stride, int samples,
+                       float* xt, float* vt, float* path, int* count, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_path_f32: the derivative of the discrete forward with K and count held fixed, from the seeds
+ * dx = dL/dxt, dv = dL/dvt ((n,3)) and dpath = dL/dpath ((M, n, 3), path's layout), each nullable: read as zeros.  ONE
+ * reverse march yields dL/dn (grad), dL/dpos and dL/dvel.  The march is drrt_backtrace_opl_f32's with dopl null; with dpath
+ * null the results are that call's bit for bit.  With e the free-flight prefix of the ray (drrt_backtrace_rays_f32):
+ *   * the seed on a sample x_k, k > e, is added to lambda in the reverse iteration that arrives at x_k, before that
+ *     iteration's lambda / mu recurrences (mu += ds lambda sees it);
+ *   * the seeds on the prefix samples x_k = pos + k ds vel, k <= e, go straight to the result behind the march, in
+ *     ascending j:  dpos += g,  dvel = fmaf((float)k * ds, g, dvel)  (the way e ds is formed for dvel);
+ *   * the seeds on padded entries are seeds on xt: they are added to dx in ascending j, in fp32, ((dx + g_count) +
+ *     g_{count+1}) + ..., before the march is initialised, so mu = dv + ds dx sees them;
+ *   * a ray that never sampled inside (e = K) gets (dx, dv) with its padding and prefix seeds as above and contributes
+ *     nothing to grad; a failed ray gets zeros, contributes nothing and counts in stats->n_failed.
+ * grad is the exact discrete derivative with DRRT_FLAG_CORRECTED_H, as for drrt_backtrace_opl_f32; the ray gradients are
+ * exact either way.  stride and samples are the forward's.
+ *   grad        out, nullable (no scatter at all): fp32[nvox], zeroed by the call unless DRRT_FLAG_NO_ZERO
+ *   dpos, dvel  out, both or neither: (n,3) fp32.  grad, dpos and dvel all null: DRRT_ERR_ARG
+ * DRRT_ERR_ARG also for stride < 1, samples < 1 and samples n 3 floats overflowing size_t.
+ * Flags and hints: as for drrt_backtrace_opl_f32.  fp32 only.                                                           */
+DRRT_API int drrt_backtrace_path_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, const float* dpath, float h, float ds,
+                       int stride, int samples,
+                       float* grad, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -897,6 +949,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_CABLE_OPL 20 /* its adjoint: dL/d(profile) and the ray gradients in one march (drrt_backtrace_cable_opl_f32) */
 #define DRRT_PROF_TRACE_CABLE_FIELD 21 /* the cable march with the line integral of a second radial profile (drrt_trace_cable_field_f32) */
 #define DRRT_PROF_BACKTRACE_CABLE_FIELD 22 /* its adjoint: dL/d(profile), dL/d(field) and the ray gradients in one march (drrt_backtrace_cable_field_f32) */
+#define DRRT_PROF_TRACE_PATH 23      /* trace with every stride-th position of every ray (drrt_trace_path_f32) */
+#define DRRT_PROF_BACKTRACE_PATH 24  /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_path_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

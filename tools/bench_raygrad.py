@@ -107,6 +107,15 @@ vector  drrt_trace_vector_f32 / drrt_backtrace_vector_f32 (k_trace_vector, k_bac
         ratios trace_vector / trace_emission, trace_vector / trace_field and backtrace_vector_* / backtrace_field.
         usage: bench_raygrad.py vector [--grid 256] [--rays 1048576] [--rounds 7] [--warmup 2] [--once] [--out FILE]
         Also writes the JSON, with the library's version string (source digest), to --out (default profiles/vector_bench.json).
+path    drrt_trace_path_f32 / drrt_backtrace_path_f32 (k_trace_path, k_backtrace_path) next to the opl calls, which run the same
+        march without the series, on the Luneburg workload of `opl`: per stride (--strides, default 1 8 64) with
+        samples = ceil(max_steps / stride) + 1, in pixel order (sort_rays off) and in sorted order (the forward sorts, the
+        adjoints take its order); all eight calls of a combination alternate in one process:
+            trace_opl / trace_path                            the forward; trace_path_extra_ms is their difference, next to
+                                                              path_bytes = samples n 12 and what writing them at 8 TB/s takes
+            backtrace_{opl,path}_{rays,grid,both}             the adjoints, every seed set (dpath: ones)
+        usage: bench_raygrad.py path [--grid 256] [--rays 1048576] [--strides 1 8 64] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string, to --out (default profiles/path_bench.json).
 
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
@@ -543,6 +552,54 @@ def vector(a, dev):
     return out
 
 
+def path(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl`
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
+    rif = bench.make_grid(a.grid, dev)
+    res = tuple(rif.shape)
+    ms = drrt.path_max_steps(res, h, ds)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, max_steps=ms, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for order_name, sort in (("pixel", False), ("sorted", True)):
+        for stride in a.strides:
+            m = -(-ms // stride) + 1
+            with drrt.using(sort_rays=sort):
+                xt, vt, pth, count, steps = T.trace_path(rif, res, pos, vel, h, ds, stride, m)
+                order = drrt.keep_order(drrt.last_order)
+                dpath = torch.ones_like(pth)
+                del pth
+                bo = lambda **kw: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order, **kw)   # noqa: E731
+                bp = lambda **kw: T.backtrace_path(rif, res, pos, vel, xt, vt, steps, one, one, dpath, h, ds, stride,   # noqa: E731
+                                                   order=order, **kw)
+                r, med = time_each({
+                    "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
+                    "trace_path": lambda: T.trace_path(rif, res, pos, vel, h, ds, stride, m),
+                    "backtrace_opl_rays": lambda: bo(grid=False), "backtrace_path_rays": lambda: bp(grid=False),
+                    "backtrace_opl_grid": lambda: bo(rays=False), "backtrace_path_grid": lambda: bp(rays=False),
+                    "backtrace_opl_both": bo, "backtrace_path_both": bp,
+                }, a)
+            del dpath
+            if r is None:
+                continue
+            r["samples"], r["mean_count"], r["path_bytes"] = m, float(count.float().mean()), m * n * 12
+            r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
+            # what the extra time would be if the path were written at the peak HBM rate of the part (8 TB/s)
+            r["path_bytes_at_8TBps_ms"] = m * n * 12 / 8e12 * 1e3
+            r["trace_path_over_trace_opl"] = med["trace_path"] / med["trace_opl"]
+            for k in ("rays", "grid", "both"):
+                r[f"backtrace_path_{k}_over_backtrace_opl_{k}"] = med[f"backtrace_path_{k}"] / med[f"backtrace_opl_{k}"]
+            out[f"{order_name}_stride{stride}"] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -585,14 +642,20 @@ def main():
     p_vec.add_argument("--rays", type=int, default=1 << 20)
     p_vec.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "vector_bench.json"))
     p_vec.set_defaults(run=vector)
-    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis, p_vec):
+    p_path = sub.add_parser("path")
+    p_path.add_argument("--grid", type=int, default=256)
+    p_path.add_argument("--rays", type=int, default=1 << 20)
+    p_path.add_argument("--strides", type=int, nargs="+", default=[1, 8, 64])
+    p_path.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "path_bench.json"))
+    p_path.set_defaults(run=path)
+    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis, p_vec, p_path):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target", "opl", "field", "emission", "vector") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl", "field", "emission", "vector", "path") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")
