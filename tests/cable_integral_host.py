@@ -1,32 +1,23 @@
 """Loader for tests/hostcheck/cable_integral_rays.hip (TEST INFRASTRUCTURE ONLY): the product's per-ray routines of the
 fibre march with its optical path length (cable_trace_opl_ray, cable_opl_backtrace_ray of csrc/drrt_device.h) and with the
-line integral of a second radial profile (cable_trace_field_ray, cable_field_backtrace_ray), compiled for the host with the
-line of hostcheck_lib.lib() and looped as the kernels run them, and the kernels' LDS rule (cable_lds_bytes).  Never imported
+line integral of a second radial profile (cable_trace_field_ray, cable_field_backtrace_ray), compiled for the host by
+hostcheck_lib.build() and looped as the kernels run them, and the kernels' LDS rule (cable_lds_bytes).  Never imported
 by the package."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostcheck_lib import _f, _p
+from hostcheck_lib import HOSTCHECK, _f, _p, build
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(_HERE, "hostcheck", "cable_integral_rays.hip")
-_HDR = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc", "drrt_device.h")
-_SO = os.path.join(_HERE, "hostcheck", "_build", "libcable_integral_rays.so")
-HIPCC = "/opt/rocm/bin/hipcc"
+SOURCE = os.path.join(HOSTCHECK, "cable_integral_rays.hip")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in (SOURCE, _HDR)):
-            subprocess.run([HIPCC, "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mfma", "-shared",
-                            "-fvisibility=hidden", "-o", _SO, SOURCE], check=True, capture_output=True)
-        _lib = C.CDLL(_SO)
+        _lib = build("libcable_integral_rays.so", [SOURCE])
         _lib.cable_host_lds_bytes.restype = C.c_size_t
     return _lib
 

@@ -12,17 +12,8 @@
 // under AddressSanitizer + UndefinedBehaviorSanitizer: it makes its own cases (see the mains) and runs that operator's two
 // routines on them, 0 = no report.
 #include <math.h>
-#include <stdint.h>
-#include <stddef.h>
-#include <stdio.h>
 
-#include <vector>
-
-#include "../../adjointnonlinearraytracing_amd/csrc/drrt_device.h"
-
-using namespace drrt;
-
-#define EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_common.h"
 
 static int max_steps_of(float length, float ds) { return (int)(4.0f * length / ds); }   // drrt_api.hip cable_begin
 
@@ -52,14 +43,10 @@ EXPORT int cable_opl_host_backtrace(const float* rif, int rres, float radius, fl
   const int max_steps = max_steps_of(length, ds);
   for (int k = 0; k < rres; ++k) grad[k] = 0.0;
   auto sink = [grad](int i0, int i1, float a0, float a1) { grad[i0] += a0; grad[i1] += a1; };
-  const float zero[3] = {0.f, 0.f, 0.f};
-  for (size_t i = 0; i < n; ++i) {
-    const RayGrad g = cable_opl_backtrace_ray(C, ds, max_steps, pos + 3 * i, xt + 3 * i, vt + 3 * i, rec_steps[i],
-                                              dx ? dx + 3 * i : zero, dv ? dv + 3 * i : zero, dopl ? dopl[i] : 0.f, sink);
-    for (int k = 0; k < 3; ++k) { dpos[3 * i + k] = g.dp[k]; dvel[3 * i + k] = g.dv[k]; }
-    rsteps[i] = g.steps; failed[i] = g.failed ? 1 : 0;
-  }
-  return 0;
+  return backtrace_rays(n, dx, dv, dpos, dvel, rsteps, failed, [&](size_t i, const float* gx, const float* gv) {
+    return cable_opl_backtrace_ray(C, ds, max_steps, pos + 3 * i, xt + 3 * i, vt + 3 * i, rec_steps[i], gx, gv,
+                                   dopl ? dopl[i] : 0.f, sink);
+  });
 }
 
 // As cable_opl_host_trace, with `field` (rres samples) and tau for opl
@@ -87,15 +74,10 @@ EXPORT int cable_field_host_backtrace(const float* rif, const float* field, int 
   for (int k = 0; k < rres; ++k) grad[k] = grad_field[k] = 0.0;
   auto sink = [grad](int i0, int i1, float a0, float a1) { grad[i0] += a0; grad[i1] += a1; };
   auto fsink = [grad_field](int i0, int i1, float a0, float a1) { grad_field[i0] += a0; grad_field[i1] += a1; };
-  const float zero[3] = {0.f, 0.f, 0.f};
-  for (size_t i = 0; i < n; ++i) {
-    const RayGrad g = cable_field_backtrace_ray(C, field, ds, max_steps, pos + 3 * i, xt + 3 * i, vt + 3 * i, rec_steps[i],
-                                                dx ? dx + 3 * i : zero, dv ? dv + 3 * i : zero, dtau ? dtau[i] : 0.f, sink,
-                                                fsink);
-    for (int k = 0; k < 3; ++k) { dpos[3 * i + k] = g.dp[k]; dvel[3 * i + k] = g.dv[k]; }
-    rsteps[i] = g.steps; failed[i] = g.failed ? 1 : 0;
-  }
-  return 0;
+  return backtrace_rays(n, dx, dv, dpos, dvel, rsteps, failed, [&](size_t i, const float* gx, const float* gv) {
+    return cable_field_backtrace_ray(C, field, ds, max_steps, pos + 3 * i, xt + 3 * i, vt + 3 * i, rec_steps[i], gx, gv,
+                                     dtau ? dtau[i] : 0.f, sink, fsink);
+  });
 }
 
 #if defined(CABLE_OPL_MAIN) || defined(CABLE_FIELD_MAIN)
@@ -212,7 +194,6 @@ int main() {
     }
 #endif
   }
-  printf("%zu poisoned rays refused, %llu reverse iterations\nsanitizer run finished without reports\n", poisoned, sum);
-  return 0;
+  return finished("%zu poisoned rays refused, %llu reverse iterations", poisoned, sum);
 }
 #endif

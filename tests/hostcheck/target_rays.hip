@@ -8,17 +8,7 @@
 //
 // With -DTARGET_RAYS_MAIN it is a stand-alone program (its own main, nothing preloaded) for a build under AddressSanitizer
 // + UndefinedBehaviorSanitizer: argv[1] names a file with one case (see main), the routine runs on it, 0 = no report.
-#include <stdint.h>
-#include <stddef.h>
-#include <stdio.h>
-
-#include <vector>
-
-#include "../../adjointnonlinearraytracing_amd/csrc/drrt_device.h"
-
-using namespace drrt;
-
-#define EXPORT extern "C" __attribute__((visibility("default")))
+#include "host_common.h"
 
 // dpos, dvel, xt, vt: (n,3); dd2: n floats or null; dist2, jstar (the iteration of the replayed record), fwd (phase A's
 // iteration count), steps (replayed + reverse iterations of the second pass), failed: n each; *iters: the global loop count
@@ -27,12 +17,9 @@ EXPORT int target_raygrad_host_backtrace_rays(const float* rif, const int* res, 
                                               float h, float ds, float* dpos, float* dvel, float* xt, float* vt, float* dist2,
                                               uint32_t* jstar, uint32_t* fwd, uint32_t* steps, uint8_t* failed,
                                               uint32_t* iters) {
-  Vol V;
-  V.data = rif; V.W = res[0]; V.H = res[1]; V.D = res[2];
-  vol_finish(V, h);
-  const int mx = res[0] > res[1] ? (res[0] > res[2] ? res[0] : res[2]) : (res[1] > res[2] ? res[1] : res[2]);
-  const int max_steps = (int)(4.0f * h * (float)mx / ds);            // the forward's bound (drrt_api.hip steps_fwd)
-  auto taps = [&](const Cell& c) -> Taps { return fetch(V.data, c); };
+  const Vol V = vol(rif, res, h);
+  const int max_steps = max_steps_of(res, h, ds);
+  const GridTaps taps{rif};
   unsigned total = 0;
   for (size_t i = 0; i < n; ++i) {                                   // k_target_rays_count
     TargetReplay r;
@@ -55,34 +42,24 @@ EXPORT int target_raygrad_host_backtrace_rays(const float* rif, const int* res, 
 #ifdef TARGET_RAYS_MAIN
 // The case file: int32 W, H, D, n; float32 h, ds; then float32 arrays rif[W*H*D], pos, vel, target, dx, dv (n*3 each), dd2[n].
 int main(int argc, char** argv) {
-  if (argc < 2) return 2;
-  FILE* f = fopen(argv[1], "rb");
-  if (!f) return 2;
-  int hd[4]; float sc[2];
-  if (fread(hd, sizeof(int), 4, f) != 4 || fread(sc, sizeof(float), 2, f) != 2) return 2;
-  if (hd[0] < 1 || hd[1] < 1 || hd[2] < 1 || hd[3] < 0) return 2;
-  const size_t nvox = (size_t)hd[0] * hd[1] * hd[2], n = (size_t)hd[3];
-  std::vector<float> rif(nvox), ray[5], dd2(n);
-  bool ok = fread(rif.data(), sizeof(float), nvox, f) == nvox;
-  for (auto& a : ray) { a.resize(3 * n); ok = ok && fread(a.data(), sizeof(float), 3 * n, f) == 3 * n; }
-  ok = ok && fread(dd2.data(), sizeof(float), n, f) == n;
-  fclose(f);
-  if (!ok) return 2;
+  CaseFile c(argc, argv);
+  const size_t n = c.n;
+  const std::vector<float> rif = c.floats(c.nvox), pos = c.floats(3 * n), vel = c.floats(3 * n), tg = c.floats(3 * n),
+                           dx = c.floats(3 * n), dv = c.floats(3 * n), dd2 = c.floats(n);
+  if (!c.ok) return 2;
   std::vector<float> out[4], d2(n);
   for (auto& a : out) a.resize(3 * n);
   std::vector<uint32_t> js(n), fw(n), st(n);
   std::vector<uint8_t> fl(n);
   uint32_t iters = 0;
-  const int res[3] = {hd[0], hd[1], hd[2]};
   unsigned long long sum = 0;
   for (int with_dd2 = 0; with_dd2 < 2; ++with_dd2) {
-    target_raygrad_host_backtrace_rays(rif.data(), res, n, ray[0].data(), ray[1].data(), ray[2].data(), ray[3].data(),
-                                       ray[4].data(), with_dd2 ? dd2.data() : nullptr, sc[0], sc[1], out[0].data(),
-                                       out[1].data(), out[2].data(), out[3].data(), d2.data(), js.data(), fw.data(),
-                                       st.data(), fl.data(), &iters);
+    target_raygrad_host_backtrace_rays(rif.data(), c.hd, n, pos.data(), vel.data(), tg.data(), dx.data(), dv.data(),
+                                       with_dd2 ? dd2.data() : nullptr, c.h, c.ds, out[0].data(), out[1].data(),
+                                       out[2].data(), out[3].data(), d2.data(), js.data(), fw.data(), st.data(), fl.data(),
+                                       &iters);
     for (size_t i = 0; i < n; ++i) sum += st[i] + js[i] + fl[i];
   }
-  printf("%zu rays, global loop %u, checksum %llu\nsanitizer run finished without reports\n", n, iters, sum);
-  return 0;
+  return finished("%zu rays, global loop %u, checksum %llu", n, iters, sum);
 }
 #endif

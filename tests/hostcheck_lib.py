@@ -3,29 +3,61 @@ __host__ __device__ per-ray code compiled for the host, so CPU-only tests can co
 oracle's `factored` arithmetic bit for bit, and its ray-state adjoints with float64 autograd.  Never imported by the
 package."""
 import ctypes as C
+import glob
 import os
 import subprocess
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(_HERE, "hostcheck", "hostcheck.hip")]     # what a build of the library compiles
+HOSTCHECK = os.path.join(_HERE, "hostcheck")
+SOURCES = [os.path.join(HOSTCHECK, "hostcheck.hip")]              # what a build of the library compiles
 _CSRC = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc")
-_HDRS = [os.path.join(_CSRC, "drrt_device.h"), os.path.join(_CSRC, "drrt_keys.h")]   # what hostcheck.hip includes
-_SO = os.path.join(_HERE, "hostcheck", "_build", "libhostcheck.so")
+_HDRS = [os.path.join(_CSRC, "drrt_device.h"), os.path.join(_CSRC, "drrt_keys.h")]   # what the units include of the product
+HIPCC = "/opt/rocm/bin/hipcc"
 _lib = None
+
+
+def build(so_name, sources):
+    """-> the CDLL of tests/hostcheck/_build/<so_name>, compiled from `sources` for the host if it is missing or older than
+    a source, a header of tests/hostcheck or one of the product's headers the units include."""
+    so = os.path.join(HOSTCHECK, "_build", so_name)
+    deps = list(sources) + glob.glob(os.path.join(HOSTCHECK, "*.h")) + _HDRS
+    os.makedirs(os.path.dirname(so), exist_ok=True)
+    if not os.path.exists(so) or os.path.getmtime(so) < max(os.path.getmtime(f) for f in deps):
+        subprocess.run([HIPCC, "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mfma", "-shared",
+                        "-fvisibility=hidden", "-o", so] + list(sources), check=True, capture_output=True)
+    return C.CDLL(so)
 
 
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in SOURCES + _HDRS):
-            subprocess.run(["/opt/rocm/bin/hipcc", "--cuda-host-only", "-O2", "-std=c++17", "-fPIC",
-                            "-ffp-contract=off", "-mfma", "-shared", "-fvisibility=hidden", "-o", _SO] + SOURCES,
-                           check=True, capture_output=True)
-        _lib = C.CDLL(_SO)
+        _lib = build("libhostcheck.so", SOURCES)
     return _lib
+
+
+def sanitized_program(tmp_path, source, define):
+    """-> the path of `source` built with -D<define> as a stand-alone program (its own main) under AddressSanitizer +
+    UndefinedBehaviorSanitizer, to be run as a child process with nothing preloaded; skips the test that calls it where
+    the image has no sanitizer runtime."""
+    import pytest
+    if not glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a") or not os.path.exists(HIPCC):
+        pytest.skip("no clang sanitizer runtime in this image")
+    exe = str(tmp_path / (define.lower() + "_sanitize"))
+    subprocess.run([HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-D" + define,
+                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
+                    "-o", exe, source], check=True, capture_output=True)
+    return exe
+
+
+def write_case(path, ints, floats, arrays):
+    """The case file of a stand-alone program: `ints` as int32, `floats` as float32, then every array as float32."""
+    with open(path, "wb") as f:
+        f.write(np.array(ints, np.int32).tobytes())
+        f.write(np.array(floats, np.float32).tobytes())
+        for a in arrays:
+            f.write(np.ascontiguousarray(a, np.float32).tobytes())
 
 
 def _p(a):

@@ -1,86 +1,84 @@
-"""Loader for tests/hostcheck/integral_rays.hip (TEST INFRASTRUCTURE ONLY): the product's per-ray routines of the integral
-operators -- optical path length (trace_opl_ray, opl_backtrace_ray), line integral of a second field (trace_field_ray,
-field_backtrace_ray), emission with self-absorption (exp_neg, trace_emission_ray, emission_backtrace_ray) of
-csrc/drrt_device.h -- compiled for the host with the line of hostcheck_lib.lib(), looped as the kernels run them.  Never
-imported by the package."""
+"""Loader for tests/hostcheck/integral_rays.hip (TEST INFRASTRUCTURE ONLY): the product's per-ray routines of the grid
+integral family -- optical path length (trace_opl_ray, opl_backtrace_ray), line integral of a second field (trace_field_ray,
+field_backtrace_ray), emission with self-absorption (exp_neg, trace_emission_ray, emission_backtrace_ray), line integral of
+a vector field (trace_vector_ray, vector_backtrace_ray) and ray paths (trace_path_ray, path_backtrace_ray) of
+csrc/drrt_device.h -- compiled for the host by hostcheck_lib.build(), looped as the kernels run them.  Never imported by
+the package."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostcheck_lib import _f, _p, _res
+from hostcheck_lib import HOSTCHECK, _f, _p, _res, build
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(_HERE, "hostcheck", "integral_rays.hip")
-_HDR = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc", "drrt_device.h")
-_SO = os.path.join(_HERE, "hostcheck", "_build", "libintegral_rays.so")
-HIPCC = "/opt/rocm/bin/hipcc"
+SOURCE = os.path.join(HOSTCHECK, "integral_rays.hip")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in (SOURCE, _HDR)):
-            subprocess.run([HIPCC, "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mfma", "-shared",
-                            "-fvisibility=hidden", "-o", _SO, SOURCE], check=True, capture_output=True)
-        _lib = C.CDLL(_SO)
+        _lib = build("libintegral_rays.so", [SOURCE])
     return _lib
+
+
+def _trace(entry, grids, res, pos, vel, h, ds, names, ints=(), more=()):
+    """entry(grids..., res, n, pos, vel, h, ds, ints..., xt, vt, <an fp32 per ray for each of names>, more..., steps,
+    &n_failed) -> dict(xt, vt, <names>, steps, n_failed)"""
+    n = len(pos)
+    xt, vt, steps, nf = np.empty_like(pos), np.empty_like(vel), np.empty(n, np.uint32), C.c_longlong(0)
+    out = {k: np.empty(n, np.float32) for k in names}
+    rc = getattr(lib(), entry)(*map(_p, grids), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), C.c_float(h), C.c_float(ds),
+                               *map(C.c_int, ints), _p(xt), _p(vt), *map(_p, out.values()), *map(_p, more), _p(steps),
+                               C.byref(nf))
+    assert rc == 0
+    return dict(xt=xt, vt=vt, **out, steps=steps, n_failed=int(nf.value))
+
+
+def _backtrace(entry, grids, res, rays, steps, more, seeds, h, ds, flags, grads):
+    """entry(grids..., res, n, pos, vel, xt, vt, steps, more..., seeds... (nullable), h, ds, flags..., grads..., dpos, dvel,
+    rsteps, failed), `grads` being {name: size} of the float64 sums -> dict(<grads>, dpos, dvel, steps (reverse iterations
+    per ray), failed, ray_steps, n_failed)"""
+    pos, vel, xt, vt = rays
+    seeds = [None if a is None else _f(a) for a in seeds]
+    steps = np.ascontiguousarray(np.asarray(steps).astype(np.uint32))
+    n = len(pos)
+    grads = {k: np.empty(size, np.float64) for k, size in grads.items()}
+    dpos, dvel = np.empty_like(pos), np.empty_like(vel)
+    rsteps, failed = np.empty(n, np.uint32), np.empty(n, np.uint8)
+    rc = getattr(lib(), entry)(*map(_p, grids), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), _p(xt), _p(vt), _p(steps),
+                               *map(_p, more), *map(_p, seeds), C.c_float(h), C.c_float(ds), *map(C.c_int, flags),
+                               *map(_p, grads.values()), _p(dpos), _p(dvel), _p(rsteps), _p(failed))
+    assert rc == 0
+    failed = failed.astype(bool)
+    return dict(**grads, dpos=dpos, dvel=dvel, steps=rsteps, failed=failed,
+                ray_steps=int(rsteps.astype(np.int64).sum()), n_failed=int(failed.sum()))
+
+
+def _grids(rif, *further, what="every further grid must have rif's shape", lead=()):
+    rif, further = _f(rif), [_f(a) for a in further]
+    assert all(a.shape == tuple(lead) + rif.shape for a in further), what
+    return [a.reshape(-1) for a in [rif] + further]
 
 
 def trace_opl(rif, res, pos, vel, h, ds):
     """-> dict(xt, vt, opl, steps, n_failed): the host build of what drrt_trace_opl_f32 computes."""
-    rif, pos, vel = _f(rif).reshape(-1), _f(pos), _f(vel)
-    n = len(pos)
-    xt, vt = np.empty_like(pos), np.empty_like(vel)
-    opl, steps = np.empty(n, np.float32), np.empty(n, np.uint32)
-    nf = C.c_longlong(0)
-    rc = lib().opl_host_trace(_p(rif), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), C.c_float(h), C.c_float(ds), _p(xt),
-                              _p(vt), _p(opl), _p(steps), C.byref(nf))
-    assert rc == 0
-    return dict(xt=xt, vt=vt, opl=opl, steps=steps, n_failed=int(nf.value))
+    return _trace("opl_host_trace", _grids(rif), res, _f(pos), _f(vel), h, ds, ("opl",))
 
 
 def backtrace_opl(rif, res, pos, vel, xt, vt, steps, dx, dv, dopl, h, ds, corrected_h=True, parts=0):
     """-> dict(grad float64[nvox], dpos, dvel, steps (reverse iterations per ray), failed, ray_steps, n_failed): the host
     build of what drrt_backtrace_opl_f32 computes; dx, dv, dopl may be None (zeros).  `parts`: 0 = the whole grid gradient,
     1 = the value weights of every contribution alone, 2 = their gradient splats alone."""
-    rif = _f(rif).reshape(-1)
-    pos, vel, xt, vt = (_f(a) for a in (pos, vel, xt, vt))
-    dx, dv, dopl = (None if a is None else _f(a) for a in (dx, dv, dopl))
-    steps = np.ascontiguousarray(np.asarray(steps).astype(np.uint32))
-    n = len(pos)
-    grad = np.empty(rif.size, np.float64)
-    dpos, dvel = np.empty_like(pos), np.empty_like(vel)
-    rsteps, failed = np.empty(n, np.uint32), np.empty(n, np.uint8)
-    rc = lib().opl_host_backtrace(_p(rif), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), _p(xt), _p(vt), _p(steps), _p(dx),
-                                  _p(dv), _p(dopl), C.c_float(h), C.c_float(ds), C.c_int(bool(corrected_h)), C.c_int(parts),
-                                  _p(grad), _p(dpos), _p(dvel), _p(rsteps), _p(failed))
-    assert rc == 0
-    failed = failed.astype(bool)
-    return dict(grad=grad, dpos=dpos, dvel=dvel, steps=rsteps, failed=failed,
-                ray_steps=int(rsteps.astype(np.int64).sum()), n_failed=int(failed.sum()))
-
-
-def _grid2(rif, field):
-    rif, field = _f(rif), _f(field)
-    assert rif.shape == field.shape, "field must have rif's shape"
-    return rif.reshape(-1), field.reshape(-1)
+    g = _grids(rif)
+    return _backtrace("opl_host_backtrace", g, res, [_f(a) for a in (pos, vel, xt, vt)], steps, (), (dx, dv, dopl), h, ds,
+                      (bool(corrected_h), parts), dict(grad=g[0].size))
 
 
 def trace_field(rif, field, res, pos, vel, h, ds):
     """-> dict(xt, vt, tau, steps, n_failed): the host build of what drrt_trace_field_f32 computes."""
-    (rif, field), pos, vel = _grid2(rif, field), _f(pos), _f(vel)
-    n = len(pos)
-    xt, vt = np.empty_like(pos), np.empty_like(vel)
-    tau, steps = np.empty(n, np.float32), np.empty(n, np.uint32)
-    nf = C.c_longlong(0)
-    rc = lib().field_host_trace(_p(rif), _p(field), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), C.c_float(h),
-                                C.c_float(ds), _p(xt), _p(vt), _p(tau), _p(steps), C.byref(nf))
-    assert rc == 0
-    return dict(xt=xt, vt=vt, tau=tau, steps=steps, n_failed=int(nf.value))
+    return _trace("field_host_trace", _grids(rif, field, what="field must have rif's shape"), res, _f(pos), _f(vel), h, ds,
+                  ("tau",))
 
 
 def backtrace_field(rif, field, res, pos, vel, xt, vt, steps, dx, dv, dtau, h, ds, corrected_h=True, parts=0):
@@ -88,22 +86,9 @@ def backtrace_field(rif, field, res, pos, vel, xt, vt, steps, dx, dv, dtau, h, d
     n_failed): the host build of what drrt_backtrace_field_f32 computes; dx, dv, dtau may be None (zeros).  `parts`: 0 = the
     whole gradients, 1 = the value weights of every contribution alone, 2 = their gradient splats alone (dL/dfield has
     none)."""
-    rif, field = _grid2(rif, field)
-    pos, vel, xt, vt = (_f(a) for a in (pos, vel, xt, vt))
-    dx, dv, dtau = (None if a is None else _f(a) for a in (dx, dv, dtau))
-    steps = np.ascontiguousarray(np.asarray(steps).astype(np.uint32))
-    n = len(pos)
-    grad, gfield = np.empty(rif.size, np.float64), np.empty(rif.size, np.float64)
-    dpos, dvel = np.empty_like(pos), np.empty_like(vel)
-    rsteps, failed = np.empty(n, np.uint32), np.empty(n, np.uint8)
-    rc = lib().field_host_backtrace(_p(rif), _p(field), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), _p(xt), _p(vt),
-                                    _p(steps), _p(dx), _p(dv), _p(dtau), C.c_float(h), C.c_float(ds),
-                                    C.c_int(bool(corrected_h)), C.c_int(parts), _p(grad), _p(gfield), _p(dpos), _p(dvel),
-                                    _p(rsteps), _p(failed))
-    assert rc == 0
-    failed = failed.astype(bool)
-    return dict(grad=grad, grad_field=gfield, dpos=dpos, dvel=dvel, steps=rsteps, failed=failed,
-                ray_steps=int(rsteps.astype(np.int64).sum()), n_failed=int(failed.sum()))
+    g = _grids(rif, field, what="field must have rif's shape")
+    return _backtrace("field_host_backtrace", g, res, [_f(a) for a in (pos, vel, xt, vt)], steps, (), (dx, dv, dtau), h, ds,
+                      (bool(corrected_h), parts), dict(grad=g[0].size, grad_field=g[0].size))
 
 
 def exp_neg(t):
@@ -114,23 +99,10 @@ def exp_neg(t):
     return out
 
 
-def _grid3(rif, emis, absb):
-    rif, emis, absb = _f(rif), _f(emis), _f(absb)
-    assert rif.shape == emis.shape == absb.shape, "emission and absorption must have rif's shape"
-    return rif.reshape(-1), emis.reshape(-1), absb.reshape(-1)
-
-
 def trace_emission(rif, emis, absb, res, pos, vel, h, ds):
     """-> dict(xt, vt, rad, tau, steps, n_failed): the host build of what drrt_trace_emission_f32 computes."""
-    (rif, emis, absb), pos, vel = _grid3(rif, emis, absb), _f(pos), _f(vel)
-    n = len(pos)
-    xt, vt = np.empty_like(pos), np.empty_like(vel)
-    rad, tau, steps = np.empty(n, np.float32), np.empty(n, np.float32), np.empty(n, np.uint32)
-    nf = C.c_longlong(0)
-    rc = lib().emission_host_trace(_p(rif), _p(emis), _p(absb), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), C.c_float(h),
-                                   C.c_float(ds), _p(xt), _p(vt), _p(rad), _p(tau), _p(steps), C.byref(nf))
-    assert rc == 0
-    return dict(xt=xt, vt=vt, rad=rad, tau=tau, steps=steps, n_failed=int(nf.value))
+    g = _grids(rif, emis, absb, what="emission and absorption must have rif's shape")
+    return _trace("emission_host_trace", g, res, _f(pos), _f(vel), h, ds, ("rad", "tau"))
 
 
 def backtrace_emission(rif, emis, absb, res, pos, vel, xt, vt, steps, tau, dx, dv, drad, dtau, h, ds, corrected_h=True,
@@ -139,19 +111,41 @@ def backtrace_emission(rif, emis, absb, res, pos, vel, xt, vt, steps, tau, dx, d
     failed, ray_steps, n_failed): the host build of what drrt_backtrace_emission_f32 computes; dx, dv, drad, dtau may be None
     (zeros).  `parts`: 0 = the whole gradients, 1 = the value weights of every contribution alone, 2 = their gradient splats
     alone (dL/de and dL/da have none)."""
-    rif, emis, absb = _grid3(rif, emis, absb)
-    pos, vel, xt, vt, tau = (_f(a) for a in (pos, vel, xt, vt, tau))
-    dx, dv, drad, dtau = (None if a is None else _f(a) for a in (dx, dv, drad, dtau))
-    steps = np.ascontiguousarray(np.asarray(steps).astype(np.uint32))
-    n = len(pos)
-    grad, ge, ga = (np.empty(rif.size, np.float64) for _ in range(3))
-    dpos, dvel = np.empty_like(pos), np.empty_like(vel)
-    rsteps, failed = np.empty(n, np.uint32), np.empty(n, np.uint8)
-    rc = lib().emission_host_backtrace(_p(rif), _p(emis), _p(absb), _p(_res(res)), C.c_size_t(n), _p(pos), _p(vel), _p(xt),
-                                       _p(vt), _p(steps), _p(tau), _p(dx), _p(dv), _p(drad), _p(dtau), C.c_float(h),
-                                       C.c_float(ds), C.c_int(bool(corrected_h)), C.c_int(parts), _p(grad), _p(ge), _p(ga),
-                                       _p(dpos), _p(dvel), _p(rsteps), _p(failed))
-    assert rc == 0
-    failed = failed.astype(bool)
-    return dict(grad=grad, grad_emission=ge, grad_absorption=ga, dpos=dpos, dvel=dvel, steps=rsteps, failed=failed,
-                ray_steps=int(rsteps.astype(np.int64).sum()), n_failed=int(failed.sum()))
+    g = _grids(rif, emis, absb, what="emission and absorption must have rif's shape")
+    return _backtrace("emission_host_backtrace", g, res, [_f(a) for a in (pos, vel, xt, vt)], steps, (_f(tau),),
+                      (dx, dv, drad, dtau), h, ds, (bool(corrected_h), parts),
+                      dict(grad=g[0].size, grad_emission=g[0].size, grad_absorption=g[0].size))
+
+
+def trace_vector(rif, vfield, res, pos, vel, h, ds):
+    """-> dict(xt, vt, circ, steps, n_failed): the host build of what drrt_trace_vector_f32 computes."""
+    g = _grids(rif, vfield, what="vfield must have shape (3,) + rif.shape", lead=(3,))
+    return _trace("vector_host_trace", g, res, _f(pos), _f(vel), h, ds, ("circ",))
+
+
+def backtrace_vector(rif, vfield, res, pos, vel, xt, vt, steps, dx, dv, dcirc, h, ds, corrected_h=True, parts=0):
+    """-> dict(grad float64[nvox], grad_vfield float64[3 nvox], dpos, dvel, steps (reverse iterations per ray), failed,
+    ray_steps, n_failed): the host build of what drrt_backtrace_vector_f32 computes; dx, dv, dcirc may be None (zeros).
+    `parts`: 0 = the whole gradients, 1 = the value weights of every contribution alone, 2 = their gradient splats alone
+    (dL/du has none)."""
+    g = _grids(rif, vfield, what="vfield must have shape (3,) + rif.shape", lead=(3,))
+    return _backtrace("vector_host_backtrace", g, res, [_f(a) for a in (pos, vel, xt, vt)], steps, (), (dx, dv, dcirc), h, ds,
+                      (bool(corrected_h), parts), dict(grad=g[0].size, grad_vfield=3 * g[0].size))
+
+
+def trace_path(rif, res, pos, vel, h, ds, stride, samples):
+    """-> dict(xt, vt, path (samples, n, 3), count, steps, n_failed): the host build of what drrt_trace_path_f32 computes."""
+    pos, vel = _f(pos).reshape(-1, 3), _f(vel).reshape(-1, 3)
+    path, count = np.empty((samples, len(pos), 3), np.float32), np.empty(len(pos), np.int32)
+    r = _trace("path_host_trace", _grids(rif), res, pos, vel, h, ds, (), (stride, samples), (path, count))
+    return dict(xt=r["xt"], vt=r["vt"], path=path, count=count, steps=r["steps"], n_failed=r["n_failed"])
+
+
+def backtrace_path(rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, h, ds, stride, samples, corrected_h=True):
+    """-> dict(grad float64[nvox], dpos, dvel, steps (reverse iterations per ray), failed, ray_steps, n_failed): the host
+    build of what drrt_backtrace_path_f32 computes; dx, dv, dpath ((samples, n, 3)) may be None (zeros)."""
+    g = _grids(rif)
+    rays = [_f(a).reshape(-1, 3) for a in (pos, vel, xt, vt)]
+    assert dpath is None or _f(dpath).shape == (samples, len(rays[0]), 3)
+    return _backtrace("path_host_backtrace", g, res, rays, steps, (), (dx, dv, dpath), h, ds,
+                      (stride, samples, bool(corrected_h)), dict(grad=g[0].size))

@@ -1,30 +1,21 @@
 """Loader for tests/hostcheck/target_rays.hip (TEST INFRASTRUCTURE ONLY): the product's per-ray ray-state adjoint of
-trace_target (target_backtrace_ray_state of csrc/drrt_device.h) compiled for the host with the line of hostcheck_lib.lib(),
+trace_target (target_backtrace_ray_state of csrc/drrt_device.h) compiled for the host by hostcheck_lib.build(),
 both passes looped as the kernels run them.  Never imported by the package."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 
-from hostcheck_lib import _f, _p, _res
+from hostcheck_lib import HOSTCHECK, _f, _p, _res, build
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCE = os.path.join(_HERE, "hostcheck", "target_rays.hip")
-_HDR = os.path.join(_HERE, "..", "adjointnonlinearraytracing_amd", "csrc", "drrt_device.h")
-_SO = os.path.join(_HERE, "hostcheck", "_build", "libtarget_rays.so")
-HIPCC = "/opt/rocm/bin/hipcc"
+SOURCE = os.path.join(HOSTCHECK, "target_rays.hip")
 _lib = None
 
 
 def lib():
     global _lib
     if _lib is None:
-        os.makedirs(os.path.dirname(_SO), exist_ok=True)
-        if not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in (SOURCE, _HDR)):
-            subprocess.run([HIPCC, "--cuda-host-only", "-O2", "-std=c++17", "-fPIC", "-ffp-contract=off", "-mfma", "-shared",
-                            "-fvisibility=hidden", "-o", _SO, SOURCE], check=True, capture_output=True)
-        _lib = C.CDLL(_SO)
+        _lib = build("libtarget_rays.so", [SOURCE])
     return _lib
 
 

@@ -16,7 +16,6 @@ cable_trace_field_ray nor cable_field_backtrace_ray), the library has neither dr
 drrt_backtrace_cable_field_f32, _lib.PROF_NAMES_LATER has no ids 21 and 22, TracerC has no trace_cable_field and tracer no
 CableFieldTracerC, and there is no examples/fiber_group_delay_demo.py."""
 import ctypes as C
-import glob
 import itertools
 import os
 import subprocess
@@ -466,14 +465,7 @@ def test_routines_under_sanitizers(tmp_path):
     for the host with ASan + UBSan and run directly (nothing preloaded): NaN / Inf positions, velocities, targets, seeds and
     entries of both profiles, a 2-sample pair, the profile as its own field, and the poisoned rec_steps -- no report, every
     loop ends, the poisoned rays are refused."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(hipcc):
-        pytest.skip("no clang sanitizer runtime in this image")
-    exe = str(tmp_path / "cable_field_sanitize")
-    subprocess.run([hipcc, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DCABLE_FIELD_MAIN",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, H.SOURCE],
-                   check=True, capture_output=True)
+    exe = HC.sanitized_program(tmp_path, H.SOURCE, "CABLE_FIELD_MAIN")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert "1024 poisoned rays refused" in r.stdout

@@ -15,7 +15,6 @@ cable_trace_opl_ray nor cable_opl_backtrace_ray), the library has neither drrt_t
 drrt_backtrace_cable_opl_f32, _lib.PROF_NAMES_LATER has no ids 19 and 20, TracerC has no trace_cable_opl and tracer no
 CableOPLTracerC, and there is no examples/fiber_delay_demo.py."""
 import ctypes as C
-import glob
 import os
 import subprocess
 import sys
@@ -384,14 +383,7 @@ def test_routines_under_sanitizers(tmp_path):
     the host with ASan + UBSan and run directly (nothing preloaded): NaN / Inf positions, velocities, targets, seeds and
     profile entries, a 2-sample profile, and the poisoned rec_steps -- no report, every loop ends, the poisoned rays are
     refused."""
-    hipcc = "/opt/rocm/bin/hipcc"
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(hipcc):
-        pytest.skip("no clang sanitizer runtime in this image")
-    exe = str(tmp_path / "cable_opl_sanitize")
-    subprocess.run([hipcc, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DCABLE_OPL_MAIN",
-                    "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-o", exe, H.SOURCE],
-                   check=True, capture_output=True)
+    exe = HC.sanitized_program(tmp_path, H.SOURCE, "CABLE_OPL_MAIN")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert "768 poisoned rays refused" in r.stdout

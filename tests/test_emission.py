@@ -25,7 +25,6 @@ Mutation checks (tried by hand on emission_backtrace_ray, one at a time, each th
     test_adjoint_matches_float64_autograd but the "dtau" ones (15 of 20), test_plane_source_on_host,
     test_uniform_medium_closed_form and test_opaque_medium fail."""
 import ctypes as C
-import glob
 import itertools
 import os
 import subprocess
@@ -520,9 +519,7 @@ def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan
     and run as a child process, nothing preloaded: scene 1 plus rays, seeds and values of both fields with NaN, Inf, huge,
     denormal and negative entries; exp_neg sees every seed on tau (NaN, +-Inf, +-3e38 among them)."""
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(EH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, EH.SOURCE, "EMISSION_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0, -2.5, -1e-40], np.float32)
@@ -540,19 +537,8 @@ def test_routines_under_sanitizers(tmp_path):
         fields.append(f)
     n = len(dtau)
     path = str(tmp_path / "case.bin")
-    with open(path, "wb") as f:
-        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
-        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-        for g in [s["rif"]] + fields:
-            f.write(np.ascontiguousarray(g, np.float32).tobytes())
-        for key in ("pos", "vel", "dx", "dv"):
-            f.write(np.ascontiguousarray(arrs[key], np.float32).tobytes())
-        f.write(drad.astype(np.float32).tobytes())
-        f.write(dtau.astype(np.float32).tobytes())
-    exe = str(tmp_path / "emission_rays_sanitize")
-    subprocess.run([EH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DEMISSION_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, EH.SOURCE], check=True, capture_output=True)
+    HC.write_case(path, list(s["res"]) + [n], [s["h"], s["ds"]],
+                  [s["rif"]] + fields + [arrs[key] for key in ("pos", "vel", "dx", "dv")] + [drad, dtau])
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert f"{n} rays" in r.stdout and "exp_neg(0) 1\n" in r.stdout

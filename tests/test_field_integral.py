@@ -20,7 +20,6 @@ Mutation checks (tried by hand on field_backtrace_ray, one at a time, each then 
     test_plane_source_on_host, test_uniform_field_closed_form, test_exit_on_first_iteration_closed_form and all five cases
     of test_consistent_with_opl fail."""
 import ctypes as C
-import glob
 import os
 import subprocess
 import sys
@@ -432,9 +431,7 @@ def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
     run as a child process, nothing preloaded: scene 1 plus rays, seeds and field values with NaN, Inf, huge and denormal
     entries."""
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(FH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, FH.SOURCE, "FIELD_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0], np.float32)
@@ -448,18 +445,8 @@ def test_routines_under_sanitizers(tmp_path):
     fld[rng.integers(0, fld.size, 40)] = rng.choice(bad, 40)
     n = len(dtau)
     path = str(tmp_path / "case.bin")
-    with open(path, "wb") as f:
-        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
-        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-        f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
-        f.write(np.ascontiguousarray(fld, np.float32).tobytes())
-        for key in ("pos", "vel", "dx", "dv"):
-            f.write(np.ascontiguousarray(arrs[key], np.float32).tobytes())
-        f.write(dtau.astype(np.float32).tobytes())
-    exe = str(tmp_path / "field_rays_sanitize")
-    subprocess.run([FH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DFIELD_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, FH.SOURCE], check=True, capture_output=True)
+    HC.write_case(path, list(s["res"]) + [n], [s["h"], s["ds"]],
+                  [s["rif"], fld] + [arrs[key] for key in ("pos", "vel", "dx", "dv")] + [dtau])
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert f"{n} rays" in r.stdout

@@ -16,7 +16,6 @@ Mutation checks (tried by hand on opl_backtrace_ray, one at a time, each then un
   * adj_recur called with mu . grad n_k instead of dn (lambda loses 2 dopl ds n_k grad n_k): the same eleven and
     test_exit_on_first_iteration_closed_form fail."""
 import ctypes as C
-import glob
 import os
 import subprocess
 import sys
@@ -329,9 +328,7 @@ def test_abi_argument_checks():
 def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
     as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries."""
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(OH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, OH.SOURCE, "OPL_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0], np.float32)
@@ -343,17 +340,8 @@ def test_routines_under_sanitizers(tmp_path):
     dopl = np.concatenate([s["dopl"], rng.choice(bad, 96)])
     n = len(dopl)
     path = str(tmp_path / "case.bin")
-    with open(path, "wb") as f:
-        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
-        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-        f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
-        for key in ("pos", "vel", "dx", "dv"):
-            f.write(np.ascontiguousarray(arrs[key], np.float32).tobytes())
-        f.write(dopl.astype(np.float32).tobytes())
-    exe = str(tmp_path / "opl_rays_sanitize")
-    subprocess.run([OH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DOPL_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, OH.SOURCE], check=True, capture_output=True)
+    HC.write_case(path, list(s["res"]) + [n], [s["h"], s["ds"]],
+                  [s["rif"]] + [arrs[key] for key in ("pos", "vel", "dx", "dv")] + [dopl])
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert f"{n} rays" in r.stdout

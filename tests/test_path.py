@@ -1,6 +1,6 @@
 """Ray paths: drrt_trace_path_f32 / drrt_backtrace_path_f32, TracerC.trace_path / backtrace_path, tracer.PathTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/path_rays.hip: trace_path_ray and
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_path_ray and
 path_backtrace_ray of csrc/drrt_device.h) against the product's own trace and opl adjoint (bit for bit), against float64
 torch.autograd through tests/path_ad (tests/opl_ad's loop, recording x where the product does) on the compared rays, against
 closed forms, and the C ABI's argument checks.  GPU tier: k_trace_path / k_backtrace_path of drrt_integral.hip against that
@@ -14,7 +14,7 @@ integral_fuzz_common.bound(e_ref, CAPS[...]); a path sample's error is the large
 rays and j < M over the box's longest edge and stays under CAPS["out"].  Modes: every seed; no seeds on the rays; dpath on
 the prefix samples alone, on the in-box samples alone, on the padded entries alone (the last three without ray seeds).
 
-On the parent commit every test here fails: tests/hostcheck/path_rays.hip does not compile (no trace_path_ray), the library
+On the parent commit every test here fails: the host build of the routines does not compile (no trace_path_ray), the library
 has no such C symbols, TracerC no such methods, tracer no such class and examples/ no such demo.
 
 Largest e_prod / max(e_ref, 2.4e-7) on the fixed scenes, host build (8 allowed): ray gradients 2.75 (lens16_h1_multi, stride 1,
@@ -28,7 +28,6 @@ tests/test_path_fuzz.py, 117 tests):
   * the padded seeds dropped: 92 fail -- the 84 referee cases, all five of test_adjoint_identities,
     test_uniform_medium_closed_form, test_exit_on_first_iteration_closed_form, test_never_entering_ray_closed_form."""
 import ctypes as C
-import glob
 import os
 import subprocess
 import sys
@@ -42,7 +41,7 @@ import hostcheck_lib as HC
 import integral_host as OH
 import opl_ad
 import path_ad
-import path_host as PH
+import integral_host as PH
 import test_opl as TO
 from integral_fuzz_common import CAPS, FLOOR, bound
 from oracle import torch_ad
@@ -439,12 +438,10 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/path_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
+    """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
     as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries, with a
     stride above every K, with M = 1, and with zero rays."""
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(PH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, PH.SOURCE, "PATH_MAIN")
     s = scene(list(SCENES)[1])
     ms = max_steps_fwd(s["res"], s["h"], s["ds"])
     rng = np.random.default_rng(0)
@@ -455,22 +452,13 @@ def test_routines_under_sanitizers(tmp_path):
         extra[rng.integers(0, 96, 60), rng.integers(0, 3, 60)] = rng.choice(bad, 60)
         arrs[key] = np.concatenate([s[key], extra])
     full = len(arrs["pos"])
-    exe = str(tmp_path / "path_rays_sanitize")
-    subprocess.run([PH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DPATH_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, PH.SOURCE], check=True, capture_output=True)
     for n, stride, M in ((full, 3, pad_m(ms, 3)), (full, ms + 5, 4), (full, 2, 1), (0, 1, 2)):
         dpath = rng.normal(size=(M, n, 3)).astype(np.float32)
         if n:
             dpath[rng.integers(0, M, 80), rng.integers(0, n, 80), rng.integers(0, 3, 80)] = rng.choice(bad, 80)
         path = str(tmp_path / f"case_{n}_{stride}_{M}.bin")
-        with open(path, "wb") as f:
-            f.write(np.array(list(s["res"]) + [n, stride, M], np.int32).tobytes())
-            f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-            f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
-            for key in ("pos", "vel", "dx", "dv"):
-                f.write(np.ascontiguousarray(arrs[key][:n], np.float32).tobytes())
-            f.write(dpath.tobytes())
+        HC.write_case(path, list(s["res"]) + [n, stride, M], [s["h"], s["ds"]],
+                      [s["rif"]] + [arrs[key][:n] for key in ("pos", "vel", "dx", "dv")] + [dpath])
         r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
         assert r.returncode == 0 and "finished without reports" in r.stdout, (n, stride, M, r.stdout[-2000:], r.stderr[-4000:])
         assert f"{n} rays" in r.stdout

@@ -22,7 +22,6 @@ Mutation checks (tried by hand on the routine, one at a time, each then undone; 
   * dropping the free-flight prefix: all ten and test_uniform_medium_closed_form fail;
   * gx = dx + dd2 (x_j - t), the factor 2 lost: all ten and both closed forms fail."""
 import ctypes as C
-import glob
 import os
 import subprocess
 
@@ -310,10 +309,7 @@ def test_abi_argument_checks():
 def test_routine_under_sanitizers(tmp_path):
     """tests/hostcheck/target_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
     as a child process, nothing preloaded: a fuzz case with NaN, Inf, huge and zero-velocity rays, targets and seeds."""
-    here = os.path.dirname(os.path.abspath(__file__))
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(TH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, TH.SOURCE, "TARGET_RAYS_MAIN")
     s = fuzz_scene(3)
     n = len(s["pos"])
     rng = np.random.default_rng(0)
@@ -325,17 +321,8 @@ def test_routine_under_sanitizers(tmp_path):
     dd2 = s["dd2"].copy()
     dd2[rng.integers(0, n, 20)] = rng.choice(bad, 20)
     path = str(tmp_path / "case.bin")
-    with open(path, "wb") as f:
-        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
-        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-        f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
-        for k in ("pos", "vel", "tg", "dx", "dv"):
-            f.write(np.ascontiguousarray(arrs[k], np.float32).tobytes())
-        f.write(dd2.tobytes())
-    exe = str(tmp_path / "target_rays_sanitize")
-    subprocess.run([TH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DTARGET_RAYS_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, TH.SOURCE], check=True, capture_output=True)
+    HC.write_case(path, list(s["res"]) + [n], [s["h"], s["ds"]],
+                  [s["rif"]] + [arrs[k] for k in ("pos", "vel", "tg", "dx", "dv")] + [dd2])
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert f"{n} rays" in r.stdout

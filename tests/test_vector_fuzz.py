@@ -8,7 +8,7 @@ Referee, yardstick, compared rays, error measure and bound are those of tests/te
 torch.autograd through tests/vector_ad; e_prod <= 8 max(e_ref, 2.4e-7), never above 1e-4 for circ -- relative to the ray's
 float64 S -- or GRAD_TOL for rays and grids).
 
-CPU tier (the host build: tests/vector_host): the forward is trace bit for bit, circ and the adjoint (with and without seeds
+CPU tier (the host build: tests/integral_host): the forward is trace bit for bit, circ and the adjoint (with and without seeds
 on the rays) under the bound, flag off, failed and never-entered rays.  GPU tier: the kernels against the host build on seeds
 4 (2-voxel axis) and 12 (rough medium), with and without the pair copy, and VectorIntegralTracerC end to end on the same two.
 

@@ -1,7 +1,7 @@
 """Line integral of a vector field along bent rays: drrt_trace_vector_f32 / drrt_backtrace_vector_f32, TracerC.trace_vector /
 backtrace_vector, tracer.VectorIntegralTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/vector_rays.hip: trace_vector_ray and
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_vector_ray and
 vector_backtrace_ray of csrc/drrt_device.h) against the product's own trace (bit for bit), against float64 torch.autograd
 through tests/vector_ad (tests/field_ad's loop with circ += ds u(x_k) . v_{k+1}), against the closed form of a uniform field,
 against opl_backtrace_ray with a zero seed on circ, and the C ABI's argument checks.  GPU tier: the vector kernels of
@@ -15,7 +15,7 @@ same restatement run in float32 against float64, on the rays that are tie-free f
 The error of circ on a ray is taken relative to that ray's float64 S = sum ds (|ux vx| + |uy vy| + |uz vz|), the scale of the
 summands, not relative to circ, which cancels.
 
-On the parent commit every test here fails: tests/hostcheck/vector_rays.hip does not compile (no trace_vector_ray), the
+On the parent commit every test here fails: the host build of the routines does not compile (no trace_vector_ray), the
 library has no such C symbols, TracerC no such methods, tracer no such class and examples/ no such demo.
 
 Largest e_prod / max(e_ref, 2.4e-7) per quantity on the host build over the five scenes and the plane source, with and
@@ -31,7 +31,6 @@ Mutation checks (tried by hand on vector_backtrace_ray, one at a time, each then
     same 32 there fail.
 The closed form, the zero seed on circ and the linearity test pass under both, as they must: none of them sees the term."""
 import ctypes as C
-import glob
 import itertools
 import os
 import subprocess
@@ -47,7 +46,7 @@ import integral_fuzz_common as IF
 import integral_host as OH
 import test_opl as TO
 import vector_ad
-import vector_host as VH
+import integral_host as VH
 from raygrad_common import SCENES, TIE_TOL, _t, rel_err
 
 ATOMIC_TOL = 2e-5       # grid gradients, kernel vs host build: only the order of the atomic sums differs
@@ -427,12 +426,10 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/vector_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
+    """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
     run as a child process, nothing preloaded: scene 1 plus rays, seeds and field values with NaN, Inf, huge and denormal
     entries."""
-    rt = glob.glob("/opt/rocm*/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.a")
-    if not rt or not os.path.exists(VH.HIPCC):
-        pytest.skip("no clang sanitizer runtime in this image")
+    exe = HC.sanitized_program(tmp_path, VH.SOURCE, "VECTOR_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0], np.float32)
@@ -446,18 +443,8 @@ def test_routines_under_sanitizers(tmp_path):
     vf[rng.integers(0, vf.size, 120)] = rng.choice(bad, 120)
     n = len(dcirc)
     path = str(tmp_path / "case.bin")
-    with open(path, "wb") as f:
-        f.write(np.array(list(s["res"]) + [n], np.int32).tobytes())
-        f.write(np.array([s["h"], s["ds"]], np.float32).tobytes())
-        f.write(np.ascontiguousarray(s["rif"], np.float32).tobytes())
-        f.write(np.ascontiguousarray(vf, np.float32).tobytes())
-        for key in ("pos", "vel", "dx", "dv"):
-            f.write(np.ascontiguousarray(arrs[key], np.float32).tobytes())
-        f.write(dcirc.astype(np.float32).tobytes())
-    exe = str(tmp_path / "vector_rays_sanitize")
-    subprocess.run([VH.HIPCC, "--cuda-host-only", "-O1", "-g", "-std=c++17", "-ffp-contract=off", "-mfma", "-DVECTOR_MAIN",
-                    "-Xarch_host", "-fsanitize=address,undefined", "-Xarch_host", "-fno-sanitize-recover=undefined",
-                    "-o", exe, VH.SOURCE], check=True, capture_output=True)
+    HC.write_case(path, list(s["res"]) + [n], [s["h"], s["ds"]],
+                  [s["rif"], vf] + [arrs[key] for key in ("pos", "vel", "dx", "dv")] + [dcirc])
     r = subprocess.run([exe, path], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "finished without reports" in r.stdout, (r.stdout[-2000:], r.stderr[-4000:])
     assert f"{n} rays" in r.stdout
