@@ -344,22 +344,27 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
   // the cell the ray stands on, located IN PLACE: flat index and coordinates of corner 000, in-cell fractions, window slot.
   // A boundary cell's clamp offsets are not carried: the boundary branch at the top of the step re-derives them from the
   // position (locate()).  The cell's predicates live in the two integers their consumers compare anyway, not in flags:
-  //   strictly interior  <=>  tbase >= 0   (the lane holds the cell's taps, gathered ahead; a boundary cell has tbase = -1)
+  //   strictly interior  <=>  tbase >= 0   (the lane holds the cell's taps, gathered ahead); a boundary cell has
+  //   tbase = kEdge when it is regular all the same and kClamped when it is not, which is how step_locate reports the new
+  //   cell's regularity to the leave
   //   regular (no clamped neighbour)  <=>  lidx > kIrregular;  lidx >= 0: window slot, kMiss: regular, outside the window
   //   (a miss votes for a re-anchor)
-  constexpr int kMiss = -1, kIrregular = -2;
+  //   still marching  <=>  lidx > kEnded: the loop's own copy of s.active (a ray that has ended, or a slot without a ray), so
+  //   that the loop exit, the vote and the lane body's mask are compares of the one integer and no flag crosses the back edge
+  constexpr int kMiss = -1, kIrregular = -2, kEnded = -3;
   constexpr int kNoFace = -(1 << 20);                        // no window slot is that far below kMiss
   int base = 0, ix = 0, iy = 0, iz = 0;
   float wx = 0.f, wy = 0.f, wz = 0.f;
-  int lidx = kIrregular;
+  int lidx = kEnded;
   f4 q0 = f4{0.f, 0.f, 0.f, 0.f}, q1 = q0;                   // the taps, as gathered (gather_rows)
-  int tbase = -1;                                            // cell whose taps the lane holds (-1: none)
+  constexpr int kClamped = -1, kEdge = -2;
+  int tbase = kClamped;                                      // cell whose taps the lane holds (negative: none)
   Taps st;                                                   // MODE 1: the sdf taps of that cell, gathered with them
   st.a = st.b = st.e = st.f = f2{0.f, 0.f};
   f2 p00 = f2{0.f, 0.f}, p10 = p00, p01 = p00, p11 = p00;   // accumulators of the cell: x-pairs at (y0,z0) (y1,z0) (y0,z1) (y1,z1)
   const TapRows R = tap_rows<PAIR>(V);                       // wave-uniform row pointers + ONE 32-bit byte offset per lane
   // step to the next sample (:420), locate its cell in place and issue its gather unless the lane holds those taps
-  auto step_locate = [&](int& nbase, bool& nregular, bool move = true) {      // move = false: locate only (a resumed ray)
+  auto step_locate = [&](int& nbase, bool move = true) {     // move = false: locate only (a resumed ray)
     if (move) { s.x = fmaf(-a.ds, s.vx, s.x); s.y = fmaf(-a.ds, s.vy, s.y); s.z = fmaf(-a.ds, s.vz, s.z); }
     const float fx = s.x * V.inv_h, fy = s.y * V.inv_h, fz = s.z * V.inv_h;
     ix = cvt_floor_i32(fx); iy = cvt_floor_i32(fy); iz = cvt_floor_i32(fz);
@@ -368,7 +373,6 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
       // v_fract == f - floor(f) bit for bit for the non-negative coordinates of an interior cell
       wx = __builtin_amdgcn_fractf(fx); wy = __builtin_amdgcn_fractf(fy); wz = __builtin_amdgcn_fractf(fz);
       nbase = mad24(iz, V.sz, mad24(iy, V.sy, ix));
-      nregular = true;
       if (nbase != tbase) {
         __builtin_assume(nbase >= 0 && nbase < (1 << 29));
         gather_rows<PAIR>(R, tap_offset<PAIR>(nbase), q0, q1);
@@ -381,19 +385,18 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     } else {
       const Cell cb = locate(V, s.x, s.y, s.z);
       wx = cb.wx; wy = cb.wy; wz = cb.wz; ix = cb.ix; iy = cb.iy; iz = cb.iz; nbase = cb.base;
-      nregular = (cb.ox == 1) & (cb.oy == V.sy) & (cb.oz == V.sz);
-      tbase = -1;
+      tbase = ((cb.ox == 1) & (cb.oy == V.sy) & (cb.oz == V.sz)) ? kEdge : kClamped;
     }
   };
   if (s.active) {
-    int nbase; bool nregular;
-    if (resume) step_locate(nbase, nregular, false);         // the saved position IS the next sample
-    else        step_locate(nbase, nregular);                // first sample
+    int nbase;
+    if (resume) step_locate(nbase, false);                   // the saved position IS the next sample
+    else        step_locate(nbase);                          // first sample
     base = nbase;
-    lidx = nregular ? kMiss : kIrregular;                    // no window yet
+    lidx = tbase != kClamped ? kMiss : kIrregular;           // no window yet
   }
   unsigned planes = 0u;                                      // z-planes of the window the lane has held a slot in since the last flush (win_index)
-  int cooldown = 0;
+  int cooldown = 0;                                          // wave-uniform (a scalar register)
   unsigned steps = 0;
   unsigned n_flush = 0;
   // CHUNK: bounding box of the samples this launch contributes at (which voxels it can have touched)
@@ -408,17 +411,18 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
 #define WSZ kWinSZ
 #define WIN_INDEX(cx, cy, cz) win_index(W.ox, W.oy, W.oz, cx, cy, cz, planes)
     for (int it = 0; it < a.max_steps; ++it) {
-      if (!__any(s.active)) break;                                              // wave-uniform exit
+      const bool marching = lidx > kEnded;
+      if (__builtin_amdgcn_ballot_w64(marching) == 0ull) break;                 // wave-uniform exit; the mask is the lane body's too
       // ---- (re-)anchor the window around the cells the rays stand on (wave-uniform branch) ----
-      const unsigned long long mm = __ballot(s.active & (lidx == kMiss));
-      if (mm != 0ull && cooldown == 0) {
+      if (cooldown != 0) {
+        --cooldown;
+      } else if (__builtin_amdgcn_ballot_w64(lidx == kMiss) != 0ull) {
         const unsigned dirty = wave_or_u32(planes);
         if (dirty != 0u) {
           win_flush(win, W.ox, W.oy, W.oz, a.grad, V, lane, dirty);
           planes = 0u; ++n_flush;
         }
-        const bool regular = lidx > kIrregular;
-        const bool ok = s.active & regular;
+        const bool ok = lidx > kIrregular;                                      // marching, in a regular cell
         const unsigned long long cm = __ballot(ok);
         const int first = __ffsll((long long)cm) - 1, last = 63 - __clzll((long long)cm);
         int ref = (first + last) >> 1;
@@ -438,11 +442,9 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
           W.oz = __builtin_amdgcn_readfirstlane(oz);
           if (ok) lidx = WIN_INDEX(ix, iy, iz);                                 // every marching lane's cell, in the new window
         }
-        cooldown = (__ballot(ok & (lidx < 0)) != 0ull) ? 4 : 0;                 // incoherent wave: do not thrash
-      } else if (cooldown > 0) {
-        --cooldown;
+        cooldown = (__builtin_amdgcn_ballot_w64(lidx == kMiss) != 0ull) ? 4 : 0;   // incoherent wave: do not thrash
       }
-      if (s.active) {
+      if (marching) {
         const bool interior = tbase >= 0, regular = lidx > kIrregular;
         if (!interior) taps_set<PAIR>(fetch(V.data, locate(V, s.x, s.y, s.z)), q0, q1);   // boundary cell (clamped neighbours): fetched here, not ahead
         Cell c;                                              // what adj_sample reads of the cell: fractions, interior
@@ -454,6 +456,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
         if (!adj_sample_st<MODE>(V, a.sdf, a.ds, s, c, taps_of<PAIR>(q0, q1), m, st, MODE == 1 && interior)) {
           // the ray has ended (:426-428): it contributes nothing here; hand over what its cell has accumulated
           if (regular) flat_emit8<true>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
+          lidx = kEnded;
         } else {
           ++steps;
           if (CHUNK) { bx0 = fminf(bx0, px); by0 = fminf(by0, py); bz0 = fminf(bz0, pz); bx1 = fmaxf(bx1, px); by1 = fmaxf(by1, py); bz1 = fmaxf(bz1, pz); }
@@ -477,8 +480,8 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
             }
             // step to the next sample and issue its gather (it + 1 == max_steps: located and fetched, never used)
             const int old_base = base;
-            int nbase; bool nregular;
-            step_locate(nbase, nregular);
+            int nbase;
+            step_locate(nbase);
             // second half of adj_contrib: lambda / mu (:434-435)
             const float hxy = m.hxy * V.inv_h2, hxz = m.hxz * V.inv_h2, hyz = m.hyz * V.inv_h2;
             const float hmx = fmaf(hxz, s.mz, hxy * s.my);
@@ -489,85 +492,88 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
             s.lz = fmaf(a.ds, fmaf(dn, m.gz, m.n * hmz), s.lz);
             s.mx = fmaf(a.ds, s.lx, s.mx); s.my = fmaf(a.ds, s.ly, s.my); s.mz = fmaf(a.ds, s.lz, s.mz);
             // ---- the ray leaves its cell ----
-            if (nbase != old_base || tbase < 0) {
-              base = nbase;
-              const int d = nbase - old_base;
-              if (d != 0 || nregular != regular) {
-                if (regular) {
-                  // One face crossed (both cells regular, the flat index moved by one stride): emit the face left behind,
-                  // carry the shared one.  Six cases, axis and direction compile-time in each: a case copies the four
-                  // emitted corners out (e0..e3, in (p, q) in-face order), moves the carried ones once, and names the face's
-                  // window slot and strides; ONE emission follows the cases (wave-steps whose lanes leave across two or more
-                  // axes are the common kind -- over half of the headline's -- so an emission per case would run twice there).
-                  // AX: 0 = x, 1 = y, 2 = z; FWD: towards the higher index.
-                  float e0, e1, e2, e3;
-                  int key = kNoFace, lp, lq;                 // the face (win_face_key; a case sets it), window strides of p and q (slots)
-                  auto face = [&](auto AX, auto FWD) {
-                    constexpr int ax = decltype(AX)::value;
-                    constexpr bool fwd = decltype(FWD)::value;
-                    constexpr f2 zero = f2{0.f, 0.f};
-                    asm volatile("");                          // keeps the case's moves under the case's test (not speculated above it)
-                    key = lidx + win_face_key(fwd ? 0 : (ax == 0 ? 1 : (ax == 1 ? WSY : WSZ)), ax);   // lidx < 2^16: no carry into the axis
-                    lp = ax == 0 ? WSY : 1; lq = ax == 2 ? WSY : WSZ;
-                    if (ax == 0) {
-                      e0 = fwd ? p00.x : p00.y; e1 = fwd ? p10.x : p10.y; e2 = fwd ? p01.x : p01.y; e3 = fwd ? p11.x : p11.y;
-                      p00 = fwd ? f2{p00.y, 0.f} : f2{0.f, p00.x}; p10 = fwd ? f2{p10.y, 0.f} : f2{0.f, p10.x};
-                      p01 = fwd ? f2{p01.y, 0.f} : f2{0.f, p01.x}; p11 = fwd ? f2{p11.y, 0.f} : f2{0.f, p11.x};
-                    } else if (ax == 1) {
-                      const f2 ea = fwd ? p00 : p10, eb = fwd ? p01 : p11;
-                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
-                      if (fwd) { p00 = p10; p01 = p11; p10 = p11 = zero; } else { p10 = p00; p11 = p01; p00 = p01 = zero; }
-                    } else {
-                      const f2 ea = fwd ? p00 : p01, eb = fwd ? p10 : p11;
-                      e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
-                      if (fwd) { p00 = p01; p10 = p11; p01 = p11 = zero; } else { p01 = p00; p11 = p10; p00 = p10 = zero; }
-                    }
-                  };
-                  using std::integral_constant;
-                  bool one = nregular;
-                  if (nregular) {
-                    if (DBG && a.dbg) {
-                      const bool ax = (d == 1) | (d == -1), ay = (d == V.sy) | (d == -V.sy), az = (d == V.sz) | (d == -V.sz);
-                      if (ax | ay | az) {
-                        const int nax = (__ballot(ax) != 0ull) + (__ballot(ay) != 0ull) + (__ballot(az) != 0ull);
-                        if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
-                      }
-                    }
-                    // flat, mutually exclusive tests (a regular cell has 1 < sy < sz), not an else-chain: each case is one
-                    // predicated region
-                    const bool yp = d == V.sy, ym = d == -V.sy, zp = d == V.sz, zm = d == -V.sz, xp = d == 1, xm = d == -1;
-                    if (yp) face(integral_constant<int, 1>{}, integral_constant<bool, true>{});
-                    if (ym) face(integral_constant<int, 1>{}, integral_constant<bool, false>{});
-                    if (zp) face(integral_constant<int, 2>{}, integral_constant<bool, true>{});
-                    if (zm) face(integral_constant<int, 2>{}, integral_constant<bool, false>{});
-                    if (xp) face(integral_constant<int, 0>{}, integral_constant<bool, true>{});
-                    if (xm) face(integral_constant<int, 0>{}, integral_constant<bool, false>{});
-                    one = key != kNoFace;
-                  }
-                  if (one) {
-                    if (lidx >= 0) {
-                      const bool add = win_emit4(win, key, lp, lq, e0, e1, e2, e3);
-                      if (DBG && a.dbg) { ++ev_face; ev_add += add; }
-                    } else {
-                      // the cell lies outside the window: straight to the grid.  |d| is the grid stride of the axis crossed, which
-                      // names the strides of p and q; a face left behind in the negative direction is the cell's far one, |d| on.
-                      if (DBG && a.dbg) ++ev_glob;
-                      const int ad = abs(d);
-                      const unsigned gp = ad == 1 ? (unsigned)V.sy : 1u, gq = ad == V.sz ? (unsigned)V.sy : (unsigned)V.sz;
-                      const unsigned g = (unsigned)(old_base + max(-d, 0)), gqq = g + gq;
-                      atomic_add_f32_at(a.grad, g, e0);   atomic_add_f32_at(a.grad, g + gp, e1);
-                      atomic_add_f32_at(a.grad, gqq, e2); atomic_add_f32_at(a.grad, gqq + gp, e3);
-                    }
-                  } else {
-                    // jump over more than one face, or into a clamped cell: hand over all eight
-                    if (DBG && a.dbg) ++ev_all8;
-                    // (no quad pre-reduction here: two-face crossings are rarely shared by a quad -- 4.87 -> 4.81 ms without it)
-                    flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, old_base, p00, p10, p01, p11);
-                    p00 = p10 = p01 = p11 = f2{0.f, 0.f};
-                  }
+            // Two regions, one behind the other, both tested on integers the lane holds anyway.  The hot one: both cells regular
+            // and the flat index moved -- one face crossed, unless no case below matches.  The cold one: whatever else changes
+            // the cell (into or out of a clamped cell, which can share its flat index with its regular neighbour; a jump over
+            // more than one face).  A ray that stays in its cell (d == 0 with the regularity unchanged) enters neither.
+            const int d = nbase - old_base;
+            const bool nregular = tbase != kClamped;
+            const bool left = (d != 0) | (nregular != regular);
+            base = nbase;
+            int key = kNoFace;                               // the face (win_face_key); a case of the hot region sets it
+            if (regular & nregular & (d != 0)) {
+              // One face crossed (the flat index moved by one stride): emit the face left behind, carry the shared one.  Six
+              // cases, axis and direction compile-time in each: a case copies the four emitted corners out (e0..e3, in (p, q)
+              // in-face order), moves the carried ones once, and names the face's window slot and strides; ONE emission follows
+              // the cases (wave-steps whose lanes leave across two or more axes are the common kind -- over half of the
+              // headline's -- so an emission per case would run twice there).
+              // AX: 0 = x, 1 = y, 2 = z; FWD: towards the higher index.
+              float e0, e1, e2, e3;
+              int lp, lq;                                    // window strides of p and q (slots)
+              auto face = [&](auto AX, auto FWD) {
+                constexpr int ax = decltype(AX)::value;
+                constexpr bool fwd = decltype(FWD)::value;
+                constexpr f2 zero = f2{0.f, 0.f};
+                asm volatile("");                            // keeps the case's moves under the case's test (not speculated above it)
+                key = lidx + win_face_key(fwd ? 0 : (ax == 0 ? 1 : (ax == 1 ? WSY : WSZ)), ax);   // lidx < 2^16: no carry into the axis
+                lp = ax == 0 ? WSY : 1; lq = ax == 2 ? WSY : WSZ;
+                if (ax == 0) {
+                  e0 = fwd ? p00.x : p00.y; e1 = fwd ? p10.x : p10.y; e2 = fwd ? p01.x : p01.y; e3 = fwd ? p11.x : p11.y;
+                  p00 = fwd ? f2{p00.y, 0.f} : f2{0.f, p00.x}; p10 = fwd ? f2{p10.y, 0.f} : f2{0.f, p10.x};
+                  p01 = fwd ? f2{p01.y, 0.f} : f2{0.f, p01.x}; p11 = fwd ? f2{p11.y, 0.f} : f2{0.f, p11.x};
+                } else if (ax == 1) {
+                  const f2 ea = fwd ? p00 : p10, eb = fwd ? p01 : p11;
+                  e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
+                  if (fwd) { p00 = p10; p01 = p11; p10 = p11 = zero; } else { p10 = p00; p11 = p01; p00 = p01 = zero; }
+                } else {
+                  const f2 ea = fwd ? p00 : p01, eb = fwd ? p10 : p11;
+                  e0 = ea.x; e1 = ea.y; e2 = eb.x; e3 = eb.y;
+                  if (fwd) { p00 = p01; p10 = p11; p01 = p11 = zero; } else { p01 = p00; p11 = p10; p00 = p10 = zero; }
                 }
-                lidx = nregular ? WIN_INDEX(ix, iy, iz) : kIrregular;
+              };
+              using std::integral_constant;
+              if (DBG && a.dbg) {
+                const bool ax = (d == 1) | (d == -1), ay = (d == V.sy) | (d == -V.sy), az = (d == V.sz) | (d == -V.sz);
+                if (ax | ay | az) {
+                  const int nax = (__ballot(ax) != 0ull) + (__ballot(ay) != 0ull) + (__ballot(az) != 0ull);
+                  if (lane == __ffsll((long long)__ballot(true)) - 1) ev_multi += nax >= 2;
+                }
               }
+              // flat, mutually exclusive tests (a regular cell has 1 < sy < sz), not an else-chain: each case is one
+              // predicated region
+              const bool yp = d == V.sy, ym = d == -V.sy, zp = d == V.sz, zm = d == -V.sz, xp = d == 1, xm = d == -1;
+              if (yp) face(integral_constant<int, 1>{}, integral_constant<bool, true>{});
+              if (ym) face(integral_constant<int, 1>{}, integral_constant<bool, false>{});
+              if (zp) face(integral_constant<int, 2>{}, integral_constant<bool, true>{});
+              if (zm) face(integral_constant<int, 2>{}, integral_constant<bool, false>{});
+              if (xp) face(integral_constant<int, 0>{}, integral_constant<bool, true>{});
+              if (xm) face(integral_constant<int, 0>{}, integral_constant<bool, false>{});
+              if (key != kNoFace) {
+                if (lidx >= 0) {
+                  const bool add = win_emit4(win, key, lp, lq, e0, e1, e2, e3);
+                  if (DBG && a.dbg) { ++ev_face; ev_add += add; }
+                } else {
+                  // the cell lies outside the window: straight to the grid.  |d| is the grid stride of the axis crossed, which
+                  // names the strides of p and q; a face left behind in the negative direction is the cell's far one, |d| on.
+                  if (DBG && a.dbg) ++ev_glob;
+                  const int ad = abs(d);
+                  const unsigned gp = ad == 1 ? (unsigned)V.sy : 1u, gq = ad == V.sz ? (unsigned)V.sy : (unsigned)V.sz;
+                  const unsigned g = (unsigned)(old_base + max(-d, 0)), gqq = g + gq;
+                  atomic_add_f32_at(a.grad, g, e0);   atomic_add_f32_at(a.grad, g + gp, e1);
+                  atomic_add_f32_at(a.grad, gqq, e2); atomic_add_f32_at(a.grad, gqq + gp, e3);
+                }
+              }
+            }
+            if (left) {
+              if (regular & (key == kNoFace)) {
+                // jump over more than one face, or into a clamped cell: hand over all eight
+                asm volatile("");                            // cold: stays under its test
+                if (DBG && a.dbg) ++ev_all8;
+                // (no quad pre-reduction here: two-face crossings are rarely shared by a quad -- 4.87 -> 4.81 ms without it)
+                flat_emit8<false>(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, old_base, p00, p10, p01, p11);
+                p00 = p10 = p01 = p11 = f2{0.f, 0.f};
+              }
+              lidx = nregular ? WIN_INDEX(ix, iy, iz) : kIrregular;
             }
           }
         }
@@ -575,7 +581,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
       if (DBG && a.dbg) ev_wsteps += lane == 0;
     }
   // rays still marching when max_steps ran out keep what their cell has accumulated: hand it over
-  if (s.active && lidx > kIrregular) flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
+  if (lidx > kIrregular) flat_emit8(win, WSY, WSZ, a.grad, V.sy, V.sz, lidx, base, p00, p10, p01, p11);
 #undef WSY
 #undef WSZ
 #undef WIN_INDEX
@@ -585,6 +591,7 @@ __global__ void __launch_bounds__(kAdjBlock, DRRT_ADJ_WAVES) k_backtrace_flat(Ba
     ++n_flush;
   }
   if (CHUNK) {
+    s.active = lidx > kEnded;
     // the state the next chunk resumes from (position = the next sample, already stepped to), and where the rays that are
     // still marching stand and head: bounding boxes of their positions [0..5] and velocities [6..11] as order-preserving
     // integer keys (min: 0..2 / 6..8, max: 3..5 / 9..11), [12] their number; [13..18] bounding box of the samples taken
