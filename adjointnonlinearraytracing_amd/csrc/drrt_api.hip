@@ -1,7 +1,7 @@
 // drrt_api.hip -- the C ABI of include/drrt_hip.h: argument checks (the reference's three error messages verbatim,
 // src/volume.cpp:28,37,124), workspace layout (ws_layout), visit-order / step hand-over (ThreadState), per-kernel timing,
 // and the launches of the kernels in drrt_forward.hip / drrt_adjoint_box.hip / drrt_adjoint_ring.hip /
-// drrt_adjoint_rays.hip / drrt_stop_rays.hip / drrt_target_rays.hip / drrt_integral.hip / drrt_cable.hip.  Host code, plus the
+// drrt_ray_adjoints.hip / drrt_integral.hip / drrt_cable.hip.  Host code, plus the
 // four small utility kernels that belong to no march (pair copy of the grid, q16 encode / decode, chunk progress reset).
 #include "drrt_host.h"
 #include "drrt_march.h"
@@ -627,7 +627,7 @@ extern "C" int drrt_backtrace_rays_f32(const float* rif, long long nvox, const i
   return timed_launch(DRRT_PROF_BACKTRACE_RAYS, s, "k_backtrace_rays", [&] { launch_backtrace_rays(a, s); });
 }
 
-// ray-state adjoints of trace_plane (MODE 1) and trace_sdf (MODE 2): drrt_stop_rays.hip
+// ray-state adjoints of trace_plane (MODE 1) and trace_sdf (MODE 2): drrt_ray_adjoints.hip
 template <int MODE>
 static int run_backtrace_stop_rays(const float* rif, const float* sdf, long long nvox, const int res[3], size_t n,
                                    const float* pos, const float* vel, const float* pln_o, const float* pln_d,
@@ -681,7 +681,7 @@ extern "C" int drrt_backtrace_sdf_rays_f32(const float* rif, const float* sdf, l
                                     ws, ws_bytes, flags, stream);
 }
 
-// ray-state adjoint of trace_target: drrt_target_rays.hip.  Keeps nothing per ray between its two launches, so the per-ray
+// ray-state adjoint of trace_target: drrt_ray_adjoints.hip.  Keeps nothing per ray between its two launches, so the per-ray
 // slot of the workspace stays untouched and an order hint is used wherever it lives.
 extern "C" int drrt_backtrace_target_rays_f32(const float* rif, long long nvox, const int res[3], size_t n,
                                               const float* pos, const float* vel, const float* target,

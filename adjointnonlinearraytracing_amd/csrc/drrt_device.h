@@ -343,6 +343,26 @@ DRRT_HD void fwd_init(const Vol& V, FwdState& s) {
   s.esc = false;                                                                      // :62
 }
 
+// The start of every forward march and of every replay of one: the ray (p, v), the mode's aux slots -- MODE 1: (a, b) = the
+// plane's origin and direction; MODE 3: a = the target, and the record's dist2 starts at |p - a|^2 (src/tracer.cpp:200);
+// otherwise zeros, a and b unused -- fwd_init, and the cell of p.
+template <int MODE>
+DRRT_HD void fwd_begin(const Vol& V, const float p[3], const float v[3], const float* a, const float* b, FwdState& s, Cell& c) {
+  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
+  if (MODE == 1) {
+    s.aux0 = a[0]; s.aux1 = a[1]; s.aux2 = a[2];
+    s.aux3 = b[0]; s.aux4 = b[1]; s.aux5 = b[2];
+  }
+  if (MODE == 3) {
+    s.aux0 = a[0]; s.aux1 = a[1]; s.aux2 = a[2];
+    const float ex = s.x - a[0], ey = s.y - a[1], ez = s.z - a[2];
+    s.aux3 = dot3(ex, ey, ez, ex, ey, ez);
+  }
+  fwd_init(V, s);
+  c = locate(V, s.x, s.y, s.z);
+}
+
 // One forward iteration.  In: `c` = cell of the current position (always located, used only when the
 // ray is inside), `t` = the 8 taps there (valid when s.inside).  Out: `c` = cell of the NEW position,
 // reused by the next iteration -- and when that cell is strictly interior the box tests are skipped
@@ -629,14 +649,8 @@ template <int MODE, int REUSE = kTapReuse>
 DRRT_HD RayOut trace_ray(const Vol& V, const float* __restrict__ sdf, float ds, int max_steps,
                          const float p[3], const float v[3], const float* pln_o, const float* pln_d) {
   FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  if (MODE == 1) {
-    s.aux0 = pln_o[0]; s.aux1 = pln_o[1]; s.aux2 = pln_o[2];
-    s.aux3 = pln_d[0]; s.aux4 = pln_d[1]; s.aux5 = pln_d[2];
-  }
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
+  Cell c;
+  fwd_begin<MODE>(V, p, v, pln_o, pln_d, s, c);
   bool act = true;
   if (MODE == 2) act = interp<false>(fetch(sdf, c), c.wx, c.wy, c.wz).n < 0.f;   // src/tracer.cpp:276-277
   unsigned steps = 0;
@@ -670,14 +684,8 @@ template <int MODE>
 DRRT_HD RayOut ray_full(const Vol& V, const float* __restrict__ sdf, float ds, unsigned total, const float p[3],
                         const float v[3], const float* pln_o, const float* pln_d) {
   FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  if (MODE == 1) {
-    s.aux0 = pln_o[0]; s.aux1 = pln_o[1]; s.aux2 = pln_o[2];
-    s.aux3 = pln_d[0]; s.aux4 = pln_d[1]; s.aux5 = pln_d[2];
-  }
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
+  Cell c;
+  fwd_begin<MODE>(V, p, v, pln_o, pln_d, s, c);
   for (unsigned it = 0; it < total; ++it) fwd_step<MODE>(V, sdf, ds, s, c);
   if (MODE != 2 && !s.esc) { s.xtx = s.x; s.xty = s.y; s.xtz = s.z; }
   RayOut o;
@@ -692,12 +700,8 @@ template <int REUSE = kTapReuse>
 DRRT_HD RayOut target_ray_a(const Vol& V, float ds, int max_steps, const float p[3], const float v[3],
                             const float tg[3], float cont[6]) {
   FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = tg[0]; s.aux1 = tg[1]; s.aux2 = tg[2]; s.aux4 = s.aux5 = 0.f;
-  float ex = s.x - tg[0], ey = s.y - tg[1], ez = s.z - tg[2];
-  s.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // src/tracer.cpp:200
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
+  Cell c;
+  fwd_begin<3>(V, p, v, tg, nullptr, s, c);
   unsigned steps = 0;
   TapCache tc;
   tc.base = -1;
@@ -772,10 +776,8 @@ template <typename TapFn, typename Integrand>
 DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], TapFn&& taps,
                                   Integrand&& q) {
   FwdState s;
-  s.x = p[0]; s.y = p[1]; s.z = p[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
-  s.aux0 = s.aux1 = s.aux2 = s.aux3 = s.aux4 = s.aux5 = 0.f;
-  fwd_init(V, s);
-  Cell c = locate(V, s.x, s.y, s.z);
+  Cell c;
+  fwd_begin<0>(V, p, v, nullptr, nullptr, s, c);
   unsigned steps = 0;
   for (int it = 0; it < max_steps; ++it) {
     Taps t = taps_zero();
@@ -797,23 +799,21 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
   return o;
 }
 
-// The reverse march for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the exit ray (xt, vt), given the forward's
-// inputs (p0, v0) and its iteration count K, and the contributions to dL/dn.
-// The forward samples n only while the ray is inside (Q4), so a ray that starts outside flies straight for e
-// iterations first (x_e = x0 + e ds v0) and is refracted by the samples at x_e .. x_{K-1}: K - e iterations.
-//   * K >= max_steps (the forward's Q5 bound): the ray failed (vt is the stale v0, Q6) -> zero gradient, failed = true,
-//     no contribution.  A ray that exits on exactly the last allowed iteration looks the same and is treated the same.
-//   * the prefix is replayed from (p0, v0) with the forward's own operations; no in-box sample among x_0 .. x_{K-1}:
-//     the ray never entered, (xt, vt) = (p0, v0), every integral is 0, the gradient is the identity (dx, dv) and there is
-//     no contribution.
-//   * otherwise K - e reverse iterations from (xt, vt) seeded like adj_init (lambda = dx, mu = dv + ds dx), with
-//     neither the backward-escape test nor the adjoint's own step bound; after the last one lambda = dL/dx_e and the
-//     mu it was updated from is dL/dv_e, so dpos = lambda and dvel = mu_prev + (e ds) lambda.  The last reverse
-//     iteration samples at the replayed x_e itself instead of its reconstruction x_{e+1} - ds v_{e+1}: a ray that
-//     starts on a face (x_e on the box boundary, where grad n jumps) would otherwise be sampled a rounding error
-//     outside it.
+// ---- the seeded reverse run: what every reverse march of the grid shares ------------------------------------------------
+// A reverse march undoes the forward iterations hi-1 .. lo of a ray from the state (x_hi, v_hi) and the seeds (gx, gv) on
+// it.  rev_seed seeds it like adj_init: lambda = gx (dL/dx), mu = gv + ds gx, and q = gv.  q is dL/dv_k; mu runs one
+// iteration ahead of it, as adj_recur leaves it (q is mu before its last update), so after the iteration that arrives at
+// x_k lambda = dL/dx_k and q = dL/dv_k: rev_store's (dpos, dvel).  The iterations come in runs of equal `inside` mask of
+// the forward (Q4: it samples n only while the ray is inside):
+//   sampled run   rev_sampled: hi - lo reverse iterations of adj_sample<0> / adj_recur with neither the backward-escape
+//                 test nor the adjoint's own step bound.  The last of them (`entry`) samples at (ex, ey, ez), the run's
+//                 first position as the forward's replay took it, instead of its reconstruction x_{lo+1} - ds v_{lo+1}: a
+//                 ray that starts on a face (where grad n jumps) would otherwise be sampled a rounding error outside it.
+//   free flight   rev_flight: m iterations outside leave lambda unchanged and add m ds lambda to mu and q.  The caller
+//                 sets the position the next sampled run starts from.
 // `taps(c)` returns the 8 taps of cell c (the caller chooses how they are fetched; the floats are the grid's).
-// What an operator adds is its `term`, called in this order in every reverse iteration, m the sample (n_k, grad n_k):
+// What an operator adds to a sampled run is its `term`, called in this order in every reverse iteration, m the sample
+// (n_k, grad n_k):
 //   term.enter(V, c, s)                    behind locate and before the sample: c is the cell of x_k and s.v still holds
 //                                          v_{k+1}, the velocity that carried the ray out of x_k; a term whose summand has
 //                                          the ray's direction in it seeds mu (dL/dv_{k+1}) here, so that dn and the
@@ -824,8 +824,7 @@ DRRT_HD RayOut trace_integral_ray(const Vol& V, float ds, int max_steps, const f
 //                                          splat_weights(c.wx, c.wy, c.wz, val, gx, gy, gz) at the 8 taps of c
 //   term.pull(V, c, m, s, entry)           the term's own pulls on lambda (the gradients of its fields at the sample
 //                                          position, a direct seed on x_k) and its contributions to its own grids, BEFORE
-//                                          adj_recur, whose closing mu += ds lambda must see the pulls; entry: this is the
-//                                          last reverse iteration, the one that samples the replayed x_e itself
+//                                          adj_recur, whose closing mu += ds lambda must see the pulls
 //   adj_recur(V, ds, s, m, dn)
 //   term.after()                           the term's running scalars
 // With grad_scale = 1 / h (DRRT_FLAG_CORRECTED_H) the sum of the contributions is the exact discrete derivative; the 1/h
@@ -836,7 +835,64 @@ struct NoTerm {                              // trace itself: nothing is integra
   DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState&, bool) {}
   DRRT_HD void after() {}
 };
+struct NoSink {                              // a ray-state adjoint: no contribution to dL/dn is formed
+  DRRT_HD void operator()(const Cell&, float, float, float, float) {}
+};
 
+struct RevMarch { AdjState s; float qx, qy, qz; };
+
+DRRT_HD void rev_seed(RevMarch& r, float ds, const float x[3], const float v[3], const float gx[3], const float gv[3]) {
+  AdjState& s = r.s;
+  s.x = x[0]; s.y = x[1]; s.z = x[2]; s.vx = v[0]; s.vy = v[1]; s.vz = v[2];
+  s.lx = gx[0]; s.ly = gx[1]; s.lz = gx[2];                                               // adj_init, :409
+  s.mx = fmaf(ds, gx[0], gv[0]); s.my = fmaf(ds, gx[1], gv[1]); s.mz = fmaf(ds, gx[2], gv[2]);   // :410
+  s.active = true; s.outside = false;
+  r.qx = gv[0]; r.qy = gv[1]; r.qz = gv[2];
+}
+
+template <typename TapFn, typename Sink, typename Term>
+DRRT_HD void rev_sampled(const Vol& V, float ds, float grad_scale, RevMarch& r, unsigned hi, unsigned lo, float ex, float ey,
+                         float ez, TapFn&& taps, Sink&& sink, Term&& term) {
+  AdjState& s = r.s;
+  for (unsigned k = hi; k > lo; --k) {
+    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
+    if (k == lo + 1u) { s.x = ex; s.y = ey; s.z = ez; }                  // the run's first sample, as the forward took it
+    const Cell c = locate(V, s.x, s.y, s.z);
+    term.enter(V, c, s);
+    AdjSample m;
+    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
+    const float dn = term.dn(V, c, m, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));         // :430
+    const float nds = (m.n * ds) * grad_scale;
+    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
+    r.qx = s.mx; r.qy = s.my; r.qz = s.mz;
+    term.pull(V, c, m, s, k == lo + 1u);
+    adj_recur(V, ds, s, m, dn);
+    term.after();
+  }
+}
+
+DRRT_HD void rev_flight(RevMarch& r, unsigned m, float ds) {
+  AdjState& s = r.s;
+  const float ads = (float)m * ds;
+  r.qx = fmaf(ads, s.lx, r.qx); r.qy = fmaf(ads, s.ly, r.qy); r.qz = fmaf(ads, s.lz, r.qz);
+  s.mx = fmaf(ads, s.lx, s.mx); s.my = fmaf(ads, s.ly, s.my); s.mz = fmaf(ads, s.lz, s.mz);
+}
+
+DRRT_HD void rev_store(const RevMarch& r, float dp[3], float dv[3]) {
+  dp[0] = r.s.lx; dp[1] = r.s.ly; dp[2] = r.s.lz;
+  dv[0] = r.qx; dv[1] = r.qy; dv[2] = r.qz;
+}
+
+// The reverse march for ONE ray: dL/dpos, dL/dvel from the seeds (dx, dv) on the exit ray (xt, vt), given the forward's
+// inputs (p0, v0) and its iteration count K, and the contributions to dL/dn.  A ray that starts outside flies straight for
+// e iterations first (x_e = x0 + e ds v0) and is refracted by the samples at x_e .. x_{K-1}: the masks are F^e T^(K-e).
+//   * K >= max_steps (the forward's Q5 bound): the ray failed (vt is the stale v0, Q6) -> zero gradient, failed = true,
+//     no contribution.  A ray that exits on exactly the last allowed iteration looks the same and is treated the same.
+//   * the prefix is replayed from (p0, v0) with the forward's own operations; no in-box sample among x_0 .. x_{K-1}:
+//     the ray never entered, (xt, vt) = (p0, v0), every integral is 0, the gradient is the identity (dx, dv) and there is
+//     no contribution.
+//   * otherwise the sampled run K-1 .. e from (xt, vt), then the free flight of the prefix -- for e = 0 too: 0 ds lambda is
+//     NaN for an infinite lambda.
 template <typename TapFn, typename Sink, typename Term>
 DRRT_HD RayGrad integral_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K,
                                        const float p0[3], const float v0[3], const float xt[3], const float vt[3],
@@ -859,29 +915,11 @@ DRRT_HD RayGrad integral_backtrace_ray(const Vol& V, float ds, float grad_scale,
     g.dp[0] = dx[0]; g.dp[1] = dx[1]; g.dp[2] = dx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
     return g;
   }
-  AdjState s;
-  s.x = xt[0]; s.y = xt[1]; s.z = xt[2]; s.vx = vt[0]; s.vy = vt[1]; s.vz = vt[2];
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
-  float qx = dv[0], qy = dv[1], qz = dv[2];                               // mu before its last update
-  for (unsigned k = K; k > e; --k) {
-    s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-    if (k == e + 1u) { s.x = px; s.y = py; s.z = pz; }                   // the first in-box sample, as the forward took it
-    const Cell c = locate(V, s.x, s.y, s.z);
-    term.enter(V, c, s);
-    AdjSample m;
-    (void)adj_sample<0>(V, nullptr, ds, s, c, taps(c), m);                // v_{k-1}; the escape test is not used
-    const float dn = term.dn(V, c, m, dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz));         // :430
-    const float nds = (m.n * ds) * grad_scale;
-    sink(c, dn * ds, nds * s.mx, nds * s.my, nds * s.mz);
-    qx = s.mx; qy = s.my; qz = s.mz;
-    term.pull(V, c, m, s, k == e + 1u);
-    adj_recur(V, ds, s, m, dn);
-    term.after();
-  }
-  const float eds = (float)e * ds;
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = fmaf(eds, s.lx, qx); g.dv[1] = fmaf(eds, s.ly, qy); g.dv[2] = fmaf(eds, s.lz, qz);
+  RevMarch r;
+  rev_seed(r, ds, xt, vt, dx, dv);
+  rev_sampled(V, ds, grad_scale, r, K, e, px, py, pz, taps, sink, term);
+  rev_flight(r, e, ds);
+  rev_store(r, g.dp, g.dv);
   g.steps = K - e;
   return g;
 }
@@ -892,8 +930,7 @@ template <typename TapFn>
 DRRT_HD RayGrad backtrace_ray_state(const Vol& V, float ds, int max_steps, unsigned K, const float p0[3],
                                     const float v0[3], const float xt[3], const float vt[3], const float dx[3],
                                     const float dv[3], TapFn&& taps) {
-  return integral_backtrace_ray(V, ds, 1.f, max_steps, K, p0, v0, xt, vt, dx, dv, taps,
-                                [](const Cell&, float, float, float, float) {}, NoTerm{});
+  return integral_backtrace_ray(V, ds, 1.f, max_steps, K, p0, v0, xt, vt, dx, dv, taps, NoSink{}, NoTerm{});
 }
 
 // ---- optical path length -------------------------------------------------------------------------------------------
@@ -1634,12 +1671,8 @@ DRRT_HD RayGrad cable_field_backtrace_ray(const Cyl& C, const float* fa, float d
 //   * trace_plane, never flagged escaped (failmask set; xt is the final x, vt stale): zero gradient, failed = true.
 //     trace_sdf has no such fix-up: a ray that never crosses keeps (xt, vt) = (p0, v0), j = 0.
 //   * j = 0: the gradient is the identity (dx, dv).
-//   * otherwise the iterations j-1 .. 0 are undone run by run, a run being a stretch [lo, hi) of equal m_k, seeded like adj_init
-//     (lambda = dx, mu = dv + ds dx, and q = dv: q is dL/dv_k, mu runs one iteration ahead of it as adj_recur leaves it):
-//       sampled run   hi - lo reverse iterations of adj_sample<0> / adj_recur with neither the backward-escape test nor the
-//                     adjoint's step bound; the last of them samples at the replayed x_lo itself instead of its
-//                     reconstruction x_{lo+1} - ds v_{lo+1} (a start exactly on a face; both existing routines do the same);
-//       free flight   lambda unchanged, mu and q += (hi - lo) ds lambda, and x set to the replayed x_lo.
+//   * otherwise the iterations j-1 .. 0 are undone run by run, a run being a stretch [lo, hi) of equal m_k: the seeded
+//     reverse run (rev_seed on the record, rev_sampled / rev_flight per run, x set to the replayed x_lo behind a flight).
 //     First pass: the march stops at its first cross, so the masks are F^e T^(j-e) -- the run that ends at j is known from
 //     the replay and what is left of it is the free-flight prefix from p0.  Second pass: the masks need not be monotone
 //     (a ray that starts in bounds past its plane and heads back through it: T, F..F, T..T, F -- m_0 carries no plane term);
@@ -1651,19 +1684,6 @@ DRRT_HD RayGrad cable_field_backtrace_ray(const Cyl& C, const float* fa, float d
 struct StopRecord { float xt[3], vt[3]; unsigned j; bool esc; };
 struct StopGrad { float dp[3], dv[3]; unsigned steps, fwd; bool failed, again; };
 
-template <int MODE>
-DRRT_HD void stop_fwd_begin(const Vol& V, const float p0[3], const float v0[3], const float* pln_o, const float* pln_d,
-                            FwdState& f, Cell& c) {
-  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
-  f.aux0 = f.aux1 = f.aux2 = f.aux3 = f.aux4 = f.aux5 = 0.f;
-  if (MODE == 1) {
-    f.aux0 = pln_o[0]; f.aux1 = pln_o[1]; f.aux2 = pln_o[2];
-    f.aux3 = pln_d[0]; f.aux4 = pln_d[1]; f.aux5 = pln_d[2];
-  }
-  fwd_init(V, f);
-  c = locate(V, f.x, f.y, f.z);
-}
-
 template <int MODE, bool FULL, typename TapFn>
 DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict__ sdf, float ds, int max_steps,
                                           unsigned total, const float p0[3], const float v0[3], const float* pln_o,
@@ -1672,7 +1692,7 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
   static_assert(MODE == 1 || MODE == 2, "trace_plane or trace_sdf");
   FwdState f;
   Cell c;
-  stop_fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
+  fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
   const unsigned lim = FULL ? total : (max_steps > 0 ? (unsigned)max_steps : 0u);
   unsigned steps = 0, j = 0;
   unsigned lo = 0, jlo = 0;                          // first iteration of the current sampled run / of the one that ended at j
@@ -1708,33 +1728,19 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
     if (g.again) return g;
   }
   if (j == 0) return g;
-  AdjState s;
-  s.x = f.xtx; s.y = f.xty; s.z = f.xtz; s.vx = f.vtx; s.vy = f.vty; s.vz = f.vtz;
-  s.lx = dx[0]; s.ly = dx[1]; s.lz = dx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, dx[0], dv[0]); s.my = fmaf(ds, dx[1], dv[1]); s.mz = fmaf(ds, dx[2], dv[2]);   // :410
-  s.active = true; s.outside = false;
-  float qx = dv[0], qy = dv[1], qz = dv[2];
+  const float xj[3] = {f.xtx, f.xty, f.xtz}, vj[3] = {f.vtx, f.vty, f.vtz};
+  RevMarch r;
+  rev_seed(r, ds, xj, vj, dx, dv);
   unsigned hi = j;
   bool sampled = true;
   lo = jlo; lx = jx; ly = jy; lz = jz;
   for (;;) {
     if (sampled) {
-      for (unsigned k = hi; k > lo; --k) {
-        s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-        if (k == lo + 1u) { s.x = lx; s.y = ly; s.z = lz; }                // the run's first sample, as the forward took it
-        const Cell ca = locate(V, s.x, s.y, s.z);
-        AdjSample m;
-        (void)adj_sample<0>(V, nullptr, ds, s, ca, taps(ca), m);            // v_{k-1}; the escape test is not used
-        const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);         // :430
-        qx = s.mx; qy = s.my; qz = s.mz;
-        adj_recur(V, ds, s, m, dn);
-      }
+      rev_sampled(V, ds, 1.f, r, hi, lo, lx, ly, lz, taps, NoSink{}, NoTerm{});
       g.steps += hi - lo;
     } else {
-      const float ads = (float)(hi - lo) * ds;
-      qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
-      s.mx = fmaf(ads, s.lx, s.mx); s.my = fmaf(ads, s.ly, s.my); s.mz = fmaf(ads, s.lz, s.mz);
-      s.x = lx; s.y = ly; s.z = lz;
+      rev_flight(r, hi - lo, ds);
+      r.s.x = lx; r.s.y = ly; r.s.z = lz;
     }
     hi = lo;
     if (hi == 0) break;
@@ -1743,7 +1749,7 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
       continue;
     }
     // the run that holds iteration hi - 1: replay the forward up to it
-    stop_fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
+    fwd_begin<MODE>(V, p0, v0, pln_o, pln_d, f, c);
     for (unsigned it = 0;; ++it) {
       if (it == 0 || f.inside != prev) { lo = it; lx = f.x; ly = f.y; lz = f.z; }
       prev = f.inside;
@@ -1755,8 +1761,7 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
     }
     sampled = prev;
   }
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  rev_store(r, g.dp, g.dv);
   return g;
 }
 
@@ -1771,15 +1776,9 @@ DRRT_HD StopGrad stop_backtrace_ray_state(const Vol& V, const float* __restrict_
 //     Phase A ends at the first cross, so its masks are F^e T^(done-e): e = the index of the first in-box sample (done
 //     when there is none), x_e the position sampled there.
 //   * The effective position seed is gx = dx + 2 dd2 (x_j - t), one fmaf per component.  j = 0: the result is (gx, dv).
-//   * Otherwise the iterations j-1 .. 0 are undone run by run, seeded like adj_init (lambda = gx, mu = dv + ds gx, q = dv:
-//     q is dL/dv_k, mu runs one iteration ahead of it as adj_recur leaves it):
-//       free flight   (the iterations after the escape, done .. j-1, and the prefix 0 .. e-1): m iterations leave lambda
-//                     unchanged and add m ds lambda to mu and q;
-//       sampled run   (e .. min(j, done)-1): reverse iterations of adj_sample<0> / adj_recur with neither the backward-escape
-//                     test nor the adjoint's step bound, started from the record itself, or, for a record written after the
-//                     escape (j > done), from phase A's end state; the last of them samples at the replayed x_e itself
-//                     instead of its reconstruction x_{e+1} - ds v_{e+1} (a start exactly on a face; the sibling routines
-//                     do the same).
+//   * Otherwise the iterations j-1 .. 0 are undone with the seeded reverse run (rev_seed with gx on the record): the free
+//     flight done .. j-1 of a record written after the escape (j > done), behind which the march continues from phase A's
+//     end state; the sampled run e .. min(j, done)-1; the free flight of the prefix 0 .. e-1, where there is one.
 //   * A ray that ran out of steps keeps its record and its gradient (as in the cable routine); `failed` only reports it.
 //   * steps = the forward iterations replayed (done, plus total - done of phase B) + the reverse iterations of the sampled
 //     run; fwd = done.
@@ -1798,12 +1797,8 @@ template <typename TapFn>
 DRRT_HD void target_replay_a(const Vol& V, float ds, int max_steps, const float p0[3], const float v0[3], const float tg[3],
                              TapFn&& taps, TargetReplay& r) {
   FwdState& f = r.f;
-  f.x = p0[0]; f.y = p0[1]; f.z = p0[2]; f.vx = v0[0]; f.vy = v0[1]; f.vz = v0[2];
-  f.aux0 = tg[0]; f.aux1 = tg[1]; f.aux2 = tg[2]; f.aux4 = f.aux5 = 0.f;
-  const float ex = f.x - tg[0], ey = f.y - tg[1], ez = f.z - tg[2];
-  f.aux3 = dot3(ex, ey, ez, ex, ey, ez);                                  // src/tracer.cpp:200
-  fwd_init(V, f);
-  Cell c = locate(V, f.x, f.y, f.z);
+  Cell c;
+  fwd_begin<3>(V, p0, v0, tg, nullptr, f, c);
   unsigned steps = 0, j = 0, e = 0;
   bool entered = false;
   r.ex = f.x; r.ey = f.y; r.ez = f.z;
@@ -1854,41 +1849,21 @@ DRRT_HD TargetGrad target_backtrace_ray_state(const Vol& V, float ds, int max_st
   const float gx[3] = {fmaf(w, xj[0] - tg[0], dx[0]), fmaf(w, xj[1] - tg[1], dx[1]), fmaf(w, xj[2] - tg[2], dx[2])};
   g.dp[0] = gx[0]; g.dp[1] = gx[1]; g.dp[2] = gx[2]; g.dv[0] = dv[0]; g.dv[1] = dv[1]; g.dv[2] = dv[2];
   if (j == 0) return g;
-  AdjState s;
-  s.lx = gx[0]; s.ly = gx[1]; s.lz = gx[2];                                               // adj_init, :409
-  s.mx = fmaf(ds, gx[0], dv[0]); s.my = fmaf(ds, gx[1], dv[1]); s.mz = fmaf(ds, gx[2], dv[2]);   // :410
-  s.active = true; s.outside = false;
-  float qx = dv[0], qy = dv[1], qz = dv[2];
+  RevMarch m;
+  rev_seed(m, ds, xj, vj, gx, dv);
   unsigned hi = j;
   if (j > done) {                                    // the record was written after the escape: free flight back to phase A's end
-    const float ads = (float)(j - done) * ds;
-    qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
-    s.mx = fmaf(ads, s.lx, s.mx); s.my = fmaf(ads, s.ly, s.my); s.mz = fmaf(ads, s.lz, s.mz);
-    s.x = f.x; s.y = f.y; s.z = f.z; s.vx = f.vx; s.vy = f.vy; s.vz = f.vz;
+    rev_flight(m, j - done, ds);
+    m.s.x = f.x; m.s.y = f.y; m.s.z = f.z; m.s.vx = f.vx; m.s.vy = f.vy; m.s.vz = f.vz;
     hi = done;
-  } else {
-    s.x = xj[0]; s.y = xj[1]; s.z = xj[2]; s.vx = vj[0]; s.vy = vj[1]; s.vz = vj[2];
   }
   if (hi > e) {                                      // the sampled run e .. hi-1
-    for (unsigned k = hi; k > e; --k) {
-      s.x = fmaf(-ds, s.vx, s.x); s.y = fmaf(-ds, s.vy, s.y); s.z = fmaf(-ds, s.vz, s.z);   // :420
-      if (k == e + 1u) { s.x = r.ex; s.y = r.ey; s.z = r.ez; }             // the first in-box sample, as the forward took it
-      const Cell ca = locate(V, s.x, s.y, s.z);
-      AdjSample m;
-      (void)adj_sample<0>(V, nullptr, ds, s, ca, taps(ca), m);              // v_{k-1}; the escape test is not used
-      const float dn = dot3(s.mx, s.my, s.mz, m.gx, m.gy, m.gz);           // :430
-      qx = s.mx; qy = s.my; qz = s.mz;
-      adj_recur(V, ds, s, m, dn);
-    }
+    rev_sampled(V, ds, 1.f, m, hi, e, r.ex, r.ey, r.ez, taps, NoSink{}, NoTerm{});
     g.steps += hi - e;
     hi = e;
   }
-  if (hi > 0) {                                      // the free-flight prefix from p0
-    const float ads = (float)hi * ds;
-    qx = fmaf(ads, s.lx, qx); qy = fmaf(ads, s.ly, qy); qz = fmaf(ads, s.lz, qz);
-  }
-  g.dp[0] = s.lx; g.dp[1] = s.ly; g.dp[2] = s.lz;
-  g.dv[0] = qx; g.dv[1] = qy; g.dv[2] = qz;
+  if (hi > 0) rev_flight(m, hi, ds);                 // the free-flight prefix from p0
+  rev_store(m, g.dp, g.dv);
   return g;
 }
 

@@ -18,7 +18,7 @@
 // (trace_opl_ray ... vector_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
 // drrt_march.h.
 //
-// One ray per lane, everything in registers, as drrt_adjoint_rays.hip: the taps of n go through OplTaps (pair copy or plain
+// One ray per lane, everything in registers, as drrt_ray_adjoints.hip: the taps of n go through HeldTaps (pair copy or plain
 // grid), those of a further field through one FieldTaps each (plain gathers of the field itself -- there is no pair copy
 // of it); both are kept while the lane stays in a strictly interior cell, and boundary cells are fetched with their clamps
 // (fetch of drrt_device.h).
@@ -46,7 +46,7 @@ __device__ __forceinline__ void trace_lanes(const Args& a, March&& march, Store&
   if (ray_index(a.perm, t, a.n, i)) {
     const Ray3 p = ld3(a.pos, i), u = ld3(a.vel, i);
     const float p0[3] = {p.x, p.y, p.z}, v0[3] = {u.x, u.y, u.z};
-    OplTaps<PAIR> taps(V, R);
+    HeldTaps<PAIR> taps(V, R);
     const RayOut r = march(i, p0, v0, taps);
     steps = r.steps; failed = r.act ? 1u : 0u;
     st3(a.xt, i, r.xt[0], r.xt[1], r.xt[2]);
@@ -75,7 +75,7 @@ __device__ __forceinline__ void backtrace_lanes(const Args& a, March&& march) {
     const Ray3 gx = a.dx ? ld3(a.dx, i) : zero, gv = a.dv ? ld3(a.dv, i) : zero;
     const AdjRay r{{p.x, p.y, p.z}, {u.x, u.y, u.z}, {xe.x, xe.y, xe.z}, {ve.x, ve.y, ve.z}, {gx.x, gx.y, gx.z},
                    {gv.x, gv.y, gv.z}, a.fsteps[i]};
-    OplTaps<PAIR> taps(V, R);
+    HeldTaps<PAIR> taps(V, R);
     const RayGrad g = march(i, r, taps);
     steps = g.steps; failed = g.failed ? 1u : 0u;
     if (a.dpos) {
@@ -107,7 +107,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_opl(OplTraceArgs a) {
   float opl;
   trace_lanes<PAIR>(a,
-    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
       return trace_opl_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, opl);
     },
     [&](size_t i) { a.opl[i] = opl; });
@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_opl(OplTraceArgs a) {
 
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_backtrace_opl(OplBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
     const float dopl = a.dopl ? a.dopl[i] : 0.f;
     HeldCorners acc(a.grad);
     const bool scatter = a.grad != nullptr;
@@ -133,7 +133,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_field(FieldTraceArgs a) {
   float tau;
   trace_lanes<PAIR>(a,
-    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
       FieldTaps ftaps(a.field);
       return trace_field_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, ftaps, tau);
     },
@@ -143,7 +143,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_field(FieldTraceArgs a) {
 // GRID / FIELD: dL/dn / dL/dfield is scattered (a.grad / a.grad_field is not null)
 template <bool PAIR, bool GRID, bool FIELD>
 __global__ void __launch_bounds__(kBlock) k_backtrace_field(FieldBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
     const float dtau = a.dtau ? a.dtau[i] : 0.f;
     FieldTaps ftaps(a.field);
     HeldCorners acc(a.grad), facc(a.grad_field);
@@ -162,7 +162,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_emission(EmissionTraceArgs a) {
   float rad, tau;
   trace_lanes<PAIR>(a,
-    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
       FieldTaps etaps(a.emission), ataps(a.absorption);
       return trace_emission_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, etaps, ataps, rad, tau);
     },
@@ -172,7 +172,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_emission(EmissionTraceArgs a) 
 // GRID / EMIS / ABSB: dL/dn / dL/de / dL/da is scattered (a.grad / a.grad_emission / a.grad_absorption is not null)
 template <bool PAIR, bool GRID, bool EMIS, bool ABSB>
 __global__ void __launch_bounds__(kBlock) k_backtrace_emission(EmissionBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
     const float drad = a.drad ? a.drad[i] : 0.f, dtau = a.dtau ? a.dtau[i] : 0.f;
     FieldTaps etaps(a.emission), ataps(a.absorption);
     HeldCorners acc(a.grad), eacc(a.grad_emission), aacc(a.grad_absorption);
@@ -201,7 +201,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_vector(VectorTraceArgs a) {
   float circ;
   trace_lanes<PAIR>(a,
-    [&](size_t, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
       VectorTaps vtaps(a.vfield, plane_size(a.vol));
       return trace_vector_ray(a.vol, a.ds, a.max_steps, p0, v0, taps, vtaps, circ);
     },
@@ -211,7 +211,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_vector(VectorTraceArgs a) {
 // GRID / VFIELD: dL/dn / the three planes of dL/du are scattered (a.grad / a.grad_vfield is not null)
 template <bool PAIR, bool GRID, bool VFIELD>
 __global__ void __launch_bounds__(kBlock) k_backtrace_vector(VectorBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
     const float dcirc = a.dcirc ? a.dcirc[i] : 0.f;
     const size_t nvox = plane_size(a.vol);
     VectorTaps vtaps(a.vfield, nvox);
@@ -236,7 +236,7 @@ template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_path(PathTraceArgs a) {
   unsigned count;
   trace_lanes<PAIR>(a,
-    [&](size_t i, const float* p0, const float* v0, OplTaps<PAIR>& taps) {
+    [&](size_t i, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
       auto store = [&](unsigned j, float x, float y, float z) { st3(a.path, (size_t)j * a.n + i, x, y, z); };
       return trace_path_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
     },
@@ -246,7 +246,7 @@ __global__ void __launch_bounds__(kBlock) k_trace_path(PathTraceArgs a) {
 // GRID: dL/dn is scattered (a.grad is not null)
 template <bool PAIR, bool GRID>
 __global__ void __launch_bounds__(kBlock) k_backtrace_path(PathBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, OplTaps<PAIR>& taps) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
     auto seed = [&](unsigned j, float* g) {
       const Ray3 zero{0.f, 0.f, 0.f};
       const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;

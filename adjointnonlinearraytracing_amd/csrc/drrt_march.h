@@ -7,11 +7,9 @@
 //                           classification, the one-atomic-per-tap cross-check kernel
 //   drrt_adjoint_ring.hip   backtrace / backtrace_sdf, fitted ring window (its own translation unit: it is built with a
 //                           different instruction-scheduling strategy, csrc/Makefile)
-//   drrt_adjoint_rays.hip   backtrace_rays: dL/dpos, dL/dvel of trace (ray-state adjoint, no grid writes)
-//   drrt_stop_rays.hip      backtrace_pln_rays / backtrace_sdf_rays: dL/dpos, dL/dvel of trace_plane / trace_sdf (ray-state
-//                           adjoint with the forward replayed, no grid writes)
-//   drrt_target_rays.hip    backtrace_target_rays: dL/dpos, dL/dvel of trace_target (ray-state adjoint with the forward
-//                           replayed over the call's global loop count, no grid writes)
+//   drrt_ray_adjoints.hip   the ray-state adjoints, dL/dpos and dL/dvel with no grid writes: backtrace_rays (of trace),
+//                           backtrace_pln_rays / backtrace_sdf_rays (of trace_plane / trace_sdf, the forward replayed),
+//                           backtrace_target_rays (of trace_target, the forward replayed over the call's global loop count)
 //   drrt_integral.hip       the integral operators, each a trace with a line integral over its samples and ONE adjoint
 //                           march that returns every gradient from seeds on all outputs (global atomics, no window):
 //                           trace_opl / backtrace_opl (opl = int n dl; dL/dn, dL/dpos, dL/dvel), trace_field /
@@ -65,13 +63,14 @@ namespace drrt {
 constexpr int kBlock = 256;
 
 // ---------------------------------------------------------------------------------------------
-// stats: block-level reduction, then 3 atomics per block
+// stats: block-level reduction, then 3 atomics per block (one each where non-zero): ray_steps += the sum of `sum_of`,
+// iters = the maximum of `max_of`, n_failed += the sum of `failed`
 // ---------------------------------------------------------------------------------------------
 template <int BLOCK = kBlock>
-__device__ __forceinline__ void block_stats(drrt_stats* stats, unsigned steps, unsigned failed) {
+__device__ __forceinline__ void block_stats(drrt_stats* stats, unsigned sum_of, unsigned max_of, unsigned failed) {
   if (!stats) return;
   __shared__ unsigned s_sum[BLOCK / kWave], s_max[BLOCK / kWave], s_fail[BLOCK / kWave];
-  unsigned ws = wave_sum_u32(steps), wm = wave_max_u32(steps), wf = wave_sum_u32(failed);
+  unsigned ws = wave_sum_u32(sum_of), wm = wave_max_u32(max_of), wf = wave_sum_u32(failed);
   int lane = threadIdx.x & (kWave - 1), wid = threadIdx.x / kWave;
   if (lane == 0) { s_sum[wid] = ws; s_max[wid] = wm; s_fail[wid] = wf; }
   __syncthreads();
@@ -83,6 +82,11 @@ __device__ __forceinline__ void block_stats(drrt_stats* stats, unsigned steps, u
     if (fail) atomicAdd(&stats->n_failed, fail);
     if (mx)   atomicMax(&stats->iters, mx);
   }
+}
+// ... with both taken from the ray's iteration count
+template <int BLOCK = kBlock>
+__device__ __forceinline__ void block_stats(drrt_stats* stats, unsigned steps, unsigned failed) {
+  block_stats<BLOCK>(stats, steps, steps, failed);
 }
 
 // Ray visited by thread t: through the visit order when there is one.  An index outside [0, n) -- only possible
@@ -253,20 +257,22 @@ __device__ __forceinline__ void taps_set(const Taps& t, f4& q0, f4& q1) {
 }
 template <bool PAIR> __device__ __forceinline__ unsigned tap_offset(int base) { return (unsigned)base << (PAIR ? 3 : 2); }
 
-// ---- one ray per lane with global atomics: drrt_integral.hip ----
-// the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell
+// ---- one ray per lane, the whole march in registers: drrt_integral.hip, drrt_ray_adjoints.hip ----
+// the taps of cell c for the lane: gathered through R, kept while the lane stays in a strictly interior cell.  "Nothing
+// held" is the offset ~0u, which no cell has (tap_offset is a multiple of 4), not a flag of its own: with one, the first
+// pass of the plane adjoint takes 76 VGPRs instead of 72 (6 waves per SIMD instead of 7) and, on MI355X at 256^3 / 1M rays,
+// 2.91 ms instead of 2.71-2.74.
 template <bool PAIR>
-struct OplTaps {
+struct HeldTaps {
   const Vol& V;
   const TapRows& R;
-  unsigned off = 0;          // byte offset (tap_offset) of the interior cell whose taps the lane holds
-  bool held = false;
+  unsigned off = ~0u;        // byte offset (tap_offset) of the interior cell whose taps the lane holds
   f4 q0 = f4{0.f, 0.f, 0.f, 0.f}, q1 = f4{0.f, 0.f, 0.f, 0.f};
-  __device__ __forceinline__ OplTaps(const Vol& v, const TapRows& r) : V(v), R(r) {}
+  __device__ __forceinline__ HeldTaps(const Vol& v, const TapRows& r) : V(v), R(r) {}
   __device__ __forceinline__ Taps operator()(const Cell& c) {
-    if (!c.interior) { held = false; return fetch(V.data, c); }
+    if (!c.interior) { off = ~0u; return fetch(V.data, c); }
     const unsigned noff = tap_offset<PAIR>(c.base);
-    if (!(held & (noff == off))) { gather_rows<PAIR>(R, noff, q0, q1); off = noff; held = true; }
+    if (noff != off) { gather_rows<PAIR>(R, noff, q0, q1); off = noff; }
     return taps_of<PAIR>(q0, q1);
   }
 };
@@ -470,7 +476,7 @@ __device__ __forceinline__ bool bundles_want_direct(const unsigned* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------
-// ray-state adjoint of trace (drrt_adjoint_rays.hip): dL/dpos, dL/dvel, no contribution to dL/dn.  Its own argument
+// ray-state adjoint of trace (drrt_ray_adjoints.hip): dL/dpos, dL/dvel, no contribution to dL/dn.  Its own argument
 // block: BackArgs keeps the field offsets the measured adjoint kernels were compiled against.
 // ---------------------------------------------------------------------------------------------
 struct RayGradArgs {
@@ -488,7 +494,7 @@ struct RayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
-// ray-state adjoint of trace_plane / trace_sdf (drrt_stop_rays.hip): takes the forward's inputs only and replays it
+// ray-state adjoint of trace_plane / trace_sdf (drrt_ray_adjoints.hip): takes the forward's inputs only and replays it
 struct StopRayGradArgs {
   Vol vol;
   const float* sdf;                         // trace_sdf
@@ -505,7 +511,7 @@ struct StopRayGradArgs {
   int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
 };
 
-// ray-state adjoint of trace_target (drrt_target_rays.hip): takes the forward's inputs only and replays it
+// ray-state adjoint of trace_target (drrt_ray_adjoints.hip): takes the forward's inputs only and replays it
 struct TargetRayGradArgs {
   Vol vol;
   const float* pos; const float* vel; const float* target;   // the forward's inputs
@@ -838,11 +844,11 @@ void launch_bundle_classify(const BackArgs& a, hipStream_t s);
 void launch_backtrace_box(int mode, bool dbg, const BackArgs& a, hipStream_t s);
 void launch_backtrace_ring(int mode, bool dbg, const BackArgs& a, hipStream_t s);
 void launch_backtrace_ring_sparse(const BackArgs& a, hipStream_t s, int which);   // the sparse-only instantiations (backtrace)
-// ray-state adjoint (drrt_adjoint_rays.hip)
+// ray-state adjoints (drrt_ray_adjoints.hip): of trace
 void launch_backtrace_rays(const RayGradArgs& a, hipStream_t s);
-// ray-state adjoint of trace_plane (mode 1) / trace_sdf (mode 2): first pass, then the flagged rays (drrt_stop_rays.hip)
+// ... of trace_plane (mode 1) / trace_sdf (mode 2): first pass, then the flagged rays
 void launch_backtrace_stop_rays(int mode, const StopRayGradArgs& a, hipStream_t s);
-// ray-state adjoint of trace_target: the count of the global loop, then replay and reverse march (drrt_target_rays.hip)
+// ... of trace_target: the count of the global loop, then replay and reverse march
 void launch_backtrace_target_rays(const TargetRayGradArgs& a, hipStream_t s);
 // the integral operators (drrt_integral.hip): optical path length, line integral of a second field, emission with
 // self-absorption, line integral of a vector field, each with its adjoint

@@ -45,6 +45,11 @@ helpers -- plus the CPU oracle:
                        Tracer::backtrace's dL/dn (h = 1 as written; h != 1 with the 1/h correction, Q3) with reference
                        code inside the loop body
 
+  ray_adjoints_host.npz  the host builds of the grid ray-state adjoints (tests/hostcheck) on the cases of
+                       tests/test_ray_adjoint_pin.py -> pins them against their own past, byte for byte.  Recorded only
+                       when asked for by name (`make_golden.py ray_adjoints_host`): a run of everything must not re-pin
+                       the routines to whatever they compute today
+
 Only DATA is stored (inputs and expected outputs); no reference source text.
 """
 import os
@@ -492,6 +497,39 @@ def cone_rays():
     out.update(cube_x=x.numpy(), cube_v=v.numpy(), cube_planes=pl.numpy(), cube_nrays=np.array(nr),
                pix=np.array(pix), spp=spp, width=width)
     save("cone_rays.npz", **out)
+
+
+def ray_adjoints_host():
+    """The host builds of the grid ray-state adjoints (tests/hostcheck) on the cases of tests/test_ray_adjoint_pin.py, as
+    they are at the commit this is run on: what a later refactor of the reverse march is held to, byte for byte.  The
+    inputs are not stored (the scene builders are deterministic).  Every kind of ray the routines tell apart must be in
+    the recorded set."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import integral_host as OH
+    import test_opl
+    import test_ray_adjoint_pin as P
+    out = {}
+    seen = dict.fromkeys(("second-pass plane rays", "failed plane rays", "target records after the escape",
+                          "rays with a free-flight prefix", "rays with e = 0 and a non-finite gradient"), 0)
+    for name in P.SCENES:
+        for routine in P.ROUTINES:
+            out.update(P.record(name, routine))
+        pln, tg = P.run(name, "pln", "built")[0], P.run(name, "target", "built")[0]
+        seen["second-pass plane rays"] += int(pln["again"].sum())
+        seen["failed plane rays"] += int(pln["failed"].sum())
+        seen["target records after the escape"] += int((tg["jstar"] > tg["fwd"]).sum())
+        for routine in ("pln", "sdf", "target", "target_nodd2"):
+            assert (P.run(name, routine, "built")[0]["jstar"] == 0).any(), (name, routine, "no ray with jstar == 0")
+        s = test_opl.scene(name)
+        K = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])["steps"]
+        o = P.run(name, "opl", "nonfinite")[0]                         # its steps: the reverse iterations, K - e
+        seen["rays with a free-flight prefix"] += int(((o["steps"] > 0) & (o["steps"] < K)).sum())
+        seen["rays with e = 0 and a non-finite gradient"] += int(((o["steps"] > 0) & (o["steps"] == K)
+                                                                   & ~np.isfinite(o["dpos"]).all(1)).sum())
+    print("ray_adjoints_host.npz:", seen)
+    assert all(seen.values()), seen
+    save("ray_adjoints_host.npz", **out)
+    assert os.path.getsize(os.path.join(HERE, "ray_adjoints_host.npz")) <= 200_000
 
 
 if __name__ == "__main__":

@@ -1,7 +1,7 @@
 // target_rays.hip -- TEST INFRASTRUCTURE ONLY (never built or loaded by the package).
 //
 // The host build of the ray-state adjoint of trace_target: target_backtrace_ray_state of
-// adjointnonlinearraytracing_amd/csrc/drrt_device.h, looped as drrt_target_rays.hip launches it -- a first pass for the
+// adjointnonlinearraytracing_amd/csrc/drrt_device.h, looped as drrt_ray_adjoints.hip launches it -- a first pass for the
 // call's global loop count, a second for the replay and the reverse march.  Compiled by tests/target_raygrad_host.py with the
 // line of tests/hostcheck_lib.py (`hipcc --cuda-host-only -O2 -ffp-contract=off -mfma`): the CPU tier compares it with float64
 // autograd (tests/target_ad.py), the GPU tier compares the kernels with it bit for bit.

@@ -5,7 +5,7 @@ CPU tier: the host build of the product's per-ray routine (tests/hostcheck, stop
 csrc/drrt_device.h, both passes) against torch.autograd in float64 through tests/stop_ad (the reference's whole global
 loop with its masks), on the tie-free rays: those whose fp32 and fp64 records agree to TIE_TOL and were written on the same
 iteration.  Rays that failed the plane march (zero gradient by contract) are checked on their own and are not part of the
-share that may be dropped.  GPU tier: the kernels of drrt_stop_rays.hip against that host build bit for bit, the two
+share that may be dropped.  GPU tier: the stop kernels of drrt_ray_adjoints.hip against that host build bit for bit, the two
 autograd classes end to end, their launches, and the metric size.
 
 On the parent commit every test here fails: tests/stop_raygrad_host does not compile (no stop_backtrace_ray_state), the

@@ -4,7 +4,7 @@ seeds on the closest-approach record (xt, vt) AND on dist2, and dL/dtarget.
 CPU tier: the host build of the product's per-ray routine (tests/hostcheck/target_rays.hip: target_backtrace_ray_state of
 csrc/drrt_device.h, both passes) against torch.autograd in float64 through tests/target_ad (the reference's whole global loop
 with its masks), on the tie-free rays: those whose fp32 and fp64 records agree to TIE_TOL and were written on the same
-iteration.  GPU tier: the kernels of drrt_target_rays.hip against that host build bit for bit, the autograd class end to end,
+iteration.  GPU tier: the target kernels of drrt_ray_adjoints.hip against that host build bit for bit, the autograd class end to end,
 and its launches.
 
 On the parent commit every test here fails: tests/hostcheck/target_rays.hip does not compile (no
@@ -364,7 +364,7 @@ def _same(got, want):
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", [f"{n}/{z}" for n, z in CASES] + [f"fuzz{k}" for k in range(5)])
 def test_kernels_match_host_routine_bitwise(gpu, case):
-    """Both launches of drrt_target_rays.hip == the host build, bit for bit (non-finite values in the same places), with the
+    """Both target launches of drrt_ray_adjoints.hip == the host build, bit for bit (non-finite values in the same places), with the
     same statistics: plain and pair-copy gathers, with the forward's visit order, its own sort and none, XCD dispatch order
     on and off.  The forward kernel's record is the one the routine replayed."""
     from adjointnonlinearraytracing_amd import drrt
