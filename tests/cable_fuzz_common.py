@@ -1,5 +1,5 @@
 """What tests/test_cable_fuzz.py is built from: the configurations, the compared rays, the float64 referee and the ensemble
-of float32 runs of the three restatements of the fibre march (tests/cable_ad, tests/cable_opl_ad, tests/cable_field_ad), the
+of float32 runs of the three restatements of the fibre march (tests/cable_ad), the
 host build of the product's per-ray routines (hostcheck_lib, cable_integral_host) and the errors that go under the bound of
 tests/integral_fuzz_common.py.  A plain module: no fixtures, no tests.  Everything is computed once per seed or per
 (seed, routine) and handed out unchanged."""
@@ -7,16 +7,13 @@ import numpy as np
 import torch
 
 import cable_ad
-import cable_field_ad
+import cable_common as CC
 import cable_integral_host as H
-import cable_opl_ad
 import cases
 import hostcheck_lib as HC
-import test_cable_field as TF
-import test_cable_opl as TO
 from integral_fuzz_common import CAPS, FLOOR, MARGIN, bound      # noqa: F401 (MARGIN, FLOOR: the bound's own, re-exported)
+from cable_common import MAX_DROPPED      # noqa: F401 (the share test_cable_fuzz.py allows)
 from raygrad_common import TIE_TOL, rel_err
-from test_cable_raygrad import MAX_DROPPED
 
 LENGTHS = (2, 3, 5, 9, 17, 33, 64, 127, 200)      # profile samples, by seed % 9
 SHAPES = ("luneburg", "random", "rising", "wavy")  # profile shape, by seed % 4
@@ -46,7 +43,7 @@ ROUTINES = {
     "opl": (("prof",), ("dx", "dv", "dopl"), "opl", ("grad",), ("dL/dprofile",)),
     "field": (("prof", "field"), ("dx", "dv", "dtau"), "tau", ("grad", "grad_field"), ("dL/dprofile", "dL/dfield")),
 }
-MODES = {"rays": {"all": ()}, "opl": TO.MODES, "field": TF.MODES}      # routine -> {mode: the seeds it leaves out}
+MODES = {"rays": {"all": ()}, "opl": CC.OPL_MODES, "field": CC.FIELD_MODES}      # routine -> {mode: the seeds it leaves out}
 
 _configs, _bases, _inputs, _refs, _hosts = {}, {}, {}, {}, {}
 
@@ -73,10 +70,10 @@ def config(seed):
     step of 0.3 .. 3 radial samples, a length of 30 .. 120 steps (a ray at rest marches 4 length / ds <= 480 iterations), all
     rounded through float32; 400 rays drawn as cases.fuzz_cable_config draws them -- radii up to 1.2 of the fibre's, y from
     -0.1 to 1.1 of the length, 5 % with x == radius and 5 % with z == radius, its three fixed first rays, a quarter heading
-    towards -y -- the last 8 at rest, 6 of them inside the fibre; targets as tests/test_cable_raygrad.py::scene draws them
+    towards -y -- the last 8 at rest, 6 of them inside the fibre; targets as tests/cable_common.py::scene draws them
     (behind the start, near the path ahead, far beyond), the path ahead taken no longer than the ray needs to cross the
     fibre; the seeds (dx, dv, dopl, dtau) from a generator of this module's own, the second profile from
-    tests/test_cable_field.py::field_profile."""
+    tests/cable_common.py::field_profile."""
     if seed in _configs:
         return _configs[seed]
     rng = np.random.default_rng(5200 + seed)
@@ -131,7 +128,7 @@ def config(seed):
     off = rng.normal(0, 0.2 * radius, (n, 3)); off[:, 1] = 0.0
     tg[rest] = pos[rest] + off[rest]
     srng = np.random.default_rng(6100 + seed)
-    c = dict(seed=seed, rres=rres, shape=shape, prof=prof, field=TF.field_profile(rres, seed), radius=radius, length=length,
+    c = dict(seed=seed, rres=rres, shape=shape, prof=prof, field=CC.field_profile(rres, seed), radius=radius, length=length,
              ds=ds, pos=pos, vel=vel, tg=tg.astype(np.float32), rest=rest, close=close,
              beyond=np.hypot(pos[:, 0].astype(np.float64) - radius, pos[:, 2].astype(np.float64) - radius) > radius,
              back=vel[:, 1] < 0, on_axis=(pos[:, 0] == np.float32(radius)) | (pos[:, 2] == np.float32(radius)),
@@ -226,8 +223,8 @@ def _march(routine, prof, field, c, p, v, j):
     if routine == "rays":
         return cable_ad.trace_cable(prof, c["radius"], c["length"], p, v, j, c["ds"])
     if routine == "opl":
-        return cable_opl_ad.trace_cable_opl(prof, c["radius"], c["length"], p, v, j, c["ds"])
-    return cable_field_ad.trace_cable_field(prof, field, c["radius"], c["length"], p, v, j, c["ds"])
+        return cable_ad.trace_cable_opl(prof, c["radius"], c["length"], p, v, j, c["ds"])
+    return cable_ad.trace_cable_field(prof, field, c["radius"], c["length"], p, v, j, c["ds"])
 
 
 def _autograd(c, routine, j, compared, pos, vel, dtype):

@@ -505,9 +505,9 @@ def ray_adjoints_host():
     inputs are not stored (the scene builders are deterministic).  Every kind of ray the routines tell apart must be in
     the recorded set."""
     sys.path.insert(0, os.path.dirname(HERE))
+    import integral_common
     import integral_host as OH
-    import test_opl
-    import test_ray_adjoint_pin as P
+    import ray_pin_common as P
     out = {}
     seen = dict.fromkeys(("second-pass plane rays", "failed plane rays", "target records after the escape",
                           "rays with a free-flight prefix", "rays with e = 0 and a non-finite gradient"), 0)
@@ -520,7 +520,7 @@ def ray_adjoints_host():
         seen["target records after the escape"] += int((tg["jstar"] > tg["fwd"]).sum())
         for routine in ("pln", "sdf", "target", "target_nodd2"):
             assert (P.run(name, routine, "built")[0]["jstar"] == 0).any(), (name, routine, "no ray with jstar == 0")
-        s = test_opl.scene(name)
+        s = integral_common.scene(name)
         K = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])["steps"]
         o = P.run(name, "opl", "nonfinite")[0]                         # its steps: the reverse iterations, K - e
         seen["rays with a free-flight prefix"] += int(((o["steps"] > 0) & (o["steps"] < K)).sum())

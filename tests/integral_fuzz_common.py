@@ -1,21 +1,16 @@
 """What tests/test_integral_fuzz.py is built from: the configurations (cases.fuzz_config plus the second fields and the
 seeds on the integrals), the float64 and float32 torch.autograd runs of the four restatements (oracle/torch_ad.trace,
-tests/opl_ad, tests/field_ad, tests/emission_ad), the host build of the product's per-ray routines, the mask of compared rays
+tests/integral_ad), the host build of the product's per-ray routines, the mask of compared rays
 and the bound.  A plain module: no fixtures, no tests.  Everything is computed once per (seed, routine) and handed out
 unchanged."""
 import numpy as np
 import torch
 
 import cases
-import emission_ad
-import field_ad
 import hostcheck_lib as HC
-import integral_host as EH
-import integral_host as FH
+import integral_ad
+import integral_common as IC
 import integral_host as OH
-import opl_ad
-import test_field_integral as TF
-import test_opl as TO
 from oracle import torch_ad
 from raygrad_common import GRAD_TOL, TIE_TOL, rel_err
 
@@ -44,7 +39,7 @@ _configs, _masks, _ads, _hosts = {}, {}, {}, {}
 
 def config(seed):
     """cases.fuzz_config(seed) with what the integrals need, drawn from a generator of this module's own: the seeds on opl,
-    tau and rad, a second field, an emission and an absorption (tests/test_field_integral.py::make_field), the absorption
+    tau and rad, a second field, an emission and an absorption (tests/integral_common.py::make_field), the absorption
     scaled as tests/test_emission.py::_with_fields scales it (the largest tau of a ray that leaves the box is 5.5)."""
     if seed in _configs:
         return _configs[seed]
@@ -54,13 +49,13 @@ def config(seed):
     for key in ("dopl", "dtau", "drad"):
         c[key] = rng.normal(size=n).astype(np.float32)
     f_seed, e_seed, a_seed = (int(v) for v in rng.integers(0, 1 << 20, 3))
-    c["field"] = TF.make_field(c["rif"].shape, f_seed)
-    c["emission"] = TF.make_field(c["rif"].shape, e_seed)
-    unit = TF.make_field(c["rif"].shape, a_seed)
-    k = FH.trace_field(c["rif"], unit, c["res"], c["pos"], c["vel"], c["h"], c["ds"])
-    ok = k["steps"] < TO.max_steps_fwd(c["res"], c["h"], c["ds"])
+    c["field"] = IC.make_field(c["rif"].shape, f_seed)
+    c["emission"] = IC.make_field(c["rif"].shape, e_seed)
+    unit = IC.make_field(c["rif"].shape, a_seed)
+    k = OH.trace_field(c["rif"], unit, c["res"], c["pos"], c["vel"], c["h"], c["ds"])
+    ok = k["steps"] < IC.max_steps_fwd(c["res"], c["h"], c["ds"])
     c["absorption"] = (unit * (MAX_TAU / k["tau"][ok].max())).astype(np.float32)
-    assert n == 600 and TO.max_steps_fwd(c["res"], c["h"], c["ds"]) <= 164
+    assert n == 600 and IC.max_steps_fwd(c["res"], c["h"], c["ds"]) <= 164
     assert min(c[key].min() for key in ("field", "emission")) > 0.5 and c["absorption"].min() > 0
     _configs[seed] = c
     return c
@@ -74,25 +69,25 @@ def _march(routine, grids, p, v, h, ds):
     """-> the restatement's differentiable outputs, in the order of the routine's seeds."""
     if routine == "rays":
         return torch_ad.trace(*grids, p, v, h, ds)
-    fn = dict(opl=opl_ad.trace_opl, field=field_ad.trace_field, emission=emission_ad.trace_emission)[routine]
+    fn = dict(opl=integral_ad.trace_opl, field=integral_ad.trace_field, emission=integral_ad.trace_emission)[routine]
     return fn(*grids, p, v, h, ds)[:-1]
 
 
 def masks(oracle, seed):
     """-> dict(k, ms, compared, nonzero, failed, tau64): the host fp32 forward, the float64 tau of the absorption, and the
     rays that are tie-free for both the product and the yardstick: the fp32 host build and the fp64 oracle leave on the same
-    iteration with exit samples within TIE_TOL (tests/test_opl.py::reference), and so do the float32 and the float64 torch
+    iteration with exit samples within TIE_TOL (tests/integral_common.py::reference), and so do the float32 and the float64 torch
     runs.  `nonzero`: compared rays whose float64 opl is not zero (they sampled inside the box, so every integral of a
     positive field is non-zero)."""
     if seed in _masks:
         return _masks[seed]
     c = config(seed)
-    k, tie_prod, opl64, ms = TO.reference(oracle, c, ("integral_fuzz", seed))
+    k, tie_prod, opl64, ms = IC.reference(oracle, c, ("integral_fuzz", seed))
     with torch.no_grad():
-        lo, hi = (opl_ad.trace_opl(_T(c["rif"], dt), _T(c["pos"], dt), _T(c["vel"], dt), c["h"], c["ds"])
+        lo, hi = (integral_ad.trace_opl(_T(c["rif"], dt), _T(c["pos"], dt), _T(c["vel"], dt), c["h"], c["ds"])
                   for dt in (torch.float32, torch.float64))
-        tau64 = field_ad.trace_field(*(_T(c[key], torch.float64) for key in ("rif", "absorption", "pos", "vel")),
-                                     c["h"], c["ds"])[2].numpy()
+        tau64 = integral_ad.trace_field(*(_T(c[key], torch.float64) for key in ("rif", "absorption", "pos", "vel")),
+                                        c["h"], c["ds"])[2].numpy()
     ms_ad = int(4 * c["h"] * max(c["rif"].shape) / c["ds"])
     close = lambda a, b: (a.double() - b).abs().max(1).values <= TIE_TOL      # noqa: E731
     tie_ref = ((lo[3] < ms_ad) & (lo[3] == hi[3]) & close(lo[0], hi[0]) & close(lo[1], hi[1])).numpy()
@@ -152,8 +147,8 @@ def host_forward(c, routine):
     if routine == "opl":
         return OH.trace_opl(c["rif"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
     if routine == "field":
-        return FH.trace_field(c["rif"], c["field"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
-    return EH.trace_emission(c["rif"], c["emission"], c["absorption"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
+        return OH.trace_field(c["rif"], c["field"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
+    return OH.trace_emission(c["rif"], c["emission"], c["absorption"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
 
 
 def host_back(c, routine, k, seeds, mode="all", sel=slice(None), **kw):
@@ -166,8 +161,8 @@ def host_back(c, routine, k, seeds, mode="all", sel=slice(None), **kw):
     if routine == "opl":
         return OH.backtrace_opl(c["rif"], c["res"], *rays, *s, c["h"], c["ds"], **kw)
     if routine == "field":
-        return FH.backtrace_field(c["rif"], c["field"], c["res"], *rays, *s, c["h"], c["ds"], **kw)
-    return EH.backtrace_emission(c["rif"], c["emission"], c["absorption"], c["res"], *rays, k["tau"][sel], *s, c["h"],
+        return OH.backtrace_field(c["rif"], c["field"], c["res"], *rays, *s, c["h"], c["ds"], **kw)
+    return OH.backtrace_emission(c["rif"], c["emission"], c["absorption"], c["res"], *rays, k["tau"][sel], *s, c["h"],
                                  c["ds"], **kw)
 
 
@@ -221,3 +216,14 @@ def report(tag, rows):
         if not e_prod <= b:
             bad.append((name, e_prod, e_ref, b))
     return bad
+
+
+def _quiet_rays(c):
+    """(rays at rest outside the box, rays outside the box that point away from it), from the geometry alone; the far faces
+    with a margin, so that no rounding of (res - 1) h decides."""
+    ext = (np.array(c["res"], np.float64) - 1) * c["h"]
+    pos, vel = c["pos"].astype(np.float64), c["vel"].astype(np.float64)
+    below, above = pos < 0, pos > ext * (1 + 1e-6)
+    rest = ~vel.any(1) & (below | above).any(1)
+    away = ((below & (vel < 0)) | (above & (vel > 0))).any(1)
+    return rest, away

@@ -30,7 +30,7 @@ import numpy as np
 import pytest
 import torch
 
-import test_box_service as svc
+import box_common as svc
 
 pytestmark = pytest.mark.gpu
 

@@ -4,7 +4,7 @@ tracer.CableFieldTracerC).
 
 CPU tier: the host build of the product's two per-ray routines (tests/cable_integral_host, cable_trace_field_ray and
 cable_field_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through
-tests/cable_field_ad.trace_cable_field (cable_opl_ad.trace_cable_opl with acc += ds n_k a_k), on the scenes, ray sets and
+tests/cable_ad.trace_cable_field (cable_ad.trace_cable_opl with acc += ds n_k a_k), on the scenes, ray sets and
 tie-free mask of tests/test_cable_raygrad.py, within the bound of the integral fuzz suite (tests/integral_fuzz_common.py:
 FLOOR, MARGIN times the error of the same restatement run in float32, never above CAPS); closed forms, identities against
 the existing cable routines, the refusals of the two entry points, and a stand-alone sanitizer build of the two routines.
@@ -16,7 +16,6 @@ cable_trace_field_ray nor cable_field_backtrace_ray), the library has neither dr
 drrt_backtrace_cable_field_f32, _lib.PROF_NAMES_LATER has no ids 21 and 22, TracerC has no trace_cable_field and tracer no
 CableFieldTracerC, and there is no examples/fiber_group_delay_demo.py."""
 import ctypes as C
-import itertools
 import os
 import subprocess
 import sys
@@ -26,16 +25,14 @@ import pytest
 import torch
 
 import cable_ad
-import cable_field_ad
+from cable_common import ATOMIC_TOL, COMBOS, FIELD_MODES as MODES, field_profile
+import cable_common as CR
 import cable_integral_host as H
 import cases
 import hostcheck_lib as HC
-import test_cable_raygrad as CR
 from integral_fuzz_common import CAPS, FLOOR, bound
 from raygrad_common import TIE_TOL, _t, rel_err
 
-ATOMIC_TOL = 2e-5       # profile gradients, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
-MODES = {"all": (), "dtau": ("dx", "dv"), "rays": ("dtau",)}      # mode: the seeds it leaves out (null pointers / zeros)
 K_BLOCK = 256           # kBlock of csrc/drrt_march.h
 RAY_KEYS = ("pos", "vel", "tg", "dx", "dv", "dtau")
 
@@ -43,14 +40,8 @@ _refs = {}
 
 
 # ---- scenes and references ------------------------------------------------------------------------------------------
-def field_profile(rres, seed):
-    """The second profile: positive (0.25 .. 1.05), not monotone, of `rres` samples."""
-    rng = np.random.default_rng(7300 + seed)
-    return (0.6 + 0.3 * np.sin(7.0 * np.linspace(0, 1, rres) + seed) + 0.1 * rng.random(rres) - 0.05).astype(np.float32)
-
-
 def scene(name):
-    """tests/test_cable_raygrad.py::scene(name) with a second profile and a seed on tau from generators of this module's
+    """tests/cable_common.py::scene(name) with a second profile and a seed on tau from generators of this module's
     own."""
     s = CR._fuzz(int(name[4:])) if name.startswith("fuzz") else CR.scene(name)
     tag = sum(map(ord, name))
@@ -93,8 +84,8 @@ def _autograd(s, j, idx, seeds, dtype):
         return out
     prof, field = T(s["prof"]).requires_grad_(True), T(s["field"]).requires_grad_(True)
     p, v = T(s["pos"][idx]).requires_grad_(True), T(s["vel"][idx]).requires_grad_(True)
-    xt, vt, tau = cable_field_ad.trace_cable_field(prof, field, s["radius"], s["length"], p, v, j[idx].astype(np.int64),
-                                                   s["ds"])
+    xt, vt, tau = cable_ad.trace_cable_field(prof, field, s["radius"], s["length"], p, v, j[idx].astype(np.int64),
+                                             s["ds"])
     grads = {}
     for mode, left_out in MODES.items():
         L = sum((o * T(np.zeros_like(seeds[name][idx]) if name in left_out else seeds[name][idx])).sum()
@@ -258,7 +249,7 @@ def test_one_iteration_closed_form():
     f = lambda y: cable_ad.sample(P.detach(), s["radius"], y[None])[1][0]            # noqa: E731
     J = torch.autograd.functional.jacobian(f, x0.detach()).numpy()
     n0, ngn = cable_ad.sample(P, s["radius"], x0[None])
-    a0 = cable_field_ad.sample_field(A, s["radius"], x0[None])
+    a0 = cable_ad.sample_field(A, s["radius"], x0[None])
     mu = s["dv"][0].astype(np.float64) + ds * s["dx"][0]
     dtau = float(s["dtau"][0])
     term = dtau * ds * n0[0] * a0[0]
@@ -536,9 +527,6 @@ def _repeat(s, k, times):
         s2[key] = np.repeat(s[key], times, axis=0)
     k2 = {key: np.repeat(k[key], times, axis=0) for key in ("xt", "vt", "rec_steps")}
     return s2, k2
-
-
-COMBOS = [c for c in itertools.product((True, False), repeat=3) if any(c)]      # (want_rif, want_field, want_rays): seven
 
 
 def _check_adjoint(T, s, k, gpu, combo, modes):

@@ -6,7 +6,7 @@ beyond the radius (i0 == i1 == rres - 1, w0 from the clamped index), a tenth hav
 towards -y and the last 8 start from rest -- where the fixed scenes of tests/test_cable_raygrad.py have 65, 33 and 2 samples,
 falling or random profiles and ray sets built so that nothing awkward happens.
 
-Referee: float64 torch.autograd through tests/cable_ad, tests/cable_opl_ad and tests/cable_field_ad, the record's iteration j
+Referee: float64 torch.autograd through tests/cable_ad, the record's iteration j
 handed in.  A ray is compared when (1) the float32 and float64 restatement records agree within TIE_TOL, (2) the host build's
 record is within TIE_TOL of the float64 one, (3) no sample in front of its record lies within 0.02 radius of the axis without
 being on it, (4) its float64 ray gradient is at most 30 times its seed; the seeds of every other ray are zero on all sides.
@@ -62,13 +62,12 @@ import numpy as np
 import pytest
 import torch
 
+from cable_common import ATOMIC_TOL, COMBOS
+from cable_fuzz_common import LENGTHS, MODES, N_RAYS, ROUTINES, SEEDS, config
 import cable_fuzz_common as CF
 import cases
 import hostcheck_lib as HC
-from cable_fuzz_common import LENGTHS, MODES, N_RAYS, ROUTINES, SEEDS, config
 from raygrad_common import _t
-from test_cable_field import COMBOS
-from test_cable_opl import ATOMIC_TOL
 
 INTEGRALS = ("opl", "field")
 ADJOINTS = [(seed, routine, mode) for seed in SEEDS for routine in ROUTINES for mode in MODES[routine]]

@@ -2,7 +2,7 @@
 drrt_backtrace_cable_opl_f32, TracerC.trace_cable_opl / backtrace_cable_opl, tracer.CableOPLTracerC).
 
 CPU tier: the host build of the product's two per-ray routines (tests/cable_integral_host, cable_trace_opl_ray and
-cable_opl_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through tests/cable_opl_ad.trace_cable_opl
+cable_opl_backtrace_ray of csrc/drrt_device.h) against torch.autograd in float64 through tests/cable_ad.trace_cable_opl
 (cable_ad.trace_cable plus the latched sum, the record's iteration handed in), on the scenes, ray sets and tie-free mask of
 tests/test_cable_raygrad.py, within the bound of the integral fuzz suite (tests/integral_fuzz_common.py: FLOOR, MARGIN times
 the error of the same restatement run in float32, never above CAPS); closed forms, identities against the existing cable
@@ -24,16 +24,14 @@ import pytest
 import torch
 
 import cable_ad
-import cable_opl_ad
+from cable_common import ATOMIC_TOL, OPL_MODES as MODES
+import cable_common as CR
 import cable_integral_host as H
 import cases
 import hostcheck_lib as HC
-import test_cable_raygrad as CR
 from integral_fuzz_common import CAPS, FLOOR, bound
 from raygrad_common import TIE_TOL, _t, rel_err
 
-ATOMIC_TOL = 2e-5       # profile gradient, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
-MODES = {"all": (), "dopl": ("dx", "dv"), "rays": ("dopl",)}      # mode: the seeds it leaves out (null pointers / zeros)
 K_BLOCK = 256           # kBlock of csrc/drrt_march.h
 
 _refs = {}
@@ -41,7 +39,7 @@ _refs = {}
 
 # ---- scenes and references ------------------------------------------------------------------------------------------
 def scene(name):
-    """tests/test_cable_raygrad.py::scene(name) with a seed on opl from a generator of this module's own."""
+    """tests/cable_common.py::scene(name) with a seed on opl from a generator of this module's own."""
     s = CR._fuzz(int(name[4:])) if name.startswith("fuzz") else CR.scene(name)
     s["dopl"] = np.random.default_rng(4100 + sum(map(ord, name))).normal(size=len(s["pos"])).astype(np.float32)
     return s
@@ -69,7 +67,7 @@ def _autograd(s, j, idx, seeds, dtype):
         return out
     prof = T(s["prof"]).requires_grad_(True)
     p, v = T(s["pos"][idx]).requires_grad_(True), T(s["vel"][idx]).requires_grad_(True)
-    xt, vt, opl = cable_opl_ad.trace_cable_opl(prof, s["radius"], s["length"], p, v, j[idx].astype(np.int64), s["ds"])
+    xt, vt, opl = cable_ad.trace_cable_opl(prof, s["radius"], s["length"], p, v, j[idx].astype(np.int64), s["ds"])
     grads = {}
     for mode, left_out in MODES.items():
         L = sum((o * T(np.zeros_like(seeds[name][idx]) if name in left_out else seeds[name][idx])).sum()

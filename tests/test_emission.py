@@ -3,11 +3,11 @@ TracerC.trace_emission / backtrace_emission, tracer.EmissionTracerC.
 
 CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: exp_neg, trace_emission_ray
 and emission_backtrace_ray of csrc/drrt_device.h) against the product's own trace and trace_field_ray (bit for bit), against
-float64 torch.autograd through tests/emission_ad (tests/field_ad's loop with rad += exp(-tau) ds n e, then tau += ds n a) on
-the tie-free rays of tests/test_opl.py::reference, against closed forms, against field_backtrace_ray with drad = 0, in an
+float64 torch.autograd through tests/integral_ad (its one loop with rad += exp(-tau) ds n e, then tau += ds n a) on
+the tie-free rays of tests/integral_common.py::reference, against closed forms, against field_backtrace_ray with drad = 0, in an
 opaque medium, and the C ABI's argument checks.  GPU tier: the emission kernels of drrt_integral.hip against that host build, the
-autograd class end to end, its launches, and the demo.  The scenes, ray sets and the plane source are tests/test_opl.py's;
-the two fields of a scene are tests/test_field_integral.py::make_field with two different seeds, the absorption scaled so
+autograd class end to end, its launches, and the demo.  The scenes, ray sets and the plane source are tests/integral_common.py's;
+the two fields of a scene are tests/integral_common.py::make_field with two different seeds, the absorption scaled so
 that the largest optical depth of a ray that leaves the box is 5.5.
 
 On the parent commit every test here fails: tests/hostcheck/integral_rays.hip does not compile (no exp_neg, no
@@ -35,12 +35,10 @@ import pytest
 import torch
 
 import cases
-import emission_ad
 import hostcheck_lib as HC
-import integral_host as EH
-import integral_host as FH
-import test_field_integral as TF
-import test_opl as TO
+import integral_ad
+import integral_common as IC
+import integral_host as OH
 from raygrad_common import GRAD_TOL, SCENES, _t, rel_err
 
 # Relative error of exp_neg against float64 exp: 4 000 001 points over [-87, 87], 2 000 001 over [-1, 1], and every
@@ -58,11 +56,11 @@ RAD_TOL = 2e-6
 # box7x11x5_h05_multi with the seed on tau alone) and in the opaque medium (4.46e-6 and 4.41e-6), rounded up to one digit; may not exceed GRAD_TOL.
 EMIS_TOL = 2e-5
 ABSB_TOL = 2e-5
-GRID_TOL = TO.GRID_TOL  # dL/drif: the bar of tests/test_opl.py (2e-5)
+GRID_TOL = IC.GRID_TOL  # dL/drif: the bar of tests/test_opl.py (2e-5)
 assert RAD_TOL <= 1e-4 and EMIS_TOL <= GRAD_TOL and ABSB_TOL <= GRAD_TOL and GRID_TOL == 2e-5 and EXP_TOL == 1e-6
 ATOMIC_TOL = 2e-5       # grid gradients, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
-KINDS = TO.KINDS
-_bits = TO._bits
+KINDS = IC.KINDS
+_bits = IC._bits
 MODES = ("all", "noray", "drad", "dtau")      # which seeds are set: all four; rad and tau; rad alone; tau alone
 
 
@@ -70,10 +68,10 @@ MODES = ("all", "noray", "drad", "dtau")      # which seeds are set: all four; r
 def _with_fields(s, seed):
     """The emission and absorption of a case: make_field with two seeds, the absorption scaled (one fp32 factor, computed
     from the product's own trace_field of the unscaled field) so that the largest tau of a ray that leaves the box is 5.5."""
-    s["emission"] = TF.make_field(s["rif"].shape, seed)
-    unit = TF.make_field(s["rif"].shape, seed + 101)
-    k = FH.trace_field(s["rif"], unit, s["res"], s["pos"], s["vel"], s["h"], s["ds"])
-    ok = k["steps"] < TO.max_steps_fwd(s["res"], s["h"], s["ds"])
+    s["emission"] = IC.make_field(s["rif"].shape, seed)
+    unit = IC.make_field(s["rif"].shape, seed + 101)
+    k = OH.trace_field(s["rif"], unit, s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    ok = k["steps"] < IC.max_steps_fwd(s["res"], s["h"], s["ds"])
     s["absorption"] = (unit * (np.float32(5.5) / k["tau"][ok].max())).astype(np.float32)
     rng = np.random.default_rng(seed + 57)
     s["drad"] = s["dopl"]
@@ -86,10 +84,10 @@ _scenes = {}
 
 
 def scene(name):
-    """tests/test_opl.py's scene (<= 672 rays, not a multiple of 256, <= 128 iterations) with its two fields and seeds on
+    """tests/integral_common.py's scene (<= 672 rays, not a multiple of 256, <= 128 iterations) with its two fields and seeds on
     rad (the scene's seed on opl) and tau."""
     if name not in _scenes:
-        _scenes[name] = _with_fields(dict(TO.scene(name)), list(SCENES).index(name))
+        _scenes[name] = _with_fields(dict(IC.scene(name)), list(SCENES).index(name))
     return _scenes[name]
 
 
@@ -98,12 +96,12 @@ _planes = {}
 
 def plane_case(h=1.0):
     if h not in _planes:
-        _planes[h] = _with_fields(dict(TO._plane_case(h)), 7)
+        _planes[h] = _with_fields(dict(IC._plane_case(h)), 7)
     return _planes[h]
 
 
 def host_trace(s, absorption=None):
-    return EH.trace_emission(s["rif"], s["emission"], s["absorption"] if absorption is None else absorption, s["res"],
+    return OH.trace_emission(s["rif"], s["emission"], s["absorption"] if absorption is None else absorption, s["res"],
                              s["pos"], s["vel"], s["h"], s["ds"])
 
 
@@ -112,18 +110,18 @@ def _ad_forward(s, absorption=None, grad=False):
     ins = [T(s["rif"]), T(s["emission"]), T(s["absorption"] if absorption is None else absorption), T(s["pos"]), T(s["vel"])]
     if grad:
         ins = [t.requires_grad_(True) for t in ins]
-    return ins, emission_ad.trace_emission(*ins, s["h"], s["ds"])
+    return ins, integral_ad.trace_emission(*ins, s["h"], s["ds"])
 
 
 _refs = {}
 
 
 def reference(oracle, s, key):
-    """tests/test_opl.py::reference (host fp32 forward, fp64 forward, its tie-free mask) plus the host trace_emission and the
+    """tests/integral_common.py::reference (host fp32 forward, fp64 forward, its tie-free mask) plus the host trace_emission and the
     float64 rad and tau; once per `key`.  Asserts what the issue asks of the absorption: over the tie-free rays max tau in
     [1.5, 6] and at least 10 rays with exp(-tau) < 0.5 -- attenuation acts, and no T is at the clamp."""
     if key not in _refs:
-        _, tie_free, _, ms = TO.reference(oracle, s, key)
+        _, tie_free, _, ms = IC.reference(oracle, s, key)
         k = host_trace(s)
         with torch.no_grad():
             _, (_, _, rad64, tau64, _) = _ad_forward(s)
@@ -147,7 +145,7 @@ _ad = {}
 
 
 def autograd64(s, seeds, key=None):
-    """float64 torch.autograd of L = <dx, xt> + <dv, vt> + <drad, rad> + <dtau, tau> through emission_ad
+    """float64 torch.autograd of L = <dx, xt> + <dv, vt> + <drad, rad> + <dtau, tau> through integral_ad
     -> (dL/drif, dL/de, dL/da, dL/dpos, dL/dvel); kept under `key` for the tests that share it."""
     if key is not None and key in _ad:
         return _ad[key]
@@ -163,7 +161,7 @@ def autograd64(s, seeds, key=None):
 
 
 def host_back(s, k, dx, dv, drad, dtau, absorption=None, **kw):
-    return EH.backtrace_emission(s["rif"], s["emission"], s["absorption"] if absorption is None else absorption, s["res"],
+    return OH.backtrace_emission(s["rif"], s["emission"], s["absorption"] if absorption is None else absorption, s["res"],
                                  s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], k["tau"], dx, dv, drad, dtau, s["h"],
                                  s["ds"], **kw)
 
@@ -186,21 +184,21 @@ def test_exp_neg():
     t = np.concatenate([np.linspace(-87, 87, 4_000_001), np.linspace(-1, 1, 2_000_001)]).astype(np.float32)
     t = np.concatenate([t, _boundaries()])
     t = t[(t >= -87) & (t <= 87)]
-    y = EH.exp_neg(t)
+    y = OH.exp_neg(t)
     ref = np.exp(-t.astype(np.float64))
     err = np.abs(y.astype(np.float64) - ref) / ref
     print(f"exp_neg: {len(t)} points, max rel err {err.max():.3e} at t = {t[err.argmax()]:.6g}")
     assert len(t) > 6_000_000 and err.max() <= EXP_TOL
     tiny = np.float32(1.17549435e-38)
     assert (y >= tiny).all() and np.isfinite(y).all()                     # normal fp32 on both sides of the range
-    one = EH.exp_neg([0.0, -0.0])
+    one = OH.exp_neg([0.0, -0.0])
     assert np.array_equal(_bits(one), _bits(np.ones(2, np.float32)))
-    lo, hi = EH.exp_neg([87.0])[0], EH.exp_neg([-87.0])[0]
-    edge = EH.exp_neg([np.inf, 3e38, 100.0, 88.0, -np.inf, -3e38, -100.0, -88.0])
+    lo, hi = OH.exp_neg([87.0])[0], OH.exp_neg([-87.0])[0]
+    edge = OH.exp_neg([np.inf, 3e38, 100.0, 88.0, -np.inf, -3e38, -100.0, -88.0])
     assert np.array_equal(_bits(edge[:4]), _bits(np.full(4, lo))) and np.array_equal(_bits(edge[4:]), _bits(np.full(4, hi)))
     assert tiny <= lo < 2e-38 and 6e37 < hi < np.float32(3.4e38)
-    assert np.isnan(EH.exp_neg([np.nan, -np.nan])).all()
-    m = EH.exp_neg(np.linspace(-87, 87, 100_001))                          # monotone to rounding: no jump at a boundary
+    assert np.isnan(OH.exp_neg([np.nan, -np.nan])).all()
+    m = OH.exp_neg(np.linspace(-87, 87, 100_001))                          # monotone to rounding: no jump at a boundary
     assert (m[1:] <= m[:-1] * (1 + 4e-7)).all()
 
 
@@ -213,10 +211,10 @@ def test_forward_identities(name):
     t = HC.trace(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(_bits(k["xt"]), _bits(t["xt"])) and np.array_equal(_bits(k["vt"]), _bits(t["vt"]))
     assert np.array_equal(k["steps"].astype(np.int64), t["steps"].astype(np.int64)) and k["n_failed"] == t["n_failed"] > 0
-    fa = FH.trace_field(s["rif"], s["absorption"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    fa = OH.trace_field(s["rif"], s["absorption"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(_bits(k["tau"]), _bits(fa["tau"])) and fa["tau"].max() > 1.0
     k0 = host_trace(s, absorption=np.zeros_like(s["absorption"]))
-    fe = FH.trace_field(s["rif"], s["emission"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    fe = OH.trace_field(s["rif"], s["emission"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(_bits(k0["rad"]), _bits(fe["tau"])) and fe["tau"].max() > 1.0 and not k0["tau"].any()
     assert not np.array_equal(k["rad"], k0["rad"]) and (k["rad"] <= k0["rad"]).all()      # absorption only dims
 
@@ -300,7 +298,7 @@ def test_failed_and_never_entered_rays(oracle, name):
     assert never.sum() >= 10
     assert np.array_equal(_bits(r["dpos"][never]), _bits(s["dx"][never])) and np.array_equal(_bits(r["dvel"][never]), _bits(s["dv"][never]))
     q = failed | never
-    qr = EH.backtrace_emission(s["rif"], s["emission"], s["absorption"], s["res"], s["pos"][q], s["vel"][q], k["xt"][q],
+    qr = OH.backtrace_emission(s["rif"], s["emission"], s["absorption"], s["res"], s["pos"][q], s["vel"][q], k["xt"][q],
                                k["vt"][q], k["steps"][q], k["tau"][q], s["dx"][q], s["dv"][q], s["drad"][q], s["dtau"][q],
                                s["h"], s["ds"])
     assert qr["ray_steps"] == 0
@@ -310,8 +308,8 @@ def test_failed_and_never_entered_rays(oracle, name):
 
 
 # the dyadic rays of tests/test_field_integral.py::test_uniform_field_closed_form: the fp32 march is exact
-_RES, _H, _DS, _C, _POS, _VEL = TF._RES, TF._H, TF._DS, TF._C, TF._POS, TF._VEL
-_DRAD = TF._DTAU
+_RES, _H, _DS, _C, _POS, _VEL = IC._RES, IC._H, IC._DS, IC._C, IC._POS, IC._VEL
+_DRAD = IC._DTAU
 # measured on the host build: rad 1.2e-7, the three sums 2.8e-8 / 4.9e-9 / 3.2e-7 (e / a / rif); 4 x the largest, rounded up
 CLOSED_RTOL = 2e-6
 
@@ -325,9 +323,9 @@ def test_uniform_medium_closed_form():
     b, q = 0.75, 1.5
     rif = np.full((_RES[2], _RES[1], _RES[0]), _C, np.float32)
     absb, emis = np.full_like(rif, b), np.full_like(rif, q)
-    k = EH.trace_emission(rif, emis, absb, _RES, _POS, _VEL, _H, _DS)
-    m = np.array([int(x.sum()) for x in TF._in_box_samples(k["steps"])], np.float64)
-    assert (k["steps"] < TO.max_steps_fwd(_RES, _H, _DS)).all() and m.min() >= 2 and m.max() >= 12 and len(set(m)) >= 4
+    k = OH.trace_emission(rif, emis, absb, _RES, _POS, _VEL, _H, _DS)
+    m = np.array([int(x.sum()) for x in IC._in_box_samples(k["steps"])], np.float64)
+    assert (k["steps"] < IC.max_steps_fwd(_RES, _H, _DS)).all() and m.min() >= 2 and m.max() >= 12 and len(set(m)) >= 4
     w = _DS * _C
     r = np.exp(-w * b)
     S = (1 - r ** m) / (1 - r)
@@ -335,7 +333,7 @@ def test_uniform_medium_closed_form():
     exact = w * q * S
     rerr = np.abs(k["rad"] - exact) / exact
     assert k["tau"].max() > 4 and exact.max() / exact.min() > 1.5         # attenuation acts: S is far from m
-    g = EH.backtrace_emission(rif, emis, absb, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], k["tau"], None, None, _DRAD,
+    g = OH.backtrace_emission(rif, emis, absb, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], k["tau"], None, None, _DRAD,
                               None, _H, _DS)
     assert np.array_equal(g["steps"].astype(np.float64), m)
     d = _DRAD.astype(np.float64)
@@ -359,17 +357,17 @@ def test_linear_emission_closed_form():
     z, y, x = np.meshgrid(np.arange(_RES[2]), np.arange(_RES[1]), np.arange(_RES[0]), indexing="ij")
     emis = (e0 + g[0] * x + g[1] * y + g[2] * z).astype(np.float32)
     zero = np.zeros_like(rif)
-    k = EH.trace_emission(rif, emis, zero, _RES, _POS, _VEL, _H, _DS)
-    masks = TF._in_box_samples(k["steps"])
+    k = OH.trace_emission(rif, emis, zero, _RES, _POS, _VEL, _H, _DS)
+    masks = IC._in_box_samples(k["steps"])
     m = np.array([mm.sum() for mm in masks], np.float64)
     ksum = np.array([np.where(mm)[0].sum() for mm in masks], np.float64)
-    r = EH.backtrace_emission(rif, emis, zero, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], k["tau"], None, None, _DRAD,
+    r = OH.backtrace_emission(rif, emis, zero, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], k["tau"], None, None, _DRAD,
                               None, _H, _DS)
     d = _DRAD.astype(np.float64)
     np.testing.assert_allclose(r["dpos"], (d * _DS * _C * m)[:, None] * g[None, :], rtol=1e-5)
     np.testing.assert_allclose(r["dvel"], (d * _DS * _DS * _C * ksum)[:, None] * g[None, :], rtol=1e-5)
     assert np.abs(r["dpos"]).min() > 1e-2 and np.abs(r["dvel"]).min() > 1e-2
-    f = FH.backtrace_field(rif, emis, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DRAD, _H, _DS)
+    f = OH.backtrace_field(rif, emis, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DRAD, _H, _DS)
     np.testing.assert_allclose(r["dpos"], f["dpos"], rtol=1e-6)
     np.testing.assert_allclose(r["dvel"], f["dvel"], rtol=1e-6)
     np.testing.assert_allclose(r["grad_emission"].sum(), (d * _DS * _C * m).sum(), rtol=1e-6)
@@ -381,8 +379,8 @@ def test_consistent_with_field_integral(name):
     one bar of the same float64 result, hence two bars here; and dL/de is exactly zero."""
     s = scene(name)
     k = host_trace(s)
-    ok = k["steps"] < TO.max_steps_fwd(s["res"], s["h"], s["ds"])
-    f = FH.backtrace_field(s["rif"], s["absorption"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"],
+    ok = k["steps"] < IC.max_steps_fwd(s["res"], s["h"], s["ds"])
+    f = OH.backtrace_field(s["rif"], s["absorption"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"],
                            s["dv"], s["dtau"], s["h"], s["ds"])
     for drad in (None, np.zeros_like(s["drad"])):
         r = host_back(s, k, s["dx"], s["dv"], drad, s["dtau"])
@@ -519,7 +517,7 @@ def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan
     and run as a child process, nothing preloaded: scene 1 plus rays, seeds and values of both fields with NaN, Inf, huge,
     denormal and negative entries; exp_neg sees every seed on tau (NaN, +-Inf, +-3e38 among them)."""
-    exe = HC.sanitized_program(tmp_path, EH.SOURCE, "EMISSION_MAIN")
+    exe = HC.sanitized_program(tmp_path, OH.SOURCE, "EMISSION_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0, -2.5, -1e-40], np.float32)
@@ -545,7 +543,7 @@ def test_routines_under_sanitizers(tmp_path):
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-_same = TO._same
+_same = IC._same
 GRIDS = ("grad", "grad_emission", "grad_absorption")
 
 

@@ -3,10 +3,10 @@ backtrace_field, tracer.FieldIntegralTracerC.
 
 CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_field_ray and
 field_backtrace_ray of csrc/drrt_device.h) against the product's own trace and trace_opl_ray (bit for bit), against float64
-torch.autograd through tests/field_ad (tests/opl_ad's loop with tau += ds n a) on the tie-free rays of
-tests/test_opl.py::reference, against closed forms, against opl_backtrace_ray with field = rif, and the C ABI's argument
+torch.autograd through tests/integral_ad (its one loop with tau += ds n a) on the tie-free rays of
+tests/integral_common.py::reference, against closed forms, against opl_backtrace_ray with field = rif, and the C ABI's argument
 checks.  GPU tier: the field kernels of drrt_integral.hip against that host build, the autograd class end to end, its launches, and
-the demo.  The scenes, ray sets and the plane source are tests/test_opl.py's; the second field of a scene is seeded, smooth,
+the demo.  The scenes, ray sets and the plane source are tests/integral_common.py's; the second field of a scene is seeded, smooth,
 strictly positive and not symmetric under a permutation of the axes.
 
 On the parent commit every test here fails: tests/hostcheck/integral_rays.hip does not compile (no trace_field_ray), the
@@ -29,11 +29,11 @@ import pytest
 import torch
 
 import cases
-import field_ad
 import hostcheck_lib as HC
-import integral_host as FH
+import integral_ad
+import integral_common as IC
 import integral_host as OH
-import test_opl as TO
+from integral_common import _C, _DS, _DTAU, _H, _POS, _RES, _VEL, _in_box_samples, make_field
 from oracle import torch_ad
 from raygrad_common import GRAD_TOL, SCENES, _t, rel_err
 
@@ -47,31 +47,22 @@ TAU_TOL = 5e-6
 # lens16_h05_half, with and without seeds on the rays; 3.20e-6 on the plane source), rounded up to one digit; may not
 # exceed GRAD_TOL.
 FIELD_TOL = 2e-5
-GRID_TOL = TO.GRID_TOL  # dL/drif: the bar of tests/test_opl.py (2e-5)
+GRID_TOL = IC.GRID_TOL  # dL/drif: the bar of tests/test_opl.py (2e-5)
 assert TAU_TOL <= 1e-4 and FIELD_TOL <= GRAD_TOL and GRID_TOL == 2e-5
 ATOMIC_TOL = 2e-5       # grid gradients, kernel vs host build: only the order of the sums differs (tests/test_gpu_parity.py's bar)
-KINDS = TO.KINDS
-_bits = TO._bits
+KINDS = IC.KINDS
+_bits = IC._bits
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------
-def make_field(shape, seed):
-    """Seeded, fp32, smooth, >= 0.55: 1 + 0.4 (mean of sines of different periods and phases along the three axes) + 0.05
-    uniform noise.  Not symmetric under a permutation of the axes."""
-    D, H, W = shape
-    z, y, x = np.meshgrid(np.arange(D), np.arange(H), np.arange(W), indexing="ij")
-    s = (np.sin(0.9 * x + 0.3) + np.sin(0.5 * y + 1.1) + np.sin(1.3 * z + 2.0)) / 3.0
-    return (1.0 + 0.4 * s + 0.05 * np.random.default_rng(seed + 23).random(shape)).astype(np.float32)
-
-
 _scenes = {}
 
 
 def scene(name):
-    """tests/test_opl.py's scene (<= 672 rays, not a multiple of 256, <= 128 iterations) with its second field; the seed on
+    """tests/integral_common.py's scene (<= 672 rays, not a multiple of 256, <= 128 iterations) with its second field; the seed on
     opl serves as the seed on tau."""
     if name not in _scenes:
-        s = dict(TO.scene(name))
+        s = dict(IC.scene(name))
         s["field"] = make_field(s["rif"].shape, list(SCENES).index(name))
         s["dtau"] = s["dopl"]
         assert s["field"].min() > 0.5 and s["field"].dtype == np.float32
@@ -80,7 +71,7 @@ def scene(name):
 
 
 def plane_case(h=1.0):
-    s = dict(TO._plane_case(h))
+    s = dict(IC._plane_case(h))
     s["field"] = make_field(s["rif"].shape, 7)
     s["dtau"] = s["dopl"]
     return s
@@ -90,14 +81,14 @@ _refs = {}
 
 
 def reference(oracle, s, key):
-    """tests/test_opl.py::reference (host fp32 forward, fp64 forward, its tie-free mask) plus the host trace_field and the
+    """tests/integral_common.py::reference (host fp32 forward, fp64 forward, its tie-free mask) plus the host trace_field and the
     float64 tau; once per `key`."""
     if key not in _refs:
-        _, tie_free, _, ms = TO.reference(oracle, s, key)
-        k = FH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+        _, tie_free, _, ms = IC.reference(oracle, s, key)
+        k = OH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
         T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
         with torch.no_grad():
-            tau64 = field_ad.trace_field(T(s["rif"]), T(s["field"]), T(s["pos"]), T(s["vel"]), s["h"], s["ds"])[2].numpy()
+            tau64 = integral_ad.trace_field(T(s["rif"]), T(s["field"]), T(s["pos"]), T(s["vel"]), s["h"], s["ds"])[2].numpy()
         _refs[key] = (k, tie_free, tau64, ms)
     return _refs[key]
 
@@ -106,13 +97,13 @@ _ad = {}
 
 
 def autograd64(s, dx, dv, dtau, key=None):
-    """float64 torch.autograd of L = <dx, xt> + <dv, vt> + <dtau, tau> through field_ad
+    """float64 torch.autograd of L = <dx, xt> + <dv, vt> + <dtau, tau> through integral_ad
     -> (dL/drif, dL/dfield, dL/dpos, dL/dvel); kept under `key` for the tests that share it."""
     if key is not None and key in _ad:
         return _ad[key]
     T = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
     r, f, p, v = (T(s[k]).requires_grad_(True) for k in ("rif", "field", "pos", "vel"))
-    xt, vt, tau, _ = field_ad.trace_field(r, f, p, v, s["h"], s["ds"])
+    xt, vt, tau, _ = integral_ad.trace_field(r, f, p, v, s["h"], s["ds"])
     L = (xt * T(dx)).sum() + (vt * T(dv)).sum() + (tau * T(dtau)).sum()
     gr, gf, gp, gv = torch.autograd.grad(L, (r, f, p, v))
     out = gr.numpy().reshape(-1), gf.numpy().reshape(-1), gp.numpy(), gv.numpy()
@@ -122,7 +113,7 @@ def autograd64(s, dx, dv, dtau, key=None):
 
 
 def host_back(s, k, dx, dv, dtau, **kw):
-    return FH.backtrace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], dx, dv, dtau,
+    return OH.backtrace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], dx, dv, dtau,
                               s["h"], s["ds"], **kw)
 
 
@@ -131,7 +122,7 @@ def host_back(s, k, dx, dv, dtau, **kw):
 def test_forward_is_trace(name):
     """trace_field_ray's (xt, vt, steps, n_failed) == the product's trace_ray<0> (tests/hostcheck), bit for bit."""
     s = scene(name)
-    k = FH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    k = OH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     t = HC.trace(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(_bits(k["xt"]), _bits(t["xt"])) and np.array_equal(_bits(k["vt"]), _bits(t["vt"]))
     assert np.array_equal(k["steps"].astype(np.int64), t["steps"].astype(np.int64)) and k["n_failed"] == t["n_failed"] > 0
@@ -141,7 +132,7 @@ def test_forward_is_trace(name):
 def test_field_equal_to_rif_is_opl(name):
     """field = rif (the same values): tau == trace_opl_ray's opl, bit for bit."""
     s = scene(name)
-    k = FH.trace_field(s["rif"], s["rif"].copy(), s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    k = OH.trace_field(s["rif"], s["rif"].copy(), s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     o = OH.trace_opl(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
     assert np.array_equal(_bits(k["tau"]), _bits(o["opl"])) and np.abs(o["opl"]).max() > 1.0
     assert np.array_equal(_bits(k["xt"]), _bits(o["xt"])) and np.array_equal(k["steps"], o["steps"])
@@ -220,28 +211,11 @@ def test_failed_and_never_entered_rays(oracle, name):
     assert never.sum() >= 10
     assert np.array_equal(_bits(r["dpos"][never]), _bits(s["dx"][never])) and np.array_equal(_bits(r["dvel"][never]), _bits(s["dv"][never]))
     quiet = failed | never
-    q = FH.backtrace_field(s["rif"], s["field"], s["res"], s["pos"][quiet], s["vel"][quiet], k["xt"][quiet], k["vt"][quiet],
+    q = OH.backtrace_field(s["rif"], s["field"], s["res"], s["pos"][quiet], s["vel"][quiet], k["xt"][quiet], k["vt"][quiet],
                            k["steps"][quiet], s["dx"][quiet], s["dv"][quiet], s["dtau"][quiet], s["h"], s["ds"])
     assert not q["grad"].any() and not q["grad_field"].any() and q["ray_steps"] == 0
     assert np.abs(r["grad"]).max() > 0 and np.abs(r["grad_field"]).max() > 0
     assert r["ray_steps"] == int(r["steps"].astype(np.int64).sum()) > 0
-
-
-# the dyadic rays of tests/test_opl.py::test_uniform_medium_closed_form: the fp32 march is exact
-_RES, _H, _DS, _C = (9, 8, 7), 1.0, 0.5, 1.25
-_POS = np.array([(3.25, -1.25, 3.5), (0.0, 2.5, 1.125), (4.5, 3.5, 2.75), (-2.0, 3.0, 3.0), (7.875, 6.75, 5.5)], np.float32)
-_VEL = np.array([(0.25, 1.0, 0.125), (1.0, 0.0, 0.0), (-0.5, 0.25, 0.75), (1.0, 0.125, -0.25), (0.125, 0.125, 0.0625)], np.float32)
-_DTAU = np.array([0.7, -1.3, 0.4, 2.0, -0.6], np.float32)
-
-
-def _in_box_samples(steps):
-    """Per ray, the boolean mask over k < K of the samples x_k = p0 + k ds v0 that fall in the box (float64: exact here)."""
-    ext = np.array([_RES[0] - 1, _RES[1] - 1, _RES[2] - 1], np.float64) * _H
-    out = []
-    for i in range(len(_POS)):
-        x = _POS[i].astype(np.float64) + _DS * np.arange(int(steps[i]))[:, None] * _VEL[i].astype(np.float64)
-        out.append(((x >= 0) & (x < ext)).all(1))
-    return out
 
 
 def test_uniform_field_closed_form():
@@ -251,17 +225,17 @@ def test_uniform_field_closed_form():
     b = 0.75
     rif = np.full((_RES[2], _RES[1], _RES[0]), _C, np.float32)
     fld = np.full_like(rif, b)
-    k = FH.trace_field(rif, fld, _RES, _POS, _VEL, _H, _DS)
+    k = OH.trace_field(rif, fld, _RES, _POS, _VEL, _H, _DS)
     m = np.array([int(x.sum()) for x in _in_box_samples(k["steps"])], np.int64)
-    assert (k["steps"] < TO.max_steps_fwd(_RES, _H, _DS)).all() and m.min() >= 2 and m.max() >= 12 and len(set(m)) >= 4
+    assert (k["steps"] < IC.max_steps_fwd(_RES, _H, _DS)).all() and m.min() >= 2 and m.max() >= 12 and len(set(m)) >= 4
     exact = _DS * _C * b * m
     assert (np.abs(k["tau"].astype(np.float64) - exact) <= m * 2.0 ** -24 * exact).all(), (k["tau"], exact)
-    r = FH.backtrace_field(rif, fld, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DTAU, _H, _DS)
+    r = OH.backtrace_field(rif, fld, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DTAU, _H, _DS)
     assert np.array_equal(r["steps"].astype(np.int64), m)
     d = _DTAU.astype(np.float64)
     np.testing.assert_allclose(r["grad_field"].sum(), (d * _DS * _C * m).sum(), rtol=1e-6)
     np.testing.assert_allclose(r["grad"].sum(), (d * _DS * b * m).sum(), rtol=1e-6)
-    one = FH.backtrace_field(rif, fld, _RES, _POS[1:2], _VEL[1:2], k["xt"][1:2], k["vt"][1:2], k["steps"][1:2], None, None,
+    one = OH.backtrace_field(rif, fld, _RES, _POS[1:2], _VEL[1:2], k["xt"][1:2], k["vt"][1:2], k["steps"][1:2], None, None,
                              _DTAU[1:2], _H, _DS)
     np.testing.assert_allclose(one["grad_field"].sum(), d[1] * _DS * _C * m[1], rtol=1e-6)
     np.testing.assert_allclose(one["grad"].sum(), d[1] * _DS * b * m[1], rtol=1e-6)
@@ -279,7 +253,7 @@ def test_linear_field_closed_form():
     z, y, x = np.meshgrid(np.arange(_RES[2]), np.arange(_RES[1]), np.arange(_RES[0]), indexing="ij")
     fld = (a0 + g[0] * x + g[1] * y + g[2] * z).astype(np.float32)
     assert fld.min() > 0
-    k = FH.trace_field(rif, fld, _RES, _POS, _VEL, _H, _DS)
+    k = OH.trace_field(rif, fld, _RES, _POS, _VEL, _H, _DS)
     masks = _in_box_samples(k["steps"])
     m, ksum, tau = [], [], []
     for i, inb in enumerate(masks):
@@ -290,7 +264,7 @@ def test_linear_field_closed_form():
     m, ksum = np.array(m, np.float64), np.array(ksum, np.float64)
     assert (np.array([mm[0] for mm in masks]) == False).sum() >= 2 and ksum.max() > 50          # noqa: E712 (rays that start outside)
     np.testing.assert_allclose(k["tau"], tau, rtol=1e-6)
-    r = FH.backtrace_field(rif, fld, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DTAU, _H, _DS)
+    r = OH.backtrace_field(rif, fld, _RES, _POS, _VEL, k["xt"], k["vt"], k["steps"], None, None, _DTAU, _H, _DS)
     d = _DTAU.astype(np.float64)
     np.testing.assert_allclose(r["dpos"], (d * _DS * _C * m)[:, None] * g[None, :], rtol=1e-5)
     np.testing.assert_allclose(r["dvel"], (d * _DS * _DS * _C * ksum)[:, None] * g[None, :], rtol=1e-5)
@@ -306,11 +280,11 @@ def test_exit_on_first_iteration_closed_form():
     h, ds, res = 1.0, 0.5, (16, 16, 16)
     pos = np.array([[14.8, 7.3, 6.1]], np.float32)          # half a step from the far x face, heading out
     vel = np.array([[1.0, 0.1, -0.05]], np.float32)
-    k = FH.trace_field(rif, fld, res, pos, vel, h, ds)
+    k = OH.trace_field(rif, fld, res, pos, vel, h, ds)
     assert k["steps"][0] == 1
     dx = np.array([[0.3, -1.2, 0.7]], np.float32); dv = np.array([[-0.4, 0.9, 0.2]], np.float32)
     dtau = np.array([1.7], np.float32)
-    r = FH.backtrace_field(rif, fld, res, pos, vel, k["xt"], k["vt"], k["steps"], dx, dv, dtau, h, ds)
+    r = OH.backtrace_field(rif, fld, res, pos, vel, k["xt"], k["vt"], k["steps"], dx, dv, dtau, h, ds)
     R, F = torch.tensor(rif, dtype=torch.float64), torch.tensor(fld, dtype=torch.float64)
     x = torch.tensor(pos[0], dtype=torch.float64)
     inside = torch.tensor([True])
@@ -332,8 +306,8 @@ def test_consistent_with_opl(name):
     sides are within one bar (GRAD_TOL, GRID_TOL) of the same float64 result, hence two bars here."""
     s = dict(scene(name))
     s["field"] = s["rif"].copy()
-    k = FH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
-    ok = k["steps"] < TO.max_steps_fwd(s["res"], s["h"], s["ds"])
+    k = OH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+    ok = k["steps"] < IC.max_steps_fwd(s["res"], s["h"], s["ds"])
     r = host_back(s, k, s["dx"], s["dv"], s["dtau"])
     o = OH.backtrace_opl(s["rif"], s["res"], s["pos"], s["vel"], k["xt"], k["vt"], k["steps"], s["dx"], s["dv"], s["dtau"],
                          s["h"], s["ds"])
@@ -431,7 +405,7 @@ def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and
     run as a child process, nothing preloaded: scene 1 plus rays, seeds and field values with NaN, Inf, huge and denormal
     entries."""
-    exe = HC.sanitized_program(tmp_path, FH.SOURCE, "FIELD_MAIN")
+    exe = HC.sanitized_program(tmp_path, OH.SOURCE, "FIELD_MAIN")
     s = scene(list(SCENES)[1])
     rng = np.random.default_rng(0)
     bad = np.array([np.nan, np.inf, -np.inf, 3e38, -3e38, 1e30, 1e-40, 0.0], np.float32)
@@ -453,7 +427,7 @@ def test_routines_under_sanitizers(tmp_path):
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-_same = TO._same
+_same = IC._same
 
 
 def _gpu_forward(T, s, dev):
@@ -478,7 +452,7 @@ _hosts = {}
 def host(name):
     if name not in _hosts:
         s = scene(name)
-        k = FH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
+        k = OH.trace_field(s["rif"], s["field"], s["res"], s["pos"], s["vel"], s["h"], s["ds"])
         _hosts[name] = (k, host_back(s, k, s["dx"], s["dv"], s["dtau"], corrected_h=True))
     return _hosts[name]
 
@@ -593,7 +567,7 @@ def test_single_ray_and_no_rays(gpu):
         with drrt.using(corrected_h=True):
             fw = _gpu_forward(T, one, gpu)
             (grad, gfield, dpos, dvel), st = _gpu_back(T, one, gpu, fw)
-        k1 = FH.trace_field(one["rif"], one["field"], one["res"], one["pos"], one["vel"], one["h"], one["ds"])
+        k1 = OH.trace_field(one["rif"], one["field"], one["res"], one["pos"], one["vel"], one["h"], one["ds"])
         r1 = host_back(one, k1, one["dx"], one["dv"], one["dtau"], corrected_h=True)
         assert _same(fw[0], k1["xt"]) and _same(fw[1], k1["vt"]) and _same(fw[2], k1["tau"])
         assert np.array_equal(fw[3].cpu().numpy().astype(np.int64), k1["steps"].astype(np.int64))

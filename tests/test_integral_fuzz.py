@@ -6,9 +6,9 @@ rest and with |v| in 0.5..1.5 -- where the fixed scenes of tests/raygrad_common.
 and unit-speed rays.  What a configuration needs beyond fuzz_config (seeds on opl, tau and rad, the second field, emission and
 absorption) is drawn in tests/integral_fuzz_common.py.
 
-Referee: float64 torch.autograd through oracle/torch_ad.trace, tests/opl_ad, tests/field_ad, tests/emission_ad.  Yardstick: the
+Referee: float64 torch.autograd through oracle/torch_ad.trace, tests/integral_ad.  Yardstick: the
 same restatement run in float32.  A ray is compared when it is tie-free for the product (fp32 host build and fp64 oracle leave
-on the same iteration, exit samples within TIE_TOL: tests/test_opl.py::reference) and for the yardstick (the same between the
+on the same iteration, exit samples within TIE_TOL: tests/integral_common.py::reference) and for the yardstick (the same between the
 float32 and the float64 torch runs); the seeds of every other ray are zero on all sides.  For every output (largest relative
 error over the compared rays with a non-zero integral), for (dpos, dvel) (largest raygrad_common.rel_err over the compared
 rays) and for every grid gradient (rel-L2, flag on), with e_prod = product against float64 and e_ref = float32 run against
@@ -60,9 +60,9 @@ import pytest
 import torch
 
 import cases
+from integral_fuzz_common import MODES, ROUTINES, SEEDS, TWO_VOXEL, _quiet_rays, config
 import integral_fuzz_common as IF
-import integral_host as FH
-from integral_fuzz_common import MODES, ROUTINES, SEEDS, TWO_VOXEL, config
+import integral_host as OH
 from raygrad_common import _t
 
 ATOMIC_TOL = 2e-5       # grid gradients, kernel vs host build: only the order of the atomic sums differs
@@ -101,10 +101,10 @@ def test_forward_identities(seed):
         assert np.array_equal(_bits(k["xt"]), _bits(t["xt"])) and np.array_equal(_bits(k["vt"]), _bits(t["vt"])), routine
         assert np.array_equal(k["steps"].astype(np.int64), t["steps"].astype(np.int64)), routine
         assert k["n_failed"] == t["n_failed"] > 0, routine
-    fa = FH.trace_field(c["rif"], c["absorption"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
+    fa = OH.trace_field(c["rif"], c["absorption"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
     assert np.array_equal(_bits(fwd["emission"]["tau"]), _bits(fa["tau"])) and fa["tau"].max() > 1.0
     k0 = IF.host_forward(dict(c, absorption=np.zeros_like(c["absorption"])), "emission")
-    fe = FH.trace_field(c["rif"], c["emission"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
+    fe = OH.trace_field(c["rif"], c["emission"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
     assert np.array_equal(_bits(k0["rad"]), _bits(fe["tau"])) and fe["tau"].max() > 1.0 and not k0["tau"].any()
     assert not np.array_equal(fwd["emission"]["rad"], k0["rad"]) and (fwd["emission"]["rad"] <= k0["rad"]).all()
 
@@ -173,17 +173,6 @@ def test_flag_off_scales_the_gradient_splat(seed, routine):
     assert np.array_equal(_bits(off["dpos"]), _bits(on["dpos"])) and np.array_equal(_bits(off["dvel"]), _bits(on["dvel"]))
 
 
-def _quiet_rays(c):
-    """(rays at rest outside the box, rays outside the box that point away from it), from the geometry alone; the far faces
-    with a margin, so that no rounding of (res - 1) h decides."""
-    ext = (np.array(c["res"], np.float64) - 1) * c["h"]
-    pos, vel = c["pos"].astype(np.float64), c["vel"].astype(np.float64)
-    below, above = pos < 0, pos > ext * (1 + 1e-6)
-    rest = ~vel.any(1) & (below | above).any(1)
-    away = ((below & (vel < 0)) | (above & (vel > 0))).any(1)
-    return rest, away
-
-
 @pytest.mark.parametrize("routine", list(ROUTINES))
 @pytest.mark.parametrize("seed", SEEDS)
 def test_failed_and_never_entered_rays(seed, routine):
@@ -193,7 +182,7 @@ def test_failed_and_never_entered_rays(seed, routine):
     k = IF.host_forward(c, routine)
     kw = {} if routine == "rays" else dict(corrected_h=True)
     r = IF.host_back(c, routine, k, c, **kw)
-    failed = k["steps"] >= IF.TO.max_steps_fwd(c["res"], c["h"], c["ds"])
+    failed = k["steps"] >= IF.IC.max_steps_fwd(c["res"], c["h"], c["ds"])
     rest, away = _quiet_rays(c)
     assert rest.sum() >= 1 and away.sum() >= 40 and failed[rest].all() and not failed[away].any()
     assert r["n_failed"] == int(failed.sum()) == k["n_failed"]

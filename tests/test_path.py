@@ -2,11 +2,11 @@
 
 CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_path_ray and
 path_backtrace_ray of csrc/drrt_device.h) against the product's own trace and opl adjoint (bit for bit), against float64
-torch.autograd through tests/path_ad (tests/opl_ad's loop, recording x where the product does) on the compared rays, against
+torch.autograd through tests/integral_ad (its one loop, recording x where the product does) on the compared rays, against
 closed forms, and the C ABI's argument checks.  GPU tier: k_trace_path / k_backtrace_path of drrt_integral.hip against that
 host build, the autograd class end to end, its launches, and the demo.
 
-The referee (`referee`, shared with tests/test_path_fuzz.py): L = <dx, xt> + <dv, vt> + <dpath, path> through path_ad in
+The referee (`referee`, shared with tests/test_path_fuzz.py): L = <dx, xt> + <dv, vt> + <dpath, path> through integral_ad in
 float64, and once more in float32 as the yardstick.  A ray is compared when it is tie-free for the product and for the
 yardstick (tests/integral_fuzz_common.py::masks); the seeds of every other ray are zero on all sides.  With e_prod the host
 build against float64 and e_ref the float32 run against float64, measured the same way, the gradients are bounded by
@@ -38,57 +38,15 @@ import torch
 
 import cases
 import hostcheck_lib as HC
+import integral_ad
+import integral_common as IC
+from integral_common import ATOMIC_TOL, _same, scene
+from integral_fuzz_common import CAPS
 import integral_host as OH
-import opl_ad
-import path_ad
-import integral_host as PH
-import test_opl as TO
-from integral_fuzz_common import CAPS, FLOOR, bound
 from oracle import torch_ad
-from raygrad_common import SCENES, TIE_TOL, _t, rel_err
-from test_opl import ATOMIC_TOL, max_steps_fwd, scene
-
-MODES = ("all", "noray", "prefix", "inbox", "padded")
-STRIDES = (1, 5)
-_bits = lambda a: np.ascontiguousarray(a).view(np.uint32)      # noqa: E731
-
-
-def pad_m(ms, stride):
-    """The smallest M that always ends on xt (the Python surface's default)."""
-    return -(-ms // stride) + 1
-
-
-def trunc_m(ms, stride):
-    """An M that cuts every ray that crosses the box: a crossing takes about max_steps / 4 iterations."""
-    return ms // (8 * stride) + 2
-
-
-def count_of(steps, stride, M):
-    return np.minimum(M, -(-steps.astype(np.int64) // stride)).astype(np.int64)
-
-
-def fwd(s, stride, M):
-    return PH.trace_path(s["rif"], s["res"], s["pos"], s["vel"], s["h"], s["ds"], stride, M)
-
-
-def back(s, k, dx, dv, dpath, stride, M, sel=slice(None), **kw):
-    cut = lambda a: None if a is None else a[sel]      # noqa: E731
-    return PH.backtrace_path(s["rif"], s["res"], s["pos"][sel], s["vel"][sel], k["xt"][sel], k["vt"][sel], k["steps"][sel],
-                             cut(dx), cut(dv), None if dpath is None else dpath[:, sel], s["h"], s["ds"], stride, M, **kw)
-
-
-def dpath_of(shape, seed):
-    return np.random.default_rng(seed + 4200).normal(size=shape).astype(np.float32)
-
-
-def classes(k, r, stride, M):
-    """(prefix, inbox, padded) masks of shape (M, n) from the host forward `k` and a host adjoint `r` of it (whose reverse
-    iteration counts give the free-flight prefix e = K - steps of every ray that did not fail)."""
-    K = k["steps"].astype(np.int64)
-    e = K - r["steps"].astype(np.int64)
-    idx = (np.arange(M, dtype=np.int64) * stride)[:, None]
-    sample = np.arange(M)[:, None] < k["count"][None, :]
-    return sample & (idx <= e[None, :]), sample & (idx > e[None, :]), ~sample
+from path_common import (STRIDES, _bits, _forward_matches, _gpu_back, _gpu_forward, back, count_of, dpath_of, fwd, pad_m, referee,
+                         trunc_m)
+from raygrad_common import SCENES, TIE_TOL, _t, max_steps_fwd, rel_err
 
 
 # ---- the referee ------------------------------------------------------------------------------------------------------
@@ -97,7 +55,7 @@ def tie_free_for_yardstick(c):
     (tests/integral_fuzz_common.py::masks)."""
     T = lambda a, dt: torch.tensor(np.asarray(a), dtype=dt)      # noqa: E731
     with torch.no_grad():
-        lo, hi = (opl_ad.trace_opl(T(c["rif"], dt), T(c["pos"], dt), T(c["vel"], dt), c["h"], c["ds"])
+        lo, hi = (integral_ad.trace_opl(T(c["rif"], dt), T(c["pos"], dt), T(c["vel"], dt), c["h"], c["ds"])
                   for dt in (torch.float32, torch.float64))
     ms_ad = int(4 * c["h"] * max(c["rif"].shape) / c["ds"])
     close = lambda a, b: (a.double() - b).abs().max(1).values <= TIE_TOL      # noqa: E731
@@ -108,72 +66,11 @@ _compared = {}
 
 
 def compared_rays(oracle, name):
-    """The fixed scene's compared rays: tie-free for the product (tests/test_opl.py::reference) and for the yardstick."""
+    """The fixed scene's compared rays: tie-free for the product (tests/integral_common.py::reference) and for the yardstick."""
     if name not in _compared:
         s = scene(name)
-        _compared[name] = TO.reference(oracle, s, name)[1] & tie_free_for_yardstick(s)
+        _compared[name] = IC.reference(oracle, s, name)[1] & tie_free_for_yardstick(s)
     return _compared[name]
-
-
-def referee(c, compared, stride, M, tag, modes=MODES):
-    """The host build against float64 autograd under the bound float32 autograd sets, on the configuration `c`, for every
-    mode -> (largest e_prod / max(e_ref, FLOOR) over the gradients, the rows that miss their bound, {mode: |seeds|_1}).
-    One forward per dtype; the host forward's count and steps must be the float64 run's on the compared rays."""
-    k = fwd(c, stride, M)
-    ms = max_steps_fwd(c["res"], c["h"], c["ds"])
-    idx = np.nonzero(compared)[0]
-    n = len(c["pos"])
-    base = dpath_of((M, n, 3), stride * 1000 + M)
-    pre, box, pad = classes(k, back(c, k, None, None, None, stride, M), stride, M)
-    keep = {"all": np.ones((M, n), bool), "noray": np.ones((M, n), bool), "prefix": pre, "inbox": box, "padded": pad}
-    edge = max((r - 1) * c["h"] for r in c["res"])
-    runs = {}
-    for dt in (torch.float64, torch.float32):
-        T = lambda a: torch.tensor(np.asarray(a), dtype=dt)      # noqa: E731
-        leaves = [T(c["rif"]).requires_grad_(True), T(c["pos"][idx]).requires_grad_(True), T(c["vel"][idx]).requires_grad_(True)]
-        runs[dt] = (leaves, path_ad.trace_path(*leaves, c["h"], c["ds"], stride, M), T)
-    hi, lo = runs[torch.float64][1], runs[torch.float32][1]
-    assert np.array_equal(hi[4].numpy(), k["steps"][idx].astype(np.int64)) and np.array_equal(lo[4].numpy(), hi[4].numpy())
-    assert np.array_equal(hi[3].numpy(), k["count"][idx]) and np.array_equal(k["count"], count_of(k["steps"], stride, M))
-    p64 = hi[2].detach().numpy()
-    e_path = float(np.abs(k["path"][:, idx].astype(np.float64) - p64).max() / edge)
-    e_path_ref = float(np.abs(lo[2].detach().numpy().astype(np.float64) - p64).max() / edge)
-    print(f"{tag} path: e_prod {e_path:.3e} e_ref {e_path_ref:.3e} ratio {e_path / max(e_path_ref, FLOOR):.2f} cap {CAPS['out']:.1e}")
-    bad = [] if e_path <= CAPS["out"] else [("path", e_path, e_path_ref, CAPS["out"])]
-    worst, weight = 0.0, {}
-    for mode in modes:
-        z = compared[:, None] if mode == "all" else np.zeros((n, 1), bool)
-        dx, dv = (c["dx"] * z).astype(np.float32), (c["dv"] * z).astype(np.float32)
-        dpath = (base * (keep[mode] & compared[None, :])[:, :, None]).astype(np.float32)
-        weight[mode] = float(np.abs(dpath).sum())
-        r = back(c, k, dx if mode == "all" else None, dv if mode == "all" else None, dpath, stride, M, corrected_h=True)
-        g = {}
-        for dt, (leaves, out, T) in runs.items():
-            L = (out[0] * T(dx[idx])).sum() + (out[1] * T(dv[idx])).sum() + (out[2] * T(dpath[:, idx])).sum()
-            gr, gp, gv = torch.autograd.grad(L, leaves, retain_graph=True, allow_unused=True)
-            rows_ = []
-            for a in (gp, gv):                                             # only the compared rays are marched
-                rows_.append(np.zeros((n, 3)))
-                if a is not None:
-                    rows_[-1][idx] = a.numpy()
-            g[dt] = (np.zeros(c["rif"].size) if gr is None else gr.numpy().reshape(-1), *rows_)
-        (gr64, gp64, gv64), (gr32, gp32, gv32) = g[torch.float64], g[torch.float32]
-        rows = [("rays", float(rel_err(r["dpos"], r["dvel"], gp64, gv64)[compared].max()),
-                 float(rel_err(gp32, gv32, gp64, gv64)[compared].max()), CAPS["rays"])]
-        if np.linalg.norm(gr64) > 0:
-            rows.append(("dL/drif", cases.rel_l2(r["grad"], gr64), cases.rel_l2(gr32, gr64), CAPS["grid"]))
-        else:
-            assert not r["grad"].any()
-        for name, e_prod, e_ref, cap in rows:
-            b = bound(e_ref, cap)
-            ratio = e_prod / max(e_ref, FLOOR)
-            worst = max(worst, ratio)
-            print(f"{tag} seeds={mode} {name}: e_prod {e_prod:.3e} e_ref {e_ref:.3e} ratio {ratio:.2f} bound {b:.3e}")
-            if not e_prod <= b:
-                bad.append((mode, name, e_prod, e_ref, b))
-        assert r["n_failed"] == int((k["steps"] >= ms).sum()) == k["n_failed"]
-    print(f"{tag}: largest ratio to the yardstick {worst:.2f}")
-    return worst, bad, weight
 
 
 # ---- CPU tier -------------------------------------------------------------------------------------------------------
@@ -441,7 +338,7 @@ def test_routines_under_sanitizers(tmp_path):
     """tests/hostcheck/integral_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan and run
     as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries, with a
     stride above every K, with M = 1, and with zero rays."""
-    exe = HC.sanitized_program(tmp_path, PH.SOURCE, "PATH_MAIN")
+    exe = HC.sanitized_program(tmp_path, OH.SOURCE, "PATH_MAIN")
     s = scene(list(SCENES)[1])
     ms = max_steps_fwd(s["res"], s["h"], s["ds"])
     rng = np.random.default_rng(0)
@@ -465,26 +362,6 @@ def test_routines_under_sanitizers(tmp_path):
 
 
 # ---- GPU tier -------------------------------------------------------------------------------------------------------
-def _same(got, want):
-    got = got.cpu().numpy()
-    return np.array_equal(np.isfinite(got), np.isfinite(want)) and np.array_equal(got, want, equal_nan=True)
-
-
-def _gpu_forward(T, s, dev, stride, M):
-    from adjointnonlinearraytracing_amd import drrt
-    out = T.trace_path(_t(s["rif"], dev), s["res"], _t(s["pos"], dev), _t(s["vel"], dev), s["h"], s["ds"], stride, M)
-    return out, drrt.read_stats(), drrt.keep_order(drrt.last_order)
-
-
-def _gpu_back(T, s, dev, out, stride, dpath, order=None, dx="dx", dv="dv", **kw):
-    from adjointnonlinearraytracing_amd import drrt
-    xt, vt, _, _, steps = out
-    seed = lambda k: None if k is None else _t(s[k], dev)      # noqa: E731
-    res = T.backtrace_path(_t(s["rif"], dev), s["res"], _t(s["pos"], dev), _t(s["vel"], dev), xt, vt, steps, seed(dx), seed(dv),
-                           None if dpath is None else _t(dpath, dev), s["h"], s["ds"], stride, order=order, **kw)
-    return res, drrt.read_stats()
-
-
 _hosts = {}
 
 
@@ -496,14 +373,6 @@ def host(name, stride, M):
         g = dpath_of(k["path"].shape, stride + M)
         _hosts[name, stride, M] = (k, g, back(s, k, s["dx"], s["dv"], g, stride, M, corrected_h=True))
     return _hosts[name, stride, M]
-
-
-def _forward_matches(out, st, k):
-    xt, vt, path, count, steps = out
-    assert _same(xt, k["xt"]) and _same(vt, k["vt"]) and _same(path, k["path"])
-    assert count.dtype == torch.int32 and np.array_equal(count.cpu().numpy(), k["count"])
-    assert np.array_equal(steps.cpu().numpy().astype(np.int64), k["steps"].astype(np.int64))
-    assert st["n_failed"] == k["n_failed"] and st["ray_steps"] == int(k["steps"].astype(np.int64).sum())
 
 
 @pytest.mark.gpu
@@ -625,13 +494,13 @@ def _ad_grads(s, dev, stride, M, seeds, rif_grad=True, x_grad=True, v_grad=True,
 @pytest.mark.gpu
 def test_path_tracer_end_to_end(gpu, oracle):
     """PathTracerC.apply -> loss on xt, vt and path -> backward against float64 autograd on the compared rays of the plane
-    source (tests/test_opl.py::_plane_case), under the bound of the CPU tier; a loss on path alone; only what is asked for
+    source (tests/integral_common.py::_plane_case), under the bound of the CPU tier; a loss on path alone; only what is asked for
     comes back; the forward's options reach the backward launch."""
     from adjointnonlinearraytracing_amd import drrt
-    s = TO._plane_case()
+    s = IC._plane_case()
     stride = 5
     M = pad_m(max_steps_fwd(s["res"], s["h"], s["ds"]), stride)
-    cmp_ = TO.reference(oracle, s, "plane12")[1] & tie_free_for_yardstick(s)
+    cmp_ = IC.reference(oracle, s, "plane12")[1] & tie_free_for_yardstick(s)
     assert cmp_.sum() >= 120
     k = fwd(s, stride, M)
     g = dpath_of(k["path"].shape, 9) * cmp_[None, :, None]
@@ -640,7 +509,7 @@ def test_path_tracer_end_to_end(gpu, oracle):
 
     def autograd64(c, sd):
         r, p, v = (T64(c[q]).requires_grad_(True) for q in ("rif", "pos", "vel"))
-        out = path_ad.trace_path(r, p, v, c["h"], c["ds"], stride, M)
+        out = integral_ad.trace_path(r, p, v, c["h"], c["ds"], stride, M)
         L = sum((o * T64(w)).sum() for o, w in zip(out, sd) if w is not None)
         gr, gp, gv = torch.autograd.grad(L, (r, p, v))
         return gr.numpy().reshape(-1), gp.numpy(), gv.numpy()
@@ -664,7 +533,7 @@ def test_path_tracer_end_to_end(gpu, oracle):
             _ad_grads(s, gpu, stride, M, seeds, True, True, False, dtype=torch.float64)
         dflt = _ad_grads(s, gpu, stride, None, (None, None, None), False, False, False)[3]
         assert dflt[2].shape[0] == M
-    s2 = TO._plane_case(h=0.5)
+    s2 = IC._plane_case(h=0.5)
     gr2 = autograd64(s2, seeds)[0]
     with drrt.using(corrected_h=True):
         on = _ad_grads(s2, gpu, stride, M, seeds)[0].cpu().numpy()
@@ -678,7 +547,7 @@ def test_path_tracer_launches(gpu):
     """Forward: ["trace_path"].  Backward: ONE backtrace_path launch, plus the zero-fill when rif requires grad; none when
     nothing requires grad."""
     from adjointnonlinearraytracing_amd import _lib, drrt
-    s = TO._plane_case()
+    s = IC._plane_case()
     stride = 5
     M = pad_m(max_steps_fwd(s["res"], s["h"], s["ds"]), stride)
     seeds = (s["dx"], s["dv"], dpath_of((M, len(s["pos"]), 3), 3))

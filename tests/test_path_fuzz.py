@@ -3,7 +3,7 @@ cases.fuzz_config(seed), seed in range(16) (non-cubic grids of 2..24 voxels per 
 never a power of two, steps of 0.2..1.7 cells, rough media on seed % 3 == 0, 600 rays inside, outside and exactly on faces, at
 rest and off unit speed).
 
-Referee, yardstick, compared rays, bound: tests/test_path.py::referee with integral_fuzz_common.masks(oracle, seed)["compared"]
+Referee, yardstick, compared rays, bound: tests/path_common.py::referee with integral_fuzz_common.masks(oracle, seed)["compared"]
 unchanged -- that set depends only on the forward march, which this operator shares -- and MARGIN, FLOOR, CAPS and bound() of
 tests/integral_fuzz_common.py.  Strides 1 and 5, an M that pads and an M that truncates, every mode of test_path.MODES.
 
@@ -18,10 +18,11 @@ import pytest
 
 import cases
 import hostcheck_lib as HC
-import integral_fuzz_common as IF
-import test_path as TP
 from integral_fuzz_common import SEEDS, config
-from test_opl import ATOMIC_TOL, max_steps_fwd
+import integral_fuzz_common as IF
+from integral_common import ATOMIC_TOL, _same
+import path_common as PC
+from raygrad_common import max_steps_fwd
 
 _bits = lambda a: np.ascontiguousarray(a).view(np.uint32)      # noqa: E731
 
@@ -34,25 +35,25 @@ def test_forward_identities(seed):
     c = config(seed)
     ms = max_steps_fwd(c["res"], c["h"], c["ds"])
     t = HC.trace(c["rif"], c["res"], c["pos"], c["vel"], c["h"], c["ds"])
-    one = TP.fwd(c, 1, TP.pad_m(ms, 1))
-    for stride in TP.STRIDES:
-        M = TP.pad_m(ms, stride)
-        k = one if stride == 1 else TP.fwd(c, stride, M)
+    one = PC.fwd(c, 1, PC.pad_m(ms, 1))
+    for stride in PC.STRIDES:
+        M = PC.pad_m(ms, stride)
+        k = one if stride == 1 else PC.fwd(c, stride, M)
         assert np.array_equal(_bits(k["xt"]), _bits(t["xt"])) and np.array_equal(_bits(k["vt"]), _bits(t["vt"]))
         assert np.array_equal(k["steps"].astype(np.int64), t["steps"].astype(np.int64)) and k["n_failed"] == t["n_failed"] > 0
-        cnt = TP.count_of(k["steps"], stride, M)
+        cnt = PC.count_of(k["steps"], stride, M)
         assert np.array_equal(k["count"], cnt) and np.array_equal(_bits(k["path"][0]), _bits(c["pos"]))
         padded = np.arange(M)[:, None] >= cnt[None, :]
         assert np.array_equal(_bits(k["path"])[padded], _bits(np.broadcast_to(k["xt"], k["path"].shape))[padded])
         rows = one["path"][::stride][:M]
         sample = ~padded[:len(rows)]
         assert np.array_equal(_bits(k["path"][:len(rows)])[sample], _bits(rows)[sample])
-        cut = TP.fwd(c, stride, 3)
+        cut = PC.fwd(c, stride, 3)
         assert np.array_equal(_bits(cut["path"][:min(M, 3)]), _bits(k["path"][:3])) and np.array_equal(cut["count"], np.minimum(cnt, 3))
 
 
 @pytest.mark.parametrize("kind", ["pad", "trunc"])
-@pytest.mark.parametrize("stride", TP.STRIDES)
+@pytest.mark.parametrize("stride", PC.STRIDES)
 @pytest.mark.parametrize("seed", SEEDS)
 def test_referee(oracle, seed, stride, kind):
     """Forward and adjoint of the host build against float64 autograd of L = <dx, xt> + <dv, vt> + <dpath, path> under the
@@ -60,8 +61,8 @@ def test_referee(oracle, seed, stride, kind):
     c, m = config(seed), IF.masks(oracle, seed)
     assert m["compared"].sum() >= 0.85 * 600 and m["nonzero"].sum() >= 250
     ms = max_steps_fwd(c["res"], c["h"], c["ds"])
-    M = TP.pad_m(ms, stride) if kind == "pad" else TP.trunc_m(ms, stride)
-    worst, bad, weight = TP.referee(c, m["compared"], stride, M, f"seed {seed} stride={stride} M={M}")
+    M = PC.pad_m(ms, stride) if kind == "pad" else PC.trunc_m(ms, stride)
+    worst, bad, weight = PC.referee(c, m["compared"], stride, M, f"seed {seed} stride={stride} M={M}")
     assert bad == []
     # every class of seed is there; at stride 5 a configuration of few, long steps (seed 14) has no in-box sample to seed
     assert min(weight[mode] for mode in ("all", "noray", "prefix", "padded")) > 0 and (weight["inbox"] > 0 or stride > 1)
@@ -81,18 +82,18 @@ def test_kernels_match_host_build(gpu, seed, pair):
     T = drrt.TracerC()
     fwd_sorts = seed % 2 == 0
     stride = 5
-    for M in (TP.pad_m(ms, stride), TP.trunc_m(ms, stride)):
-        k = TP.fwd(c, stride, M)
-        g = TP.dpath_of(k["path"].shape, seed)
-        r = TP.back(c, k, c["dx"], c["dv"], g, stride, M, corrected_h=True)
+    for M in (PC.pad_m(ms, stride), PC.trunc_m(ms, stride)):
+        k = PC.fwd(c, stride, M)
+        g = PC.dpath_of(k["path"].shape, seed)
+        r = PC.back(c, k, c["dx"], c["dv"], g, stride, M, corrected_h=True)
         with drrt.using(pair_grid=pair, corrected_h=True, check_failed=False):
             with drrt.using(sort_rays=fwd_sorts):
-                out, st, order = TP._gpu_forward(T, c, gpu, stride, M)
+                out, st, order = PC._gpu_forward(T, c, gpu, stride, M)
             assert (order is not None) == fwd_sorts
-            TP._forward_matches(out, st, k)
+            PC._forward_matches(out, st, k)
             with drrt.using(sort_rays=True):
-                (grad, dpos, dvel), bst = TP._gpu_back(T, c, gpu, out, stride, g, order=order)
-        assert TP._same(dpos, r["dpos"]) and TP._same(dvel, r["dvel"])
+                (grad, dpos, dvel), bst = PC._gpu_back(T, c, gpu, out, stride, g, order=order)
+        assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
         assert bst["ray_steps"] == r["ray_steps"] > 0 and bst["n_failed"] == r["n_failed"] > 0
         err = cases.rel_l2(grad.cpu().numpy(), r["grad"])
         print(f"seed {seed} pair={pair} M={M}: grid rel-L2 vs host {err:.3e}")

@@ -28,8 +28,7 @@ import torch
 
 from oracle import ray16_ref as R16
 from oracle import sortkey_ref as SK
-from test_sort_order import referee
-from test_ray16_ref import MODES, SEEDS, HALF_MIN_NORMAL, options_of, pos_sweep, reference, same_bits, vel_sweep
+from ray16_common import MODES, SEEDS, HALF_MIN_NORMAL, options_of, pos_sweep, referee, reference, same_bits, vel_sweep
 
 pytestmark = pytest.mark.gpu
 

@@ -14,30 +14,10 @@ import torch
 import cases
 import hostcheck_lib as HC
 from oracle import torch_ad
-from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grads, grid, ray_sets, rel_err
+from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grads, max_steps_fwd, rel_err, scene
 
 
 # ---- scenes ---------------------------------------------------------------------------------------------------------
-def scene(name, seed=0):
-    kind, h, ds = SCENES[name]
-    rif = grid(kind)
-    D, H, W = rif.shape
-    res = (W, H, D)
-    ext = ((W - 1) * h, (H - 1) * h, (D - 1) * h)
-    sets = ray_sets(ext, ds, seed)
-    pos = np.concatenate([s[0] for s in sets.values()])
-    vel = np.concatenate([s[1] for s in sets.values()])
-    labels = np.concatenate([[k] * len(s[0]) for k, s in sets.items()])
-    rng = np.random.default_rng(seed + 11)
-    dx = rng.normal(size=pos.shape).astype(np.float32)
-    dv = rng.normal(size=pos.shape).astype(np.float32)
-    return dict(rif=rif, res=res, h=h, ds=ds, pos=pos, vel=vel, labels=labels, dx=dx, dv=dv)
-
-
-def max_steps_fwd(res, h, ds):
-    return int(np.float32(4.0) * np.float32(h) * np.float32(max(res)) / np.float32(ds))
-
-
 def autograd64(rif, pos, vel, dx, dv, h, ds):
     """float64 torch.autograd of L = <dx, xt> + <dv, vt> through torch_ad.trace -> (dpos, dvel)."""
     r = torch.tensor(rif, dtype=torch.float64)

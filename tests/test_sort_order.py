@@ -23,7 +23,7 @@ import torch
 import cases
 import hostcheck_lib as H
 from oracle import sortkey_ref as S
-from test_ray16_ref import SEEDS
+from ray16_common import SEEDS, referee
 
 pytestmark = pytest.mark.gpu
 
@@ -46,15 +46,6 @@ def expected_order(res, h, pos, vel, sign, chord):
     """-> (host-build keys, their stable argsort)"""
     keys = (H.chord_keys if chord else H.lightfield_keys)(res, h, pos, vel, sign)
     return keys, S.visit_order(keys)
-
-
-def referee(res, h, pos, vel, sign, chord):
-    """-> (float64 keys, decided)"""
-    if chord:
-        r = S.chord64(res, h, pos, vel, sign, hit32=S.chord32(res, h, pos, vel, sign)["hit"])
-    else:
-        r = S.lightfield64(res, h, pos, vel, sign)
-    return r["key"], r["decided"]
 
 
 @functools.lru_cache(maxsize=None)

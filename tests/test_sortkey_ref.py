@@ -21,7 +21,7 @@ import pytest
 import cases
 import hostcheck_lib as H
 from oracle import sortkey_ref as S
-from test_ray16_ref import SEEDS
+from ray16_common import SEEDS
 
 SIGNS = (1.0, -1.0)
 CELL_SHIFT = 2 * S.POS_BITS

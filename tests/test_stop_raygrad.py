@@ -30,85 +30,13 @@ import torch
 import cases
 import hostcheck_lib as HC
 import stop_ad
-from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, _unit, grads, grid, ray_sets, rel_err
+from raygrad_common import (GRAD_TOL, PLANES, SCENES, TIE_TOL, _t, grads, host_plane, host_sdf, plane_scene, rel_err, sdf_scene,
+                            sphere_sdf)
 
 MAX_DROPPED = 0.10      # share of a case's non-failed rays that may be left out as not tie-free
 
-PLANES = {
-    # name: (origin as a fraction of the box extents, direction)
-    "axis": ((0.5, 0.6, 0.5), (0.0, 1.0, 0.0)),
-    "tilted": ((0.5, 0.45, 0.5), (0.3, 0.9, 0.1)),
-}
-
-
-def _concat(s, sets):
-    pos = np.concatenate([a for a, _ in sets.values()]).astype(np.float32)
-    vel = np.concatenate([b for _, b in sets.values()]).astype(np.float32)
-    s["labels"] = np.concatenate([[k] * len(a) for k, (a, _) in sets.items()])
-    rng = np.random.default_rng(17)
-    s.update(pos=pos, vel=vel, dx=rng.normal(size=pos.shape).astype(np.float32),
-             dv=rng.normal(size=pos.shape).astype(np.float32))
-    return s
-
-
-def _base(name):
-    kind, h, ds = SCENES[name]
-    rif = grid(kind)
-    D, H, W = rif.shape
-    ext = np.array([(W - 1) * h, (H - 1) * h, (D - 1) * h])
-    return dict(rif=rif, res=(W, H, D), h=h, ds=ds, ext=ext), dict(ray_sets(ext, ds, 0))
-
-
-def plane_scene(name, plane):
-    """The box march's scene and ray sets (raygrad_common), one sensor plane for all rays, and the "back" set: rays that
-    start in bounds PAST the plane and head back through it (the global-loop case: their record is overwritten when they
-    leave again)."""
-    s, sets = _base(name)
-    ext = s["ext"]
-    o = np.array(PLANES[plane][0]) * ext
-    d = _unit(PLANES[plane][1])
-    rng = np.random.default_rng(23)
-    p = rng.uniform(0.12, 0.88, (4000, 3)) * ext
-    dist = (p - o) @ d
-    p = p[dist > 1.5 * s["ds"]][:96]
-    assert len(p) == 96
-    sets["back"] = (p, _unit(-d + rng.normal(0, 0.12, (96, 3))))
-    s = _concat(s, sets)
-    n = len(s["pos"])
-    s["po"] = np.tile(o.astype(np.float32), (n, 1))
-    s["pd"] = np.tile(d.astype(np.float32), (n, 1))
-    return s
-
-
-def sphere_sdf(s):
-    W, H, D = s["res"]
-    h = s["h"]
-    z, y, x = np.meshgrid(np.arange(D) * h, np.arange(H) * h, np.arange(W) * h, indexing="ij")
-    c = s["ext"] / 2
-    return (np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2) - 0.42 * s["ext"].min()).astype(np.float32)
-
-
-def sdf_scene(name):
-    """The box march's scene and ray sets (raygrad_common), a sphere of radius 0.42 of the smallest extent as the object,
-    and the "object" set: rays that start inside it."""
-    s, sets = _base(name)
-    s["sdf"] = sphere_sdf(s)
-    rng = np.random.default_rng(29)
-    r = 0.42 * s["ext"].min()
-    u = _unit(rng.normal(size=(96, 3))) * (r * 0.85 * rng.uniform(0, 1, (96, 1)) ** (1 / 3))
-    sets["object"] = (s["ext"] / 2 + u, _unit(rng.normal(size=(96, 3))))
-    return _concat(s, sets)
-
 
 PLANE_CASES = [(n, p) for n in SCENES for p in PLANES]
-
-
-def host_plane(s):
-    return HC.backtrace_pln_rays(s["rif"], s["res"], s["pos"], s["vel"], s["po"], s["pd"], s["dx"], s["dv"], s["h"], s["ds"])
-
-
-def host_sdf(s):
-    return HC.backtrace_sdf_rays(s["rif"], s["sdf"], s["res"], s["pos"], s["vel"], s["dx"], s["dv"], s["h"], s["ds"])
 
 
 def autograd64(s, mode):

@@ -34,58 +34,11 @@ import hostcheck_lib as HC
 import stop_ad
 import target_ad
 import target_raygrad_host as TH
-from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grads, grid, ray_sets, rel_err
+from raygrad_common import GRAD_TOL, SCENES, TIE_TOL, _t, grads, rel_err, target_scene
 
 MAX_DROPPED = 0.10      # share of a case's rays that may be left out as not tie-free (test_stop_raygrad's cap)
 ENTERING = ("plane", "point", "inside", "face")
 CASES = [(n, z) for n in SCENES for z in ("zero", "nozero")]
-
-
-def _targets(sets, ext, ds):
-    """Every set in quarters: somewhere in the middle of the box; just beyond the box along the ray (the record is written
-    after the escape); the ray's origin (j = 0); 2.4 steps ahead (inside the prefix for the sets that start outside)."""
-    rng = np.random.default_rng(31)
-    out = []
-    for pos, vel in sets.values():
-        pos, vel = pos.astype(np.float64), vel.astype(np.float64)
-        n = len(pos)
-        q = [slice(k * n // 4, (k + 1) * n // 4) for k in range(4)]
-        speed = np.linalg.norm(vel, axis=1, keepdims=True)
-        u = np.divide(vel, speed, out=np.zeros_like(vel), where=speed > 0)
-        tg = np.empty_like(pos)
-        tg[q[0]] = (0.5 + rng.uniform(-0.2, 0.2, (q[0].stop - q[0].start, 3))) * ext
-        tg[q[1]] = 0.5 * ext + u[q[1]] * (0.5 * np.linalg.norm(ext) + 4 * ds) + rng.normal(0, 0.5 * ds, (q[1].stop - q[1].start, 3))
-        tg[q[2]] = pos[q[2]]
-        tg[q[3]] = pos[q[3]] + vel[q[3]] * 2.4 * ds + rng.normal(0, 0.3 * ds, (q[3].stop - q[3].start, 3))
-        out.append(tg)
-    return np.concatenate(out).astype(np.float32)
-
-
-_scenes = {}
-
-
-def target_scene(name, zero):
-    """The box march's scene and ray sets (raygrad_common), with (`zero` = "zero") or without the "zero" set: without it the
-    global loop count is the slowest ray's and not max_steps, so phase B's dependence on the other rays shows."""
-    if (name, zero) in _scenes:
-        return _scenes[name, zero]
-    kind, h, ds = SCENES[name]
-    rif = grid(kind)
-    D, H, W = rif.shape
-    ext = np.array([(W - 1) * h, (H - 1) * h, (D - 1) * h])
-    sets = dict(ray_sets(ext, ds, 0))
-    if zero != "zero":
-        del sets["zero"]
-    pos = np.concatenate([a for a, _ in sets.values()]).astype(np.float32)
-    vel = np.concatenate([b for _, b in sets.values()]).astype(np.float32)
-    rng = np.random.default_rng(17)
-    s = dict(rif=rif, res=(W, H, D), h=h, ds=ds, ext=ext, pos=pos, vel=vel,
-             labels=np.concatenate([[k] * len(a) for k, (a, _) in sets.items()]),
-             dx=rng.normal(size=pos.shape).astype(np.float32), dv=rng.normal(size=pos.shape).astype(np.float32),
-             dd2=rng.normal(size=len(pos)).astype(np.float32), tg=_targets(sets, ext, ds))
-    assert len(pos) % 256 != 0
-    _scenes[name, zero] = s
-    return s
 
 
 def fuzz_scene(k):
