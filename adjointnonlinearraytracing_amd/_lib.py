@@ -63,6 +63,16 @@ def _sensor_signatures():
             for family, (rays, host, *tails) in families.items() for dframe in ("", "_dframe") for bwd in ("", "_bwd")}
 
 
+def _radiance_signatures():
+    """The 8 radiance-splat entries, drrt_sensor_radiance[_far][_dframe][_bwd]_f32: the rays (n, x, v, rad, channels; the
+    far field has no x), the frame as in _sensor_signatures(), then (res, span, image, flags) or (res, span, grad_image,
+    grad_rad, grad_x, grad_v), and the stream."""
+    tails = ([_i, _f, _vp, _u, _vp], [_i, _f, _vp, _vp, _vp, _vp, _vp])
+    families = {"radiance": ([_sz, _vp, _vp, _vp, _i], 4), "radiance_far": ([_sz, _vp, _vp, _i], 2)}
+    return {f"drrt_sensor_{family}{dframe}{bwd}_f32": (_i, rays + [_vp] * (1 if dframe else host) + tails[bool(bwd)])
+            for family, (rays, host) in families.items() for dframe in ("", "_dframe") for bwd in ("", "_bwd")}
+
+
 SIGNATURES = {
     # name: (restype, argtypes)   -- must stay in sync with include/drrt_hip.h
     "drrt_workspace_bytes": (_sz, [_sz, _u]),
@@ -110,6 +120,7 @@ SIGNATURES = {
     "drrt_backtrace_sdf_rays_f32": (_i, [_vp, _vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     "drrt_backtrace_target_rays_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _vp, _vp] + _tail),
     **_sensor_signatures(),
+    **_radiance_signatures(),
     "drrt_rays_to_plane_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     "drrt_rays_to_plane_bwd_f32": (_i, [_sz, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "drrt_upres_volume_f32": (_i, [_vp, _vp, _vp, _vp, _vp]),

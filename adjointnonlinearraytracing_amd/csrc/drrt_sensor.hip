@@ -39,6 +39,9 @@ struct SensorArgs {
   float* f_out;                // tex_get forward out: one value per ray
   float* grad_x; float* grad_v;
   size_t n_rays;
+  const float* rad;            // radiance splats: (n, channels) per-ray values (`e` stays null, so SensorRay::F is |v.n| or 1)
+  int channels;                // ... image and grad_image are then (channels, res, res)
+  float* grad_rad;             // radiance backward out (n, channels); like grad_x / grad_v there, written only when non-null
 };
 
 __device__ __forceinline__ void sensor_frame(SensorArgs& a) {       // wave-uniform scalar loads
@@ -96,48 +99,67 @@ __device__ __forceinline__ SensorRay sensor_locate(const SensorArgs& a, size_t i
 constexpr int kTile = 48;                       // tile edge in pixels (48*48 doubles = 18 KiB)
 constexpr int kVoteCell = 32, kVote = 40;       // anchor vote: 40x40 coarse cells of 32 pixels (images up to 1277^2; larger ones clamp)
 
-__global__ void __launch_bounds__(256) k_sensor_splat(SensorArgs a) {
-  sensor_frame(a);
-  __shared__ double s_tile[kTile * kTile];
-  __shared__ unsigned s_vote[kVote * kVote];
-  __shared__ int s_min[2];
-  __shared__ unsigned s_best;
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  for (int k = threadIdx.x; k < kTile * kTile; k += 256) s_tile[k] = 0.0;
-  for (int k = threadIdx.x; k < kVote * kVote; k += 256) s_vote[k] = 0u;
-  if (threadIdx.x < 2) s_min[threadIdx.x] = 0x7fffffff;
-  if (threadIdx.x == 0) s_best = 0u;
-  __syncthreads();
-  float x[3], v[3];
-  SensorRay r;
-  r.ok = false; r.i1[0] = r.i1[1] = 0; r.u[0] = r.u[1] = 0.f; r.F = 0.f; r.den = 1.f; r.t = 0.f;
-  if (i < a.n_rays) r = sensor_locate(a, i, x, v);
-  // Tile anchor.  If all the block's hits fit one tile, anchor at the smallest hit pixel.  Otherwise (a focused
-  // bundle plus stray rays: the min corner would leave the FOCUS outside the tile, on the slow same-address
-  // global atomics) the rays vote on a coarse kVoteCell-pixel grid and the tile is centred on the winning cell.
+// The tile anchor of a block, shared by the two forward splats.  If all the block's hits fit one tile, anchor at the
+// smallest hit pixel.  Otherwise (a focused bundle plus stray rays: the min corner would leave the FOCUS outside the
+// tile, on the slow same-address global atomics) the rays vote on a coarse kVoteCell-pixel grid and the tile is centred
+// on the winning cell.
+struct TileAnchor {
+  unsigned vote[kVote * kVote];
+  int min[2];
+  unsigned best;
+};
+
+__device__ __forceinline__ void anchor_reset(TileAnchor& s) {           // the caller's __syncthreads() follows
+  for (int k = threadIdx.x; k < kVote * kVote; k += 256) s.vote[k] = 0u;
+  if (threadIdx.x < 2) s.min[threadIdx.x] = 0x7fffffff;
+  if (threadIdx.x == 0) s.best = 0u;
+}
+
+__device__ __forceinline__ void anchor_vote(TileAnchor& s, const SensorRay& r, int& oa, int& ob) {   // -> tile origin (block-uniform)
   int ca = 0, cb = 0;
   if (r.ok) {
-    atomicMin(&s_min[0], r.i1[0] - 1); atomicMin(&s_min[1], r.i1[1] - 1);
+    atomicMin(&s.min[0], r.i1[0] - 1); atomicMin(&s.min[1], r.i1[1] - 1);
     ca = min(max((r.i1[0] + 3) / kVoteCell, 0), kVote - 1); cb = min(max((r.i1[1] + 3) / kVoteCell, 0), kVote - 1);
-    atomicAdd(&s_vote[ca * kVote + cb], 1u);
+    atomicAdd(&s.vote[ca * kVote + cb], 1u);
   }
   __syncthreads();
   {
     // argmax over the votes: pack (count, cell) so that atomicMax picks the fullest cell
     unsigned best = 0u;
-    for (int k = threadIdx.x; k < kVote * kVote; k += 256) best = max(best, (s_vote[k] << 12) | (unsigned)k);
-    if (best >> 12) atomicMax(&s_best, best);
+    for (int k = threadIdx.x; k < kVote * kVote; k += 256) best = max(best, (s.vote[k] << 12) | (unsigned)k);
+    if (best >> 12) atomicMax(&s.best, best);
   }
   __syncthreads();
-  int oa = s_min[0], ob = s_min[1];             // tile origin (block-uniform)
+  oa = s.min[0]; ob = s.min[1];
   {
-    const int wa = (int)((s_best & 0xfffu) / kVote), wb = (int)((s_best & 0xfffu) % kVote);
+    const int wa = (int)((s.best & 0xfffu) / kVote), wb = (int)((s.best & 0xfffu) % kVote);
     const int va = wa * kVoteCell - 3 - (kTile - kVoteCell) / 2, vb = wb * kVoteCell - 3 - (kTile - kVoteCell) / 2;
     // keep the min-corner anchor when it already covers the winning cell entirely
     if (va + (kTile - kVoteCell) / 2 + kVoteCell + 3 > oa + kTile || vb + (kTile - kVoteCell) / 2 + kVoteCell + 3 > ob + kTile) {
       oa = va; ob = vb;
     }
   }
+}
+
+__device__ __forceinline__ SensorRay no_ray() {                          // a thread past the last ray
+  SensorRay r;
+  r.ok = false; r.i1[0] = r.i1[1] = 0; r.u[0] = r.u[1] = 0.f; r.F = 0.f; r.den = 1.f; r.t = 0.f;
+  return r;
+}
+
+__global__ void __launch_bounds__(256) k_sensor_splat(SensorArgs a) {
+  sensor_frame(a);
+  __shared__ double s_tile[kTile * kTile];
+  __shared__ TileAnchor s_anchor;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  for (int k = threadIdx.x; k < kTile * kTile; k += 256) s_tile[k] = 0.0;
+  anchor_reset(s_anchor);
+  __syncthreads();
+  float x[3], v[3];
+  SensorRay r = no_ray();
+  if (i < a.n_rays) r = sensor_locate(a, i, x, v);
+  int oa, ob;
+  anchor_vote(s_anchor, r, oa, ob);
   if (r.ok) {
     float w[16], wsum = 0.f;
 #pragma unroll
@@ -225,6 +247,151 @@ __global__ void __launch_bounds__(256) k_sensor_splat_bwd(SensorArgs a) {
   }
   a.grad_x[3 * i] = gx[0]; a.grad_x[3 * i + 1] = gx[1]; a.grad_x[3 * i + 2] = gx[2];
   a.grad_v[3 * i] = gv[0]; a.grad_v[3 * i + 1] = gv[1]; a.grad_v[3 * i + 2] = gv[2];
+}
+
+// ---- radiance splats: a per-ray, per-channel energy rad (n, C) onto an image (C, res, res), differentiable w.r.t. the
+// rays AND rad.  Channel c is generate_sensor / generate_inf_sensor with e = rad[:, c]; all channels of a ray share its
+// landing point, its 16 weights and its block's tile anchor, which are formed once.
+constexpr int kMaxChannels = 32;
+
+// Forward.  k_sensor_splat with a loop over the channels around its accumulate / flush: the ONE LDS tile is reused by every
+// channel (the flush hands it back zeroed), so the LDS footprint does not grow with C, and the focused-bundle reasoning
+// above holds for each channel as it stands -- a channel's taps meet the same pixels as any other's.
+__global__ void __launch_bounds__(256) k_sensor_radiance(SensorArgs a) {
+  sensor_frame(a);
+  __shared__ double s_tile[kTile * kTile];
+  __shared__ TileAnchor s_anchor;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  for (int k = threadIdx.x; k < kTile * kTile; k += 256) s_tile[k] = 0.0;
+  anchor_reset(s_anchor);
+  __syncthreads();
+  float x[3], v[3];
+  SensorRay r = no_ray();
+  if (i < a.n_rays) r = sensor_locate(a, i, x, v);
+  int oa, ob;
+  anchor_vote(s_anchor, r, oa, ob);
+  float w[16], wsum = 0.f;
+#pragma unroll
+  for (int ja = 0; ja < 4; ++ja) {
+    const float da = r.u[0] - (float)(r.i1[0] - 1 + ja);
+#pragma unroll
+    for (int jb = 0; jb < 4; ++jb) {
+      const float db = r.u[1] - (float)(r.i1[1] - 1 + jb);
+      const float ww = fmaxf(1.41421356237f - sqrtf(da * da + db * db), 0.f);     // grid.py:79
+      w[ja * 4 + jb] = ww; wsum += ww;
+    }
+  }
+  const int la = r.i1[0] - 1 - oa, lb = r.i1[1] - 1 - ob;               // tile coords of the first tap
+  const bool in_tile = (la >= 0) & (lb >= 0) & (la + 3 < kTile) & (lb + 3 < kTile);
+  const size_t plane = (size_t)a.res * a.res;
+  for (int ch = 0; ch < a.channels; ++ch) {
+    float* const image = a.image + ch * plane;
+    if (r.ok) {
+      const float scale = r.F * a.rad[i * a.channels + ch] / wsum;      // grid.py:145 (all 16 taps)
+#pragma unroll
+      for (int ja = 0; ja < 4; ++ja) {
+        const int ia = r.i1[0] - 1 + ja;
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+          const int ib = r.i1[1] - 1 + jb;
+          const float c = w[ja * 4 + jb] * scale;
+          if (((unsigned)ia < (unsigned)a.res) & ((unsigned)ib < (unsigned)a.res) & (c != 0.f)) {   // grid.py:140
+            if (in_tile) atomicAdd(&s_tile[(la + ja) * kTile + (lb + jb)], (double)c);
+            else unsafeAtomicAdd(image + (size_t)ia * a.res + ib, c);
+          }
+        }
+      }
+    }
+    __syncthreads();
+    for (int k = threadIdx.x; k < kTile * kTile; k += 256) {
+      const double g = s_tile[k];
+      if (g != 0.0) {
+        const int ia = oa + k / kTile, ib = ob + k % kTile;     // only in-image taps were accumulated
+        unsafeAtomicAdd(image + (size_t)ia * a.res + ib, (float)g);
+        s_tile[k] = 0.0;                                        // ... and the next channel finds the tile empty
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Backward: a deterministic gather, no atomics.  With gI the (C, res, res) seed and sums over the 16 taps j of the ray,
+//   W = sum_j w_j,   G_c = sum_{j in image} gI[c, tap_j] w_j / W,
+//   dL/drad_c = |v.n| G_c  (far field: G_c),
+//   dL/du_a   = (1 / W) sum_c F_c (sum_{j in image} gI[c, tap_j] dw_j/du_a - G_c sum_j dw_j/du_a),   F_c = |v.n| rad_c,
+// then k_sensor_splat_bwd's chain through inv_hs, the frame and the plane; the foreshortening term of dL/dv is
+// (sum_c G_c rad_c) sign(v.n) n.  Register strategy: the 16 weights and their 32 derivatives are HELD and each channel
+// re-gathers its 16 seed values against them in a rolled loop -- the register count does not depend on C (per-channel
+// accumulators would take 3 C of them).  G_c is summed in the tap order ja, jb whatever C is and whichever outputs are
+// asked for, so dL/drad[:, c] of a C-channel call is the 1-channel call's bit for bit.  Each of grad_rad, grad_x, grad_v
+// is written only when non-null; with neither ray output asked for the derivative weights stay zero (no divides).
+__global__ void __launch_bounds__(256) k_sensor_radiance_bwd(SensorArgs a) {
+  sensor_frame(a);
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= a.n_rays) return;
+  float x[3], v[3];
+  const SensorRay r = sensor_locate(a, i, x, v);
+  const int C = a.channels;
+  const bool rays = (a.grad_x != nullptr) | (a.grad_v != nullptr);
+  float gx[3] = {0.f, 0.f, 0.f}, gv[3] = {0.f, 0.f, 0.f};
+  if (r.ok) {
+    float w[16], dwa[16], dwb[16], W = 0.f, sda = 0.f, sdb = 0.f;
+#pragma unroll
+    for (int ja = 0; ja < 4; ++ja) {
+      const float da = r.u[0] - (float)(r.i1[0] - 1 + ja);
+#pragma unroll
+      for (int jb = 0; jb < 4; ++jb) {
+        const float db = r.u[1] - (float)(r.i1[1] - 1 + jb);
+        const float rr = sqrtf(da * da + db * db);
+        const float ww = fmaxf(1.41421356237f - rr, 0.f);
+        const bool live = (ww > 0.f) & (rr > 0.f) & rays;
+        const float inv_r = live ? 1.f / rr : 0.f;
+        w[ja * 4 + jb] = ww; dwa[ja * 4 + jb] = -da * inv_r; dwb[ja * 4 + jb] = -db * inv_r;       // d w / d u
+        W += ww; sda += dwa[ja * 4 + jb]; sdb += dwb[ja * 4 + jb];
+      }
+    }
+    const size_t plane = (size_t)a.res * a.res;
+    float ga = 0.f, gb = 0.f, ef = 0.f;
+    for (int ch = 0; ch < C; ++ch) {
+      const float* const seed = a.grad_image + ch * plane;
+      float gw = 0.f, gda = 0.f, gdb = 0.f;
+#pragma unroll
+      for (int ja = 0; ja < 4; ++ja) {
+        const int ia = r.i1[0] - 1 + ja;
+#pragma unroll
+        for (int jb = 0; jb < 4; ++jb) {
+          const int ib = r.i1[1] - 1 + jb;
+          const bool valid = ((unsigned)ia < (unsigned)a.res) & ((unsigned)ib < (unsigned)a.res);
+          const float g = valid ? seed[(size_t)ia * a.res + ib] : 0.f;
+          gw += g * w[ja * 4 + jb]; gda += g * dwa[ja * 4 + jb]; gdb += g * dwb[ja * 4 + jb];
+        }
+      }
+      const float G = gw / W;
+      if (a.grad_rad) a.grad_rad[i * C + ch] = r.F * G;
+      if (rays) {
+        const float rc = a.rad[i * C + ch];
+        ga += rc * (gda - G * sda); gb += rc * (gdb - G * sdb); ef += G * rc;
+      }
+    }
+    const float k = r.F / W * a.inv_hs;
+    ga *= k; gb *= k;                                                   // dL/d xn
+    const float gp0 = ga * a.t1[0] + gb * a.t2[0], gp1 = ga * a.t1[1] + gb * a.t2[1], gp2 = ga * a.t1[2] + gb * a.t2[2];
+    if (a.far) {                                                        // d vhat / d v = (I - vhat vhat^T) / |v|
+      const float inv = 1.f / r.den;
+      const float h0 = v[0] * inv, h1 = v[1] * inv, h2 = v[2] * inv;
+      const float hg = h0 * gp0 + h1 * gp1 + h2 * gp2;
+      gv[0] = (gp0 - h0 * hg) * inv; gv[1] = (gp1 - h1 * hg) * inv; gv[2] = (gp2 - h2 * hg) * inv;
+    } else {
+      const float vg = (v[0] * gp0 + v[1] * gp1 + v[2] * gp2) / r.den;
+      gx[0] = gp0 - a.n[0] * vg; gx[1] = gp1 - a.n[1] * vg; gx[2] = gp2 - a.n[2] * vg;   // (I - v n^T/den)^T
+      ef *= r.den > 0.f ? 1.f : (r.den < 0.f ? -1.f : 0.f);
+      gv[0] = r.t * gx[0] + ef * a.n[0]; gv[1] = r.t * gx[1] + ef * a.n[1]; gv[2] = r.t * gx[2] + ef * a.n[2];
+    }
+  } else if (a.grad_rad) {
+    for (int ch = 0; ch < C; ++ch) a.grad_rad[i * C + ch] = 0.f;        // a ray that misses: exactly 0
+  }
+  if (a.grad_x) { a.grad_x[3 * i] = gx[0]; a.grad_x[3 * i + 1] = gx[1]; a.grad_x[3 * i + 2] = gx[2]; }
+  if (a.grad_v) { a.grad_v[3 * i] = gv[0]; a.grad_v[3 * i + 1] = gv[1]; a.grad_v[3 * i + 2] = gv[2]; }
 }
 
 // ---- texture lookups at the sensor: core/sensor.py:102-138 get_sdf_vals_near / get_sdf_vals_far ---------------------
@@ -367,17 +534,38 @@ static int fill_tex(SensorArgs& a, size_t n, const float* x, const float* v, con
   return DRRT_OK;
 }
 
+// Radiance splats: the near or the far family's coordinates with a per-ray, per-channel energy in place of `e` (which
+// stays null with e_scalar 1, so that the kernels find F = |v.n| or 1 in SensorRay).  `span` is ang_cut for the far field.
+static int fill_radiance(SensorArgs& a, bool far, size_t n, const float* x, const float* v, const float* rad, int channels,
+                         const Frame& f, int res, float span) {
+  if (int rc = far ? fill_far(a, n, v, nullptr, 1.f, f, res, span) : fill_near(a, n, x, v, nullptr, 1.f, f, res, span)) return rc;
+  if (!rad) return fail(DRRT_ERR_ARG, "null pointer");
+  if (channels < 1 || channels > kMaxChannels) return fail(DRRT_ERR_ARG, "channels must lie in 1..32");
+  a.rad = rad; a.channels = channels;
+  return DRRT_OK;
+}
+
 // The runners differ in when they look at their outputs, and callers rely on it: the splats check theirs before the
 // n == 0 return (and the forward has zeroed the image by then), the lookups return DRRT_OK for n == 0 first.
 static int run_image(SensorArgs& a, float* image, unsigned flags, void* stream) {
   if (!image) return fail(DRRT_ERR_ARG, "null image pointer");
   if (!(flags & DRRT_FLAG_NO_ZERO)) {
-    const hipError_t e = hipMemsetAsync(image, 0, (size_t)a.res * a.res * sizeof(float), (hipStream_t)stream);
+    const size_t planes = a.rad ? (size_t)a.channels : 1;             // a radiance image is (channels, res, res)
+    const hipError_t e = hipMemsetAsync(image, 0, planes * a.res * a.res * sizeof(float), (hipStream_t)stream);
     if (e != hipSuccess) return fail(DRRT_ERR_HIP, hipGetErrorString(e));
   }
   if (a.n_rays == 0) return DRRT_OK;
   a.image = image;
-  return launch_1d(k_sensor_splat, a.n_rays, stream, a);
+  return launch_1d(a.rad ? k_sensor_radiance : k_sensor_splat, a.n_rays, stream, a);
+}
+
+// The radiance backward: every output is optional, and a call that asks for none has nothing to launch.
+static int run_radiance_grads(SensorArgs& a, const float* grad_image, float* grad_rad, float* grad_x, float* grad_v,
+                              void* stream) {
+  if (!grad_image) return fail(DRRT_ERR_ARG, "null gradient pointer");
+  if (a.n_rays == 0 || (!grad_rad && !grad_x && !grad_v)) return DRRT_OK;
+  a.grad_image = grad_image; a.grad_rad = grad_rad; a.grad_x = grad_x; a.grad_v = grad_v;
+  return launch_1d(k_sensor_radiance_bwd, a.n_rays, stream, a);
 }
 
 // `seed`: dL/dimage of a splat, dL/df of a lookup (whose texture fill_tex has put where the splat's dL/dimage goes)
@@ -458,6 +646,66 @@ extern "C" int drrt_sensor_far_splat_dframe_bwd_f32(size_t n, const float* v, co
   SensorArgs a{};
   const int rc = fill_far(a, n, v, e, e_scalar, device_frame(frame12), res, ang_cut);
   return rc ? rc : run_ray_grads(false, a, grad_image, grad_x, grad_v, stream);
+}
+
+extern "C" int drrt_sensor_radiance_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                        const float plane_p[3], const float plane_n[3], const float t1[3],
+                                        const float t2[3], int res, float span, float* image, unsigned flags, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, false, n, x, v, rad, channels, host_frame(plane_p, plane_n, t1, t2), res, span);
+  return rc ? rc : run_image(a, image, flags, stream);
+}
+extern "C" int drrt_sensor_radiance_dframe_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                               const float* frame12, int res, float span, float* image, unsigned flags,
+                                               void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, false, n, x, v, rad, channels, device_frame(frame12), res, span);
+  return rc ? rc : run_image(a, image, flags, stream);
+}
+extern "C" int drrt_sensor_radiance_bwd_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                            const float plane_p[3], const float plane_n[3], const float t1[3],
+                                            const float t2[3], int res, float span, const float* grad_image,
+                                            float* grad_rad, float* grad_x, float* grad_v, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, false, n, x, v, rad, channels, host_frame(plane_p, plane_n, t1, t2), res, span);
+  return rc ? rc : run_radiance_grads(a, grad_image, grad_rad, grad_x, grad_v, stream);
+}
+extern "C" int drrt_sensor_radiance_dframe_bwd_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                                   const float* frame12, int res, float span, const float* grad_image,
+                                                   float* grad_rad, float* grad_x, float* grad_v, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, false, n, x, v, rad, channels, device_frame(frame12), res, span);
+  return rc ? rc : run_radiance_grads(a, grad_image, grad_rad, grad_x, grad_v, stream);
+}
+
+extern "C" int drrt_sensor_radiance_far_f32(size_t n, const float* v, const float* rad, int channels, const float t1[3],
+                                            const float t2[3], int res, float ang_cut, float* image, unsigned flags,
+                                            void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, true, n, v, v, rad, channels, host_frame(t1, t2), res, ang_cut);
+  return rc ? rc : run_image(a, image, flags, stream);
+}
+extern "C" int drrt_sensor_radiance_far_dframe_f32(size_t n, const float* v, const float* rad, int channels,
+                                                   const float* frame12, int res, float ang_cut, float* image,
+                                                   unsigned flags, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, true, n, v, v, rad, channels, device_frame(frame12), res, ang_cut);
+  return rc ? rc : run_image(a, image, flags, stream);
+}
+extern "C" int drrt_sensor_radiance_far_bwd_f32(size_t n, const float* v, const float* rad, int channels, const float t1[3],
+                                                const float t2[3], int res, float ang_cut, const float* grad_image,
+                                                float* grad_rad, float* grad_x, float* grad_v, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, true, n, v, v, rad, channels, host_frame(t1, t2), res, ang_cut);
+  return rc ? rc : run_radiance_grads(a, grad_image, grad_rad, grad_x, grad_v, stream);
+}
+extern "C" int drrt_sensor_radiance_far_dframe_bwd_f32(size_t n, const float* v, const float* rad, int channels,
+                                                       const float* frame12, int res, float ang_cut,
+                                                       const float* grad_image, float* grad_rad, float* grad_x,
+                                                       float* grad_v, void* stream) {
+  SensorArgs a{};
+  const int rc = fill_radiance(a, true, n, v, v, rad, channels, device_frame(frame12), res, ang_cut);
+  return rc ? rc : run_radiance_grads(a, grad_image, grad_rad, grad_x, grad_v, stream);
 }
 
 extern "C" int drrt_sensor_tex_get_f32(size_t n, const float* x, const float* v, const float plane_p[3],

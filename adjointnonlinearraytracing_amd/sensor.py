@@ -231,6 +231,87 @@ def generate_inf_sensor(rays, e, plane, res, angle_span=120, tangent=None):
     return _FarSensorSplat.apply(v, e, t1, t2, res, ang_cut)
 
 
+MAX_CHANNELS = 32          # kMaxChannels of csrc/drrt_sensor.hip
+
+
+def _radiance(op, rad, nr: int):
+    """The `rad` of a radiance splat -> ((N, C) view, whether it came as (N,)): one value per ray, or one per ray and
+    channel (colour or spectral bands, absorption lines, time gates built from an optical path length, ...)."""
+    if not isinstance(rad, torch.Tensor) or rad.dim() == 0:
+        raise RuntimeError(f"{op}: `rad` is a tensor with one value per ray, (N,), or per ray and channel, (N, C); for "
+                           f"one energy shared by all rays use generate_sensor / generate_inf_sensor")
+    if rad.dim() > 2 or rad.shape[0] != nr:
+        raise RuntimeError(f"{op}: `rad` must have shape (N,) or (N, C) for the N = {nr} rays, got {tuple(rad.shape)}")
+    if rad.dim() == 2 and not 1 <= rad.shape[1] <= MAX_CHANNELS:
+        raise RuntimeError(f"{op}: `rad` must have 1 to {MAX_CHANNELS} channels, got {rad.shape[1]}")
+    return (rad[:, None] if rad.dim() == 1 else rad), rad.dim() == 1
+
+
+class _RadianceSplat(torch.autograd.Function):
+    """splat_radiance / splat_radiance_far (`far`): k_sensor_radiance forward, and ONE launch of k_sensor_radiance_bwd
+    that computes the gradients ctx.needs_input_grad asks for (the others go in as NULL and are not computed)."""
+
+    @staticmethod
+    def forward(ctx, x, v, rad, p, n, t1, t2, res, span, far):
+        op = "splat_radiance_far" if far else "splat_radiance"
+        if not v.is_cuda:
+            raise RuntimeError(f"{op} expects tensors on the cuda (ROCm) device (no CPU path)")
+        _single_plane(p, n)
+        dev = v.device
+        with torch.cuda.device(dev):
+            x_, v_, rad_ = (_f32(t, dev) for t in (x, v, rad))
+            nr, nc = rad_.shape
+            img = torch.empty(nc, int(res), int(res), dtype=torch.float32, device=dev)
+            fdev, frame = _frame(dev, None if far else p, None if far else n, t1, t2)
+            head = (nr, v_, rad_, nc) if far else (nr, x_, v_, rad_, nc)
+            entry = "drrt_sensor_radiance_far{}" if far else "drrt_sensor_radiance{}"
+            _call(entry + "_f32", head, fdev, frame, int(res), float(span), img, 0)
+        ctx.saved = (entry, head, fdev, frame, int(res), float(span))
+        return img
+
+    @staticmethod
+    def backward(ctx, grad_img):
+        entry, head, fdev, frame, res, span = ctx.saved
+        v_, rad_ = head[-3], head[-2]
+        want_x, want_v, want_rad = ctx.needs_input_grad[:3]
+        with torch.cuda.device(v_.device):
+            g = _f32(grad_img, v_.device)
+            gx = torch.empty_like(v_) if want_x and len(head) == 5 else None      # the far field does not read x
+            gv = torch.empty_like(v_) if want_v else None
+            grad = torch.empty_like(rad_) if want_rad else None
+            _call(entry + "_bwd_f32", head, fdev, frame, res, span, g, grad, gx, gv)
+        return gx, gv, grad, None, None, None, None, None, None, None
+
+
+def _splat_radiance(op, far, rays, rad, plane, res, span, tangent):
+    x, v = rays
+    p, n = plane
+    _refuse_grad(op, **({"n": n} if far else {"p": p, "n": n}), tangent=tangent)
+    rad2, flat = _radiance(op, rad, v.shape[0])
+    t1, t2 = get_tan_vecs(n, tangent)
+    img = _RadianceSplat.apply(x, v, rad2, p, n, t1, t2, res, span, far)
+    return img[0] if flat else img
+
+
+def splat_radiance(rays, rad, plane, res, span, tangent=None):
+    """generate_sensor for a per-ray, per-channel energy, differentiable w.r.t. the rays AND `rad`: `rad` (N,) gives the
+    image (res, res), `rad` (N, C) with 1 <= C <= 32 gives (C, res, res), whose channel c is
+    ``generate_sensor(rays, rad[:, c], plane, res, span, tangent)`` -- same plane intersection, frame, 4 x 4 tent taps,
+    normalisation and foreshortening |v.n|.  The channels of a ray share its landing point and its 16 weights, which one
+    fused HIP kernel forms once (csrc/drrt_sensor.hip k_sensor_radiance); the backward is one launch that computes the
+    gradients asked for.  E.g. a shadowgraph through an absorbing, refracting volume: ``rad = exp(-tau)`` with ``tau``
+    from FieldIntegralTracerC -- the image then depends on the volume through the landing point and through the weight.
+    A plane or tangent that requires grad raises, as in generate_sensor."""
+    return _splat_radiance("splat_radiance", False, rays, rad, plane, res, float(span), tangent)
+
+
+def splat_radiance_far(rays, rad, plane, res, angle_span=120, tangent=None):
+    """generate_inf_sensor for a per-ray, per-channel energy (see splat_radiance): the far-field image(s) of the
+    normalised directions, differentiable w.r.t. the directions and `rad`; the positions do not enter."""
+    ang_cut = float(torch.sin(0.5 * torch.deg2rad(torch.tensor(float(angle_span), dtype=torch.float32))))
+    return _splat_radiance("splat_radiance_far", True, rays, rad, plane, res, ang_cut, tangent)
+
+
 class _TexGet(torch.autograd.Function):
 
     @staticmethod

@@ -861,6 +861,38 @@ DRRT_API int drrt_sensor_tex_get_dframe_bwd_f32(size_t n, const float* x, const 
                                        const float* tex, int res, float span, int mode, const float* grad_f,
                                        float* grad_x, float* grad_v, void* stream);
 
+/* Radiance splats: a per-ray, PER-CHANNEL energy rad (n, channels) fp32, 1 <= channels <= 32, splatted onto an image
+ * (channels, res, res); channel c is drrt_sensor_splat_f32 / drrt_sensor_far_splat_f32 with e = rad[:, c] (same plane
+ * intersection, frame, taps, normalisation over all 16 taps, foreshortening |v.n| in the near field only).  The channels
+ * of a ray share its landing point and its 16 weights.  DRRT_FLAG_NO_ZERO holds for all channels*res*res floats.
+ * Backward: gradient of sum(grad_image * image), grad_image (channels, res, res), w.r.t. rad (grad_rad, (n, channels)) and
+ * the rays (grad_x, grad_v, (n,3)); each of the three outputs may be NULL and is then not computed (all three NULL: nothing
+ * is launched).  A ray that misses the image gets zeros.  The far-field entries write zeros to a non-NULL grad_x.
+ * `_dframe`: the frame as 12 device floats, as above.                                                                   */
+DRRT_API int drrt_sensor_radiance_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                             const float plane_p[3], const float plane_n[3], const float t1[3], const float t2[3],
+                             int res, float span, float* image, unsigned flags, void* stream);
+DRRT_API int drrt_sensor_radiance_bwd_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                 const float plane_p[3], const float plane_n[3], const float t1[3], const float t2[3],
+                                 int res, float span, const float* grad_image, float* grad_rad, float* grad_x,
+                                 float* grad_v, void* stream);
+DRRT_API int drrt_sensor_radiance_dframe_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                    const float* frame12, int res, float span, float* image, unsigned flags, void* stream);
+DRRT_API int drrt_sensor_radiance_dframe_bwd_f32(size_t n, const float* x, const float* v, const float* rad, int channels,
+                                        const float* frame12, int res, float span, const float* grad_image,
+                                        float* grad_rad, float* grad_x, float* grad_v, void* stream);
+DRRT_API int drrt_sensor_radiance_far_f32(size_t n, const float* v, const float* rad, int channels, const float t1[3],
+                                 const float t2[3], int res, float ang_cut, float* image, unsigned flags, void* stream);
+DRRT_API int drrt_sensor_radiance_far_bwd_f32(size_t n, const float* v, const float* rad, int channels, const float t1[3],
+                                     const float t2[3], int res, float ang_cut, const float* grad_image,
+                                     float* grad_rad, float* grad_x, float* grad_v, void* stream);
+DRRT_API int drrt_sensor_radiance_far_dframe_f32(size_t n, const float* v, const float* rad, int channels,
+                                        const float* frame12, int res, float ang_cut, float* image, unsigned flags,
+                                        void* stream);
+DRRT_API int drrt_sensor_radiance_far_dframe_bwd_f32(size_t n, const float* v, const float* rad, int channels,
+                                            const float* frame12, int res, float ang_cut, const float* grad_image,
+                                            float* grad_rad, float* grad_x, float* grad_v, void* stream);
+
 /* core/sensor.py:195-202 trace_rays_to_plane, the statement right after the march in every experiment: x_out = x + t v with
  * t = n.(p - x) / n.v (v passes through unchanged), and its analytic backward w.r.t. the rays (grad_x, grad_v receive the
  * part of the gradient that flows through x_out).  plane_stride 3 = one (p, n) per ray, 0 = one plane for all rays.
