@@ -105,6 +105,9 @@ SIGNATURES = {
     "drrt_trace_path_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp] + _tail),
     "drrt_backtrace_path_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp]
                                 + _tail),
+    "drrt_trace_phase_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _f, _f, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp] + _tail),
+    "drrt_backtrace_phase_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _f, _f, _i, _i, _vp, _vp,
+                                      _vp] + _tail),
     "drrt_backtrace_chunk_state_bytes": (_sz, [_sz]),
     "drrt_backtrace_max_steps": (_i, [_vp, _f, _f]),
     "drrt_backtrace_chunk_f32": (_i, [_vp, _ll, _vp, _sz, _vp, _vp, _vp, _vp, _f, _f, _vp] + _tail + [_vp, _sz, _i, _i, _vp]),
@@ -149,7 +152,8 @@ PROF_NAMES = {1: "trace", 2: "backtrace", 3: "sort", 4: "zero", 5: "quad", 6: "b
 PROF_NAMES_MORE = {15: "trace_emission", 16: "backtrace_emission"}
 # ... and after PROF_NAMES_MORE was: this table stays open, a later id goes here
 PROF_NAMES_LATER = {17: "trace_vector", 18: "backtrace_vector", 19: "trace_cable_opl", 20: "backtrace_cable_opl",
-                    21: "trace_cable_field", 22: "backtrace_cable_field", 23: "trace_path", 24: "backtrace_path"}
+                    21: "trace_cable_field", 22: "backtrace_cable_field", 23: "trace_path", 24: "backtrace_path",
+                    25: "trace_phase", 26: "backtrace_phase"}
 
 _lib: Optional[C.CDLL] = None
 

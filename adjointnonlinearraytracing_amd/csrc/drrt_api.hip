@@ -928,6 +928,33 @@ extern "C" int drrt_backtrace_path_f32(const float* rif, long long nvox, const i
                                 dpos, dvel, DRRT_PROF_BACKTRACE_PATH, "k_backtrace_path", launch_backtrace_path);
 }
 
+// the two series of the phase entries have one extent (samples, n, 3): check_path_series covers each
+extern "C" int drrt_trace_phase_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                    const float* pos, const float* vel, float h, float ds, int stride, int samples,
+                                    float* xt, float* vt, float* path, float* vpath, int* count, uint32_t* steps_out,
+                                    drrt_stats* stats, void* ws, size_t ws_bytes, unsigned flags, void* stream) {
+  int rc = check_path_series(stride, samples, n); if (rc) return rc;
+  PhaseTraceArgs a{};
+  a.path = path; a.vpath = vpath; a.count = count; a.stride = (unsigned)stride; a.samples = (unsigned)samples;
+  return run_trace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {},
+                            {path, vpath, (const float*)count}, xt, vt, steps_out, DRRT_PROF_TRACE_PHASE, "k_trace_phase",
+                            launch_trace_phase);
+}
+
+extern "C" int drrt_backtrace_phase_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                                        const float* pos, const float* vel, const float* xt, const float* vt,
+                                        const uint32_t* fwd_steps, const float* dx, const float* dv, const float* dpath,
+                                        const float* dvpath, float h, float ds, int stride, int samples, float* grad,
+                                        float* dpos, float* dvel, drrt_stats* stats, void* ws, size_t ws_bytes,
+                                        unsigned flags, void* stream) {
+  int rc = check_path_series(stride, samples, n); if (rc) return rc;
+  PhaseBackArgs a{};
+  a.dpath = dpath; a.dvpath = dvpath; a.grad = grad; a.stride = (unsigned)stride; a.samples = (unsigned)samples;
+  return run_backtrace_integral(a, {rif, nvox, res, n, pos, vel, h, ds, stats, ws, ws_bytes, flags, stream}, {}, {}, {grad},
+                                "null output pointers: grad, or dpos and dvel, or all three", xt, vt, fwd_steps, dx, dv,
+                                dpos, dvel, DRRT_PROF_BACKTRACE_PHASE, "k_backtrace_phase", launch_backtrace_phase);
+}
+
 extern "C" size_t drrt_backtrace_chunk_state_bytes(size_t n) { return (size_t)adj_grid_for(n) * kAdjBlock * 13 * sizeof(float); }
 extern "C" int drrt_backtrace_max_steps(const int res[3], float h, float ds) {
   if (!res || !(h > 0.f) || !(ds > 0.f)) return -1;

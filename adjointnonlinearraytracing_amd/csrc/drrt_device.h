@@ -1367,6 +1367,122 @@ DRRT_HD RayGrad path_backtrace_ray(const Vol& V, float ds, float grad_scale, int
   return r;
 }
 
+// ---- ray paths with velocities (the march's phase-space state) -----------------------------------------------------------
+// trace_path_ray with a second series beside path: with v_k the marching velocity in front of iteration k (v_0 = v, and for
+// k >= 1 the velocity that carried the ray from x_{k-1} to x_k, x_k = fmaf(ds, v_k, x_{k-1}) in fwd_step_c),
+//   vpath[j] = v_{j stride}  for j < count
+//   vpath[j] = vt            for count <= j < M   (padding: the stale v for a failed ray, Q6; v for a ray that never
+//                                                  samples inside)
+// so (path[j], vpath[j]) is the march's state at sample j and a series that is long enough ends on (xt, vt).  |v| = n along
+// the march, so |vpath[j]| is the refractive index the ray saw there.  Everything else is trace_path_ray's bit for bit.
+// Not in the reference.
+
+// `store(j, x, y, z, vx, vy, vz)` writes path[j] and vpath[j] of the ray; counted down as PathIntegrand.  The state behind
+// iteration `it` is (x_{it+1}, v_{it+1}).
+template <typename StoreFn>
+struct PhaseIntegrand {
+  StoreFn& store;
+  unsigned stride, M, cd, j;
+  DRRT_HD void operator()(const Cell&, bool, float) {}
+  DRRT_HD void step(const FwdState& s) {
+    if (--cd != 0u) return;
+    cd = stride;
+    if (!s.esc & (j < M)) store(j, s.x, s.y, s.z, s.vx, s.vy, s.vz);
+    ++j;
+  }
+};
+
+// trace for ONE ray, with both series: stride >= 1, M >= 1.  All M entries of each are written.
+template <typename TapFn, typename StoreFn>
+DRRT_HD RayOut trace_phase_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], unsigned stride,
+                               unsigned M, TapFn&& taps, StoreFn&& store, unsigned& count) {
+  store(0u, p[0], p[1], p[2], v[0], v[1], v[2]);
+  PhaseIntegrand<StoreFn> q{store, stride, M, stride, 1u};
+  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
+  count = path_count(o.steps, stride, M);
+  for (unsigned j = count; j < M; ++j) store(j, o.xt[0], o.xt[1], o.xt[2], o.vt[0], o.vt[1], o.vt[2]);
+  return o;
+}
+
+// Adjoint of trace_phase_ray for ONE ray: path_backtrace_ray with `vseed(j, g)` beside `seed(j, g)`: it writes the seed on
+// vpath[j] to g[3] and returns true, or returns false when there is none (nothing is added then, so the results are
+// path_backtrace_ray's bit for bit).  The position seeds are placed as there.  A sample v_k, e < k < K, enters only through
+// x_k = x_{k-1} + ds v_k and v_{k+1} = v_k + ..., so its seed is one on the total adjoint of v_k: mu when the reverse
+// iteration that arrives at x_{k-1} begins.  It is added in `enter`, in front of that iteration's sample, so that dn, the
+// contribution to dL/dn and q (dL/dvel) see it -- one reverse iteration behind the position seed on x_k; the sample k = e + 1
+// is seeded in the entry iteration.  Around the march, in this order:
+//   * padding: the seeds on vpath[count .. M-1] are seeds on vt and are added to dv in ascending j, in fp32, before the
+//     march is initialised, so mu = dv + ds dx sees them;
+//   * prefix: v_k = v bit for bit for k <= e, so these seeds are added to dvel behind the march (and behind the position
+//     seeds of the prefix) in ascending j; they add nothing to dpos.
+// A ray that never sampled inside (e = K) returns path_backtrace_ray's result with every vpath seed added to dvel; a failed
+// ray returns zeros (no seed is read).
+template <typename SeedFn, typename VSeedFn>
+struct PhaseTerm {
+  SeedFn& seed;
+  VSeedFn& vseed;
+  unsigned stride, cd, cdv;                  // cd / cdv: reverse iterations until one arrives at x_k / x_{k-1} of a sample k
+  int j, jv;                                 // the next sample of each series; < 0: none left
+  DRRT_HD void enter(const Vol&, const Cell&, AdjState& s) {
+    if (cdv-- != 0u) return;
+    cdv = stride - 1u;
+    if (jv >= 0) {
+      float g[3];
+      if (vseed((unsigned)jv, g)) { s.mx += g[0]; s.my += g[1]; s.mz += g[2]; }
+    }
+    --jv;
+  }
+  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState& s, bool entry) {   // PathTerm's
+    if (cd-- != 0u) return;
+    cd = stride - 1u;
+    if ((j >= 0) & !entry) {
+      float g[3];
+      seed((unsigned)j, g);
+      s.lx += g[0]; s.ly += g[1]; s.lz += g[2];
+    }
+    --j;
+  }
+  DRRT_HD void after() {}
+};
+
+template <typename TapFn, typename SeedFn, typename VSeedFn, typename Sink>
+DRRT_HD RayGrad phase_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                    const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                    const float dv[3], unsigned stride, unsigned M, SeedFn&& seed, VSeedFn&& vseed,
+                                    TapFn&& taps, Sink&& sink) {
+  float dxp[3] = {dx[0], dx[1], dx[2]}, dvp[3] = {dv[0], dv[1], dv[2]};
+  unsigned count = 0;
+  const bool failed = max_steps <= 0 || K >= (unsigned)max_steps;
+  if (!failed) {
+    count = path_count(K, stride, M);
+    for (unsigned j = count; j < M; ++j) {
+      float g[3];
+      seed(j, g);
+      dxp[0] += g[0]; dxp[1] += g[1]; dxp[2] += g[2];
+      if (vseed(j, g)) { dvp[0] += g[0]; dvp[1] += g[1]; dvp[2] += g[2]; }
+    }
+  }
+  // the last sample is x_k, k = (count - 1) stride <= K - 1: the march arrives at x_k after K - 1 - k iterations and at
+  // x_{k-1} one later (never for k = 0: the countdown then outlasts the march)
+  const unsigned back = count ? (K - 1u) - (count - 1u) * stride : 0u;
+  PhaseTerm<SeedFn, VSeedFn> term{seed, vseed, stride, back, back + 1u, (int)count - 1, (int)count - 1};
+  RayGrad r = integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dxp, dvp, taps, sink, term);
+  if (r.failed) return r;
+  const unsigned e = K - r.steps;                                         // the skeleton's free-flight prefix
+  for (unsigned j = 0, k = 0; j < count && k <= e; ++j, k += stride) {
+    float g[3];
+    seed(j, g);
+    const float kds = (float)k * ds;
+    for (int a = 0; a < 3; ++a) { r.dp[a] += g[a]; r.dv[a] = fmaf(kds, g[a], r.dv[a]); }
+  }
+  for (unsigned j = 0, k = 0; j < count && k <= e; ++j, k += stride) {
+    float g[3];
+    if (vseed(j, g)) { r.dv[0] += g[0]; r.dv[1] += g[1]; r.dv[2] += g[2]; }
+  }
+  return r;
+}
+
 // ---- the fibre (cable) march: one forward loop, one record-anchored reverse march -------------------------------------
 // trace_cable, with or without a line integral over the samples it takes anyway, is one loop; the adjoints that start
 // from its closest-approach record are one reverse march.  Both skeletons are written once here; an operator supplies an

@@ -14,9 +14,13 @@
 //   drrt_trace_path_f32 / drrt_backtrace_path_f32          path = every stride-th marching position, padded with xt: the
 //                                                          first operator whose per-ray output is a series; dL/dn and the
 //                                                          ray gradients from (xt, vt, path)
+//   drrt_trace_phase_f32 / drrt_backtrace_phase_f32        the path entries with vpath beside path: the marching velocity
+//                                                          at every sample, padded with vt, so that (path[j], vpath[j]) is
+//                                                          the march's state; dL/dn and the ray gradients from
+//                                                          (xt, vt, path, vpath)
 // Per-ray arithmetic: trace_integral_ray / integral_backtrace_ray of drrt_device.h with each operator's integrand and term
-// (trace_opl_ray ... vector_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
-// drrt_march.h.
+// (trace_opl_ray ... phase_backtrace_ray), which tests/hostcheck/integral_rays.hip and phase_path_rays.hip run on the host;
+// shared pieces: drrt_march.h.
 //
 // One ray per lane, everything in registers, as drrt_ray_adjoints.hip: the taps of n go through HeldTaps (pair copy or plain
 // grid), those of a further field through one FieldTaps each (plain gathers of the field itself -- there is no pair copy
@@ -261,6 +265,48 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_path(PathBackArgs a) {
   });
 }
 
+// ---- ray paths with velocities -------------------------------------------------------------------------------------------
+// vpath is laid out and stored like path, one store behind it: in caller order a wave writes one contiguous run of 768 bytes
+// per sample and series.
+template <bool PAIR>
+__global__ void __launch_bounds__(kBlock) k_trace_phase(PhaseTraceArgs a) {
+  unsigned count;
+  trace_lanes<PAIR>(a,
+    [&](size_t i, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
+      auto store = [&](unsigned j, float x, float y, float z, float vx, float vy, float vz) {
+        const size_t e = (size_t)j * a.n + i;
+        st3(a.path, e, x, y, z);
+        st3(a.vpath, e, vx, vy, vz);
+      };
+      return trace_phase_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
+    },
+    [&](size_t i) { a.count[i] = (int)count; });
+}
+
+// GRID: dL/dn is scattered (a.grad is not null)
+template <bool PAIR, bool GRID>
+__global__ void __launch_bounds__(kBlock) k_backtrace_phase(PhaseBackArgs a) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
+    auto seed = [&](unsigned j, float* g) {
+      const Ray3 zero{0.f, 0.f, 0.f};
+      const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;
+      g[0] = d.x; g[1] = d.y; g[2] = d.z;
+    };
+    auto vseed = [&](unsigned j, float* g) {
+      if (!a.dvpath) return false;
+      const Ray3 d = ld3(a.dvpath, (size_t)j * a.n + i);
+      g[0] = d.x; g[1] = d.y; g[2] = d.z;
+      return true;
+    };
+    HeldCorners acc(a.grad);
+    SplatSink<GRID> sink{acc};
+    const RayGrad g = phase_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
+                                          a.stride, a.samples, seed, vseed, taps, sink);
+    if (GRID) acc.flush();
+    return g;
+  });
+}
+
 // ---- launchers ---------------------------------------------------------------------------------------------------------
 // which instantiation of a kernel a call gets: with_bools (drrt_march.h)
 #define LAUNCH_INTEGRAL(kernel, a, s) hipLaunchKernelGGL(kernel, dim3(grid_for((a).n)), dim3(kBlock), 0, s, a)
@@ -302,6 +348,14 @@ void launch_trace_path(const PathTraceArgs& a, hipStream_t s) {
 void launch_backtrace_path(const PathBackArgs& a, hipStream_t s) {
   with_bools([&](auto pair, auto grid) {
     LAUNCH_INTEGRAL((k_backtrace_path<decltype(pair)::value, decltype(grid)::value>), a, s);
+  }, a.vol.pair != nullptr, a.grad != nullptr);
+}
+void launch_trace_phase(const PhaseTraceArgs& a, hipStream_t s) {
+  with_bools([&](auto pair) { LAUNCH_INTEGRAL(k_trace_phase<decltype(pair)::value>, a, s); }, a.vol.pair != nullptr);
+}
+void launch_backtrace_phase(const PhaseBackArgs& a, hipStream_t s) {
+  with_bools([&](auto pair, auto grid) {
+    LAUNCH_INTEGRAL((k_backtrace_phase<decltype(pair)::value, decltype(grid)::value>), a, s);
   }, a.vol.pair != nullptr, a.grad != nullptr);
 }
 

@@ -698,6 +698,41 @@ struct PathBackArgs {
   unsigned stride, samples;                 // the forward's
 };
 
+// ray paths with velocities (drrt_integral.hip): the path entries with a second series, the marching velocity at each sample
+struct PhaseTraceArgs {
+  Vol vol;
+  const float* pos; const float* vel;
+  float* xt; float* vt;
+  float* path; float* vpath;                // (samples, n, 3) each: entry j of ray i at (j n + i) 3
+  int* count;                               // per ray: the entries that are samples (the rest is padding with (xt, vt))
+  uint32_t* steps_out;                      // per-ray iteration counts, caller ray order
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  int max_steps;
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+  unsigned stride, samples;                 // both >= 1; samples n 3 fits size_t (checked by the entry point)
+};
+struct PhaseBackArgs {
+  Vol vol;
+  const float* pos; const float* vel;       // the forward's inputs
+  const float* xt; const float* vt;         // its outputs
+  const uint32_t* fsteps;                   // its per-ray iteration counts, caller ray order
+  const float* dx; const float* dv;         // nullable: seeds on (xt, vt), read as zeros
+  const float* dpath; const float* dvpath;  // nullable: seeds on path / vpath, (samples, n, 3) each
+  float* grad;                              // nullable: no scatter
+  float* dpos; float* dvel;                 // both null: no ray outputs
+  const uint32_t* perm;                     // nullable: visit order
+  drrt_stats* stats;
+  size_t n;
+  float ds;
+  float grad_scale;                         // 1 (as written, Q3) or 1/h (DRRT_FLAG_CORRECTED_H)
+  int max_steps;                            // the FORWARD's (steps_fwd): K >= max_steps marks a failed ray
+  int xcd_order;                            // 1: the launch's blocks take the visit order XCD by XCD (xcd_block)
+  unsigned stride, samples;                 // the forward's
+};
+
 // ---------------------------------------------------------------------------------------------
 // cable (radial profile) variants, src/tracer.cpp:312-382 and :511-567
 // The profile (<= a few hundred floats) lives in LDS; the adjoint accumulates into an LDS copy
@@ -862,6 +897,8 @@ void launch_trace_vector(const VectorTraceArgs& a, hipStream_t s);
 void launch_backtrace_vector(const VectorBackArgs& a, hipStream_t s);
 void launch_trace_path(const PathTraceArgs& a, hipStream_t s);
 void launch_backtrace_path(const PathBackArgs& a, hipStream_t s);
+void launch_trace_phase(const PhaseTraceArgs& a, hipStream_t s);
+void launch_backtrace_phase(const PhaseBackArgs& a, hipStream_t s);
 // cable (drrt_cable.hip): the march and the reference's adjoint; its ray-state adjoint; the march with its optical path
 // length, and its adjoint: grad and/or (dpos, dvel), whichever are non-null; the march with the line integral of a second
 // radial profile, and its adjoint: grad, grad_field and/or (dpos, dvel), whichever are non-null

@@ -882,7 +882,47 @@ class TracerC:
         ``samples=None`` is ``ceil(max_steps / stride) + 1``, the smallest that always ends on xt.  fp32 rays only."""
         return self._trace_path(rif, res, pos, vel, h, ds, stride, samples)[0]
 
+    def _trace_phase(self, rif, res, pos, vel, h, ds, stride, samples=None):
+        stride = int(stride)
+        if samples is None:
+            samples = -(-max(path_max_steps(res, h, ds), 0) // max(stride, 1)) + 1
+        samples = int(samples)
+
+        def outputs(rif_, r):
+            n, dev = r[0].shape[0], r[0].device
+            return _like_rays(rif_, r) + (r[0].new_empty((max(samples, 0), n, 3)), r[0].new_empty((max(samples, 0), n, 3)),
+                                          torch.empty(n, dtype=torch.int32, device=dev),
+                                          torch.empty(n, dtype=torch.int32, device=dev))
+        return _grid_call("drrt_trace_phase_f32", rif, res, [pos, vel], h, ds, outputs, adjoint=False, steps=False,
+                          warn=True, scalars=(stride, samples))
+
+    def trace_phase(self, rif, res, pos, vel, h, ds, stride, samples=None):
+        """``trace_path`` with the marching velocities beside the positions (drrt_trace_phase_f32, include/drrt_hip.h; not
+        in the reference) -> (xt, vt, path, vpath, count, steps).  xt, vt, path, count and steps are ``trace_path``'s bit for
+        bit.  `vpath` is fp32 ``(samples, n, 3)`` in `path`'s layout: ``vpath[j]`` is the velocity the march carries in front
+        of iteration j stride (``vpath[0] = vel``; for j > 0 the velocity that carried the ray into ``path[j]``), `count` of
+        them, then vt repeated.  ``(path[j], vpath[j])`` is the march's state at sample j, and ``|vpath[j]|`` the refractive
+        index the ray saw there.  `samples`: as for ``trace_path``.  fp32 rays only."""
+        return self._trace_phase(rif, res, pos, vel, h, ds, stride, samples)[0]
+
     # ---- adjoint ------------------------------------------------------------------------
+    def backtrace_phase(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, dvpath, h, ds, stride, grid: bool = True,
+                        rays: bool = True, into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
+                        samples: Optional[int] = None):
+        """Adjoint of ``trace_phase`` (drrt_backtrace_phase_f32, include/drrt_hip.h) -> (grad | None, dpos | None, dvel |
+        None): ``backtrace_path`` with one more seed, `dvpath` ((samples, n, 3), None: zeros), from ONE reverse march.  With
+        `dvpath` None the results are ``backtrace_path``'s bit for bit.  `samples` is read off whichever of `dpath` and
+        `dvpath` is given; it is needed only when both are None (then any value gives the same result, and the default is
+        1).  Seeds on padded `vpath` entries are seeds on vt, added to dv in ascending j.  Everything else: as for
+        ``backtrace_path``."""
+        if samples is None:
+            given = dpath if dpath is not None else dvpath
+            samples = 1 if given is None else int(given.shape[0])
+        shape = (int(samples), None, 3)
+        return _backtrace_integral("phase", rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (), ((grid, into, "into"),),
+                                   rays, h, ds, order, series=((dpath, shape), (dvpath, shape)),
+                                   scalars=(int(stride), int(samples)))
+
     def backtrace_path(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, h, ds, stride, grid: bool = True,
                        rays: bool = True, into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
                        samples: Optional[int] = None):

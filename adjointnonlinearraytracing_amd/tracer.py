@@ -494,6 +494,36 @@ class PathTracerC(torch.autograd.Function):
         return (*_integral_backward(ctx, back, grad_x, grad_v, grad_path), None, None, None, None)
 
 
+class PhasePathTracerC(torch.autograd.Function):
+    """``apply(rif, x, v, h, ds, stride, samples) -> (xt, vt, path, vpath, count)``: PathTracerC with the marching velocities
+    beside the positions.  ``vpath`` has ``path``'s shape: ``vpath[j]`` is the velocity the march carries in front of
+    iteration j stride (``vpath[0] = v``), ``count`` of them per ray, then vt repeated, so ``(path[j], vpath[j])`` is the
+    march's state at sample j and ``|vpath[j]|`` the refractive index the ray saw there -- what a chord of ``path`` cannot
+    give at a stride above 1.  xt, vt, path and vpath are differentiable w.r.t. ``rif``, ``x`` and ``v``: an integrand that
+    depends on the ray's direction (a Doppler or Faraday term with an analytic or MLP flow, an anisotropic emitter) or a
+    loss on the direction of a bundle at depth is a few lines of torch.  Not in the reference.
+
+    The forward is ``TracerC.trace_phase``; backward is ONE ``TracerC.backtrace_phase`` launch (plus the zero-fill of the
+    grid gradient when ``rif`` requires grad), the derivative of the discrete forward with the iteration counts and
+    ``count`` held fixed.  Options, kept copies, failed rays and dtypes: as for PathTracerC."""
+
+    @staticmethod
+    def forward(ctx, rif, x, v, h, ds, stride, samples=None):
+        def march(*a):
+            out, order, left = drrt.TracerC()._trace_phase(*a, stride, samples)
+            ctx.stride, ctx.samples = int(stride), int(out[2].shape[0])
+            return out, order, left
+        xt, vt, path, vpath, count = _integral_forward(ctx, "PhasePathTracerC", march, rif, (), x, v, h, ds)
+        ctx.mark_non_differentiable(count)
+        return xt, vt, path, vpath, count
+
+    @staticmethod
+    def backward(ctx, grad_x, grad_v, grad_path, grad_vpath, _grad_count=None):
+        def back(*a, **kw):             # a: (rif, shape, x0, v0, xt, vt, steps, dx, dv, dpath, dvpath, h, ds, grid, rays)
+            return drrt.TracerC().backtrace_phase(*a[:13], ctx.stride, *a[13:], samples=ctx.samples, **kw)
+        return (*_integral_backward(ctx, back, grad_x, grad_v, grad_path, grad_vpath), None, None, None, None)
+
+
 def _cable_integral_forward(ctx, name, march, profiles, radius, length, x, v, sp, ds):
     """Forward of a fibre march with an integral up to the record: ``march(flat profiles..., radius, length, x, v, sp, ds)
     -> (xt, vt, dist2, integral, rec_steps)`` (``TracerC.trace_cable_opl`` / ``trace_cable_field``) on detached inputs ->

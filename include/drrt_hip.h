@@ -579,6 +579,52 @@ DRRT_API int drrt_backtrace_path_f32(const float* rif, long long nvox, const int
                        drrt_stats* stats, void* workspace, size_t workspace_bytes,
                        unsigned flags, void* stream);
 
+/* ---- ray paths with velocities: the march's state at every sample (not in the reference) ------------------------------
+ * drrt_trace_phase_f32 is drrt_trace_path_f32 with one more output, vpath: xt, vt, path, count, steps_out and the
+ * statistics are that call's bit for bit.  Per ray, with v_k the marching velocity in front of iteration k -- v_0 = vel,
+ * and for k >= 1 the velocity that carried the ray from x_{k-1} to x_k: x_k = fmaf(ds, v_k, x_{k-1}), fp32, the march's own
+ * values -- and count as there:
+ *   vpath[j]   = v_{j stride}  for j < count
+ *   vpath[j]   = vt            for count <= j < M (padding, whatever the march's conventions make vt: the stale vel for a
+ *                failed ray, Q6, and vel for a ray that never samples inside)
+ * so (path[j], vpath[j]) is the march's state at sample j, and a series that is long enough ends on (xt, vt).  |v| = n along
+ * the march: |vpath[j]| is the refractive index the ray saw at sample j.  A chord of path, (path[j+1] - path[j]) /
+ * (ds stride), is NOT vpath[j] for stride > 1.
+ *   vpath      out, required: fp32 (M, n, 3) in path's layout, stored in path's order (one contiguous run per sample and
+ *              series from a wave that visits the rays in caller order)
+ * Everything else -- arguments, flags, workspace, DRRT_ERR_ARG (the size_t overflow check holds for each series; vpath is
+ * checked with the ray pointers) -- is as for drrt_trace_path_f32.  fp32 only.                                            */
+DRRT_API int drrt_trace_phase_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel, float h, float ds, int stride, int samples,
+                       float* xt, float* vt, float* path, float* vpath, int* count, uint32_t* steps_out,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
+/* Adjoint of drrt_trace_phase_f32: drrt_backtrace_path_f32 with one more seed, dvpath = dL/dvpath ((M, n, 3), nullable:
+ * read as zeros), the derivative of the discrete forward with K and count held fixed.  ONE reverse march yields dL/dn
+ * (grad), dL/dpos and dL/dvel; with dvpath null every result is drrt_backtrace_path_f32's bit for bit.  The seeds on path
+ * are placed as there.  With e the free-flight prefix of the ray:
+ *   * the seed on a sample v_k, e < k < K, is a seed on the total adjoint of v_k (v_k enters only through x_k = x_{k-1} +
+ *     ds v_k and v_{k+1} = v_k + ...): it is added to mu at the start of the reverse iteration that arrives at x_{k-1}, in
+ *     front of that iteration's sample, so that mu . grad n, the contribution to grad and dL/dvel see it.  That is one
+ *     reverse iteration behind the position seed on x_k; the sample k = e + 1 is seeded in the entry iteration;
+ *   * v_k = vel bit for bit for k <= e: these seeds are added to dvel behind the march (and behind the prefix's position
+ *     seeds) in ascending j, and add nothing to dpos;
+ *   * the seeds on padded entries are seeds on vt: they are added to dv in ascending j, in fp32, ((dv + g_count) +
+ *     g_{count+1}) + ..., before the march is initialised, so mu = dv + ds dx sees them;
+ *   * a ray that never sampled inside (e = K) gets drrt_backtrace_path_f32's result with every vpath seed added to dvel;
+ *     a failed ray gets zeros (no seed is read), contributes nothing and counts in stats->n_failed.
+ * Outputs, flags, hints and DRRT_ERR_ARG: as for drrt_backtrace_path_f32.  fp32 only.                                    */
+DRRT_API int drrt_backtrace_phase_f32(const float* rif, long long nvox, const int res[3], size_t n,
+                       const float* pos, const float* vel,
+                       const float* xt, const float* vt,
+                       const uint32_t* fwd_steps,
+                       const float* dx, const float* dv, const float* dpath, const float* dvpath, float h, float ds,
+                       int stride, int samples,
+                       float* grad, float* dpos, float* dvel,
+                       drrt_stats* stats, void* workspace, size_t workspace_bytes,
+                       unsigned flags, void* stream);
+
 /* fp16 ray-state variant of drrt_backtrace_f32: xt, vt, dx, dv are (n,3) IEEE half, the adjoint
  * recurrences and the accumulation into `grad` stay fp32.                                        */
 DRRT_API int drrt_backtrace_f16io(const float* rif, long long nvox, const int res[3], size_t n,
@@ -983,6 +1029,8 @@ DRRT_API int drrt_gen_cone_rays_f32(const float* u, const float* view_rot, int n
 #define DRRT_PROF_BACKTRACE_CABLE_FIELD 22 /* its adjoint: dL/d(profile), dL/d(field) and the ray gradients in one march (drrt_backtrace_cable_field_f32) */
 #define DRRT_PROF_TRACE_PATH 23      /* trace with every stride-th position of every ray (drrt_trace_path_f32) */
 #define DRRT_PROF_BACKTRACE_PATH 24  /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_path_f32) */
+#define DRRT_PROF_TRACE_PHASE 25     /* trace with every stride-th position AND velocity of every ray (drrt_trace_phase_f32) */
+#define DRRT_PROF_BACKTRACE_PHASE 26 /* its adjoint: dL/dn and the ray gradients in one march (drrt_backtrace_phase_f32) */
 DRRT_API int  drrt_profile_begin(int capacity);
 DRRT_API int  drrt_profile_collect(int* kernel_ids, float* ms, int max_out);
 DRRT_API void drrt_profile_end(void);

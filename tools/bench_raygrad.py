@@ -116,6 +116,14 @@ path    drrt_trace_path_f32 / drrt_backtrace_path_f32 (k_trace_path, k_backtrace
             backtrace_{opl,path}_{rays,grid,both}             the adjoints, every seed set (dpath: ones)
         usage: bench_raygrad.py path [--grid 256] [--rays 1048576] [--strides 1 8 64] [--rounds 7] [--warmup 2] [--once] [--out FILE]
         Also writes the JSON, with the library's version string, to --out (default profiles/path_bench.json).
+phase   drrt_trace_phase_f32 / drrt_backtrace_phase_f32 (k_trace_phase, k_backtrace_phase) next to the path calls, on the
+        workload, strides and orders of `path`; all nine calls of a combination alternate in one process:
+            trace_opl / trace_path / trace_phase              the forward; trace_path_extra_ms = trace_path - trace_opl and
+                                                              trace_phase_extra_ms = trace_phase - trace_path are each the
+                                                              cost of writing one series of samples n 12 bytes
+            backtrace_{path,phase}_{rays,grid,both}           the adjoints, every seed set (dpath, dvpath: ones)
+        usage: bench_raygrad.py phase [--grid 256] [--rays 1048576] [--strides 1 8 64] [--rounds 7] [--warmup 2] [--once] [--out FILE]
+        Also writes the JSON, with the library's version string, to --out (default profiles/phase_bench.json).
 
 cable, stop and target time the three calls of a case alternately (one of each per round) with device events around the whole
 call, so that drift of the machine hits all three alike.  Output: per case and call the median, minimum and maximum ms
@@ -600,6 +608,58 @@ def path(a, dev):
     return out
 
 
+def phase(a, dev):
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl` and `path`
+    h = 1.0 / (a.grid - 1)
+    ds = h / 2
+    n = pos.shape[0]
+    T = drrt.TracerC()
+    one = torch.ones_like(pos)
+    rif = bench.make_grid(a.grid, dev)
+    res = tuple(rif.shape)
+    ms = drrt.path_max_steps(res, h, ds)
+    out = dict(grid=a.grid, rays=n, h=h, ds=ds, max_steps=ms, rounds=a.rounds, library=_lib.load().drrt_version().decode())
+    for order_name, sort in (("pixel", False), ("sorted", True)):
+        for stride in a.strides:
+            m = -(-ms // stride) + 1
+            with drrt.using(sort_rays=sort):
+                xt, vt, pth, count, steps = T.trace_path(rif, res, pos, vel, h, ds, stride, m)
+                order = drrt.keep_order(drrt.last_order)
+                dpath = torch.ones_like(pth)
+                dvpath = torch.ones_like(pth)
+                del pth
+                bp = lambda **kw: T.backtrace_path(rif, res, pos, vel, xt, vt, steps, one, one, dpath, h, ds, stride,   # noqa: E731
+                                                   order=order, **kw)
+                bq = lambda **kw: T.backtrace_phase(rif, res, pos, vel, xt, vt, steps, one, one, dpath, dvpath, h, ds, stride,   # noqa: E731
+                                                    order=order, **kw)
+                r, med = time_each({
+                    "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
+                    "trace_path": lambda: T.trace_path(rif, res, pos, vel, h, ds, stride, m),
+                    "trace_phase": lambda: T.trace_phase(rif, res, pos, vel, h, ds, stride, m),
+                    "backtrace_path_rays": lambda: bp(grid=False), "backtrace_phase_rays": lambda: bq(grid=False),
+                    "backtrace_path_grid": lambda: bp(rays=False), "backtrace_phase_grid": lambda: bq(rays=False),
+                    "backtrace_path_both": bp, "backtrace_phase_both": bq,
+                }, a)
+            del dpath, dvpath
+            if r is None:
+                continue
+            r["samples"], r["mean_count"], r["series_bytes"] = m, float(count.float().mean()), m * n * 12
+            # both differences are the cost of writing one series of samples n 12 bytes
+            r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
+            r["trace_phase_extra_ms"] = med["trace_phase"] - med["trace_path"]
+            r["series_bytes_at_8TBps_ms"] = m * n * 12 / 8e12 * 1e3
+            r["trace_phase_over_trace_path"] = med["trace_phase"] / med["trace_path"]
+            for k in ("rays", "grid", "both"):
+                r[f"backtrace_phase_{k}_over_backtrace_path_{k}"] = med[f"backtrace_phase_{k}"] / med[f"backtrace_path_{k}"]
+            out[f"{order_name}_stride{stride}"] = r
+    if a.once:
+        return {}
+    with open(a.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser(description="ray-state adjoint timings; see the module docstring")
     sub = ap.add_subparsers(dest="workload", required=True)
@@ -648,14 +708,20 @@ def main():
     p_path.add_argument("--strides", type=int, nargs="+", default=[1, 8, 64])
     p_path.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "path_bench.json"))
     p_path.set_defaults(run=path)
-    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis, p_vec, p_path):
+    p_phase = sub.add_parser("phase")
+    p_phase.add_argument("--grid", type=int, default=256)
+    p_phase.add_argument("--rays", type=int, default=1 << 20)
+    p_phase.add_argument("--strides", type=int, nargs="+", default=[1, 8, 64])
+    p_phase.add_argument("--out", default=os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "phase_bench.json"))
+    p_phase.set_defaults(run=phase)
+    for p in (p_cable, p_stop, p_target, p_opl, p_field, p_emis, p_vec, p_path, p_phase):
         p.add_argument("--rounds", type=int, default=7)
         p.add_argument("--warmup", type=int, default=2)
         p.add_argument("--once", action="store_true")
     a = ap.parse_args()
     if a.workload == "cable" and (a.side < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--side and --rounds must be positive, --warmup non-negative")
-    if a.workload in ("stop", "target", "opl", "field", "emission", "vector", "path") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
+    if a.workload in ("stop", "target", "opl", "field", "emission", "vector", "path", "phase") and (a.grid < 4 or a.rays < 1 or a.rounds < 1 or a.warmup < 0):
         ap.error("--grid >= 4, --rays and --rounds positive, --warmup non-negative")
     if not torch.cuda.is_available():
         sys.exit("bench_raygrad: needs a GPU")

@@ -5,7 +5,7 @@ the working tree.
 Every unit of the library is compiled with the Makefile's own commands (``make -n``: its CXXFLAGS, and RINGFLAGS for
 the ring-window unit) with ``-c`` replaced by ``--cuda-device-only -S``, once from ``git archive BASE_REV`` and once
 from the working tree.  The bodies of k_backtrace_flat, k_backtrace_ring, k_backtrace_direct, k_backtrace_rays,
-k_backtrace_opl, k_backtrace_field, k_backtrace_emission, k_backtrace_vector, k_backtrace_path (k_trace_opl, k_trace_field, k_trace_emission, k_trace_vector and k_trace_path come with k_trace*), k_backtrace_cable*, k_backtrace_stop_rays*, k_backtrace_target_rays, k_target_* (the forward target march and the count pass
+k_backtrace_opl, k_backtrace_field, k_backtrace_emission, k_backtrace_vector, k_backtrace_path, k_backtrace_phase (k_trace_opl, k_trace_field, k_trace_emission, k_trace_vector, k_trace_path and k_trace_phase come with k_trace*), k_backtrace_cable*, k_backtrace_stop_rays*, k_backtrace_target_rays, k_target_* (the forward target march and the count pass
 of its ray-state adjoint), k_bundle_classify, k_trace*, the utility kernels of drrt_api.hip (k_build_pair,
 k_q16_*, k_chunk_progress_init), the sort-key kernels (k_lightfield_keys, k_chord_keys) and the operator kernels around the march (k_sensor_*, k_gen_*, k_upres, k_adam_masked,
 k_rays_to_plane*) are compared instantiation by instantiation, with the label numbers (which depend on a function's
@@ -18,7 +18,7 @@ import subprocess
 import sys
 import tempfile
 
-KERNELS = ("k_backtrace_flat", "k_backtrace_ring", "k_backtrace_direct", "k_backtrace_rays", "k_backtrace_opl", "k_backtrace_field", "k_backtrace_emission", "k_backtrace_vector", "k_backtrace_path", "k_backtrace_cable",
+KERNELS = ("k_backtrace_flat", "k_backtrace_ring", "k_backtrace_direct", "k_backtrace_rays", "k_backtrace_opl", "k_backtrace_field", "k_backtrace_emission", "k_backtrace_vector", "k_backtrace_path", "k_backtrace_phase", "k_backtrace_cable",
            "k_backtrace_stop_rays", "k_backtrace_target_rays", "k_target_", "k_bundle_classify", "k_trace", "k_build_pair", "k_q16_", "k_chunk_progress_init",
            "k_sensor_", "k_gen_", "k_upres", "k_adam_masked", "k_rays_to_plane", "k_lightfield_keys", "k_chord_keys")
 CSRC = "adjointnonlinearraytracing_amd/csrc"
