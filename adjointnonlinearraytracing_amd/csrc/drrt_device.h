@@ -838,6 +838,9 @@ struct NoTerm {                              // trace itself: nothing is integra
 struct NoSink {                              // a ray-state adjoint: no contribution to dL/dn is formed
   DRRT_HD void operator()(const Cell&, float, float, float, float) {}
 };
+struct NoVSeed {                             // a ray path without the velocity series: statically no seed on vpath
+  DRRT_HD bool operator()(unsigned, float*) const { return false; }
+};
 
 struct RevMarch { AdjState s; float qx, qy, qz; };
 
@@ -1264,123 +1267,33 @@ DRRT_HD RayGrad vector_backtrace_ray(const Vol& V, float ds, float grad_scale, i
 }
 
 // ---- ray paths ---------------------------------------------------------------------------------------------------------
-// Where the ray went: every stride-th marching position, as a series of M entries per ray.  With K the ray's iteration
-// count and x_k the marching position in front of iteration k (x_0 = p, the march's own fp32 values),
-//   count   = min(M, ceil(K / stride))      the strided samples x_{j stride} with j stride < K that fit
-//   path[j] = x_{j stride}   for j < count
-//   path[j] = xt             for count <= j < M   (padding: a series that is long enough ends on the exit position; a
-//                                                  ray that never samples inside the box has xt = p, Q6)
-// M stride < K truncates the series (no padding, no error).  x_K, the position behind the last iteration, is no sample: it
-// is xt for a ray that left through a face.  Not in the reference.
+// Where the ray went: the march's state in front of every stride-th iteration, as two series of M entries per ray, the
+// positions (path) and, for a caller that asks for it, the velocities beside them (vpath: the march's phase-space state).
+// With K the ray's iteration count, x_k the marching position in front of iteration k (x_0 = p, the march's own fp32 values)
+// and v_k the marching velocity there (v_0 = v, and for k >= 1 the velocity that carried the ray from x_{k-1} to x_k,
+// x_k = fmaf(ds, v_k, x_{k-1}) in fwd_step_c),
+//   count    = min(M, ceil(K / stride))              the strided samples with j stride < K that fit
+//   path[j]  = x_{j stride},  vpath[j] = v_{j stride}   for j < count
+//   path[j]  = xt,            vpath[j] = vt             for count <= j < M
+// The padding makes a series that is long enough end on the exit state (xt, vt): a ray that never samples inside the box
+// has xt = p and vt = v (Q6), and vt is the stale v for a failed ray (Q6).  M stride < K truncates the series (no padding,
+// no error).  x_K, the position behind the last iteration, is no sample: it is xt for a ray that left through a face.
+// |v| = n along the march, so |vpath[j]| is the refractive index the ray saw there.  One routine pair does this,
+// trace_phase_ray / phase_backtrace_ray; path alone is the same pair with the velocity series absent -- trace_path_ray
+// drops the velocities in front of the caller's store, path_backtrace_ray seeds none (NoVSeed) -- and every other output,
+// and the adjoint without a seed on vpath, is bit for bit what it is with the series.  Not in the reference.
 constexpr unsigned path_count(unsigned K, unsigned stride, unsigned M) {
   const unsigned all = K ? (K - 1u) / stride + 1u : 0u;
   return all < M ? all : M;
 }
 
-// `store(j, x, y, z)` writes path[j] of the ray.  The iteration behind which the next sample is due is counted down to
-// (no division in the loop).  The position behind iteration `it` is x_{it+1}: it is written when it + 1 is a multiple of
-// stride, the series has room, and the iteration did not flag the ray (then K = it + 1 and x_K is no sample).  A failed ray
-// (K = max_steps, never flagged) may write x_K when stride divides K; that entry is padding, and xt = x_K for such a ray.
+// `store(j, x, y, z, vx, vy, vz)` writes path[j] and vpath[j] of the ray.  The iteration behind which the next sample is due
+// is counted down to (no division in the loop).  The state behind iteration `it` is (x_{it+1}, v_{it+1}): it is written when
+// it + 1 is a multiple of stride, the series has room, and the iteration did not flag the ray (then K = it + 1 and x_K is no
+// sample).  A failed ray (K = max_steps, never flagged) may write x_K when stride divides K; that entry is padding, and
+// xt = x_K for such a ray.
 template <typename StoreFn>
 struct PathIntegrand {
-  StoreFn& store;
-  unsigned stride, M, cd, j;
-  DRRT_HD void operator()(const Cell&, bool, float) {}
-  DRRT_HD void step(const FwdState& s) {
-    if (--cd != 0u) return;
-    cd = stride;
-    if (!s.esc & (j < M)) store(j, s.x, s.y, s.z);
-    ++j;
-  }
-};
-
-// trace for ONE ray, with its path: stride >= 1, M >= 1.  All M entries are written: x_0 in front of the loop, the samples
-// from the loop, the padding behind it.
-template <typename TapFn, typename StoreFn>
-DRRT_HD RayOut trace_path_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], unsigned stride,
-                              unsigned M, TapFn&& taps, StoreFn&& store, unsigned& count) {
-  store(0u, p[0], p[1], p[2]);
-  PathIntegrand<StoreFn> q{store, stride, M, stride, 1u};
-  const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
-  count = path_count(o.steps, stride, M);
-  for (unsigned j = count; j < M; ++j) store(j, o.xt[0], o.xt[1], o.xt[2]);
-  return o;
-}
-
-// Adjoint of trace_path_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn from the seeds (dx, dv) on
-// (xt, vt) and `seed(j, g)`, which writes the seed on path[j] to g[3] (zeros when there is none), with K and count held
-// fixed.  The reverse iteration that arrives at x_k adds the seed on a sample x_k, k > e, to lambda in `pull`, in front of
-// adj_recur, whose closing mu += ds lambda must see it (x_k = x_{k-1} + ds v_k).  The iterations are counted down to the
-// next sample as in the forward.  What the reverse march does not reach is added around it, in this order:
-//   * padding: the seeds on path[count .. M-1] are seeds on xt and are added to dx in ascending j, in fp32, before the march
-//     is initialised, so mu = dv + ds dx sees them;
-//   * prefix: the samples x_k = p + k ds v of the free flight in front of the box, k <= e (x_e included: the reverse march
-//     ends on lambda = dL/dx_e), are added to the result behind the march in ascending j: dpos += g,
-//     dvel = fmaf((float)k * ds, g, dvel), k = j stride -- the way the skeleton forms e ds.
-// A ray that never sampled inside (e = K) returns (dx, dv) with its padding and prefix seeds and contributes nothing; a
-// failed ray returns zeros (no seed is read).
-template <typename SeedFn>
-struct PathTerm {
-  SeedFn& seed;
-  unsigned stride, cd;                       // cd: reverse iterations until one arrives at the sample j
-  int j;                                     // the next sample the march arrives at; < 0: none left
-  DRRT_HD void enter(const Vol&, const Cell&, AdjState&) {}
-  DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
-  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState& s, bool entry) {
-    if (cd-- != 0u) return;
-    cd = stride - 1u;
-    if ((j >= 0) & !entry) {
-      float g[3];
-      seed((unsigned)j, g);
-      s.lx += g[0]; s.ly += g[1]; s.lz += g[2];
-    }
-    --j;
-  }
-  DRRT_HD void after() {}
-};
-
-template <typename TapFn, typename SeedFn, typename Sink>
-DRRT_HD RayGrad path_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
-                                   const float v0[3], const float xt[3], const float vt[3], const float dx[3],
-                                   const float dv[3], unsigned stride, unsigned M, SeedFn&& seed, TapFn&& taps, Sink&& sink) {
-  float dxp[3] = {dx[0], dx[1], dx[2]};
-  unsigned count = 0;
-  const bool failed = max_steps <= 0 || K >= (unsigned)max_steps;
-  if (!failed) {
-    count = path_count(K, stride, M);
-    for (unsigned j = count; j < M; ++j) {
-      float g[3];
-      seed(j, g);
-      dxp[0] += g[0]; dxp[1] += g[1]; dxp[2] += g[2];
-    }
-  }
-  PathTerm<SeedFn> term{seed, stride, count ? (K - 1u) - (count - 1u) * stride : 0u, (int)count - 1};
-  RayGrad r = integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dxp, dv, taps, sink, term);
-  if (r.failed) return r;
-  const unsigned e = K - r.steps;                                         // the skeleton's free-flight prefix
-  for (unsigned j = 0, k = 0; j < count && k <= e; ++j, k += stride) {
-    float g[3];
-    seed(j, g);
-    const float kds = (float)k * ds;
-    for (int a = 0; a < 3; ++a) { r.dp[a] += g[a]; r.dv[a] = fmaf(kds, g[a], r.dv[a]); }
-  }
-  return r;
-}
-
-// ---- ray paths with velocities (the march's phase-space state) -----------------------------------------------------------
-// trace_path_ray with a second series beside path: with v_k the marching velocity in front of iteration k (v_0 = v, and for
-// k >= 1 the velocity that carried the ray from x_{k-1} to x_k, x_k = fmaf(ds, v_k, x_{k-1}) in fwd_step_c),
-//   vpath[j] = v_{j stride}  for j < count
-//   vpath[j] = vt            for count <= j < M   (padding: the stale v for a failed ray, Q6; v for a ray that never
-//                                                  samples inside)
-// so (path[j], vpath[j]) is the march's state at sample j and a series that is long enough ends on (xt, vt).  |v| = n along
-// the march, so |vpath[j]| is the refractive index the ray saw there.  Everything else is trace_path_ray's bit for bit.
-// Not in the reference.
-
-// `store(j, x, y, z, vx, vy, vz)` writes path[j] and vpath[j] of the ray; counted down as PathIntegrand.  The state behind
-// iteration `it` is (x_{it+1}, v_{it+1}).
-template <typename StoreFn>
-struct PhaseIntegrand {
   StoreFn& store;
   unsigned stride, M, cd, j;
   DRRT_HD void operator()(const Cell&, bool, float) {}
@@ -1392,33 +1305,49 @@ struct PhaseIntegrand {
   }
 };
 
-// trace for ONE ray, with both series: stride >= 1, M >= 1.  All M entries of each are written.
+// trace for ONE ray, with both series: stride >= 1, M >= 1.  All M entries are written: sample 0 in front of the loop, the
+// samples from the loop, the padding behind it.
 template <typename TapFn, typename StoreFn>
 DRRT_HD RayOut trace_phase_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], unsigned stride,
                                unsigned M, TapFn&& taps, StoreFn&& store, unsigned& count) {
   store(0u, p[0], p[1], p[2], v[0], v[1], v[2]);
-  PhaseIntegrand<StoreFn> q{store, stride, M, stride, 1u};
+  PathIntegrand<StoreFn> q{store, stride, M, stride, 1u};
   const RayOut o = trace_integral_ray(V, ds, max_steps, p, v, taps, q);
   count = path_count(o.steps, stride, M);
   for (unsigned j = count; j < M; ++j) store(j, o.xt[0], o.xt[1], o.xt[2], o.vt[0], o.vt[1], o.vt[2]);
   return o;
 }
+// with the positions alone: `store(j, x, y, z)` writes path[j]
+template <typename TapFn, typename StoreFn>
+DRRT_HD RayOut trace_path_ray(const Vol& V, float ds, int max_steps, const float p[3], const float v[3], unsigned stride,
+                              unsigned M, TapFn&& taps, StoreFn&& store, unsigned& count) {
+  auto positions = [&](unsigned j, float x, float y, float z, float, float, float) { store(j, x, y, z); };
+  return trace_phase_ray(V, ds, max_steps, p, v, stride, M, taps, positions, count);
+}
 
-// Adjoint of trace_phase_ray for ONE ray: path_backtrace_ray with `vseed(j, g)` beside `seed(j, g)`: it writes the seed on
-// vpath[j] to g[3] and returns true, or returns false when there is none (nothing is added then, so the results are
-// path_backtrace_ray's bit for bit).  The position seeds are placed as there.  A sample v_k, e < k < K, enters only through
-// x_k = x_{k-1} + ds v_k and v_{k+1} = v_k + ..., so its seed is one on the total adjoint of v_k: mu when the reverse
-// iteration that arrives at x_{k-1} begins.  It is added in `enter`, in front of that iteration's sample, so that dn, the
-// contribution to dL/dn and q (dL/dvel) see it -- one reverse iteration behind the position seed on x_k; the sample k = e + 1
-// is seeded in the entry iteration.  Around the march, in this order:
-//   * padding: the seeds on vpath[count .. M-1] are seeds on vt and are added to dv in ascending j, in fp32, before the
-//     march is initialised, so mu = dv + ds dx sees them;
-//   * prefix: v_k = v bit for bit for k <= e, so these seeds are added to dvel behind the march (and behind the position
-//     seeds of the prefix) in ascending j; they add nothing to dpos.
-// A ray that never sampled inside (e = K) returns path_backtrace_ray's result with every vpath seed added to dvel; a failed
-// ray returns zeros (no seed is read).
+// Adjoint of trace_phase_ray for ONE ray: dL/dpos, dL/dvel and the contributions to dL/dn from the seeds (dx, dv) on
+// (xt, vt), `seed(j, g)`, which writes the seed on path[j] to g[3] (zeros when there is none), and `vseed(j, g)`, which
+// writes the seed on vpath[j] to g[3] and returns true, or returns false when there is none (nothing is added then), with K
+// and count held fixed.  Where each kind of seed enters:
+//   * a sample x_k, k > e: the reverse iteration that arrives at x_k adds its seed to lambda in `pull`, in front of
+//     adj_recur, whose closing mu += ds lambda must see it (x_k = x_{k-1} + ds v_k);
+//   * a sample v_k, e < k < K, enters only through x_k = x_{k-1} + ds v_k and v_{k+1} = v_k + ..., so its seed is one on
+//     the total adjoint of v_k: mu when the reverse iteration that arrives at x_{k-1} begins.  It is added in `enter`, in
+//     front of that iteration's sample, so that dn, the contribution to dL/dn and q (dL/dvel) see it -- one reverse
+//     iteration behind the position seed on x_k; the sample k = e + 1 is seeded in the entry iteration.
+// The iterations are counted down to the next sample as in the forward.  What the reverse march does not reach is added
+// around it, in this order:
+//   * padding: the seeds on path[count .. M-1] / vpath[count .. M-1] are seeds on xt / vt and are added to dx / dv in
+//     ascending j, in fp32, before the march is initialised, so mu = dv + ds dx sees them;
+//   * prefix: the samples x_k = p + k ds v of the free flight in front of the box, k <= e (x_e included: the reverse march
+//     ends on lambda = dL/dx_e), are added to the result behind the march in ascending j: dpos += g,
+//     dvel = fmaf((float)k * ds, g, dvel), k = j stride -- the way the skeleton forms e ds.  v_k = v bit for bit for
+//     k <= e, so the velocity seeds of the prefix are added to dvel behind the position seeds, in ascending j; they add
+//     nothing to dpos.
+// A ray that never sampled inside (e = K) returns (dx, dv) with its padding and prefix seeds (every vpath seed on dvel) and
+// contributes nothing; a failed ray returns zeros (no seed is read).
 template <typename SeedFn, typename VSeedFn>
-struct PhaseTerm {
+struct PathTerm {
   SeedFn& seed;
   VSeedFn& vseed;
   unsigned stride, cd, cdv;                  // cd / cdv: reverse iterations until one arrives at x_k / x_{k-1} of a sample k
@@ -1433,7 +1362,7 @@ struct PhaseTerm {
     --jv;
   }
   DRRT_HD float dn(const Vol&, const Cell&, const AdjSample&, float mg) { return mg; }
-  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState& s, bool entry) {   // PathTerm's
+  DRRT_HD void pull(const Vol&, const Cell&, const AdjSample&, AdjState& s, bool entry) {
     if (cd-- != 0u) return;
     cd = stride - 1u;
     if ((j >= 0) & !entry) {
@@ -1466,7 +1395,7 @@ DRRT_HD RayGrad phase_backtrace_ray(const Vol& V, float ds, float grad_scale, in
   // the last sample is x_k, k = (count - 1) stride <= K - 1: the march arrives at x_k after K - 1 - k iterations and at
   // x_{k-1} one later (never for k = 0: the countdown then outlasts the march)
   const unsigned back = count ? (K - 1u) - (count - 1u) * stride : 0u;
-  PhaseTerm<SeedFn, VSeedFn> term{seed, vseed, stride, back, back + 1u, (int)count - 1, (int)count - 1};
+  PathTerm<SeedFn, VSeedFn> term{seed, vseed, stride, back, back + 1u, (int)count - 1, (int)count - 1};
   RayGrad r = integral_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dxp, dvp, taps, sink, term);
   if (r.failed) return r;
   const unsigned e = K - r.steps;                                         // the skeleton's free-flight prefix
@@ -1481,6 +1410,13 @@ DRRT_HD RayGrad phase_backtrace_ray(const Vol& V, float ds, float grad_scale, in
     if (vseed(j, g)) { r.dv[0] += g[0]; r.dv[1] += g[1]; r.dv[2] += g[2]; }
   }
   return r;
+}
+// Adjoint of trace_path_ray: no seed on vpath
+template <typename TapFn, typename SeedFn, typename Sink>
+DRRT_HD RayGrad path_backtrace_ray(const Vol& V, float ds, float grad_scale, int max_steps, unsigned K, const float p0[3],
+                                   const float v0[3], const float xt[3], const float vt[3], const float dx[3],
+                                   const float dv[3], unsigned stride, unsigned M, SeedFn&& seed, TapFn&& taps, Sink&& sink) {
+  return phase_backtrace_ray(V, ds, grad_scale, max_steps, K, p0, v0, xt, vt, dx, dv, stride, M, seed, NoVSeed{}, taps, sink);
 }
 
 // ---- the fibre (cable) march: one forward loop, one record-anchored reverse march -------------------------------------

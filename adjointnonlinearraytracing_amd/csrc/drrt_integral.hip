@@ -17,10 +17,11 @@
 //   drrt_trace_phase_f32 / drrt_backtrace_phase_f32        the path entries with vpath beside path: the marching velocity
 //                                                          at every sample, padded with vt, so that (path[j], vpath[j]) is
 //                                                          the march's state; dL/dn and the ray gradients from
-//                                                          (xt, vt, path, vpath)
+//                                                          (xt, vt, path, vpath).  The same routine and lane bodies as the
+//                                                          path entries, which are these with the velocity series absent
 // Per-ray arithmetic: trace_integral_ray / integral_backtrace_ray of drrt_device.h with each operator's integrand and term
-// (trace_opl_ray ... phase_backtrace_ray), which tests/hostcheck/integral_rays.hip and phase_path_rays.hip run on the host;
-// shared pieces: drrt_march.h.
+// (trace_opl_ray ... phase_backtrace_ray), which tests/hostcheck/integral_rays.hip runs on the host; shared pieces:
+// drrt_march.h.
 //
 // One ray per lane, everything in registers, as drrt_ray_adjoints.hip: the taps of n go through HeldTaps (pair copy or plain
 // grid), those of a further field through one FieldTaps each (plain gathers of the field itself -- there is no pair copy
@@ -235,75 +236,77 @@ __global__ void __launch_bounds__(kBlock) k_backtrace_vector(VectorBackArgs a) {
 // ---- ray paths -----------------------------------------------------------------------------------------------------------
 // path is (samples, n, 3), sample-major: entry j of ray i at (j n + i) 3, so that in caller order a wave's 64 stores of one
 // sample are one contiguous run of 768 bytes.  Under a visit order (perm) they are 64 scattered 12-byte stores on 1 / stride
-// of the iterations; they are not staged (DESIGN.md 6 has what that costs).
+// of the iterations; they are not staged (DESIGN.md 6 has what that costs).  vpath is laid out and stored like path, one
+// store behind it: in caller order a wave writes one contiguous run of 768 bytes per sample and series.
+// VEL: the call carries the velocity series (the phase entries: a.vpath / a.dvpath exist); without it the velocities handed
+// to the store are dropped and NoVSeed seeds none, and the compiler removes the series completely.
+template <bool VEL, typename Args, typename TapFn>
+__device__ __forceinline__ RayOut trace_path_lane(const Args& a, size_t i, const float* p0, const float* v0, TapFn& taps,
+                                                  unsigned& count) {
+  auto store = [&](unsigned j, float x, float y, float z, float vx, float vy, float vz) {
+    const size_t e = (size_t)j * a.n + i;
+    st3(a.path, e, x, y, z);
+    if constexpr (VEL) st3(a.vpath, e, vx, vy, vz);
+  };
+  return trace_phase_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
+}
+
+// GRID: dL/dn is scattered (a.grad is not null)
+template <bool GRID, bool VEL, typename Args, typename TapFn>
+__device__ __forceinline__ RayGrad backtrace_path_lane(const Args& a, size_t i, const AdjRay& r, TapFn& taps) {
+  auto seed = [&](unsigned j, float* g) {
+    const Ray3 zero{0.f, 0.f, 0.f};
+    const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;
+    g[0] = d.x; g[1] = d.y; g[2] = d.z;
+  };
+  auto vseed = [&] {
+    if constexpr (VEL) {
+      return [&a, i](unsigned j, float* g) {
+        if (!a.dvpath) return false;
+        const Ray3 d = ld3(a.dvpath, (size_t)j * a.n + i);
+        g[0] = d.x; g[1] = d.y; g[2] = d.z;
+        return true;
+      };
+    } else {
+      return NoVSeed{};
+    }
+  }();
+  HeldCorners acc(a.grad);
+  SplatSink<GRID> sink{acc};
+  const RayGrad g = phase_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
+                                        a.stride, a.samples, seed, vseed, taps, sink);
+  if (GRID) acc.flush();
+  return g;
+}
+
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_path(PathTraceArgs a) {
   unsigned count;
   trace_lanes<PAIR>(a,
     [&](size_t i, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
-      auto store = [&](unsigned j, float x, float y, float z) { st3(a.path, (size_t)j * a.n + i, x, y, z); };
-      return trace_path_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
+      return trace_path_lane<false>(a, i, p0, v0, taps, count);
     },
     [&](size_t i) { a.count[i] = (int)count; });
 }
-
-// GRID: dL/dn is scattered (a.grad is not null)
-template <bool PAIR, bool GRID>
-__global__ void __launch_bounds__(kBlock) k_backtrace_path(PathBackArgs a) {
-  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
-    auto seed = [&](unsigned j, float* g) {
-      const Ray3 zero{0.f, 0.f, 0.f};
-      const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;
-      g[0] = d.x; g[1] = d.y; g[2] = d.z;
-    };
-    HeldCorners acc(a.grad);
-    SplatSink<GRID> sink{acc};
-    const RayGrad g = path_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
-                                         a.stride, a.samples, seed, taps, sink);
-    if (GRID) acc.flush();
-    return g;
-  });
-}
-
-// ---- ray paths with velocities -------------------------------------------------------------------------------------------
-// vpath is laid out and stored like path, one store behind it: in caller order a wave writes one contiguous run of 768 bytes
-// per sample and series.
 template <bool PAIR>
 __global__ void __launch_bounds__(kBlock) k_trace_phase(PhaseTraceArgs a) {
   unsigned count;
   trace_lanes<PAIR>(a,
     [&](size_t i, const float* p0, const float* v0, HeldTaps<PAIR>& taps) {
-      auto store = [&](unsigned j, float x, float y, float z, float vx, float vy, float vz) {
-        const size_t e = (size_t)j * a.n + i;
-        st3(a.path, e, x, y, z);
-        st3(a.vpath, e, vx, vy, vz);
-      };
-      return trace_phase_ray(a.vol, a.ds, a.max_steps, p0, v0, a.stride, a.samples, taps, store, count);
+      return trace_path_lane<true>(a, i, p0, v0, taps, count);
     },
     [&](size_t i) { a.count[i] = (int)count; });
 }
-
-// GRID: dL/dn is scattered (a.grad is not null)
+template <bool PAIR, bool GRID>
+__global__ void __launch_bounds__(kBlock) k_backtrace_path(PathBackArgs a) {
+  backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
+    return backtrace_path_lane<GRID, false>(a, i, r, taps);
+  });
+}
 template <bool PAIR, bool GRID>
 __global__ void __launch_bounds__(kBlock) k_backtrace_phase(PhaseBackArgs a) {
   backtrace_lanes<PAIR>(a, [&](size_t i, const AdjRay& r, HeldTaps<PAIR>& taps) {
-    auto seed = [&](unsigned j, float* g) {
-      const Ray3 zero{0.f, 0.f, 0.f};
-      const Ray3 d = a.dpath ? ld3(a.dpath, (size_t)j * a.n + i) : zero;
-      g[0] = d.x; g[1] = d.y; g[2] = d.z;
-    };
-    auto vseed = [&](unsigned j, float* g) {
-      if (!a.dvpath) return false;
-      const Ray3 d = ld3(a.dvpath, (size_t)j * a.n + i);
-      g[0] = d.x; g[1] = d.y; g[2] = d.z;
-      return true;
-    };
-    HeldCorners acc(a.grad);
-    SplatSink<GRID> sink{acc};
-    const RayGrad g = phase_backtrace_ray(a.vol, a.ds, a.grad_scale, a.max_steps, r.K, r.p0, r.v0, r.xt, r.vt, r.dx, r.dv,
-                                          a.stride, a.samples, seed, vseed, taps, sink);
-    if (GRID) acc.flush();
-    return g;
+    return backtrace_path_lane<GRID, true>(a, i, r, taps);
   });
 }
 

@@ -858,7 +858,8 @@ class TracerC:
         uniform u it telescopes to ``u . (xt - x_e)``).  fp32 rays only."""
         return self._trace_vector(rif, vfield, res, pos, vel, h, ds)[0]
 
-    def _trace_path(self, rif, res, pos, vel, h, ds, stride, samples=None):
+    def _trace_path(self, rif, res, pos, vel, h, ds, stride, samples=None, velocities=False):
+        """The path march, and with `velocities` the phase march: the same call with vpath behind path."""
         stride = int(stride)
         if samples is None:
             samples = -(-max(path_max_steps(res, h, ds), 0) // max(stride, 1)) + 1
@@ -866,11 +867,11 @@ class TracerC:
 
         def outputs(rif_, r):
             n, dev = r[0].shape[0], r[0].device
-            return _like_rays(rif_, r) + (r[0].new_empty((max(samples, 0), n, 3)),
-                                          torch.empty(n, dtype=torch.int32, device=dev),
-                                          torch.empty(n, dtype=torch.int32, device=dev))
-        return _grid_call("drrt_trace_path_f32", rif, res, [pos, vel], h, ds, outputs, adjoint=False, steps=False,
-                          warn=True, scalars=(stride, samples))
+            series = tuple(r[0].new_empty((max(samples, 0), n, 3)) for _ in range(2 if velocities else 1))
+            return _like_rays(rif_, r) + series + (torch.empty(n, dtype=torch.int32, device=dev),
+                                                   torch.empty(n, dtype=torch.int32, device=dev))
+        return _grid_call("drrt_trace_phase_f32" if velocities else "drrt_trace_path_f32", rif, res, [pos, vel], h, ds,
+                          outputs, adjoint=False, steps=False, warn=True, scalars=(stride, samples))
 
     def trace_path(self, rif, res, pos, vel, h, ds, stride, samples=None):
         """``trace`` with the path of every ray (drrt_trace_path_f32, include/drrt_hip.h; not in the reference) ->
@@ -882,20 +883,6 @@ class TracerC:
         ``samples=None`` is ``ceil(max_steps / stride) + 1``, the smallest that always ends on xt.  fp32 rays only."""
         return self._trace_path(rif, res, pos, vel, h, ds, stride, samples)[0]
 
-    def _trace_phase(self, rif, res, pos, vel, h, ds, stride, samples=None):
-        stride = int(stride)
-        if samples is None:
-            samples = -(-max(path_max_steps(res, h, ds), 0) // max(stride, 1)) + 1
-        samples = int(samples)
-
-        def outputs(rif_, r):
-            n, dev = r[0].shape[0], r[0].device
-            return _like_rays(rif_, r) + (r[0].new_empty((max(samples, 0), n, 3)), r[0].new_empty((max(samples, 0), n, 3)),
-                                          torch.empty(n, dtype=torch.int32, device=dev),
-                                          torch.empty(n, dtype=torch.int32, device=dev))
-        return _grid_call("drrt_trace_phase_f32", rif, res, [pos, vel], h, ds, outputs, adjoint=False, steps=False,
-                          warn=True, scalars=(stride, samples))
-
     def trace_phase(self, rif, res, pos, vel, h, ds, stride, samples=None):
         """``trace_path`` with the marching velocities beside the positions (drrt_trace_phase_f32, include/drrt_hip.h; not
         in the reference) -> (xt, vt, path, vpath, count, steps).  xt, vt, path, count and steps are ``trace_path``'s bit for
@@ -903,9 +890,20 @@ class TracerC:
         of iteration j stride (``vpath[0] = vel``; for j > 0 the velocity that carried the ray into ``path[j]``), `count` of
         them, then vt repeated.  ``(path[j], vpath[j])`` is the march's state at sample j, and ``|vpath[j]|`` the refractive
         index the ray saw there.  `samples`: as for ``trace_path``.  fp32 rays only."""
-        return self._trace_phase(rif, res, pos, vel, h, ds, stride, samples)[0]
+        return self._trace_path(rif, res, pos, vel, h, ds, stride, samples, velocities=True)[0]
 
     # ---- adjoint ------------------------------------------------------------------------
+    def _backtrace_path(self, op, series, rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds, stride, grid, rays, into, order,
+                        samples):
+        """What ``backtrace_path`` (`op` "path", `series` (dpath,)) and ``backtrace_phase`` ("phase", (dpath, dvpath)) share:
+        `samples` is read off the first seed of `series` that is given."""
+        if samples is None:
+            samples = next((int(s.shape[0]) for s in series if s is not None), 1)
+        shape = (int(samples), None, 3)
+        return _backtrace_integral(op, rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (), ((grid, into, "into"),),
+                                   rays, h, ds, order, series=tuple((s, shape) for s in series),
+                                   scalars=(int(stride), int(samples)))
+
     def backtrace_phase(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, dvpath, h, ds, stride, grid: bool = True,
                         rays: bool = True, into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
                         samples: Optional[int] = None):
@@ -915,13 +913,8 @@ class TracerC:
         `dvpath` is given; it is needed only when both are None (then any value gives the same result, and the default is
         1).  Seeds on padded `vpath` entries are seeds on vt, added to dv in ascending j.  Everything else: as for
         ``backtrace_path``."""
-        if samples is None:
-            given = dpath if dpath is not None else dvpath
-            samples = 1 if given is None else int(given.shape[0])
-        shape = (int(samples), None, 3)
-        return _backtrace_integral("phase", rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (), ((grid, into, "into"),),
-                                   rays, h, ds, order, series=((dpath, shape), (dvpath, shape)),
-                                   scalars=(int(stride), int(samples)))
+        return self._backtrace_path("phase", (dpath, dvpath), rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds, stride, grid,
+                                    rays, into, order, samples)
 
     def backtrace_path(self, rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, h, ds, stride, grid: bool = True,
                        rays: bool = True, into: Optional[torch.Tensor] = None, order: Optional[torch.Tensor] = None,
@@ -935,11 +928,8 @@ class TracerC:
         ascending j.  `grid` / `rays` / `into` / `order`: as for ``backtrace_opl``.  Honours ``options.corrected_h`` (with it
         the grid gradient is the exact discrete derivative; the ray gradients do not depend on it).  Rays that failed the
         forward get zeros and contribute nothing."""
-        if samples is None:
-            samples = 1 if dpath is None else int(dpath.shape[0])
-        return _backtrace_integral("path", rif, (), res, pos, vel, xt, vt, steps, (), dx, dv, (), ((grid, into, "into"),),
-                                   rays, h, ds, order, series=((dpath, (int(samples), None, 3)),),
-                                   scalars=(int(stride), int(samples)))
+        return self._backtrace_path("path", (dpath,), rif, res, pos, vel, xt, vt, steps, dx, dv, h, ds, stride, grid, rays,
+                                    into, order, samples)
 
     def backtrace_vector(self, rif, vfield, res, pos, vel, xt, vt, steps, dx, dv, dcirc, h, ds, grid: bool = True,
                          vfield_grid: bool = True, rays: bool = True, into: Optional[torch.Tensor] = None,

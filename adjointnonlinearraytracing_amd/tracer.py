@@ -463,6 +463,27 @@ class VectorIntegralTracerC(torch.autograd.Function):
         return (*_integral_backward(ctx, drrt.TracerC().backtrace_vector, grad_x, grad_v, grad_circ), None, None)
 
 
+def _path_forward(ctx, name, velocities, rif, x, v, h, ds, stride, samples):
+    """Forward of PathTracerC and, with `velocities`, of PhasePathTracerC -> (xt, vt, path[, vpath], count); keeps the stride
+    and the length of the series for the backward."""
+    def march(*a):
+        out, order, left = drrt.TracerC()._trace_path(*a, stride, samples, velocities=velocities)
+        ctx.stride, ctx.samples = int(stride), int(out[2].shape[0])
+        return out, order, left
+    *out, count = _integral_forward(ctx, name, march, rif, (), x, v, h, ds)
+    ctx.mark_non_differentiable(count)
+    return (*out, count)
+
+
+def _path_backward(ctx, backtrace, grad_x, grad_v, *seeds):
+    """Backward of the same two: ONE launch of `backtrace` (``TracerC.backtrace_path`` / ``backtrace_phase``), with the kept
+    stride and series length spliced into `_integral_backward`'s call."""
+    def back(*a, **kw):                 # a: (rif, shape, x0, v0, xt, vt, steps, dx, dv, *seeds, h, ds, grid, rays)
+        k = 11 + len(seeds)
+        return backtrace(*a[:k], ctx.stride, *a[k:], samples=ctx.samples, **kw)
+    return (*_integral_backward(ctx, back, grad_x, grad_v, *seeds), None, None, None, None)
+
+
 class PathTracerC(torch.autograd.Function):
     """``apply(rif, x, v, h, ds, stride, samples) -> (xt, vt, path, count)``: ``trace`` with the path of every ray, ``path``
     of shape ``(samples, n, 3)`` (``path[j]``: every ray at sample j; ``path[:, i]``: ray i's polyline): the marching
@@ -479,19 +500,11 @@ class PathTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds, stride, samples=None):
-        def march(*a):
-            out, order, left = drrt.TracerC()._trace_path(*a, stride, samples)
-            ctx.stride, ctx.samples = int(stride), int(out[2].shape[0])
-            return out, order, left
-        xt, vt, path, count = _integral_forward(ctx, "PathTracerC", march, rif, (), x, v, h, ds)
-        ctx.mark_non_differentiable(count)
-        return xt, vt, path, count
+        return _path_forward(ctx, "PathTracerC", False, rif, x, v, h, ds, stride, samples)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_path, _grad_count=None):
-        def back(*a, **kw):             # a: (rif, shape, x0, v0, xt, vt, steps, dx, dv, dpath, h, ds, grid, rays)
-            return drrt.TracerC().backtrace_path(*a[:12], ctx.stride, *a[12:], samples=ctx.samples, **kw)
-        return (*_integral_backward(ctx, back, grad_x, grad_v, grad_path), None, None, None, None)
+        return _path_backward(ctx, drrt.TracerC().backtrace_path, grad_x, grad_v, grad_path)
 
 
 class PhasePathTracerC(torch.autograd.Function):
@@ -509,19 +522,11 @@ class PhasePathTracerC(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rif, x, v, h, ds, stride, samples=None):
-        def march(*a):
-            out, order, left = drrt.TracerC()._trace_phase(*a, stride, samples)
-            ctx.stride, ctx.samples = int(stride), int(out[2].shape[0])
-            return out, order, left
-        xt, vt, path, vpath, count = _integral_forward(ctx, "PhasePathTracerC", march, rif, (), x, v, h, ds)
-        ctx.mark_non_differentiable(count)
-        return xt, vt, path, vpath, count
+        return _path_forward(ctx, "PhasePathTracerC", True, rif, x, v, h, ds, stride, samples)
 
     @staticmethod
     def backward(ctx, grad_x, grad_v, grad_path, grad_vpath, _grad_count=None):
-        def back(*a, **kw):             # a: (rif, shape, x0, v0, xt, vt, steps, dx, dv, dpath, dvpath, h, ds, grid, rays)
-            return drrt.TracerC().backtrace_phase(*a[:13], ctx.stride, *a[13:], samples=ctx.samples, **kw)
-        return (*_integral_backward(ctx, back, grad_x, grad_v, grad_path, grad_vpath), None, None, None, None)
+        return _path_backward(ctx, drrt.TracerC().backtrace_phase, grad_x, grad_v, grad_path, grad_vpath)
 
 
 def _cable_integral_forward(ctx, name, march, profiles, radius, length, x, v, sp, ds):

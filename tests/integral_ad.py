@@ -133,21 +133,37 @@ def trace_vector(rif, vfield, pos, vel, h, ds, extent=False):
     return xt, vt, circ, steps, scale.detach()
 
 
-def trace_path(rif, pos, vel, h, ds, stride, samples):
+def trace_path(rif, pos, vel, h, ds, stride, samples, velocities=False):
     """Records the marching position x in front of every iteration that is a multiple of `stride`, `samples` = M entries at
-    most.  The per-ray count ``min(M, ceil(steps / stride))`` is known behind the loop; the entries at and behind it are
-    replaced by xt with ``torch.where``, so autograd sees xt there and x_{j stride} in front of it.  The loop ends when every
-    ray is flagged; the entries it has not reached then belong to no ray's samples (j stride >= steps for every ray) and are
-    padding.  Differentiable w.r.t. rif, pos, vel.  -> (xt, vt, path (samples, n, 3), count, steps)."""
-    rec = []
+    most, and with `velocities` the velocity v in front of it beside x: vel for iteration 0 and the `kicked` value of
+    iteration k - 1 behind it.  The per-ray count ``min(M, ceil(steps / stride))`` is known behind the loop; the entries at
+    and behind it are replaced by xt (vt) with ``torch.where``, so autograd sees xt (vt) there and x_{j stride}
+    (v_{j stride}) in front of it.  The loop ends when every ray is flagged; the entries it has not reached then belong to no
+    ray's samples (j stride >= steps for every ray) and are padding.  Differentiable w.r.t. rif, pos, vel.
+    -> (xt, vt, path (samples, n, 3)[, vpath (samples, n, 3)], count, steps)."""
+    rec, vrec = [], []
+    carried = vel
 
     def front(it, x, n, inside, esc):
         if it % stride == 0 and len(rec) < samples:
             rec.append(x)
+            vrec.append(carried)
 
-    xt, vt, steps = _march(rif, pos, vel, h, ds, front)
+    def kicked(v):
+        nonlocal carried
+        carried = v
+
+    xt, vt, steps = _march(rif, pos, vel, h, ds, front, kicked if velocities else None)
     count = torch.clamp((steps + stride - 1) // stride, max=samples)
-    rows = []
-    for j in range(samples):
-        rows.append(torch.where((j < count)[:, None], rec[j], xt) if j < len(rec) else xt)
-    return xt, vt, torch.stack(rows), count, steps
+    series = []
+    for recorded, pad in ((rec, xt), (vrec, vt))[:2 if velocities else 1]:
+        rows = []
+        for j in range(samples):
+            rows.append(torch.where((j < count)[:, None], recorded[j], pad) if j < len(rec) else pad)
+        series.append(torch.stack(rows))
+    return (xt, vt, *series, count, steps)
+
+
+def trace_phase(rif, pos, vel, h, ds, stride, samples):
+    """trace_path with both series -> (xt, vt, path, vpath, count, steps)."""
+    return trace_path(rif, pos, vel, h, ds, stride, samples, velocities=True)

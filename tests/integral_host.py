@@ -1,9 +1,9 @@
 """Loader for tests/hostcheck/integral_rays.hip (TEST INFRASTRUCTURE ONLY): the product's per-ray routines of the grid
 integral family -- optical path length (trace_opl_ray, opl_backtrace_ray), line integral of a second field (trace_field_ray,
 field_backtrace_ray), emission with self-absorption (exp_neg, trace_emission_ray, emission_backtrace_ray), line integral of
-a vector field (trace_vector_ray, vector_backtrace_ray) and ray paths (trace_path_ray, path_backtrace_ray) of
-csrc/drrt_device.h -- compiled for the host by hostcheck_lib.build(), looped as the kernels run them.  Never imported by
-the package."""
+a vector field (trace_vector_ray, vector_backtrace_ray) and ray paths without and with the velocity series (trace_path_ray,
+path_backtrace_ray; trace_phase_ray, phase_backtrace_ray) of csrc/drrt_device.h -- compiled for the host by
+hostcheck_lib.build(), looped as the kernels run them.  Never imported by the package."""
 import ctypes as C
 import os
 
@@ -133,19 +133,42 @@ def backtrace_vector(rif, vfield, res, pos, vel, xt, vt, steps, dx, dv, dcirc, h
                       (bool(corrected_h), parts), dict(grad=g[0].size, grad_vfield=3 * g[0].size))
 
 
+def _trace_series(entry, names, rif, res, pos, vel, h, ds, stride, samples):
+    pos, vel = _f(pos).reshape(-1, 3), _f(vel).reshape(-1, 3)
+    series = {k: np.empty((samples, len(pos), 3), np.float32) for k in names}
+    count = np.empty(len(pos), np.int32)
+    r = _trace(entry, _grids(rif), res, pos, vel, h, ds, (), (stride, samples), (*series.values(), count))
+    return dict(xt=r["xt"], vt=r["vt"], **series, count=count, steps=r["steps"], n_failed=r["n_failed"])
+
+
+def _backtrace_series(entry, rif, res, pos, vel, xt, vt, steps, dx, dv, series, h, ds, stride, samples, corrected_h):
+    g = _grids(rif)
+    rays = [_f(a).reshape(-1, 3) for a in (pos, vel, xt, vt)]
+    assert all(a is None or _f(a).shape == (samples, len(rays[0]), 3) for a in series)
+    return _backtrace(entry, g, res, rays, steps, (), (dx, dv, *series), h, ds, (stride, samples, bool(corrected_h)),
+                      dict(grad=g[0].size))
+
+
 def trace_path(rif, res, pos, vel, h, ds, stride, samples):
     """-> dict(xt, vt, path (samples, n, 3), count, steps, n_failed): the host build of what drrt_trace_path_f32 computes."""
-    pos, vel = _f(pos).reshape(-1, 3), _f(vel).reshape(-1, 3)
-    path, count = np.empty((samples, len(pos), 3), np.float32), np.empty(len(pos), np.int32)
-    r = _trace("path_host_trace", _grids(rif), res, pos, vel, h, ds, (), (stride, samples), (path, count))
-    return dict(xt=r["xt"], vt=r["vt"], path=path, count=count, steps=r["steps"], n_failed=r["n_failed"])
+    return _trace_series("path_host_trace", ("path",), rif, res, pos, vel, h, ds, stride, samples)
+
+
+def trace_phase(rif, res, pos, vel, h, ds, stride, samples):
+    """-> dict(xt, vt, path, vpath ((samples, n, 3) each), count, steps, n_failed): the host build of what
+    drrt_trace_phase_f32 computes."""
+    return _trace_series("phase_host_trace", ("path", "vpath"), rif, res, pos, vel, h, ds, stride, samples)
 
 
 def backtrace_path(rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, h, ds, stride, samples, corrected_h=True):
     """-> dict(grad float64[nvox], dpos, dvel, steps (reverse iterations per ray), failed, ray_steps, n_failed): the host
     build of what drrt_backtrace_path_f32 computes; dx, dv, dpath ((samples, n, 3)) may be None (zeros)."""
-    g = _grids(rif)
-    rays = [_f(a).reshape(-1, 3) for a in (pos, vel, xt, vt)]
-    assert dpath is None or _f(dpath).shape == (samples, len(rays[0]), 3)
-    return _backtrace("path_host_backtrace", g, res, rays, steps, (), (dx, dv, dpath), h, ds,
-                      (stride, samples, bool(corrected_h)), dict(grad=g[0].size))
+    return _backtrace_series("path_host_backtrace", rif, res, pos, vel, xt, vt, steps, dx, dv, (dpath,), h, ds, stride,
+                             samples, corrected_h)
+
+
+def backtrace_phase(rif, res, pos, vel, xt, vt, steps, dx, dv, dpath, dvpath, h, ds, stride, samples, corrected_h=True):
+    """-> dict(grad float64[nvox], dpos, dvel, steps (reverse iterations per ray), failed, ray_steps, n_failed): the host
+    build of what drrt_backtrace_phase_f32 computes; dx, dv, dpath, dvpath ((samples, n, 3)) may be None."""
+    return _backtrace_series("phase_host_backtrace", rif, res, pos, vel, xt, vt, steps, dx, dv, (dpath, dvpath), h, ds,
+                             stride, samples, corrected_h)

@@ -5,7 +5,7 @@ rest and off unit speed).
 
 Referee, yardstick, compared rays, bound: tests/path_common.py::referee with integral_fuzz_common.masks(oracle, seed)["compared"]
 unchanged -- that set depends only on the forward march, which this operator shares -- and MARGIN, FLOOR, CAPS and bound() of
-tests/integral_fuzz_common.py.  Strides 1 and 5, an M that pads and an M that truncates, every mode of test_path.MODES.
+tests/integral_fuzz_common.py.  Strides 1 and 5, an M that pads and an M that truncates, every mode of path_common.PATH_MODES.
 
 CPU tier: forward identities bit for bit, forward and adjoint under the bound.  GPU tier: the kernels against the host build
 with and without the pair copy (the forward sorts on even seeds and the adjoint takes its order; on odd seeds the forward

@@ -1,13 +1,14 @@
 """Ray paths with velocities: drrt_trace_phase_f32 / drrt_backtrace_phase_f32, TracerC.trace_phase / backtrace_phase,
 tracer.PhasePathTracerC.
 
-CPU tier: the host build of the product's per-ray routines (tests/hostcheck/phase_path_rays.hip: trace_phase_ray and
-phase_backtrace_ray of csrc/drrt_device.h) against the host build of the path routines (bit for bit), against float64
-torch.autograd through tests/phase_path_ad (integral_ad's one loop, recording (x, v) where the product does) on the compared
-rays, against closed forms, and the C ABI's argument checks.  GPU tier: k_trace_phase / k_backtrace_phase of
-drrt_integral.hip against that host build, the autograd class end to end, its launches, and the demo.
+CPU tier: the host build of the product's per-ray routines (tests/hostcheck/integral_rays.hip: trace_phase_ray and
+phase_backtrace_ray of csrc/drrt_device.h) against the host build of the path routines (their forwards without the velocity
+series; bit for bit), against float64 torch.autograd through tests/integral_ad (its one loop, recording (x, v) where the
+product does) on the compared rays, against closed forms, and the C ABI's argument checks.  GPU tier:
+k_trace_phase / k_backtrace_phase of drrt_integral.hip against that host build, the autograd class end to end, its
+launches, and the demo.
 
-The referee (phase_path_common.referee, shared with tests/test_phase_path_fuzz.py): L = <dx, xt> + <dv, vt> + <dpath, path> +
+The referee (path_common.referee_phase, shared with tests/test_phase_path_fuzz.py): L = <dx, xt> + <dv, vt> + <dpath, path> +
 <dvpath, vpath> in float64, and once more in float32 as the yardstick.  Compared rays, bound and caps are test_path.py's
 (integral_fuzz_common.bound, FLOOR, MARGIN, CAPS unchanged); a vpath sample's error is the largest absolute difference over
 the compared rays and j < M over the largest |v| of the float64 run and stays under CAPS["out"], like a path sample's over
@@ -45,13 +46,10 @@ import integral_ad
 import integral_common as IC
 from integral_common import ATOMIC_TOL, _same, scene
 from integral_fuzz_common import CAPS
+import integral_host as OH
 from oracle import torch_ad
 import path_common as PC
-from path_common import STRIDES, _bits, count_of, dpath_of, pad_m, trunc_m
-import phase_path_ad
-import phase_path_common as PP
-from phase_path_common import back, dvpath_of, fwd
-import phase_path_host as PH
+from path_common import STRIDES, _bits, back_phase as back, count_of, dpath_of, dvpath_of, fwd_phase as fwd, pad_m, trunc_m
 from raygrad_common import SCENES, TIE_TOL, _t, max_steps_fwd, rel_err
 
 
@@ -179,7 +177,7 @@ def test_referee_on_fixed_scenes(oracle, name, stride, kind):
     cmp_ = compared_rays(oracle, name)
     assert cmp_.sum() >= 400
     M = pad_m(ms, stride) if kind == "pad" else trunc_m(ms, stride)
-    worst, bad, weight = PP.referee(s, cmp_, stride, M, f"{name} stride={stride} M={M}")
+    worst, bad, weight = PC.referee_phase(s, cmp_, stride, M, f"{name} stride={stride} M={M}")
     assert bad == []
     assert min(weight[m] for m in ("all", "noray", "vprefix", "vinbox", "inbox")) > 100
     assert weight["vpadded"] > (100 if kind == "pad" else 0)
@@ -422,10 +420,10 @@ def test_abi_argument_checks():
 
 
 def test_routines_under_sanitizers(tmp_path):
-    """tests/hostcheck/phase_path_rays.hip as a stand-alone program (its own main), compiled for the host with ASan + UBSan
-    and run as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries, with
+    """tests/hostcheck/integral_rays.hip (-DPHASE_MAIN) as a stand-alone program (its own main), compiled for the host with
+    ASan + UBSan and run as a child process, nothing preloaded: scene 1 plus rays and seeds with NaN, Inf, huge and denormal entries, with
     a stride above every K, with M = 1, and with zero rays."""
-    exe = HC.sanitized_program(tmp_path, PH.SOURCE, "PHASE_MAIN")
+    exe = HC.sanitized_program(tmp_path, OH.SOURCE, "PHASE_MAIN")
     s = scene(list(SCENES)[1])
     ms = max_steps_fwd(s["res"], s["h"], s["ds"])
     rng = np.random.default_rng(0)
@@ -482,10 +480,10 @@ def test_kernels_match_host_build(gpu, name, pair):
             assert k["n_failed"] > 0
             for sort in (False, True):
                 with drrt.using(pair_grid=pair, corrected_h=True, sort_rays=sort):
-                    out, st, order = PP._gpu_forward(T, s, gpu, stride, M)
+                    out, st, order = PC._gpu_forward_phase(T, s, gpu, stride, M)
                     assert (order is not None) == sort
-                    PP._forward_matches(out, st, k)
-                    (grad, dpos, dvel), bst = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order)
+                    PC._forward_matches(out, st, k)
+                    (grad, dpos, dvel), bst = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order)
                 assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
                 assert bst["ray_steps"] == r["ray_steps"] and bst["n_failed"] == r["n_failed"] > 0
                 err = cases.rel_l2(grad.cpu().numpy(), r["grad"])
@@ -506,44 +504,44 @@ def test_kernel_variants(gpu):
     T = drrt.TracerC()
     ok = lambda grad, want: cases.rel_l2(grad.cpu().numpy(), want["grad"]) <= ATOMIC_TOL      # noqa: E731
     with drrt.using(corrected_h=True, pair_grid=False):
-        out, st, order = PP._gpu_forward(T, s, gpu, stride, M)
-        (grad, dpos, dvel), bst = PP._gpu_back(T, s, gpu, out, stride, g, w)                 # sorts for itself
+        out, st, order = PC._gpu_forward_phase(T, s, gpu, stride, M)
+        (grad, dpos, dvel), bst = PC._gpu_back_phase(T, s, gpu, out, stride, g, w)                 # sorts for itself
         assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"]) and ok(grad, r)
         assert bst["ray_steps"] == r["ray_steps"] and bst["n_failed"] == r["n_failed"]
         fill = torch.full((s["rif"].size,), 3.0, device=gpu)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order, into=fill)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order, into=fill)
         assert grad.data_ptr() == fill.data_ptr() and _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
         assert cases.rel_l2(fill.cpu().numpy().astype(np.float64) - 3.0, r["grad"]) <= ATOMIC_TOL
-        (grad, dpos, dvel), bst = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order, grid=False)
+        (grad, dpos, dvel), bst = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order, grid=False)
         assert grad is None and _same(dpos, r["dpos"]) and _same(dvel, r["dvel"]) and bst["ray_steps"] == r["ray_steps"]
-        (grad, dpos, dvel), bst = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order, rays=False)
+        (grad, dpos, dvel), bst = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order, rays=False)
         assert dpos is None and dvel is None and ok(grad, r)
         assert bst["ray_steps"] == r["ray_steps"] and bst["n_failed"] == r["n_failed"]
         with pytest.raises(RuntimeError, match="nothing to compute"):
-            PP._gpu_back(T, s, gpu, out, stride, g, w, grid=False, rays=False)
+            PC._gpu_back_phase(T, s, gpu, out, stride, g, w, grid=False, rays=False)
         # each seed null in turn
         r0 = back(s, k, None, s["dv"], g, w, stride, M, corrected_h=True)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order, dx=None)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order, dx=None)
         assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"]) and ok(grad, r0) and not np.array_equal(r0["dpos"], r["dpos"])
         r0 = back(s, k, s["dx"], None, g, w, stride, M, corrected_h=True)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, g, w, order=order, dv=None)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, g, w, order=order, dv=None)
         assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"]) and ok(grad, r0) and not np.array_equal(r0["dvel"], r["dvel"])
         r0 = back(s, k, s["dx"], s["dv"], None, w, stride, M, corrected_h=True)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, None, w, order=order)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, None, w, order=order)
         assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"]) and ok(grad, r0) and not np.array_equal(r0["dpos"], r["dpos"])
         r0 = back(s, k, s["dx"], s["dv"], g, None, stride, M, corrected_h=True)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, g, None, order=order)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, g, None, order=order)
         assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"]) and ok(grad, r0) and not np.array_equal(r0["dvel"], r["dvel"])
         (pgrad, ppos, pvel), _ = PC._gpu_back(T, s, gpu, (out[0], out[1], out[2], out[4], out[5]), stride, g, order=order)
         assert torch.equal(ppos, dpos) and torch.equal(pvel, dvel) and ok(pgrad, r0)
-        (grad, dpos, dvel), _ = PP._gpu_back(T, s, gpu, out, stride, None, None, order=order, samples=M, grid=False)
+        (grad, dpos, dvel), _ = PC._gpu_back_phase(T, s, gpu, out, stride, None, None, order=order, samples=M, grid=False)
         r0 = back(s, k, s["dx"], s["dv"], None, None, stride, M, corrected_h=True)
         assert _same(dpos, r0["dpos"]) and _same(dvel, r0["dvel"])
         # the forward == trace_path's on the device; samples=None is the smallest M that always ends on (xt, vt)
         pout, _, _ = PC._gpu_forward(T, s, gpu, stride, M)
         for a, b in zip((out[0], out[1], out[2], out[4], out[5]), pout):
             assert torch.equal(a, b)
-        dflt, _, _ = PP._gpu_forward(T, s, gpu, stride, None)
+        dflt, _, _ = PC._gpu_forward_phase(T, s, gpu, stride, None)
         assert dflt[3].shape[0] == M and _same(dflt[3], k["vpath"])
 
 
@@ -570,9 +568,9 @@ def test_edge_sizes(gpu, n):
         g, w = dpath_of(k1["path"].shape, 5), dvpath_of(k1["path"].shape, 5)
         r1 = back(one, k1, one["dx"], one["dv"], g, w, stride, M, corrected_h=True)
         with drrt.using(corrected_h=True, check_failed=False):
-            out, st, _ = PP._gpu_forward(T, one, gpu, stride, M)
-            (grad, dpos, dvel), bst = PP._gpu_back(T, one, gpu, out, stride, g, w)
-        PP._forward_matches(out, st, k1)
+            out, st, _ = PC._gpu_forward_phase(T, one, gpu, stride, M)
+            (grad, dpos, dvel), bst = PC._gpu_back_phase(T, one, gpu, out, stride, g, w)
+        PC._forward_matches(out, st, k1)
         assert tuple(out[3].shape) == (M, n, 3) and tuple(dpos.shape) == (n, 3)
         assert _same(dpos, r1["dpos"]) and _same(dvel, r1["dvel"])
         assert bst["ray_steps"] == r1["ray_steps"] and bst["n_failed"] == r1["n_failed"]
@@ -619,7 +617,7 @@ def test_phase_tracer_end_to_end(gpu, oracle):
     T64 = lambda a: torch.tensor(np.asarray(a), dtype=torch.float64)      # noqa: E731
     for sd in (seeds, (None, None, None, w)):
         r_, p_, v_ = (T64(s[q]).requires_grad_(True) for q in ("rif", "pos", "vel"))
-        out64 = phase_path_ad.trace_phase(r_, p_, v_, s["h"], s["ds"], stride, M)
+        out64 = integral_ad.trace_phase(r_, p_, v_, s["h"], s["ds"], stride, M)
         L = sum((o * T64(a)).sum() for o, a in zip(out64, sd) if a is not None)
         gr, gp, gv = (t.numpy() for t in torch.autograd.grad(L, (r_, p_, v_)))
         r = back(s, k, sd[0], sd[1], sd[2], sd[3], stride, M, corrected_h=True)

@@ -3,10 +3,10 @@ integral_fuzz_common.config(seed), seed in range(16), the configurations tests/t
 2..24 voxels per axis, 2-voxel axes on seeds 0, 4, 7, 14, h never a power of two, steps of 0.2..1.7 cells, rough media on
 seed % 3 == 0, 600 rays inside, outside and exactly on faces, at rest and off unit speed).
 
-Referee, yardstick, compared rays, bound: tests/phase_path_common.py::referee with
+Referee, yardstick, compared rays, bound: tests/path_common.py::referee_phase with
 integral_fuzz_common.masks(oracle, seed)["compared"] unchanged -- that set depends only on the forward march, which this
 operator shares -- and MARGIN, FLOOR, CAPS and bound() of tests/integral_fuzz_common.py.  Strides 1 and 5, an M that pads and
-an M that truncates, every mode of phase_path_common.MODES.
+an M that truncates, every mode of path_common.PHASE_MODES.
 
 CPU tier: forward identities bit for bit, forward and adjoint under the bound.  GPU tier: the kernels against the host build
 with and without the pair copy (the forward sorts on even seeds and the adjoint takes its order; on odd seeds the forward
@@ -23,7 +23,6 @@ from integral_fuzz_common import SEEDS, config
 import integral_fuzz_common as IF
 from integral_common import ATOMIC_TOL, _same
 import path_common as PC
-import phase_path_common as PP
 from raygrad_common import max_steps_fwd
 
 _bits = lambda a: np.ascontiguousarray(a).view(np.uint32)      # noqa: E731
@@ -36,10 +35,10 @@ def test_forward_identities(seed):
     every 5th row of the stride-1 vpath; M = 3 leaves the first rows unchanged: bit for bit."""
     c = config(seed)
     ms = max_steps_fwd(c["res"], c["h"], c["ds"])
-    one = PP.fwd(c, 1, PC.pad_m(ms, 1))
+    one = PC.fwd_phase(c, 1, PC.pad_m(ms, 1))
     for stride in PC.STRIDES:
         M = PC.pad_m(ms, stride)
-        k = one if stride == 1 else PP.fwd(c, stride, M)
+        k = one if stride == 1 else PC.fwd_phase(c, stride, M)
         p = PC.fwd(c, stride, M)
         for key in ("xt", "vt", "path"):
             assert np.array_equal(_bits(k[key]), _bits(p[key])), key
@@ -52,7 +51,7 @@ def test_forward_identities(seed):
         rows = one["vpath"][::stride][:M]
         sample = ~padded[:len(rows)]
         assert np.array_equal(_bits(k["vpath"][:len(rows)])[sample], _bits(rows)[sample])
-        cut = PP.fwd(c, stride, 3)
+        cut = PC.fwd_phase(c, stride, 3)
         assert np.array_equal(_bits(cut["vpath"][:min(M, 3)]), _bits(k["vpath"][:3])) and np.array_equal(cut["count"], np.minimum(cnt, 3))
 
 
@@ -67,7 +66,7 @@ def test_referee(oracle, seed, stride, kind):
     assert m["compared"].sum() >= 0.85 * 600 and m["nonzero"].sum() >= 250
     ms = max_steps_fwd(c["res"], c["h"], c["ds"])
     M = PC.pad_m(ms, stride) if kind == "pad" else PC.trunc_m(ms, stride)
-    worst, bad, weight = PP.referee(c, m["compared"], stride, M, f"seed {seed} stride={stride} M={M}")
+    worst, bad, weight = PC.referee_phase(c, m["compared"], stride, M, f"seed {seed} stride={stride} M={M}")
     assert bad == []
     # every class of seed is there; at stride 5 a configuration of few, long steps (seed 14) has no in-box sample to seed
     assert min(weight[mode] for mode in ("all", "noray", "vprefix", "vpadded")) > 0
@@ -89,16 +88,16 @@ def test_kernels_match_host_build(gpu, seed, pair):
     fwd_sorts = seed % 2 == 0
     stride = 5
     for M in (PC.pad_m(ms, stride), PC.trunc_m(ms, stride)):
-        k = PP.fwd(c, stride, M)
-        g, w = PC.dpath_of(k["path"].shape, seed), PP.dvpath_of(k["path"].shape, seed)
-        r = PP.back(c, k, c["dx"], c["dv"], g, w, stride, M, corrected_h=True)
+        k = PC.fwd_phase(c, stride, M)
+        g, w = PC.dpath_of(k["path"].shape, seed), PC.dvpath_of(k["path"].shape, seed)
+        r = PC.back_phase(c, k, c["dx"], c["dv"], g, w, stride, M, corrected_h=True)
         with drrt.using(pair_grid=pair, corrected_h=True, check_failed=False):
             with drrt.using(sort_rays=fwd_sorts):
-                out, st, order = PP._gpu_forward(T, c, gpu, stride, M)
+                out, st, order = PC._gpu_forward_phase(T, c, gpu, stride, M)
             assert (order is not None) == fwd_sorts
-            PP._forward_matches(out, st, k)
+            PC._forward_matches(out, st, k)
             with drrt.using(sort_rays=True):
-                (grad, dpos, dvel), bst = PP._gpu_back(T, c, gpu, out, stride, g, w, order=order)
+                (grad, dpos, dvel), bst = PC._gpu_back_phase(T, c, gpu, out, stride, g, w, order=order)
         assert _same(dpos, r["dpos"]) and _same(dvel, r["dvel"])
         assert bst["ray_steps"] == r["ray_steps"] > 0 and bst["n_failed"] == r["n_failed"] > 0
         err = cases.rel_l2(grad.cpu().numpy(), r["grad"])

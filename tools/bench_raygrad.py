@@ -560,56 +560,13 @@ def vector(a, dev):
     return out
 
 
-def path(a, dev):
-    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl`
-    h = 1.0 / (a.grid - 1)
-    ds = h / 2
-    n = pos.shape[0]
-    T = drrt.TracerC()
-    one, g = torch.ones_like(pos), torch.ones(n, device=dev)
-    rif = bench.make_grid(a.grid, dev)
-    res = tuple(rif.shape)
-    ms = drrt.path_max_steps(res, h, ds)
-    out = dict(grid=a.grid, rays=n, h=h, ds=ds, max_steps=ms, rounds=a.rounds, library=_lib.load().drrt_version().decode())
-    for order_name, sort in (("pixel", False), ("sorted", True)):
-        for stride in a.strides:
-            m = -(-ms // stride) + 1
-            with drrt.using(sort_rays=sort):
-                xt, vt, pth, count, steps = T.trace_path(rif, res, pos, vel, h, ds, stride, m)
-                order = drrt.keep_order(drrt.last_order)
-                dpath = torch.ones_like(pth)
-                del pth
-                bo = lambda **kw: T.backtrace_opl(rif, res, pos, vel, xt, vt, steps, one, one, g, h, ds, order=order, **kw)   # noqa: E731
-                bp = lambda **kw: T.backtrace_path(rif, res, pos, vel, xt, vt, steps, one, one, dpath, h, ds, stride,   # noqa: E731
-                                                   order=order, **kw)
-                r, med = time_each({
-                    "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
-                    "trace_path": lambda: T.trace_path(rif, res, pos, vel, h, ds, stride, m),
-                    "backtrace_opl_rays": lambda: bo(grid=False), "backtrace_path_rays": lambda: bp(grid=False),
-                    "backtrace_opl_grid": lambda: bo(rays=False), "backtrace_path_grid": lambda: bp(rays=False),
-                    "backtrace_opl_both": bo, "backtrace_path_both": bp,
-                }, a)
-            del dpath
-            if r is None:
-                continue
-            r["samples"], r["mean_count"], r["path_bytes"] = m, float(count.float().mean()), m * n * 12
-            r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
-            # what the extra time would be if the path were written at the peak HBM rate of the part (8 TB/s)
-            r["path_bytes_at_8TBps_ms"] = m * n * 12 / 8e12 * 1e3
-            r["trace_path_over_trace_opl"] = med["trace_path"] / med["trace_opl"]
-            for k in ("rays", "grid", "both"):
-                r[f"backtrace_path_{k}_over_backtrace_opl_{k}"] = med[f"backtrace_path_{k}"] / med[f"backtrace_opl_{k}"]
-            out[f"{order_name}_stride{stride}"] = r
-    if a.once:
-        return {}
-    with open(a.out, "w") as f:
-        json.dump(out, f, indent=1)
-        f.write("\n")
-    return out
-
-
-def phase(a, dev):
-    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))      # the rays of `opl` and `path`
+def _series(a, dev, velocities, calls, derive):
+    """What `path` and `phase` share: the rays of `opl`, and per visit order and stride one trace_path whose outputs feed
+    the adjoints, with a seed of ones per series (two with `velocities`).  `calls(T, fwd, back, seeds, stride, m)` -> the
+    timed calls of one setting: `fwd` = (rif, res, pos, vel, h, ds), the arguments of every forward, and
+    `back(method, *tail, **kw)` calls an adjoint on the setting's forward outputs with seeds of ones on (xt, vt), `tail` being
+    what follows them.  `derive(r, med, nbytes)` adds the mode's own figures, `nbytes` the size of one series."""
+    pos, vel = (t.to(dev) for t in bench.make_rays(a.rays, seed=0))
     h = 1.0 / (a.grid - 1)
     ds = h / 2
     n = pos.shape[0]
@@ -625,32 +582,16 @@ def phase(a, dev):
             with drrt.using(sort_rays=sort):
                 xt, vt, pth, count, steps = T.trace_path(rif, res, pos, vel, h, ds, stride, m)
                 order = drrt.keep_order(drrt.last_order)
-                dpath = torch.ones_like(pth)
-                dvpath = torch.ones_like(pth)
+                seeds = [torch.ones_like(pth) for _ in range(2 if velocities else 1)]
                 del pth
-                bp = lambda **kw: T.backtrace_path(rif, res, pos, vel, xt, vt, steps, one, one, dpath, h, ds, stride,   # noqa: E731
-                                                   order=order, **kw)
-                bq = lambda **kw: T.backtrace_phase(rif, res, pos, vel, xt, vt, steps, one, one, dpath, dvpath, h, ds, stride,   # noqa: E731
-                                                    order=order, **kw)
-                r, med = time_each({
-                    "trace_opl": lambda: T.trace_opl(rif, res, pos, vel, h, ds),
-                    "trace_path": lambda: T.trace_path(rif, res, pos, vel, h, ds, stride, m),
-                    "trace_phase": lambda: T.trace_phase(rif, res, pos, vel, h, ds, stride, m),
-                    "backtrace_path_rays": lambda: bp(grid=False), "backtrace_phase_rays": lambda: bq(grid=False),
-                    "backtrace_path_grid": lambda: bp(rays=False), "backtrace_phase_grid": lambda: bq(rays=False),
-                    "backtrace_path_both": bp, "backtrace_phase_both": bq,
-                }, a)
-            del dpath, dvpath
+                back = lambda method, *tail, **kw: method(rif, res, pos, vel, xt, vt, steps, one, one, *tail,   # noqa: E731
+                                                          order=order, **kw)
+                r, med = time_each(calls(T, (rif, res, pos, vel, h, ds), back, seeds, stride, m), a)
+            del seeds
             if r is None:
                 continue
-            r["samples"], r["mean_count"], r["series_bytes"] = m, float(count.float().mean()), m * n * 12
-            # both differences are the cost of writing one series of samples n 12 bytes
-            r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
-            r["trace_phase_extra_ms"] = med["trace_phase"] - med["trace_path"]
-            r["series_bytes_at_8TBps_ms"] = m * n * 12 / 8e12 * 1e3
-            r["trace_phase_over_trace_path"] = med["trace_phase"] / med["trace_path"]
-            for k in ("rays", "grid", "both"):
-                r[f"backtrace_phase_{k}_over_backtrace_path_{k}"] = med[f"backtrace_phase_{k}"] / med[f"backtrace_path_{k}"]
+            r["samples"], r["mean_count"] = m, float(count.float().mean())
+            derive(r, med, m * n * 12)
             out[f"{order_name}_stride{stride}"] = r
     if a.once:
         return {}
@@ -658,6 +599,59 @@ def phase(a, dev):
         json.dump(out, f, indent=1)
         f.write("\n")
     return out
+
+
+def path(a, dev):
+    def calls(T, fwd, back, seeds, stride, m):
+        h, ds = fwd[4:]
+        g = torch.ones(fwd[2].shape[0], device=dev)
+        bo = lambda **kw: back(T.backtrace_opl, g, h, ds, **kw)      # noqa: E731
+        bp = lambda **kw: back(T.backtrace_path, seeds[0], h, ds, stride, **kw)      # noqa: E731
+        return {
+            "trace_opl": lambda: T.trace_opl(*fwd),
+            "trace_path": lambda: T.trace_path(*fwd, stride, m),
+            "backtrace_opl_rays": lambda: bo(grid=False), "backtrace_path_rays": lambda: bp(grid=False),
+            "backtrace_opl_grid": lambda: bo(rays=False), "backtrace_path_grid": lambda: bp(rays=False),
+            "backtrace_opl_both": bo, "backtrace_path_both": bp,
+        }
+
+    def derive(r, med, nbytes):
+        r["path_bytes"] = nbytes
+        r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
+        # what the extra time would be if the path were written at the peak HBM rate of the part (8 TB/s)
+        r["path_bytes_at_8TBps_ms"] = nbytes / 8e12 * 1e3
+        r["trace_path_over_trace_opl"] = med["trace_path"] / med["trace_opl"]
+        for k in ("rays", "grid", "both"):
+            r[f"backtrace_path_{k}_over_backtrace_opl_{k}"] = med[f"backtrace_path_{k}"] / med[f"backtrace_opl_{k}"]
+
+    return _series(a, dev, False, calls, derive)
+
+
+def phase(a, dev):
+    def calls(T, fwd, back, seeds, stride, m):
+        h, ds = fwd[4:]
+        bp = lambda **kw: back(T.backtrace_path, seeds[0], h, ds, stride, **kw)      # noqa: E731
+        bq = lambda **kw: back(T.backtrace_phase, *seeds, h, ds, stride, **kw)      # noqa: E731
+        return {
+            "trace_opl": lambda: T.trace_opl(*fwd),
+            "trace_path": lambda: T.trace_path(*fwd, stride, m),
+            "trace_phase": lambda: T.trace_phase(*fwd, stride, m),
+            "backtrace_path_rays": lambda: bp(grid=False), "backtrace_phase_rays": lambda: bq(grid=False),
+            "backtrace_path_grid": lambda: bp(rays=False), "backtrace_phase_grid": lambda: bq(rays=False),
+            "backtrace_path_both": bp, "backtrace_phase_both": bq,
+        }
+
+    def derive(r, med, nbytes):
+        r["series_bytes"] = nbytes
+        # both differences are the cost of writing one series of samples n 12 bytes
+        r["trace_path_extra_ms"] = med["trace_path"] - med["trace_opl"]
+        r["trace_phase_extra_ms"] = med["trace_phase"] - med["trace_path"]
+        r["series_bytes_at_8TBps_ms"] = nbytes / 8e12 * 1e3
+        r["trace_phase_over_trace_path"] = med["trace_phase"] / med["trace_path"]
+        for k in ("rays", "grid", "both"):
+            r[f"backtrace_phase_{k}_over_backtrace_path_{k}"] = med[f"backtrace_phase_{k}"] / med[f"backtrace_path_{k}"]
+
+    return _series(a, dev, True, calls, derive)
 
 
 def main():
